@@ -89,7 +89,13 @@ def parse(argv=None):
                          "the rate is not a scaling figure and the line says so (config.rehearsal)")
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="launcher / sharding / gather plumbing only, on the CPU with the gloo backend (no GPU, no kernels): used by tests")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0: write what the last timed step returned (the result fields of the rank's pairs and the assembled records of every "
+                         "pair) as DIR/<name>.npy, float32 / float64, at most 64 MB in all -- for comparing two builds output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def conf(rows, cols):
@@ -469,6 +475,9 @@ class BatchWorkload:
             self.step()
         self.barrier()
         dt = time.perf_counter() - t0
+        if getattr(self.args, "dump_outputs", None):
+            # what the last timed step returned, before the profiled pass and the extra lines overwrite the record buffers (--dump-outputs)
+            self.timed_last = {"res": self.last["res"], "gathered": self.last["gathered"].cpu().numpy().copy()}
         dt_serial = None
         if profile:
             ctx.set_concurrency(1); ctx.set_profiling(True)
@@ -1399,6 +1408,39 @@ def check_records_crc(allrec, rows, cols, write=False, omega_storage="exact9", m
             "note": "records of pair p are the same bits whatever GPU / rank / sub-batch aligned it; a mismatch with a stale file (other kernel sources) means nothing"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def timed_outputs(last, total, seeds):
+    """{name: float32 / float64 array} of what the last timed step returned: every field of the rank's result array except the host timing
+    (in partition mode also the four depth-agreement scores per pair), the rank's global pair ids, and the records of every pair of the job
+    in global pair order"""
+    from g2o_frontend_amd import shard
+    res, sc = last["res"] if isinstance(last["res"], tuple) else (last["res"], None)
+    out = {"pair_ids": np.asarray(seeds, np.float64)}
+    for name in (res.dtype.names if res is not None else ()):      # a rank without pairs of its own has no result array
+        if name == "total_time_ms":
+            continue
+        a = res[name]
+        out[name] = a.astype(np.float64) if a.dtype.kind in "iu" else a.astype(np.float32)
+    if sc is not None:
+        out["scores"] = np.asarray([(m.image_non_zeros, m.image_outliers, m.image_inliers, m.image_reprojection_distance) for m in sc], np.float64)
+    out["records"] = np.ascontiguousarray(shard.assemble(last["gathered"], total), np.float32)
+    return out
+
+
+def dump_outputs(d, arrays, max_bytes=DUMP_MAX_BYTES):
+    """DIR/<name>.npy per array; above max_bytes in all, every array keeps the same fraction of its rows, chosen by a fixed seed"""
+    os.makedirs(d, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > max_bytes and a.ndim and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * max_bytes / total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
+    return sorted(arrays)
+
+
 # ------------------------------------------------------------------------------------------------ CPU dry run of the N-rank plumbing
 def dry_run_cpu(args, rank, world):
     """launcher -> ranks -> shard -> records (the real pwn_hip_align_result layout) -> all-gather (gloo) -> assemble, no GPU"""
@@ -1658,6 +1700,8 @@ def main():
         # that travelled through export / broadcast / import -- so the records any N assembles must equal, bit for bit, those of the one-GPU run
         gather_info["records_vs_single_gpu_run"] = check_records_crc(allrec, rows, cols, write=args.write_records_crc and world == 1 and not use_dist,
                                                                      omega_storage=args.omega_storage, mode=args.mode)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, timed_outputs(w.timed_last, total, seeds))
 
     extra = {}
     if not args.no_latency and rank == 0 and world == 1 and not partition:

@@ -6,6 +6,7 @@ import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
@@ -215,3 +216,52 @@ def test_host_cpu_info_names_what_cores_means():
     info = bench.host_cpu_info()
     assert info["logical_cpus"] >= 1 and 1 <= info["physical_cores"] <= info["logical_cpus"] and isinstance(info["smt"], bool)
     assert "cgroup_cpu_quota" in info
+
+
+def test_dump_outputs_writes_the_timed_steps_results(tmp_path):
+    """--dump-outputs: every result field but the host timing, the pair ids and the records in global pair order, float32 / float64 only;
+    over the byte budget every array keeps the same seeded rows"""
+    sys.path.insert(0, ROOT)
+    import bench
+    from g2o_frontend_amd import api, shard
+    res = np.zeros(3, api.ALIGN_RESULT_DTYPE)
+    res["T"] = np.eye(4, dtype=np.float32).reshape(-1)
+    res["error"] = [1.5, 2.5, 3.5]; res["inliers"] = [10, 20, 30]; res["iterations"] = 10; res["total_time_ms"] = 7.0
+    res["n_reference"] = 100; res["n_current"] = 101
+    seeds = [4, 5, 6]
+    rec = shard.pack_results_raw(res, seeds)
+    gathered = np.concatenate([np.full((1, shard.RECORD_FLOATS), -1, np.float32), rec[::-1]])     # a padding row, pairs out of order
+    full = np.zeros((7, shard.RECORD_FLOATS), np.float32); full[:, 19] = np.arange(7); full[4:] = rec
+    out = bench.timed_outputs({"res": res, "gathered": np.concatenate([gathered, full[:4]])}, 7, seeds)
+    assert "total_time_ms" not in out and set(res.dtype.names) - {"total_time_ms"} <= set(out)
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert np.array_equal(out["records"], full) and np.array_equal(out["pair_ids"], seeds) and np.array_equal(out["inliers"], [10, 20, 30])
+    names = bench.dump_outputs(str(tmp_path / "d"), out)
+    assert sorted(f[:-4] for f in os.listdir(tmp_path / "d")) == names
+    assert np.array_equal(np.load(tmp_path / "d" / "error.npy"), np.float32([1.5, 2.5, 3.5]))
+    big = {"a": np.arange(4000, dtype=np.float64), "b": np.arange(4000, dtype=np.float64) * 2}
+    bench.dump_outputs(str(tmp_path / "s"), big, max_bytes=16000)
+    a, b = np.load(tmp_path / "s" / "a.npy"), np.load(tmp_path / "s" / "b.npy")
+    assert a.nbytes + b.nbytes <= 16000 and len(a) == 1000 and np.array_equal(b, 2 * a) and np.all(np.diff(a) > 0)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_two_runs_are_the_same_and_are_the_records(tmp_path):
+    """two runs of bench.py with different --steps dump the same outputs, bit for bit (same inputs, no state carried between steps), and the
+    dumped records are the dumped result fields; the line reports the timed steps it was asked for"""
+    lines = []
+    for k in (2, 3):
+        out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--pairs", "6", "--steps", str(k), "--warmup", "1", "--no-cpu-baseline", "--no-latency",
+                              "--no-extras", "--render-workers", "1", "--dump-outputs", str(tmp_path / str(k))],
+                             capture_output=True, text=True, timeout=600, env=_clean_env())
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads(out.stdout.strip().splitlines()[-1]))
+    assert [l["steps"] for l in lines] == [2, 3] and all(l["ms_per_step"] > 0 for l in lines)
+    names = sorted(os.listdir(tmp_path / "2"))
+    assert names == sorted(os.listdir(tmp_path / "3")) and "records.npy" in names and "T.npy" in names
+    d = {n[:-4]: np.load(tmp_path / "2" / n) for n in names}
+    for n in names:
+        assert np.array_equal(d[n[:-4]], np.load(tmp_path / "3" / n)), n
+    assert d["records"].shape == (6, 64) and np.array_equal(d["records"][:, 19], np.arange(6))
+    assert np.array_equal(d["records"][:, :16], d["T"]) and np.array_equal(d["records"][:, 16], d["error"])
+    assert np.array_equal(d["records"][:, 17], d["inliers"])

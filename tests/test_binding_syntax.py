@@ -1,75 +1,10 @@
-"""The reference-side binding (bindings/pwn_hip/*.cpp: HipAligner : Aligner, HipDepthImageConverter : DepthImageConverterIntegralImage,
-the Cloud* -> device-cloud registry) meets a compiler: `g++ -std=gnu++98 -fsyntax-only` against the reference's OWN headers where they
-lie (pwn_core/aligner.h:308, depthimageconverter.h:47, cloud.h, ...), with ~200 lines of stand-in DECLARATIONS for the two libraries the
-image lacks (tests/stubs/Eigen, tests/stubs/opencv2: no function has a body, every Eigen expression has one loose type).
-
-What this checks: every reference class, member, accessor, virtual signature, access level and constness the binding relies on, every
-call into include/pwn_hip.h, and C++ syntax (it found a most-vexing-parse in hipaligner.cpp that the name checker could not see).
-What it does NOT check: anything about Eigen / OpenCV semantics -- the stand-ins accept any matrix expression.  It produces no object
-code, is not a build of the reference, is not parity evidence and has nothing to do with the oracle.  Skipped where /root/reference
-does not exist (the GPU box).
-
-The reference's own headers carry two diagnostics under a current g++ (an uninstantiated member template of InformationMatrix:
-`other.block<3,3>(0,0)` without `.template`, and `return *this` from a const method -- informationmatrix.h:79,81; compilers of the
-reference's time did not look into uninstantiated templates).  They are listed below and tolerated; anything else fails the test."""
+"""The stand-in declarations under tests/stubs (Eigen, opencv2) with which tools/check_binding_syntax.py puts the reference-side binding
+(bindings/pwn_hip/*.cpp) through `g++ -fsyntax-only` against the reference's own headers.  That pass needs a checkout of the reference,
+whose headers cannot be stored here, so it is a tool; what it relies on in this repository is checked here."""
 import os
 import re
-import shutil
-import subprocess
-
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-KNOWN_REFERENCE_DIAGNOSTICS = {("g2o_frontend/pwn_core/informationmatrix.h", 79), ("g2o_frontend/pwn_core/informationmatrix.h", 81)}
-SOURCES = ["devicecloudregistry.cpp", "hipdepthimageconverter.cpp", "hipaligner.cpp"]
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "g2o_frontend", "pwn_core")) or shutil.which("g++") is None,
-                                reason="needs the reference headers under /root/reference and g++")
-
-
-def _syntax_pass(path, extra=()):
-    cmd = ["g++", "-std=gnu++98", "-fsyntax-only", "-Wall", "-Woverloaded-virtual", "-Wno-unused", "-Wno-deprecated",
-           "-I", os.path.join(ROOT, "tests", "stubs"), "-I", REF, "-I", os.path.join(REF, "g2o_frontend", "basemath"),
-           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "bindings", "pwn_hip")] + list(extra) + [path]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    diags = []
-    for line in out.stderr.splitlines():
-        m = re.match(r"(.+?):(\d+):(\d+): (error|warning): (.*)", line)
-        if m:
-            diags.append((m.group(1), int(m.group(2)), m.group(4), m.group(5)))
-    return out.returncode, diags
-
-
-@pytest.mark.parametrize("src", SOURCES)
-def test_binding_source_passes_the_compilers_front_end(src):
-    rc, diags = _syntax_pass(os.path.join(ROOT, "bindings", "pwn_hip", src))
-    ours = [d for d in diags if not d[0].startswith(REF)]
-    assert not ours, "diagnostics in the binding / stand-ins / C-ABI header:\n" + "\n".join(map(str, ours))
-    theirs = {(os.path.relpath(d[0], REF), d[1]) for d in diags if d[0].startswith(REF) and d[2] == "error"}
-    assert theirs <= KNOWN_REFERENCE_DIAGNOSTICS, "new diagnostics inside the reference's headers: %s" % sorted(theirs - KNOWN_REFERENCE_DIAGNOSTICS)
-    assert rc == 0 or theirs, "the compiler failed without a located diagnostic"
-
-
-def test_the_pass_is_not_vacuous(tmp_path):
-    """a member the reference does not declare, a protected member reached from outside, a wrong argument count of a C-ABI call and a
-    virtual hidden by a different signature are all caught"""
-    cases = {
-        "no_member": '#include "hipaligner.h"\nvoid f(pwn::HipAligner& a) { a.setOuterIterationz(3); }\n',
-        "protected": '#include "hipaligner.h"\nint f(pwn::HipAligner& a) { return a._outerIterations; }\n',
-        "capi_args": '#include "pwn_hip.h"\nint f(pwn_hip_ctx* c) { return pwn_hip_ctx_set_subbatch(c, 1); }\n',
-        "const": '#include "g2o_frontend/pwn_core/cloud.h"\nvoid f(const pwn::Cloud& c) { c.points().clear(); }\n',
-    }
-    for name, code in cases.items():
-        p = tmp_path / (name + ".cpp")
-        p.write_text(code)
-        rc, diags = _syntax_pass(str(p))
-        mine = [d for d in diags if d[0] == str(p) and d[2] == "error"]
-        assert rc != 0 and mine, (name, diags[:3])
-    ok = tmp_path / "ok.cpp"
-    ok.write_text('#include "hipaligner.h"\n#include "hipdepthimageconverter.h"\nvoid f(pwn::HipAligner& a) { a.setOuterIterations(3); a.align(); }\n')
-    rc, diags = _syntax_pass(str(ok))
-    assert not [d for d in diags if d[0] == str(ok)], diags
 
 
 def test_stand_ins_stay_declarations_only():

@@ -1,15 +1,15 @@
 """The host mirrors (g2o_frontend_amd/api.py, g2o_frontend_amd/host/pwn_hip.hpp) carry the public accessor names of the reference classes they stand
 for, so that configuration and caller code written against pwn_core reads the same here (same names, argument meaning).  The names
-are taken from the `inline` members of the reference headers where they lie under /root/reference (studied as text; skipped on the GPU box)."""
+are those of the `inline` members of the reference headers, extracted from the reference tree into tests/golden/reference_names.json by
+tests/golden/make_reference_names.py."""
+import json
 import os
 import re
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/g2o_frontend/pwn_core"
-TRK = "/root/reference/g2o_frontend/pwn_tracker"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference headers under /root/reference")
+NAMES = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_names.json")))["inline_accessors"]
 
 CLASSES = [("Aligner", "aligner.h"), ("CorrespondenceFinder", "correspondencefinder.h"), ("Linearizer", "linearizer.h"),
            ("DepthImageConverterIntegralImage", "depthimageconverter.h"), ("StatsCalculatorIntegralImage", "statscalculatorintegralimage.h"),
@@ -22,13 +22,7 @@ NOT_MIRRORED = {"StatsCalculatorIntegralImage": {"integralImage", "intervalImage
 
 
 def _inline_names(header):
-    text = open(os.path.join(TRK if header.startswith("pwn_") else REF, header)).read()
-    names = set()
-    for m in re.finditer(r"inline\s+[^;{(]*?[\s&*]([A-Za-z]\w*)\s*\(", text):
-        n = m.group(1)
-        if not n.startswith("_") and n != "operator":
-            names.add(n)
-    return names
+    return set(NAMES[header])
 
 
 @pytest.mark.parametrize("cls,header", CLASSES)
