@@ -11,11 +11,14 @@ on both frames, then Aligner::align (10 outer x 1 inner iterations), then an all
 `python bench.py --gpus N` without a torchrun environment starts the N ranks itself (one process per GPU, before
 anything touches a GPU); under `python -m torch.distributed.run ... bench.py --gpus N` it is one of the N ranks.
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel, live hipEvent timing),
-`cpu_baseline` (the CPU oracle = a port of the reference path, timed on this box's host cores on a bounded sample
-of the same workload) and, at N = 1, the other lines of SURVEY.md §8(d) as extra keys: `chi2_match`, `align_only`,
-`closure_match_batch` (the loop-closure call proper: non-identity guesses + matchClouds scores), `config5_1280x960`,
-`tracker_config2` (BASELINE configs[2]: 200-frame VGA stream through PwnTracker::processFrame).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps, writes `--dump-outputs` if asked and
+prints the contract fields and `config`: nothing else.  With `--full` the line also carries `roofline` (dominant kernel,
+hipEvent timing of a serial profiled pass), `gather` (the assembled records checked against the rank's own and against
+the committed single-GPU digests), `multi_gpu` (N > 1), `cpu_baseline` (the CPU oracle = a port of the reference path,
+timed on this box's host cores on a bounded sample of the same workload) and, at N = 1, the other lines of SURVEY.md
+§8(d) as extra keys: `chi2_match`, `align_only`, `closure_match_batch` (the loop-closure call proper: non-identity
+guesses + matchClouds scores), `config5_1280x960`, `tracker_config2` (BASELINE configs[2]: 200-frame VGA stream through
+PwnTracker::processFrame).  The --no-* options leave out parts of a --full run.
 """
 from __future__ import annotations
 
@@ -48,6 +51,9 @@ def parse(argv=None):
     ap.add_argument("--cols", type=int, default=640)
     ap.add_argument("--sub-frames", type=int, default=int(os.environ.get("PWN_SUB_FRAMES", 64)))
     ap.add_argument("--sub-pairs", type=int, default=int(os.environ.get("PWN_SUB_PAIRS", 64)))
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: CPU baseline, serial profiled pass (roofline), record checks, multi-GPU diagnostics, "
+                         "latency, chi2 gate, bandwidth probe and the extra lines; off: the timed steps and the result line only")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of each leg of the CPU baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency", action="store_true")
@@ -70,7 +76,7 @@ def parse(argv=None):
                     help="strong-scaling mode: shard the SAME list of this many pairs (BASELINE configs[3]: 1024) over the N ranks, instead of --pairs per rank")
     ap.add_argument("--write-records-crc", action="store_true",
                     help="N = 1 only: write profiles/records_crc.json (per-pair CRC32 of the result records) -- multi-GPU runs check their assembled records against it")
-    ap.add_argument("--check-gather", action="store_true", help="kept for scripts: the `gather` object (backend, records, equality with the local records) is always in the line")
+    ap.add_argument("--check-gather", action="store_true", help="kept for scripts: the `gather` object (backend, records, equality with the local records) is in every --full line")
     ap.add_argument("--partition-serial", action="store_true",
                     help="--mode partition without the look-ahead: convert `current`, export, broadcast the buffer's bound, import, match -- one after the other "
                          "(round 5's step; the default converts and broadcasts the next keyframes beside the matches)")
@@ -1594,13 +1600,14 @@ def main():
     rows, cols, P = args.rows, args.cols, args.pairs
     K, conv, alig = conf(rows, cols)
     partition = args.mode == "partition"
-    extras_on = rank == 0 and world == 1 and not args.no_extras and not partition      # the extra lines are single-GPU measurements of the headline workload
+    full = args.full
+    extras_on = full and rank == 0 and world == 1 and not args.no_extras and not partition      # the extra lines are single-GPU measurements of the headline workload
 
     # CPU baseline first (rank 0 at N = 1 only: the other ranks of a multi-GPU run would wait for it), in a child process started
     # before anything touches the GPU: the process that drives the GPU never loads the oracle library
     cpu = None
     traces = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-baseline-only", "--rows", str(rows), "--cols", str(cols),
                               "--cpu-seconds", str(args.cpu_seconds)], capture_output=True, text=True, timeout=900)
         try:
@@ -1668,8 +1675,9 @@ def main():
     else:
         w = BatchWorkload(args, local, rows, cols, P, frames_mm, seeds, use_dist, world)
         w.total = total; w.Pmax = (total + world - 1) // world
-    _progress(rank, world, "workload resident; warm-up + timed region + serial profiled pass")
-    dt_rank, dt_serial = w.run(args.steps, args.warmup, profile=not args.no_profile)
+    profile = full and not args.no_profile
+    _progress(rank, world, "workload resident; warm-up + timed region" + (" + serial profiled pass" if profile else ""))
+    dt_rank, dt_serial = w.run(args.steps, args.warmup, profile=profile)
     _progress(rank, world, f"timed region {dt_rank / max(args.steps, 1) * 1e3:.3f} ms per step on this rank")
     dt = dt_rank
     if use_dist:
@@ -1678,9 +1686,9 @@ def main():
         dt = float(t.item())
     rep = w.report(args.steps, dt, dt_serial, world)
     # what a sub-linear scaling curve would have to be explained with: every rank's own step time, the collectives alone, the cores each rank ran on
-    multi = multi_gpu_diagnostics(w, args, rank, world, dt_rank, dt_serial, pinned) if use_dist else None
+    multi = multi_gpu_diagnostics(w, args, rank, world, dt_rank, dt_serial, pinned) if (use_dist and full) else None
     gather_info = None
-    if rank == 0:
+    if rank == 0 and (full or args.write_records_crc):      # writing the digests is asked for by name: it does not need --full
         allrec = shard.assemble(w.last["gathered"].cpu().numpy(), total)          # every pair of every rank arrived exactly once
         assert allrec.shape[0] == total
         if partition:
@@ -1700,11 +1708,11 @@ def main():
         # that travelled through export / broadcast / import -- so the records any N assembles must equal, bit for bit, those of the one-GPU run
         gather_info["records_vs_single_gpu_run"] = check_records_crc(allrec, rows, cols, write=args.write_records_crc and world == 1 and not use_dist,
                                                                      omega_storage=args.omega_storage, mode=args.mode)
-        if args.dump_outputs:
-            dump_outputs(args.dump_outputs, timed_outputs(w.timed_last, total, seeds))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, timed_outputs(w.timed_last, total, seeds))
 
     extra = {}
-    if not args.no_latency and rank == 0 and world == 1 and not partition:
+    if full and not args.no_latency and rank == 0 and world == 1 and not partition:
         lat = []
         for _ in range(5):
             torch.cuda.synchronize(); a = time.perf_counter()
@@ -1724,7 +1732,7 @@ def main():
     if rank == 0 and traces and not partition:
         extra["chi2_match"] = chi2_match(traces, w.last["res"], w)
     hbm_read = hbm_copy = None
-    if rank == 0 and world == 1:      # (at N > 1 the other ranks would wait in the final barrier meanwhile)
+    if full and rank == 0 and world == 1:      # (at N > 1 the other ranks would wait in the final barrier meanwhile)
         try:      # the bandwidth this box actually delivers, next to the 8 TB/s spec figure (float4 streaming read / copy of 2 GiB)
             hbm_read, hbm_copy = w.ctx.measure_hbm(1 << 31)
         except Exception:
@@ -1781,7 +1789,7 @@ def main():
         except Exception as e:
             extra["tracker_error"] = repr(e)[:300]
 
-    if rank == 0 and rep.get("path_roofline"):
+    if full and rank == 0 and rep.get("path_roofline"):
         # the latency configurations against the same peak (BASELINE configs[1], [2]): algorithmic bytes of ONE pair / ONE tracked frame over the
         # measured latency.  One pair is a chain of ~35 dependent launches of 150-600 workgroups each: it cannot fill the memory system, and the
         # fraction says by how much (missing #5)
@@ -1806,10 +1814,6 @@ def main():
         if "single_pair_roofline_frac" in extra:
             extra["single_pair_roofline_frac_note"] = "algorithmic bytes of one pair (path_roofline.algorithmic_bytes_per_pair) / single_pair_latency_ms / 8 TB/s"
     if rank == 0:
-        rep["roofline"]["measured_hbm_read_GBps"] = hbm_read; rep["roofline"]["measured_hbm_copy_GBps"] = hbm_copy
-        if "chi2_match" in extra:      # the parity gate travels with the number (flat, so that summaries of the line keep it)
-            rep["roofline"]["chi2_max_rel_diff_vs_cpu"] = extra["chi2_match"]["max_rel_diff"]
-            rep["roofline"]["chi2_match_ok"] = extra["chi2_match"]["ok"]
         if partition:
             workload = (f"PwnCloser::processPartition: one {cols}x{rows} `current` frame (converted per step on rank 0, its cloud broadcast to every GPU) matched "
                         f"against {P} cached keyframe clouds per GPU (matchClouds: Aligner::align {alig['outer_iterations']}x{alig['inner_iterations']} GN iterations "
@@ -1831,27 +1835,36 @@ def main():
                        "rehearsal": (f"{n_seen} rank processes on ONE device, collectives through gloo: a correctness rehearsal of the multi-rank step, "
                                      f"not a scaling measurement") if args.one_device else None,
                        "cpus_of_rank0": (len(pinned) if pinned else None)},
-            "roofline": rep["roofline"],
-            "cpu_baseline": cpu,
-            "path_roofline": rep.get("path_roofline"),
-            "stage_ms_per_step": rep["stage_ms_per_step"],
-            "stage_launches_per_step": rep.get("stage_launches_per_step"),
-            "counters_mean": rep["counters_mean"],
-            "gather": gather_info,
-            "multi_gpu": multi,
-            "gather_queueing": ({"from_inside_the_call": bool(getattr(w, "inside", False)),
-                                 "host_ms_per_step_inside_the_callback": getattr(w, "cb_s", 0.0) / max(getattr(w, "k", 1), 1) * 1e3,
-                                 "host_ms_per_step_in_the_library_calls": getattr(w, "call_s", 0.0) / max(getattr(w, "k", 1), 1) * 1e3} if (use_dist and not partition) else None),
+            "full": full,
         }
-        if partition:
-            out["partition"] = {"accepted_by_closer_thresholds_rank0": rep["accepted_by_closer_thresholds_rank0"], "keyframes_rank0": P,
-                                "max_translation_error_m_rank0": rep["max_translation_error_m_rank0"],
-                                "flat_cloud_bytes": int(w.flat_bytes) if use_dist else None,
-                                "broadcast_bytes_per_step": (int(w.flat_bytes) if w.pipeline else int(w.flat[0].numel())) if use_dist else None,
-                                "flat_buffer_bound_bytes": int(w.flat[0].numel()) if w.flat[0] is not None else None,
-                                "replica_roundtrip_on_rank0": bool(w.roundtrip), "pipelined": bool(w.pipeline),
-                                "pipeline": rep.get("pipeline")}
-        out.update(extra)
+        if gather_info is not None:
+            out["gather"] = gather_info
+        if full:
+            rep["roofline"]["measured_hbm_read_GBps"] = hbm_read; rep["roofline"]["measured_hbm_copy_GBps"] = hbm_copy
+            if "chi2_match" in extra:      # the parity gate travels with the number (flat, so that summaries of the line keep it)
+                rep["roofline"]["chi2_max_rel_diff_vs_cpu"] = extra["chi2_match"]["max_rel_diff"]
+                rep["roofline"]["chi2_match_ok"] = extra["chi2_match"]["ok"]
+            out.update({
+                "roofline": rep["roofline"],
+                "cpu_baseline": cpu,
+                "path_roofline": rep.get("path_roofline"),
+                "stage_ms_per_step": rep["stage_ms_per_step"],
+                "stage_launches_per_step": rep.get("stage_launches_per_step"),
+                "counters_mean": rep["counters_mean"],
+                "multi_gpu": multi,
+                "gather_queueing": ({"from_inside_the_call": bool(getattr(w, "inside", False)),
+                                     "host_ms_per_step_inside_the_callback": getattr(w, "cb_s", 0.0) / max(getattr(w, "k", 1), 1) * 1e3,
+                                     "host_ms_per_step_in_the_library_calls": getattr(w, "call_s", 0.0) / max(getattr(w, "k", 1), 1) * 1e3} if (use_dist and not partition) else None),
+            })
+            if partition:
+                out["partition"] = {"accepted_by_closer_thresholds_rank0": rep["accepted_by_closer_thresholds_rank0"], "keyframes_rank0": P,
+                                    "max_translation_error_m_rank0": rep["max_translation_error_m_rank0"],
+                                    "flat_cloud_bytes": int(w.flat_bytes) if use_dist else None,
+                                    "broadcast_bytes_per_step": (int(w.flat_bytes) if w.pipeline else int(w.flat[0].numel())) if use_dist else None,
+                                    "flat_buffer_bound_bytes": int(w.flat[0].numel()) if w.flat[0] is not None else None,
+                                    "replica_roundtrip_on_rank0": bool(w.roundtrip), "pipelined": bool(w.pipeline),
+                                    "pipeline": rep.get("pipeline")}
+            out.update(extra)
         print(json.dumps(out))
     if use_dist:
         _progress(rank, world, "done; final barrier")

@@ -218,6 +218,13 @@ def test_host_cpu_info_names_what_cores_means():
     assert "cgroup_cpu_quota" in info
 
 
+def test_a_plain_run_is_the_default_and_full_is_asked_for():
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse([]).full is False
+    assert bench.parse(["--full", "--no-cpu-baseline"]).full is True
+
+
 def test_dump_outputs_writes_the_timed_steps_results(tmp_path):
     """--dump-outputs: every result field but the host timing, the pair ids and the records in global pair order, float32 / float64 only;
     over the byte budget every array keeps the same seeded rows"""
@@ -265,3 +272,18 @@ def test_dump_outputs_of_two_runs_are_the_same_and_are_the_records(tmp_path):
     assert d["records"].shape == (6, 64) and np.array_equal(d["records"][:, 19], np.arange(6))
     assert np.array_equal(d["records"][:, :16], d["T"]) and np.array_equal(d["records"][:, 16], d["error"])
     assert np.array_equal(d["records"][:, 17], d["inliers"])
+
+
+@pytest.mark.gpu
+def test_a_plain_run_prints_the_headline_only():
+    """without --full the run sets up, warms up, times its steps and prints the contract fields and `config`: no CPU baseline, no serial
+    profiled pass, no record checks, no extra lines"""
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--pairs", "6", "--steps", "2", "--warmup", "1", "--render-workers", "1"],
+                         capture_output=True, text=True, timeout=600, env=_clean_env())
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert set(line) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                         "data", "config", "full"}, sorted(line)
+    assert line["full"] is False and line["unit"] == "alignments/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["config"]["total_pairs"] == 6
+    assert line["value"] > 0 and abs(line["value"] * line["ms_per_step"] * 1e-3 - 6) < 1e-6      # pairs per step / seconds per step

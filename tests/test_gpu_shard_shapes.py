@@ -119,7 +119,7 @@ def test_result_gather_through_rccl_world_size_1():
     env = dict(os.environ, PWN_BENCH_FORCE_DIST="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--pairs", "6", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-latency", "--no-extras", "--render-workers", "1", "--check-gather"],
+                          "--full", "--no-cpu-baseline", "--no-latency", "--no-extras", "--render-workers", "1", "--check-gather"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -139,7 +139,7 @@ def test_strong_mode_at_configs3_size_on_one_gpu_matches_the_committed_record_di
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--total-pairs", "1024", "--steps", "1", "--warmup", "0",
-                          "--no-cpu-baseline", "--no-latency", "--no-extras", "--no-profile"], env=env, capture_output=True, text=True, timeout=1100)
+                          "--full", "--no-cpu-baseline", "--no-latency", "--no-extras", "--no-profile"], env=env, capture_output=True, text=True, timeout=1100)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     g = line["gather"]["records_vs_single_gpu_run"]

@@ -242,7 +242,7 @@ def test_bench_partition_mode_original_and_replica_give_the_same_records(tmp_pat
         e = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PWN_BENCH_FORCE_DIST")}
         e.update(env)
         out = subprocess.run([sys.executable, str(driver), "--gpus", "1", "--mode", "partition", "--pairs", "40", "--steps", "2", "--warmup", "1",
-                              "--no-cpu-baseline", "--render-workers", "1"] + args, env=e, capture_output=True, text=True, timeout=900)
+                              "--full", "--no-cpu-baseline", "--render-workers", "1"] + args, env=e, capture_output=True, text=True, timeout=900)
         assert out.returncode == 0, out.stderr[-2000:]
         return json.loads(out.stdout.strip().splitlines()[-1])
 

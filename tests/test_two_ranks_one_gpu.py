@@ -19,7 +19,7 @@ def _run(extra, timeout=900):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PWN_BENCH_FORCE_DIST")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--one-device", "--pairs", "64", "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-latency", "--no-extras"] + extra, env=env, capture_output=True, text=True, timeout=timeout)
+                          "--full", "--no-cpu-baseline", "--no-latency", "--no-extras"] + extra, env=env, capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, out.stderr[-3000:]
     return json.loads(out.stdout.strip().splitlines()[-1]), out.stderr
 
@@ -66,7 +66,7 @@ def test_partition_mode_three_ranks_rotate_the_look_ahead():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PWN_BENCH_FORCE_DIST")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--one-device", "--mode", "partition", "--pairs", "32", "--steps", "5", "--warmup", "2",
-                          "--no-cpu-baseline", "--no-latency", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline", "--no-latency", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     c = line["gather"]["records_vs_single_gpu_run"]

@@ -4,7 +4,7 @@
 set -u
 OUT=${1:-gpurun_out/pmc}; shift || true
 # no child processes under rocprofv3 (its preloaded library has initialised the GPU): no CPU baseline child, frames rendered in-process
-ARGS=${@:---pairs 128 --steps 1 --warmup 1 --no-cpu-baseline --no-latency --no-profile --no-extras --render-workers 1 --streams 1}
+ARGS=${@:---full --pairs 128 --steps 1 --warmup 1 --no-cpu-baseline --no-latency --no-profile --no-extras --render-workers 1 --streams 1}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
 run() { name=$1; shift; echo "pass $name"; timeout -k 5 240 rocprofv3 --pmc "$@" --output-format csv -d "$OUT/$name" -- python3 bench.py $ARGS > "$OUT/$name.json" 2> "$OUT/$name.err" || { echo "pass $name failed or timed out"; exit 1; }; }

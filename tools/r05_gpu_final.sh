@@ -6,8 +6,8 @@ echo "== full GPU suite"; date
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/gpu_suite.txt 2>&1; echo "rc $?"; tail -4 $O/gpu_suite.txt
 echo "== smoke"; timeout -k 10 200 python __graft_entry__.py --smoke 2>&1 | tail -2
 echo "== bench lines"; date
-timeout -k 10 500 python bench.py --steps 20 --warmup 3 > $O/bench_default.json 2> $O/bench_default.err; echo "rc $?"
-timeout -k 10 300 python bench.py --mode partition --steps 20 --warmup 3 > $O/bench_partition.json 2> $O/bench_partition.err; echo "rc $?"
+timeout -k 10 500 python bench.py --full --steps 20 --warmup 3 > $O/bench_default.json 2> $O/bench_default.err; echo "rc $?"
+timeout -k 10 300 python bench.py --full --mode partition --steps 20 --warmup 3 > $O/bench_partition.json 2> $O/bench_partition.err; echo "rc $?"
 python - <<'PY'
 import json
 for f in ("bench_default", "bench_partition"):

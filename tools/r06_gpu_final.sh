@@ -7,11 +7,11 @@ echo "== full GPU suite"; date
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/gpu_suite.txt 2>&1; echo "rc $?"; tail -4 $O/gpu_suite.txt
 echo "== smoke"; timeout -k 10 200 python __graft_entry__.py --smoke 2>&1 | tail -2
 echo "== bench lines"; date
-timeout -k 10 500 python bench.py --steps 20 --warmup 3 > $O/bench_default.json 2> $O/bench_default.err; echo "rc $?"
-timeout -k 10 300 python bench.py --mode partition --steps 30 --warmup 3 --no-cpu-baseline > $O/bench_partition.json 2> $O/bench_partition.err; echo "rc $?"
-PWN_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29541 timeout -k 10 300 python bench.py --mode partition --steps 30 --warmup 3 --no-cpu-baseline > $O/bench_partition_rccl.json 2> $O/bench_partition_rccl.err; echo "rc $?"
-PWN_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29542 timeout -k 10 300 python bench.py --mode partition --partition-serial --steps 30 --warmup 3 --no-cpu-baseline > $O/bench_partition_rccl_serial.json 2> $O/bench_partition_rccl_serial.err; echo "rc $?"
-PWN_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29543 timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/bench_default_rccl.json 2> $O/bench_default_rccl.err; echo "rc $?"
+timeout -k 10 500 python bench.py --full --steps 20 --warmup 3 > $O/bench_default.json 2> $O/bench_default.err; echo "rc $?"
+timeout -k 10 300 python bench.py --full --mode partition --steps 30 --warmup 3 --no-cpu-baseline > $O/bench_partition.json 2> $O/bench_partition.err; echo "rc $?"
+PWN_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29541 timeout -k 10 300 python bench.py --full --mode partition --steps 30 --warmup 3 --no-cpu-baseline > $O/bench_partition_rccl.json 2> $O/bench_partition_rccl.err; echo "rc $?"
+PWN_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29542 timeout -k 10 300 python bench.py --full --mode partition --partition-serial --steps 30 --warmup 3 --no-cpu-baseline > $O/bench_partition_rccl_serial.json 2> $O/bench_partition_rccl_serial.err; echo "rc $?"
+PWN_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29543 timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/bench_default_rccl.json 2> $O/bench_default_rccl.err; echo "rc $?"
 python - <<'PY'
 import json
 for f in ("bench_default", "bench_default_rccl", "bench_partition", "bench_partition_rccl", "bench_partition_rccl_serial"):
