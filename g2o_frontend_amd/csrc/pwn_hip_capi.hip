@@ -1050,6 +1050,80 @@ int pwn_hip_debug_projection_fallbacks(pwn_hip_ctx* ctx, int* calls) {
   *calls = ctx->projection_fallbacks;
   return PWN_HIP_OK;
 }
+// Test hook: the converter's stats pass (k_stats, launched as launch_convert launches it) on caller-supplied integral planes, index and
+// interval images -- windows that no depth frame produces.  The clouds hold the points the index images refer to (pwn_hip_cloud_upload).
+int pwn_hip_debug_stats_from_integral(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, int rows, int cols, int nframes, const float* integral,
+                                      const int* index_image, const int* interval_image, pwn_hip_cloud* const* clouds, int keep_stats) {
+  if (!ctx || !p || !integral || !index_image || !interval_image || !clouds) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (nframes < 1 || nframes > ctx->max_batch) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "nframes must be 1..max_batch");
+  if (int rc = check_image(ctx, rows, cols)) return rc;
+  if (int rc = absorb_copies(ctx)) return rc;
+  if (int rc = ensure_desc(ctx, nframes)) return rc;
+  const size_t N = (size_t)rows * cols;
+  ConvertParams cp = make_convert_params(ctx, p, nullptr, rows, cols, keep_stats);
+  cp.lean = 0;
+  for (int i = 0; i < nframes; ++i) {
+    pwn_hip_cloud* c = clouds[i];
+    if (!c) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null cloud");
+    if (i == 0) cp.omSym = c->d.omSym;
+    else if (c->d.omSym != cp.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds of one call must share one omega storage (exact9 / sym6)");
+    const int* idx = index_image + (size_t)i * N;
+    for (size_t k = 0; k < N; ++k)
+      if (idx[k] >= c->n_host) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "index image refers to a point the cloud does not hold");
+  }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  for (int i = 0; i < nframes; ++i) {
+    pwn_hip_cloud* c = clouds[i];
+    cloud_changes(ctx, c);
+    if (keep_stats) { if (int rc = ensure_stats(ctx, c)) return rc; }
+    c->has_stats = keep_stats != 0;
+    c->n_gauss = 0;
+    c->idx_valid = false;
+    if (c->d.OmN) { (void)hipFree(c->d.OmN); c->d.OmN = nullptr; }
+    make_omega_n_classes(p, c->d);
+    fill_frame(ctx, i, i, nullptr, c->d, rows);
+    const FrameDesc& f = ctx->frames_host[i];
+    HIPCHK(ctx, hipMemcpyAsync(f.index, index_image + (size_t)i * N, N * sizeof(int), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+    HIPCHK(ctx, hipMemcpyAsync(f.interval, interval_image + (size_t)i * N, N * sizeof(int), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+    HIPCHK(ctx, hipMemcpyAsync(f.integral, integral + (size_t)i * N * kIntegralChannels, N * kIntegralChannels * sizeof(float), hipMemcpyHostToDevice,
+                               ctx->stream), PWN_HIP_ERR_COPY);
+  }
+  HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev, ctx->frames_host, sizeof(FrameDesc) * nframes, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+  const unsigned perFrame = (unsigned)cp.rows * (unsigned)((cp.cols + 255) / 256);
+  const unsigned nblk = (nframes >= 8 ? 8u * (unsigned)((nframes + 7) / 8) : (unsigned)nframes) * perFrame;      // launch_convert's grid
+  hipLaunchKernelGGL(k_stats, dim3(nblk), dim3(256), 0, ctx->stream, ctx->frames_dev, cp, nframes);
+  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  return PWN_HIP_OK;
+}
+__global__ void __launch_bounds__(256) k_debug_trig(int n, const float* __restrict__ y, const float* __restrict__ x, float* __restrict__ theta,
+                                                    float* __restrict__ c, float* __restrict__ s) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  PWN_EIG3_TRIG(y[i], x[i], t, ct, st);      // the text eig3_direct expands
+  theta[i] = t; c[i] = ct; s[i] = st;
+}
+// Test hook: PWN_EIG3_TRIG (the eigensolver's three trig values, as eig3_direct computes them) on the device for n host arguments
+int pwn_hip_debug_trig_eval(pwn_hip_ctx* ctx, int n, const float* y, const float* x, float* theta, float* cos_theta, float* sin_theta) {
+  if (!ctx || n < 0 || (n > 0 && (!y || !x || !theta || !cos_theta || !sin_theta))) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (n == 0) return PWN_HIP_OK;
+  float* d = nullptr;
+  const size_t bytes = (size_t)n * sizeof(float);
+  HIPCHK(ctx, hipMalloc((void**)&d, 5 * bytes), PWN_HIP_ERR_ALLOCATION);
+  hipError_t e = hipMemcpy(d, y, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + n, x, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_debug_trig, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, n, d, d + n, d + 2 * (size_t)n, d + 3 * (size_t)n, d + 4 * (size_t)n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(theta, d + 2 * (size_t)n, bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(cos_theta, d + 3 * (size_t)n, bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(sin_theta, d + 4 * (size_t)n, bytes, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess) return fail(ctx, PWN_HIP_ERR_LAUNCH, std::string("trig eval: ") + hipGetErrorString(e));
+  return PWN_HIP_OK;
+}
 int pwn_hip_set_profiling(pwn_hip_ctx* ctx, int enabled) {
   if (!ctx) return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, "null ctx");
   ctx->profiling = enabled != 0;

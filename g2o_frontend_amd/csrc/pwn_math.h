@@ -244,6 +244,16 @@ PWN_TRIG_HD void pwn_sincos_small(double x, double& s, double& c) {      // 0 <=
   s = x * ps; c = pc;
 }
 
+// The three trig calls of eig3_direct for y = sqrt(q), x = half_b: declares theta = atan2(y, x) / 3, cos_theta, sin_theta, each rounded to
+// float.  A macro, so that eig3_direct and the test kernel of pwn_hip_debug_trig_eval expand the very same text (a function, even a
+// force-inlined one, reorders k_stats' instruction schedule).
+#define PWN_EIG3_TRIG(y, x, theta, cos_theta, sin_theta)                                    \
+  const float theta = (float)pwn_atan2_pos((double)(y), (double)(x)) * (1.0f / 3.0f);     \
+  double theta##_sd, theta##_cd;                                                           \
+  pwn_sincos_small((double)theta, theta##_sd, theta##_cd);                                 \
+  const float cos_theta = (float)theta##_cd;                                               \
+  const float sin_theta = (float)theta##_sd
+
 // ---- SelfAdjointEigenSolver<Matrix3f>::computeDirect(A, ComputeEigenvectors) -------------------------
 // (closed-form roots of the characteristic polynomial on the shifted+scaled matrix, eigenvectors by
 // kernel extraction with cross products).  Reads the lower triangle.  evals ascending.
@@ -297,11 +307,7 @@ PWN_HD void eig3_direct(float a00, float a10, float a20, float a11, float a21, f
     const float rho = sqrtf(a_over_3);
     // The three trig calls: fixed double-precision algorithms rounded once to float (see pwn_atan2_pos): the same bits on the host and on
     // the device, a third of the instructions of the ocml double routines (this kernel is VALU-bound).
-    const float theta = (float)pwn_atan2_pos((double)sqrtf(q), (double)half_b) * s_inv3;
-    double sd, cd;
-    pwn_sincos_small((double)theta, sd, cd);
-    const float cos_theta = (float)cd;
-    const float sin_theta = (float)sd;
+    PWN_EIG3_TRIG(sqrtf(q), half_b, theta, cos_theta, sin_theta);
     e[0] = c2_over_3 - rho * (cos_theta + s_sqrt3 * sin_theta);
     e[1] = c2_over_3 - rho * (cos_theta - s_sqrt3 * sin_theta);
     e[2] = c2_over_3 + 2.0f * rho * cos_theta;

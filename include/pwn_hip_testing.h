@@ -34,6 +34,17 @@ int pwn_hip_debug_set_index_shortcut(pwn_hip_ctx* ctx, int enabled);
 int pwn_hip_debug_set_settle_guard(pwn_hip_ctx* ctx, int rounds);
 int pwn_hip_debug_projection_fallbacks(pwn_hip_ctx* ctx, int* calls);
 
+/* The converter's stats pass (the kernel DepthImageConverter::compute runs after its integral image) on windows the caller supplies:
+ * integral = nframes x [10][rows][cols] planes (x, y, z, n, xx, xy, xz, yy, yz, zz), index_image / interval_image = nframes x [rows][cols];
+ * clouds[i] holds the points (pwn_hip_cloud_upload) index image i refers to.  Normals, curvature, information matrices (and stats with
+ * keep_stats) are written as a convert call writes them; read them back with pwn_hip_cloud_download / pwn_hip_cloud_download_stats.
+ * 1 <= nframes <= max_batch; from 8 frames on the kernel takes its XCD-aware placement, as in a convert call. */
+int pwn_hip_debug_stats_from_integral(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, int rows, int cols, int nframes, const float* integral,
+                                      const int* index_image, const int* interval_image, pwn_hip_cloud* const* clouds, int keep_stats);
+/* The eigensolver's three trig values (theta = atan2(y, x) / 3, cos theta, sin theta as floats) evaluated on the device for n host arguments
+ * y = sqrt(q) >= 0, x = half_b: the lines of the stats kernel's eigensolver that compute them (one macro, expanded in both places). */
+int pwn_hip_debug_trig_eval(pwn_hip_ctx* ctx, int n, const float* y, const float* x, float* theta, float* cos_theta, float* sin_theta);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,7 @@ def lib():
         L.orc_unproject.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.orc_project_intervals.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.orc_integral_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.orc_stats_from_integral.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.orc_convert.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_project.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                   C.c_void_p, C.c_void_p]
@@ -340,6 +341,19 @@ def integral_image(index_image, points):
     out = np.empty((10, rows, cols), np.float32)
     lib().orc_integral_image(_p(idx), _p(pts), rows, cols, _p(out))
     return out
+
+
+def stats_from_integral(p: ConverterParams, planes, index_image, interval_image, points) -> "Cloud":
+    """The converter after its integral image (StatsCalculatorIntegralImage::compute, the information matrices, the sensor offset) on
+    given planes [10][rows][cols], index / interval images and the points (n x 4) the index image refers to."""
+    idx = np.ascontiguousarray(index_image, np.int32); itv = np.ascontiguousarray(interval_image, np.int32); pl = _f32(planes)
+    rows, cols = idx.shape
+    assert itv.shape == idx.shape and pl.shape == (10, rows, cols)
+    pts = _f32(points); n = len(pts)
+    z4, z16 = np.zeros((n, 4), np.float32), np.zeros((n, 16), np.float32)
+    c = Cloud.from_arrays(pts, z4, np.zeros(n, np.float32), z16, z16)
+    lib().orc_stats_from_integral(C.byref(p), _p(pl), _p(idx), _p(itv), rows, cols, c.h)
+    return c
 
 
 def convert(p: ConverterParams, depth):

@@ -584,14 +584,12 @@ Projector make_projector(const float K[9], const float T[16], float minD, float 
   Projector pr; std::memcpy(pr.K.m, K, sizeof(pr.K.m)); pr.T = m4_load(T); pr.minD = minD; pr.maxD = maxD; pr.update(); return pr;
 }
 
-/* statscalculatorintegralimage.cpp:14-82 */
-void stats_compute(const orc_converter_params* P, const int* index, const int* interval, int rows, int cols,
-                   const std::vector<V4>& points, std::vector<V4>& normals, std::vector<Stats>& stats) {
+/* statscalculatorintegralimage.cpp:33-80: the per-pixel loop over a given integral image I */
+void stats_from_integral(const orc_converter_params* P, const int* index, const int* interval, int rows, int cols, const std::vector<Acc>& I,
+                         const std::vector<V4>& points, std::vector<V4>& normals, std::vector<Stats>& stats) {
   const size_t M = points.size();
   normals.assign(M, V4{ {0,0,0,0} });
   stats.assign(M, Stats());
-  std::vector<Acc> I;
-  integral_image(index, points.data(), rows, cols, I);
 #pragma omp parallel for schedule(dynamic, 4)
   for (int r = 0; r < rows; ++r)
     for (int c = 0; c < cols; ++c) {
@@ -627,6 +625,13 @@ void stats_compute(const orc_converter_params* P, const int* index, const int* i
       } else { nrm = V4{ {0,0,0,0} }; }
       normals[idx] = nrm;
     }
+}
+/* statscalculatorintegralimage.cpp:14-82 */
+void stats_compute(const orc_converter_params* P, const int* index, const int* interval, int rows, int cols,
+                   const std::vector<V4>& points, std::vector<V4>& normals, std::vector<Stats>& stats) {
+  std::vector<Acc> I;
+  integral_image(index, points.data(), rows, cols, I);
+  stats_from_integral(P, index, interval, rows, cols, I, points, normals, stats);
 }
 
 inline M4 diag4(const float d[3]) { M4 r = m4_zero(); r(0,0) = d[0]; r(1,1) = d[1]; r(2,2) = d[2]; return r; }
@@ -1012,6 +1017,18 @@ void orc_convert(const orc_converter_params* p, const float* depth, int rows, in
   cloud_transform_in_place(cloud, p->sensor_offset);
   if (index_image) std::memcpy(index_image, idx.data(), N * sizeof(int));
   if (interval_image) std::memcpy(interval_image, itv.data(), N * sizeof(int));
+}
+
+void orc_stats_from_integral(const orc_converter_params* p, const float* planes, const int* index_image, const int* interval_image,
+                             int rows, int cols, orc_cloud* cloud) {
+  /* the tail of orc_convert from the integral image on: stats, information matrices, sensor offset -- in that order */
+  const size_t N = (size_t)rows * cols;
+  std::vector<Acc> I(N);
+  for (int k = 0; k < CH; ++k) for (size_t i = 0; i < N; ++i) I[i].c[k] = planes[k * N + i];
+  cloud->gaussians.clear();
+  stats_from_integral(p, index_image, interval_image, rows, cols, I, cloud->points, cloud->normals, cloud->stats);
+  info_compute(p, cloud->stats, cloud->normals, cloud->omegaP, cloud->omegaN);
+  cloud_transform_in_place(cloud, p->sensor_offset);
 }
 
 void orc_project(const float K[9], const float T[16], float min_distance, float max_distance, int rows, int cols,

@@ -117,6 +117,12 @@ void orc_integral_image(const int* index_image, const float* points, int rows, i
 void orc_convert(const orc_converter_params* p, const float* depth, int rows, int cols,
                  orc_cloud* cloud, int* index_image, int* interval_image);
 
+/* the steps of orc_convert after the integral image, on caller-supplied planes [10][rows][cols] (orc_integral_image's layout), index and
+ * interval images: StatsCalculatorIntegralImage::compute, the information matrices, the sensor offset.  The cloud's points (orc_cloud_set)
+ * are the ones the index image refers to; its normals, stats and information matrices are replaced. */
+void orc_stats_from_integral(const orc_converter_params* p, const float* planes, const int* index_image, const int* interval_image,
+                             int rows, int cols, orc_cloud* cloud);
+
 /* pinholepointprojector.cpp:33-66 with transform T (projector pose) */
 void orc_project(const float K[9], const float T[16], float min_distance, float max_distance,
                  int rows, int cols, const float* points, int n, int* index_image, float* depth_image);
