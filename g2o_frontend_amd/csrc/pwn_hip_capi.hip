@@ -101,7 +101,6 @@ struct pwn_hip_ctx {
   int spin_limit = kSpinLimit; int dbg_withhold = -1;        // pwn_hip_debug_withhold_carry (test hook)
   int dbg_withhold_once = 0;                                 // the hook switches itself off after the first launch that timed out
   int convert_retries = 0;                                   // conversions repeated after a hand-over time-out (pwn_hip_debug_convert_retries)
-  bool in_step_retry = false;
   // align workspaces (per slot)
   unsigned long long* zref_ws = nullptr;        // 64-bit z-buffer of the stand-alone projection and of Merger::merge (one image)
   unsigned* z32ref_ws = nullptr; unsigned* z32cur_ws = nullptr;      // the aligner's 32-bit z-buffers (tag | index), one image per slot
@@ -455,14 +454,30 @@ int ensure_zdepth(pwn_hip_ctx* ctx) {
   if (!ctx->zdepth_ws) HIPCHK(ctx, hipMalloc((void**)&ctx->zdepth_ws, (size_t)ctx->max_batch * ctx->N * sizeof(unsigned)), PWN_HIP_ERR_ALLOCATION);
   return PWN_HIP_OK;
 }
-// after the wait that ends an alignment call: did a projection of it give up on a pixel?  (the word is host memory the kernels store to)
-bool take_align_fault(pwn_hip_ctx* ctx) {
+// An alignment attempt starts here and ends in take_align_fault; a robust one (the repeat) runs every projection with the two-pass kernels
+int start_align_attempt(pwn_hip_ctx* ctx, bool robust) {
+  ctx->last_align_fault = 0;
+  return robust ? ensure_zdepth(ctx) : PWN_HIP_OK;
+}
+const char* const kSettleMessage = "projection: a pixel's z-buffer settle loop gave up (too many points of one cloud in one pixel)";
+// after the attempt's final wait: did a projection of it give up on a pixel?  (the word is host memory the kernels store to)
+int take_align_fault(pwn_hip_ctx* ctx) {
   const bool f = ctx->align_fault_host && *(volatile int*)ctx->align_fault_host != 0;
   if (f) *(volatile int*)ctx->align_fault_host = 0;
   ctx->last_align_fault = f ? 1 : 0;
-  return f;
+  return f ? fail(ctx, PWN_HIP_ERR_LAUNCH, kSettleMessage) : PWN_HIP_OK;
 }
-const char* const kSettleMessage = "projection: a pixel's z-buffer settle loop gave up (too many points of one cloud in one pixel)";
+// attempt(false); if it failed with the given fault (a projection's settle loop gave up, or a converter strip's hand-over timed out), the
+// repeat is counted and attempt(true) runs.  Once only: a second fault is reported.
+enum RepeatOn { kSettleFault, kHandoverTimeout };
+template <typename Attempt>
+int repeat_once(pwn_hip_ctx* ctx, RepeatOn on, Attempt attempt) {
+  const int rc = attempt(false);
+  if (rc != PWN_HIP_ERR_LAUNCH || !ctx || (on == kSettleFault ? ctx->last_align_fault : ctx->last_convert_fault) != 1) return rc;
+  if (on == kSettleFault) ++ctx->projection_fallbacks;
+  else ++ctx->convert_retries;
+  return attempt(true);
+}
 int align_nblocks(int N) { return (N + kAlignBlock * kPixPerThread - 1) / (kAlignBlock * kPixPerThread); }
 
 // descriptor / state arrays for a batch of n items
@@ -688,58 +703,55 @@ int convert_finish(pwn_hip_ctx* ctx, const ConvertJob& job, pwn_hip_cloud* const
 
 template <typename SRC>
 int convert_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n,
-                       int rows, int cols, pwn_hip_cloud* const* clouds, int keep_stats, bool want_interval = false, bool retried = false) {
+                       int rows, int cols, pwn_hip_cloud* const* clouds, int keep_stats, bool want_interval = false) {
   if (!ctx || !p || !frames || !clouds || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (int rc = check_image(ctx, rows, cols)) return rc;
   if (int rc = absorb_copies(ctx)) return rc;
-  ctx->stages.clear();
-  const StreamPlan plan = make_plan(ctx, ctx->sub_frames, n);
-  const int sub = plan.sub;
-  std::vector<int> slot((size_t)std::max(n, 0));
-  for (int i = 0; i < n; ++i) slot[i] = plan.slot0(i / sub) + i % sub;
-  const bool direct = n > 0 && n < kSinglePassMinFrames && n <= sub;
-  ConvertJob job;
-  if (int rc = convert_prepare<SRC>(ctx, p, frames, depth_scale, n, rows, cols, clouds, keep_stats, want_interval, slot, direct, job)) return rc;
-  if (int rc = plan_fork(ctx, plan)) return rc;
-  // Host frames travel on the copy stream, ahead of the kernels: the frames of sub-batch k are copied while sub-batches k-1, k-2 ... are
-  // being converted (with the copies on the sub-batch's own stream the two streams copy at the same time and then compute at the same
-  // time: 7.5 ms per 256 VGA frames against 5).  copied[k] orders convert k after its copies; converted[k] orders the copies into a
-  // staging block after the kernels that read its previous content.
-  const int nsub = (n + sub - 1) / sub;
-  const bool ahead = job.host_input && ctx->copy_stream && plan.dual();
-  if (ahead) {
-    while ((int)ctx->sync_events.size() < 2 * nsub) {
-      hipEvent_t e = nullptr;
-      HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming), PWN_HIP_ERR_ALLOCATION);
-      ctx->sync_events.push_back(e);
-    }
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->fork_ev, 0), PWN_HIP_ERR_LAUNCH);      // after everything queued before this call
-  }
-  for (int base = 0, k = 0; base < n; base += sub, ++k) {
-    const int m = std::min(sub, n - base);
-    hipStream_t st = plan.stream(k);
-    if (job.host_input) {
-      hipStream_t cs = ahead ? ctx->copy_stream : st;
-      if (ahead && k >= plan.ns) HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->sync_events[2 * (k - plan.ns) + 1], 0), PWN_HIP_ERR_LAUNCH);
-      if (int rc = convert_stage_frames(ctx, job, base, m, cs)) return rc;
-      if (ahead) {
-        HIPCHK(ctx, hipEventRecord(ctx->sync_events[2 * k], cs), PWN_HIP_ERR_LAUNCH);
-        HIPCHK(ctx, hipStreamWaitEvent(st, ctx->sync_events[2 * k], 0), PWN_HIP_ERR_LAUNCH);
+  // A strip waited for its left neighbour longer than the poll bound (~1 s): the neighbour's workgroup was not dispatched in time -- a device
+  // shared with another process's long kernels -- and the planes of this call are invalid.  Nothing is left behind (epoch-tagged words), so
+  // the call is simply made again, once; a second time-out is reported.
+  return repeat_once(ctx, kHandoverTimeout, [&](bool) -> int {
+    ctx->stages.clear();
+    const StreamPlan plan = make_plan(ctx, ctx->sub_frames, n);
+    const int sub = plan.sub;
+    std::vector<int> slot((size_t)std::max(n, 0));
+    for (int i = 0; i < n; ++i) slot[i] = plan.slot0(i / sub) + i % sub;
+    const bool direct = n > 0 && n < kSinglePassMinFrames && n <= sub;
+    ConvertJob job;
+    if (int rc = convert_prepare<SRC>(ctx, p, frames, depth_scale, n, rows, cols, clouds, keep_stats, want_interval, slot, direct, job)) return rc;
+    if (int rc = plan_fork(ctx, plan)) return rc;
+    // Host frames travel on the copy stream, ahead of the kernels: the frames of sub-batch k are copied while sub-batches k-1, k-2 ... are
+    // being converted (with the copies on the sub-batch's own stream the two streams copy at the same time and then compute at the same
+    // time: 7.5 ms per 256 VGA frames against 5).  copied[k] orders convert k after its copies; converted[k] orders the copies into a
+    // staging block after the kernels that read its previous content.
+    const int nsub = (n + sub - 1) / sub;
+    const bool ahead = job.host_input && ctx->copy_stream && plan.dual();
+    if (ahead) {
+      while ((int)ctx->sync_events.size() < 2 * nsub) {
+        hipEvent_t e = nullptr;
+        HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming), PWN_HIP_ERR_ALLOCATION);
+        ctx->sync_events.push_back(e);
       }
+      HIPCHK(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->fork_ev, 0), PWN_HIP_ERR_LAUNCH);      // after everything queued before this call
     }
-    if (int rc = launch_convert(ctx, job.cp, base, m, st, direct ? ctx->counts_host + n : nullptr)) return rc;
-    if (ahead) HIPCHK(ctx, hipEventRecord(ctx->sync_events[2 * k + 1], st), PWN_HIP_ERR_LAUNCH);
-  }
-  if (int rc = plan_join(ctx, plan)) return rc;
-  const int rc = convert_finish(ctx, job, clouds);
-  if (rc != PWN_HIP_OK && ctx->last_convert_fault == 1 && !retried) {
-    // A strip waited for its left neighbour longer than the poll bound (~1 s): the neighbour's workgroup was not dispatched in time -- a device
-    // shared with another process's long kernels -- and the planes of this call are invalid.  Nothing is left behind (epoch-tagged words), so
-    // the call is simply made again, once; a second time-out is reported.
-    ++ctx->convert_retries;
-    return convert_batch_impl<SRC>(ctx, p, frames, depth_scale, n, rows, cols, clouds, keep_stats, want_interval, true);
-  }
-  return rc;
+    for (int base = 0, k = 0; base < n; base += sub, ++k) {
+      const int m = std::min(sub, n - base);
+      hipStream_t st = plan.stream(k);
+      if (job.host_input) {
+        hipStream_t cs = ahead ? ctx->copy_stream : st;
+        if (ahead && k >= plan.ns) HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->sync_events[2 * (k - plan.ns) + 1], 0), PWN_HIP_ERR_LAUNCH);
+        if (int rc = convert_stage_frames(ctx, job, base, m, cs)) return rc;
+        if (ahead) {
+          HIPCHK(ctx, hipEventRecord(ctx->sync_events[2 * k], cs), PWN_HIP_ERR_LAUNCH);
+          HIPCHK(ctx, hipStreamWaitEvent(st, ctx->sync_events[2 * k], 0), PWN_HIP_ERR_LAUNCH);
+        }
+      }
+      if (int rc = launch_convert(ctx, job.cp, base, m, st, direct ? ctx->counts_host + n : nullptr)) return rc;
+      if (ahead) HIPCHK(ctx, hipEventRecord(ctx->sync_events[2 * k + 1], st), PWN_HIP_ERR_LAUNCH);
+    }
+    if (int rc = plan_join(ctx, plan)) return rc;
+    return convert_finish(ctx, job, clouds);
+  });
 }
 
 }  // namespace
@@ -1810,6 +1822,64 @@ struct AlignHooks {
   std::function<int()> before_sync;                                        // on ctx->stream, after the streams have joined
   std::function<int()> after_sync;                                         // after the final wait, before the results are filled in
 };
+// the parameter checks of every alignment call (each entry point checks its own pointer arguments first)
+static int check_align_params(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p) {
+  if (int rc = check_image(ctx, p->rows, p->cols)) return rc;
+  if (p->min_distance < 0.f) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "min_distance must be >= 0");
+  const int nit = p->outer_iterations * p->inner_iterations;
+  if (p->outer_iterations < 0 || p->inner_iterations < 0 || nit > PWN_HIP_MAX_ITERATIONS)
+    return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "outer*inner iterations exceeds PWN_HIP_MAX_ITERATIONS");
+  return PWN_HIP_OK;
+}
+// the aligner's 32-bit z-buffer word indexes 2^21 points (every frame up to 1448 x 1448 pixels); larger clouds are scenes (merge, voxelize)
+static int check_pair_points(pwn_hip_ctx* ctx, const pwn_hip_cloud* ref, const pwn_hip_cloud* cur) {
+  if (std::min(ref->n_host, ref->d.capacity) > kMaxAlignerPoints || std::min(cur->n_host, cur->d.capacity) > kMaxAlignerPoints)
+    return fail(ctx, PWN_HIP_ERR_CAPACITY, "Aligner::align: a cloud holds more than 2^21 points (index field of the aligner's z-buffer word)");
+  return PWN_HIP_OK;
+}
+// descriptor `entry` of a call (its state: state_ws[entry]): the pair's clouds and the buffers of workspace slot `slot`
+static void fill_pair(pwn_hip_ctx* ctx, int entry, int slot, const pwn_hip_cloud* ref, const pwn_hip_cloud* cur, PairState* state_out, bool robust) {
+  PairDesc& pd = ctx->pairs_host[entry];
+  pd.ref = ref->d; pd.cur = cur->d;
+  pd.zref = ctx->z32ref_ws + (size_t)slot * ctx->N;
+  pd.zcur = ctx->z32cur_ws + (size_t)slot * ctx->N;
+  pd.curidx = ctx->curidx_ws + (size_t)slot * ctx->N;
+  pd.refidx0 = nullptr;
+  pd.partials = ctx->partials_ws + (size_t)slot * ctx->nblocks_max * kAccN;
+  pd.state = ctx->state_ws + entry;
+  pd.state_out = state_out;
+  pd.fault = ctx->align_fault_host;
+  pd.zdepth = robust ? ctx->zdepth_ws + (size_t)slot * ctx->N : nullptr;
+}
+// the pose part of a pair's state at the start of an outer iteration with transform T (aligner.cpp:72-73,84)
+static void set_pose(PairState& st, const Mat4& T, const AlignParams& ap, const Mat4& KRtCur) {
+  st.T = T;
+  st.invTcorr = iso_inverse(T);
+  st.invT = st.invTcorr; set_last_row(st.invT);
+  Mat4 iKRt; Mat3 iK;
+  projector_matrices(ap.K, iso_mul(T, ap.refOffset), st.KRt, iKRt, iK);
+  st.KRtLast = st.KRt;
+  st.KRtCur = KRtCur;
+}
+// a pair's result from its final state (transform, iterations, traces)
+static void fill_result(pwn_hip_align_result& r, const PairState& st, const pwn_hip_cloud* ref, const pwn_hip_cloud* cur, float ms) {
+  std::memset(&r, 0, sizeof(r));
+  std::memcpy(r.T, st.T.m, sizeof(r.T));
+  r.iterations = st.it;
+  for (int k = 0; k < st.it && k < PWN_HIP_MAX_ITERATIONS; ++k) {
+    r.chi2[k] = st.chi2[k]; r.iter_inliers[k] = st.inliers[k]; r.iter_correspondences[k] = st.ncorr[k]; r.iter_candidates[k] = st.ncand[k];
+  }
+  if (st.it > 0) { r.error = st.chi2[st.it - 1]; r.inliers = st.inliers[st.it - 1]; }
+  r.n_reference = ref->n_host; r.n_current = cur->n_host;
+  r.total_time_ms = ms;
+}
+// Aligner::_computeStatistics from the re-linearization at the final transform T (so: its sums; nullptr when the call ran no iteration)
+static void fill_statistics(pwn_hip_align_statistics& q, const SolveOut* so, const Mat4& T) {
+  std::memset(&q, 0, sizeof(q));
+  if (!so) return;
+  std::memcpy(q.H, so->H, sizeof(q.H)); std::memcpy(q.b, so->b, sizeof(q.b)); q.error = so->chi2; q.inliers = so->inliers;
+  compute_statistics(so->H, T, q.mean, q.omega, &q.translational_eigen_ratio, &q.rotational_eigen_ratio);
+}
 // records (optional): n * PWN_HIP_RECORD_FLOATS floats, device or host, written by k_pack_records; pair_ids (optional, host): the id in
 // record word 19 (else first_pair_id + i).  results may be NULL when records are asked for.
 // robust: every projection of the call by the two-pass kernels (what align_batch_impl repeats a call with whose k_project gave up on a pixel)
@@ -1818,15 +1888,11 @@ static int align_batch_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, i
                             pwn_hip_align_statistics* statistics, const AlignHooks* hooks, float* records,
                             const int* pair_ids, int first_pair_id, bool match_records, bool robust) {
   if (!ctx || !p || !refs || !curs || (!results && !records) || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  if (int rc = check_image(ctx, p->rows, p->cols)) return rc;
-  ctx->last_align_fault = 0;
-  if (robust) { if (int rc = ensure_zdepth(ctx)) return rc; }
+  if (int rc = check_image(ctx, p->rows, p->cols)) return rc;      // (first: a call refused for its image size keeps the last alignment's images)
   ctx->img_valid = false;                 // whatever happens below, the finder images of an earlier alignment are gone (set again on success)
+  if (int rc = check_align_params(ctx, p)) return rc;
+  if (int rc = start_align_attempt(ctx, robust)) return rc;
   const bool want_scores = scores != nullptr || (records && match_records);      // the score words of the long records come from the same accumulators
-  if (p->min_distance < 0.f) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "min_distance must be >= 0");
-  const int nit = p->outer_iterations * p->inner_iterations;
-  if (p->outer_iterations < 0 || p->inner_iterations < 0 || nit > PWN_HIP_MAX_ITERATIONS)
-    return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "outer*inner iterations exceeds PWN_HIP_MAX_ITERATIONS");
   const int N = p->rows * p->cols;
   const AlignParams ap = make_align_params(ctx, p);
   const int nb = align_nblocks(N);
@@ -1852,26 +1918,13 @@ static int align_batch_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, i
     const pwn_hip_cloud* r = refs[i]; const pwn_hip_cloud* c = curs[i];
     if (!r || !c) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null cloud in batch");
     if (c->d.omSym != omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "current clouds of one batch must share one omega storage (exact9 / sym6)");
-    // the aligner's 32-bit z-buffer word indexes 2^21 points (every frame up to 1448 x 1448 pixels); larger clouds are scenes (merge, voxelize)
-    if (std::min(r->n_host, r->d.capacity) > kMaxAlignerPoints || std::min(c->n_host, c->d.capacity) > kMaxAlignerPoints)
-      return fail(ctx, PWN_HIP_ERR_CAPACITY, "Aligner::align: a cloud holds more than 2^21 points (index field of the aligner's z-buffer word)");
-    const int slot = plan.slot0(i / sub) + i % sub;
-    PairDesc& pd = ctx->pairs_host[i];
-    pd.ref = r->d; pd.cur = c->d;
-    pd.zref = ctx->z32ref_ws + (size_t)slot * ctx->N;
-    pd.zcur = ctx->z32cur_ws + (size_t)slot * ctx->N;
-    pd.curidx = ctx->curidx_ws + (size_t)slot * ctx->N;
-    // the converter's own index image is what projecting the current cloud would give (see pwn_hip_cloud::idximg)
-    pd.refidx0 = nullptr;
-    own_index[i] = batch_shortcut && c->idx_valid && c->idx_rows == p->rows && c->idx_cols == p->cols && c->idx_minD == p->min_distance &&
-                   c->idx_maxD == p->max_distance && std::memcmp(c->idx_K, p->K, sizeof(c->idx_K)) == 0;
-    pd.partials = ctx->partials_ws + (size_t)slot * ctx->nblocks_max * kAccN;
-    pd.state = ctx->state_ws + i;
+    if (int rc = check_pair_points(ctx, r, c)) return rc;
     // a few pairs (latency path): k_solve_update writes the pose and the traces into the page-locked host copy itself, no copy back at the end;
     // batches copy the states back in one transfer (64 workgroups storing across PCIe in every solve launch cost more than that: 16 against 11 us per launch)
-    pd.state_out = direct_state ? ctx->state_host + i : nullptr;
-    pd.fault = ctx->align_fault_host;
-    pd.zdepth = robust ? ctx->zdepth_ws + (size_t)slot * ctx->N : nullptr;
+    fill_pair(ctx, i, plan.slot0(i / sub) + i % sub, r, c, direct_state ? ctx->state_host + i : nullptr, robust);
+    // the converter's own index image is what projecting the current cloud would give (see pwn_hip_cloud::idximg)
+    own_index[i] = batch_shortcut && c->idx_valid && c->idx_rows == p->rows && c->idx_cols == p->cols && c->idx_minD == p->min_distance &&
+                   c->idx_maxD == p->max_distance && std::memcmp(c->idx_K, p->K, sizeof(c->idx_K)) == 0;
     // initial state: aligner.cpp:60-64,72-73,79,84
     PairState& st = ctx->state_host[i];
     std::memset(&st, 0, offsetof(PairState, chi2));
@@ -1881,14 +1934,7 @@ static int align_batch_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, i
     // image, like the current cloud's; later iterations (and the last one, whose z-buffer the statistics pass re-reads) project as usual
     own_ref[i] = batch_shortcut && p->outer_iterations > 1 && ident_ref && is_identity(T) && r->idx_valid && r->idx_rows == p->rows &&
                  r->idx_cols == p->cols && r->idx_minD == p->min_distance && r->idx_maxD == p->max_distance && std::memcmp(r->idx_K, p->K, sizeof(r->idx_K)) == 0;
-    st.T = T;
-    st.invTcorr = iso_inverse(T);
-    st.invT = st.invTcorr; set_last_row(st.invT);
-    Mat4 iKRt; Mat3 iK;
-    projector_matrices(ap.K, iso_mul(T, ap.refOffset), st.KRt, iKRt, iK);
-    st.KRtLast = st.KRt;
-    st.KRtCur = KRtCur0;
-    st.it = 0;
+    set_pose(st, T, ap, KRtCur0);
   }
   // a sub-batch skips the projection kernels only if every pair of it can
   std::vector<char> sub_own((size_t)(n + sub - 1) / sub + 1, 1);
@@ -2007,31 +2053,13 @@ static int align_batch_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, i
   if (ctx->enqueued_cb && n > 0) ctx->enqueued_cb(ctx->enqueued_user);
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
   if (hooks && hooks->after_sync) { if (int rc = hooks->after_sync()) return rc; }
-  if (take_align_fault(ctx)) return fail(ctx, PWN_HIP_ERR_LAUNCH, kSettleMessage);
+  if (int rc = take_align_fault(ctx)) return rc;
   for (int i = 0; i < n && scores; ++i) finish_match(ctx->match_host[i], &scores[i]);      // with or without `results` (pwn_hip_match_batch_records)
-  for (int i = 0; i < n && results; ++i) {
-    const PairState& st = ctx->state_host[i];
-    pwn_hip_align_result& r = results[i];
-    std::memset(&r, 0, sizeof(r));
-    std::memcpy(r.T, st.T.m, sizeof(r.T));
-    r.iterations = st.it;
-    for (int k = 0; k < st.it && k < PWN_HIP_MAX_ITERATIONS; ++k) {
-      r.chi2[k] = st.chi2[k]; r.iter_inliers[k] = st.inliers[k]; r.iter_correspondences[k] = st.ncorr[k]; r.iter_candidates[k] = st.ncand[k];
-    }
-    if (st.it > 0) { r.error = st.chi2[st.it - 1]; r.inliers = st.inliers[st.it - 1]; }
-    r.n_reference = refs[i]->n_host; r.n_current = curs[i]->n_host;
-    if (statistics) {
-      pwn_hip_align_statistics& q = statistics[i];
-      std::memset(&q, 0, sizeof(q));
-      if (p->outer_iterations > 0) {
-        const SolveOut& so = ctx->stats_host[i];
-        std::memcpy(q.H, so.H, sizeof(q.H)); std::memcpy(q.b, so.b, sizeof(q.b)); q.error = so.chi2; q.inliers = so.inliers;
-        compute_statistics(so.H, st.T, q.mean, q.omega, &q.translational_eigen_ratio, &q.rotational_eigen_ratio);
-      }
-    }
-  }
   float ms = 0.f; (void)hipEventElapsedTime(&ms, ctx->t0, ctx->t1);
-  for (int i = 0; i < n && results; ++i) results[i].total_time_ms = n > 0 ? ms / n : 0.f;
+  for (int i = 0; i < n && results; ++i) {
+    fill_result(results[i], ctx->state_host[i], refs[i], curs[i], ms / n);
+    if (statistics) fill_statistics(statistics[i], p->outer_iterations > 0 ? ctx->stats_host + i : nullptr, ctx->state_host[i].T);
+  }
   // batches: no current z-buffer after a skipped projection; a single alignment makes it on demand
   ctx->img_rows = p->rows; ctx->img_cols = p->cols; ctx->img_valid = n > 0 && (!any_own || n == 1);
   ctx->img_cur_lazy = n == 1 && any_own; ctx->img_ap = ap; ctx->img_cur_capacity = n == 1 ? curs[0]->d.capacity : 0;
@@ -2046,12 +2074,9 @@ static int align_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, i
                             const float* guesses, pwn_hip_align_result* results, pwn_hip_match_result* scores, float match_threshold,
                             pwn_hip_align_statistics* statistics = nullptr, const AlignHooks* hooks = nullptr, float* records = nullptr,
                             const int* pair_ids = nullptr, int first_pair_id = 0, bool match_records = false) {
-  int rc = align_batch_once(ctx, p, n, refs, curs, guesses, results, scores, match_threshold, statistics, hooks, records, pair_ids, first_pair_id, match_records, false);
-  if (rc == PWN_HIP_ERR_LAUNCH && ctx && ctx->last_align_fault) {
-    ++ctx->projection_fallbacks;
-    rc = align_batch_once(ctx, p, n, refs, curs, guesses, results, scores, match_threshold, statistics, hooks, records, pair_ids, first_pair_id, match_records, true);
-  }
-  return rc;
+  return repeat_once(ctx, kSettleFault, [&](bool robust) {
+    return align_batch_once(ctx, p, n, refs, curs, guesses, results, scores, match_threshold, statistics, hooks, records, pair_ids, first_pair_id, match_records, robust);
+  });
 }
 int pwn_hip_align_batch(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs,
                         const float* guesses, pwn_hip_align_result* results) {
@@ -2066,56 +2091,33 @@ int pwn_hip_align_with_priors(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p,
                               const pwn_hip_prior* priors, pwn_hip_align_result* result) {
   return pwn_hip_align_with_priors_ex(ctx, p, ref, cur, n_priors, priors, result, nullptr);
 }
-static int align_with_priors_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, const pwn_hip_cloud* ref, const pwn_hip_cloud* cur, int n_priors,
-                                  const pwn_hip_prior* priors, pwn_hip_align_result* result, pwn_hip_align_statistics* statistics, bool robust);
-int pwn_hip_align_with_priors_ex(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, const pwn_hip_cloud* ref, const pwn_hip_cloud* cur, int n_priors,
-                                 const pwn_hip_prior* priors, pwn_hip_align_result* result, pwn_hip_align_statistics* statistics) {
-  int rc = align_with_priors_once(ctx, p, ref, cur, n_priors, priors, result, statistics, false);
-  if (rc == PWN_HIP_ERR_LAUNCH && n_priors > 0 && ctx && ctx->last_align_fault) {      // see align_batch_impl (which handles the prior-less case itself)
-    ++ctx->projection_fallbacks;
-    rc = align_with_priors_once(ctx, p, ref, cur, n_priors, priors, result, statistics, true);
-  }
-  return rc;
-}
+// n_priors > 0 (pwn_hip_align_with_priors_ex); robust: see align_batch_once
 static int align_with_priors_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, const pwn_hip_cloud* ref, const pwn_hip_cloud* cur, int n_priors,
                                   const pwn_hip_prior* priors, pwn_hip_align_result* result, pwn_hip_align_statistics* statistics, bool robust) {
-  if (n_priors <= 0) {
-    pwn_hip_cloud* r[1] = { const_cast<pwn_hip_cloud*>(ref) };
-    pwn_hip_cloud* c[1] = { const_cast<pwn_hip_cloud*>(cur) };
-    return align_batch_impl(ctx, p, 1, r, c, nullptr, result, nullptr, 0.f, statistics);
-  }
   if (!ctx || !p || !ref || !cur || !priors || !result) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  if (int rc = check_image(ctx, p->rows, p->cols)) return rc;
-  if (p->min_distance < 0.f) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "min_distance must be >= 0");
-  const int nit = p->outer_iterations * p->inner_iterations;
-  if (p->outer_iterations < 0 || p->inner_iterations < 0 || nit > PWN_HIP_MAX_ITERATIONS)
-    return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "outer*inner iterations exceeds PWN_HIP_MAX_ITERATIONS");
+  if (int rc = check_align_params(ctx, p)) return rc;
   std::vector<PriorHost> pr(n_priors);
   for (int i = 0; i < n_priors; ++i) {
     pr[i].kind = priors[i].kind; pr[i].mean = mat4_from(priors[i].mean);
     pr[i].invReference = priors[i].kind == 1 ? iso_inverse(mat4_from(priors[i].reference_transform)) : mat4_identity();
     std::memcpy(pr[i].information, priors[i].information, sizeof(pr[i].information));
   }
-  if (std::min(ref->n_host, ref->d.capacity) > kMaxAlignerPoints || std::min(cur->n_host, cur->d.capacity) > kMaxAlignerPoints)
-    return fail(ctx, PWN_HIP_ERR_CAPACITY, "Aligner::align: a cloud holds more than 2^21 points (index field of the aligner's z-buffer word)");
+  if (int rc = check_pair_points(ctx, ref, cur)) return rc;
   const int N = p->rows * p->cols;
   const AlignParams ap = make_align_params(ctx, p);
   const int nb = align_nblocks(N);
   hipStream_t st = ctx->stream;
-  PairDesc& pd = ctx->pairs_host[0];
-  pd.ref = ref->d; pd.cur = cur->d;
-  pd.zref = ctx->z32ref_ws; pd.zcur = ctx->z32cur_ws; pd.curidx = ctx->curidx_ws; pd.partials = ctx->partials_ws; pd.state = ctx->state_ws;
-  pd.refidx0 = nullptr; pd.state_out = nullptr;
-  ctx->last_align_fault = 0;
-  if (robust) { if (int rc = ensure_zdepth(ctx)) return rc; }
-  pd.fault = ctx->align_fault_host; pd.zdepth = robust ? ctx->zdepth_ws : nullptr;
+  if (int rc = start_align_attempt(ctx, robust)) return rc;
+  fill_pair(ctx, 0, 0, ref, cur, nullptr, robust);
+  const PairDesc& pd = ctx->pairs_host[0];
   ctx->img_valid = false;
   ctx->img_pair = 0; ctx->img_ref_cloud = ref; ctx->img_cur_cloud = cur;
   PairState& hs = ctx->state_host[0];
   std::memset(&hs, 0, sizeof(hs));
   Mat4 T = mat4_from(p->initial_guess); set_last_row(T);
-  Mat4 iKRt; Mat3 iK;
-  projector_matrices(ap.K, mat4_from(p->current_sensor_offset), hs.KRtCur, iKRt, iK);
+  Mat4 KRtCur, iKRt; Mat3 iK;
+  projector_matrices(ap.K, mat4_from(p->current_sensor_offset), KRtCur, iKRt, iK);
+  set_pose(hs, T, ap, KRtCur);
   HIPCHK(ctx, hipEventRecord(ctx->t0, st), PWN_HIP_ERR_LAUNCH);
   HIPCHK(ctx, hipMemcpyAsync(ctx->pairs_dev, ctx->pairs_host, sizeof(PairDesc), hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipMemcpyAsync(ctx->state_ws, &hs, sizeof(PairState), hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
@@ -2125,14 +2127,11 @@ static int align_with_priors_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params
   if (int rc = take_tags32(ctx, (unsigned)std::max(1, p->outer_iterations), &tag0)) return rc;
   if (int rc = launch_project(ctx, cur->d.capacity, 1, st, ctx->pairs_dev, ap, 1, tag0, pd.zdepth)) return rc;
   hipLaunchKernelGGL(k_resolve_cur, dim3(std::min((N + 255) / 256, 1024), 1), dim3(256), 0, st, ctx->pairs_dev, N, tag0);
-  std::memset(result, 0, sizeof(*result));
   int it = 0;
   for (int i = 0; i < p->outer_iterations; ++i) {
     const unsigned tag = tag0 - (unsigned)i;
     set_last_row(T);                                                                 // aligner.cpp:72
-    hs.T = T; hs.invTcorr = iso_inverse(T);
-    projector_matrices(ap.K, iso_mul(T, ap.refOffset), hs.KRt, iKRt, iK);            // :73
-    hs.KRtLast = hs.KRt;
+    set_pose(hs, T, ap, KRtCur);                                                     // :73
     Mat4 invT = iso_inverse(T);                                                      // :84
     for (int k = 0; k < p->inner_iterations; ++k, ++it) {
       set_last_row(invT);                                                            // :86
@@ -2146,7 +2145,7 @@ static int align_with_priors_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params
       HIPCHK(ctx, hipMemcpyAsync(ctx->stats_host, ctx->stats_dev, sizeof(SolveOut), hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
       HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
       const SolveOut& so = ctx->stats_host[0];
-      result->chi2[it] = so.chi2; result->iter_inliers[it] = so.inliers; result->iter_correspondences[it] = so.ncorr; result->iter_candidates[it] = so.ncand;
+      hs.chi2[it] = so.chi2; hs.inliers[it] = so.inliers; hs.ncorr[it] = so.ncorr; hs.ncand[it] = so.ncand;      // the traces k_solve_update keeps
       float H[36], b[6];
       std::memcpy(H, so.H, sizeof(H)); std::memcpy(b, so.b, sizeof(b));
       for (int d = 0; d < 6; ++d) H[d + 6 * d] = H[d + 6 * d] + 1.0f;                // :92
@@ -2161,36 +2160,39 @@ static int align_with_priors_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params
     float v[6]; t2v(T, v); T = v2t(v); set_last_row(T);
   }
   const unsigned lastRefTag = tag0 - (unsigned)std::max(0, p->outer_iterations - 1);
-  if (statistics) {
+  if (statistics && p->outer_iterations > 0) {
     // Aligner::_computeStatistics (aligner.cpp:127,152-199) runs after the loop whether or not priors exist: one more
     // Linearizer::update at the final transform on the finder's last correspondences, H + I without the prior terms (:168-170)
-    std::memset(statistics, 0, sizeof(*statistics));
-    if (p->outer_iterations > 0) {
-      hs.invTcorrPrev = hs.invTcorr;
-      hs.invT = iso_inverse(T); set_last_row(hs.invT);                                // :165-167
-      HIPCHK(ctx, hipMemcpyAsync(ctx->state_ws, &hs, sizeof(PairState), hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
-      launch_corr_linearize<false, true>(ctx, cur->d.omSym, nb, 1, st, ctx->pairs_dev, ap, lastRefTag, 1, 0);
-      hipLaunchKernelGGL(k_reduce_pairs, dim3(1), dim3(256), 0, st, ctx->pairs_dev, nb, ctx->stats_dev);
-      HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
-      HIPCHK(ctx, hipMemcpyAsync(ctx->stats_host, ctx->stats_dev, sizeof(SolveOut), hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
-      HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
-      const SolveOut& so = ctx->stats_host[0];
-      std::memcpy(statistics->H, so.H, sizeof(statistics->H)); std::memcpy(statistics->b, so.b, sizeof(statistics->b));
-      statistics->error = so.chi2; statistics->inliers = so.inliers;
-      compute_statistics(so.H, T, statistics->mean, statistics->omega, &statistics->translational_eigen_ratio, &statistics->rotational_eigen_ratio);
-    }
+    hs.invTcorrPrev = hs.invTcorr;
+    hs.invT = iso_inverse(T); set_last_row(hs.invT);                                  // :165-167
+    HIPCHK(ctx, hipMemcpyAsync(ctx->state_ws, &hs, sizeof(PairState), hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
+    launch_corr_linearize<false, true>(ctx, cur->d.omSym, nb, 1, st, ctx->pairs_dev, ap, lastRefTag, 1, 0);
+    hipLaunchKernelGGL(k_reduce_pairs, dim3(1), dim3(256), 0, st, ctx->pairs_dev, nb, ctx->stats_dev);
+    HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->stats_host, ctx->stats_dev, sizeof(SolveOut), hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
+    HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
   }
   HIPCHK(ctx, hipEventRecord(ctx->t1, st), PWN_HIP_ERR_LAUNCH);
   HIPCHK(ctx, hipEventSynchronize(ctx->t1), PWN_HIP_ERR_LAUNCH);
-  if (take_align_fault(ctx)) return fail(ctx, PWN_HIP_ERR_LAUNCH, kSettleMessage);
+  if (int rc = take_align_fault(ctx)) return rc;
   float ms = 0.f; (void)hipEventElapsedTime(&ms, ctx->t0, ctx->t1);
-  std::memcpy(result->T, T.m, sizeof(result->T));
-  result->iterations = it; result->total_time_ms = ms;
-  if (it > 0) { result->error = result->chi2[it - 1]; result->inliers = result->iter_inliers[it - 1]; }
-  result->n_reference = ref->n_host; result->n_current = cur->n_host;
+  hs.T = T; hs.it = it;
+  fill_result(*result, hs, ref, cur, ms);
+  if (statistics) fill_statistics(*statistics, p->outer_iterations > 0 ? ctx->stats_host : nullptr, T);
   ctx->img_rows = p->rows; ctx->img_cols = p->cols; ctx->img_valid = true; ctx->img_cur_lazy = false;
   ctx->img_ref_tag = lastRefTag; ctx->img_cur_tag = tag0;
   return PWN_HIP_OK;
+}
+int pwn_hip_align_with_priors_ex(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, const pwn_hip_cloud* ref, const pwn_hip_cloud* cur, int n_priors,
+                                 const pwn_hip_prior* priors, pwn_hip_align_result* result, pwn_hip_align_statistics* statistics) {
+  if (n_priors <= 0) {
+    pwn_hip_cloud* r[1] = { const_cast<pwn_hip_cloud*>(ref) };
+    pwn_hip_cloud* c[1] = { const_cast<pwn_hip_cloud*>(cur) };
+    return align_batch_impl(ctx, p, 1, r, c, nullptr, result, nullptr, 0.f, statistics);
+  }
+  return repeat_once(ctx, kSettleFault, [&](bool robust) {
+    return align_with_priors_once(ctx, p, ref, cur, n_priors, priors, result, statistics, robust);
+  });
 }
 int pwn_hip_align_batch_ex(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs,
                            const float* guesses, pwn_hip_align_result* results, float threshold, pwn_hip_match_result* scores,
@@ -2224,47 +2226,42 @@ int pwn_hip_convert_align_batch_u16(pwn_hip_ctx* ctx, const pwn_hip_converter_pa
     std::sort(all.begin(), all.end());
     if (std::adjacent_find(all.begin(), all.end()) != all.end()) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "the 2 n clouds of a step must be distinct");
   }
-  if (int rc = absorb_copies(ctx)) return rc;
-  if (int rc = ensure_desc(ctx, 2 * n)) return rc;       // once, before anything is queued: growing the descriptor arrays waits for the stream
-  // the sub-batches and streams the alignment will use (align_batch_impl makes the same plan); the frames of sub-batch k -- its reference
-  // frames, then its current frames -- are converted on k's stream in front of k's alignment, in launches of at most sub_frames frames that
-  // reuse the stream's own block of frame slots
-  const StreamPlan plan = make_plan(ctx, ctx->sub_pairs, n);
-  const int sub = plan.sub;
-  const int fslots = std::max(1, std::min(ctx->sub_frames, ctx->max_batch / plan.ns));
-  std::vector<const uint16_t*> frames((size_t)2 * std::max(n, 0));
-  std::vector<pwn_hip_cloud*> clouds((size_t)2 * std::max(n, 0));
-  std::vector<int> slot((size_t)2 * std::max(n, 0));
-  for (int base = 0, k = 0; base < n; base += sub, ++k) {
-    const int m = std::min(sub, n - base);
-    for (int j = 0; j < m; ++j) {
-      frames[2 * base + j] = ref_frames[base + j]; clouds[2 * base + j] = refs[base + j];
-      frames[2 * base + m + j] = cur_frames[base + j]; clouds[2 * base + m + j] = curs[base + j];
+  // a hand-over time-out (see convert_batch_impl): the step once more, its conversions included
+  return repeat_once(ctx, kHandoverTimeout, [&](bool) -> int {
+    if (int rc = absorb_copies(ctx)) return rc;
+    if (int rc = ensure_desc(ctx, 2 * n)) return rc;       // before anything of the step is queued: growing the descriptor arrays waits for the stream
+    // the sub-batches and streams the alignment will use (align_batch_impl makes the same plan); the frames of sub-batch k -- its reference
+    // frames, then its current frames -- are converted on k's stream in front of k's alignment, in launches of at most sub_frames frames that
+    // reuse the stream's own block of frame slots
+    const StreamPlan plan = make_plan(ctx, ctx->sub_pairs, n);
+    const int sub = plan.sub;
+    const int fslots = std::max(1, std::min(ctx->sub_frames, ctx->max_batch / plan.ns));
+    std::vector<const uint16_t*> frames((size_t)2 * std::max(n, 0));
+    std::vector<pwn_hip_cloud*> clouds((size_t)2 * std::max(n, 0));
+    std::vector<int> slot((size_t)2 * std::max(n, 0));
+    for (int base = 0, k = 0; base < n; base += sub, ++k) {
+      const int m = std::min(sub, n - base);
+      for (int j = 0; j < m; ++j) {
+        frames[2 * base + j] = ref_frames[base + j]; clouds[2 * base + j] = refs[base + j];
+        frames[2 * base + m + j] = cur_frames[base + j]; clouds[2 * base + m + j] = curs[base + j];
+      }
+      for (int f = 0; f < 2 * m; ++f) slot[2 * base + f] = (k % plan.ns) * fslots + f % fslots;
     }
-    for (int f = 0; f < 2 * m; ++f) slot[2 * base + f] = (k % plan.ns) * fslots + f % fslots;
-  }
-  ConvertJob job;
-  if (int rc = convert_prepare<uint16_t>(ctx, cp, frames.data(), depth_scale, 2 * n, rows, cols, clouds.data(), 0, false, slot, false, job)) return rc;
-  AlignHooks hooks;
-  hooks.pre_sub = [&](int base, int m, int, hipStream_t st) -> int {
-    for (int f = 0; f < 2 * m; f += fslots) {
-      const int cnt = std::min(fslots, 2 * m - f);
-      if (job.host_input) { if (int rc = convert_stage_frames(ctx, job, 2 * base + f, cnt, st)) return rc; }
-      if (int rc = launch_convert(ctx, job.cp, 2 * base + f, cnt, st)) return rc;
-    }
-    return PWN_HIP_OK;
-  };
-  hooks.before_sync = [&]() -> int { return counts_enqueue(ctx, 2 * n); };
-  hooks.after_sync = [&]() -> int { return counts_apply(ctx, clouds.data(), 2 * n); };
-  const int rc = align_batch_impl(ctx, ap, n, refs, curs, guesses, results, nullptr, 0.f, nullptr, &hooks, records, pair_ids, first_pair_id);
-  if (rc != PWN_HIP_OK && ctx->last_convert_fault == 1 && !ctx->in_step_retry) {      // a hand-over time-out (see convert_batch_impl): the step once more
-    ++ctx->convert_retries;
-    ctx->in_step_retry = true;
-    const int rc2 = pwn_hip_convert_align_batch_u16(ctx, cp, ap, n, ref_frames, cur_frames, depth_scale, rows, cols, refs, curs, guesses, pair_ids, first_pair_id, results, records);
-    ctx->in_step_retry = false;
-    return rc2;
-  }
-  return rc;
+    ConvertJob job;
+    if (int rc = convert_prepare<uint16_t>(ctx, cp, frames.data(), depth_scale, 2 * n, rows, cols, clouds.data(), 0, false, slot, false, job)) return rc;
+    AlignHooks hooks;
+    hooks.pre_sub = [&](int base, int m, int, hipStream_t st) -> int {
+      for (int f = 0; f < 2 * m; f += fslots) {
+        const int cnt = std::min(fslots, 2 * m - f);
+        if (job.host_input) { if (int rc = convert_stage_frames(ctx, job, 2 * base + f, cnt, st)) return rc; }
+        if (int rc = launch_convert(ctx, job.cp, 2 * base + f, cnt, st)) return rc;
+      }
+      return PWN_HIP_OK;
+    };
+    hooks.before_sync = [&]() -> int { return counts_enqueue(ctx, 2 * n); };
+    hooks.after_sync = [&]() -> int { return counts_apply(ctx, clouds.data(), 2 * n); };
+    return align_batch_impl(ctx, ap, n, refs, curs, guesses, results, nullptr, 0.f, nullptr, &hooks, records, pair_ids, first_pair_id);
+  });
 }
 void pwn_hip_compute_statistics(const float H[36], const float T[16], float mean[6], float omega[36], float* tr, float* rr) {
   compute_statistics(H, mat4_from(T), mean, omega, tr, rr);
