@@ -340,10 +340,7 @@ ConvertParams make_convert_params(const pwn_hip_ctx* ctx, const pwn_hip_converte
   const Mat3 K = mat3_from(p->K);
   Mat4 KRt; Mat3 iK;
   projector_matrices(K, T ? mat4_from(T) : mat4_identity(), KRt, cp.iKRt, iK);
-  // _projectInterval: p = K * (R, R, 0)   (pinholepointprojector.h:269)
-  const float R = p->world_radius;
-  cp.ivx = dot3seq(K(0,0), R, K(0,1), R, K(0,2), 0.f);
-  cp.ivy = dot3seq(K(1,0), R, K(1,1), R, K(1,2), 0.f);
+  interval_scale(K, p->world_radius, cp.ivx, cp.ivy);
   cp.minD = p->min_distance; cp.maxD = p->max_distance;
   cp.minRadius = p->min_image_radius; cp.maxRadius = p->max_image_radius; cp.minPoints = p->min_points;
   cp.statsCurvThr = p->stats_curvature_threshold;
@@ -2326,14 +2323,11 @@ int pwn_hip_project_point(const float K[9], const float T[16], float min_distanc
   if (!K || !T || !p) return 0;
   Mat4 KRt, iKRt; Mat3 iK;
   projector_matrices(mat3_from(K), mat4_from(T), KRt, iKRt, iK);
-  // _project: ip = KRt * p; d = ip.z; ip *= 1 / d; round (the expressions of z32_insert / project_point in pwn_kernels.h)
-  const float ix = dot4seq(KRt(0,0), p[0], KRt(0,1), p[1], KRt(0,2), p[2], KRt(0,3), 1.0f);
-  const float iy = dot4seq(KRt(1,0), p[0], KRt(1,1), p[1], KRt(1,2), p[2], KRt(1,3), 1.0f);
-  const float dd = dot4seq(KRt(2,0), p[0], KRt(2,1), p[1], KRt(2,2), p[2], KRt(2,3), 1.0f);
-  if (d) *d = dd;
-  if (dd < min_distance || dd > max_distance) return 0;
-  const float inv = 1.0f / dd;
-  const float fx = roundf(ix * inv), fy = roundf(iy * inv);
+  const Vec3 ip = project_plane(KRt, p[0], p[1], p[2]);
+  if (d) *d = ip.z;
+  if (!depth_in_range(ip.z, min_distance, max_distance)) return 0;
+  float fx, fy;
+  round_to_pixel(ip, fx, fy);
   // the reference converts whatever comes out to int (undefined for values an int cannot hold); saturate instead
   const float lim = 2147483520.0f;
   if (x) *x = (int)(fx > lim ? lim : (fx < -lim ? -lim : fx));
@@ -2342,25 +2336,19 @@ int pwn_hip_project_point(const float K[9], const float T[16], float min_distanc
 }
 int pwn_hip_unproject_pixel(const float K[9], const float T[16], float min_distance, float max_distance, int x, int y, float d, float p[3]) {
   if (!K || !T || !p) return 0;
-  if (d < min_distance || d > max_distance) return 0;
+  if (!depth_in_range(d, min_distance, max_distance)) return 0;
   Mat4 KRt, iKRt; Mat3 iK;
   projector_matrices(mat3_from(K), mat4_from(T), KRt, iKRt, iK);
-  const float a = (float)x * d, b = (float)y * d;                      // _unProject: iKRt * (x d, y d, d, 1): the expressions of k_unproject
-  p[0] = dot4seq(iKRt(0,0), a, iKRt(0,1), b, iKRt(0,2), d, iKRt(0,3), 1.0f);
-  p[1] = dot4seq(iKRt(1,0), a, iKRt(1,1), b, iKRt(1,2), d, iKRt(1,3), 1.0f);
-  p[2] = dot4seq(iKRt(2,0), a, iKRt(2,1), b, iKRt(2,2), d, iKRt(2,3), 1.0f);
+  const Vec3 q = unproject_pixel(iKRt, x, y, d);
+  p[0] = q.x; p[1] = q.y; p[2] = q.z;
   return 1;
 }
 int pwn_hip_project_interval(const float K[9], float min_distance, float max_distance, float d, float world_radius) {
   if (!K) return -1;
-  if (d < min_distance || d > max_distance) return -1;
-  const Mat3 Km = mat3_from(K);
-  // _projectInterval: p = K * (R, R, 0); p *= 1 / d; the larger of x, y truncated (make_convert_params / k_unproject evaluate the same)
-  const float ivx = dot3seq(Km(0,0), world_radius, Km(0,1), world_radius, Km(0,2), 0.f);
-  const float ivy = dot3seq(Km(1,0), world_radius, Km(1,1), world_radius, Km(1,2), 0.f);
-  const float inv = 1.0f / d;
-  const float px = ivx * inv, py = ivy * inv;
-  return (px > py) ? (int)px : (int)py;
+  if (!depth_in_range(d, min_distance, max_distance)) return -1;
+  float ivx, ivy;
+  interval_scale(mat3_from(K), world_radius, ivx, ivy);
+  return depth_interval(ivx, ivy, d);
 }
 void pwn_hip_iso_inverse(const float T[16], float out[16]) { const Mat4 r = iso_inverse(mat4_from(T)); std::memcpy(out, r.m, sizeof(r.m)); }
 void pwn_hip_iso_mul(const float A[16], const float B[16], float out[16]) { const Mat4 r = iso_mul(mat4_from(A), mat4_from(B)); std::memcpy(out, r.m, sizeof(r.m)); }

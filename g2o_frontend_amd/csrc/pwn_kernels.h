@@ -254,8 +254,7 @@ struct RawDesc { const uint16_t* src; float* dst; };
 __global__ void k_u16_to_f32(const RawDesc* __restrict__ d, int n, float scale) {
   const RawDesc rd = d[blockIdx.y];
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const uint16_t s = rd.src[i];
-    rd.dst[i] = s ? scale * (float)s : 0.0f;
+    rd.dst[i] = raw_to_metres(rd.src[i], scale);
   }
 }
 // DepthImage_convert_32FC1_to_16UC1 (pwn_core/pwn_static.cpp:38-52)
@@ -288,9 +287,9 @@ __global__ void k_depth_scale(const float* __restrict__ src, int srows, int scol
   dst[i] = out;
 }
 
-// depth of pixel i of a frame: the float image, or the raw uint16 image converted on the fly (pwn_static.cpp:54-68)
+// depth of pixel i of a frame: the float image, or the raw uint16 image converted on the fly
 __device__ __forceinline__ float frame_depth(const FrameDesc& f, size_t i) {
-  if (f.raw) { const uint16_t s = f.raw[i]; return s ? f.raw_scale * (float)s : 0.0f; }
+  if (f.raw) return raw_to_metres(f.raw[i], f.raw_scale);
   return f.depth[i];
 }
 // ------------------------------------------------------------------------------------------------------------------
@@ -302,7 +301,7 @@ __global__ void __launch_bounds__(256) k_row_count(const FrameDesc* __restrict__
   int cnt = 0;
   for (int c = threadIdx.x; c < cp.cols; c += 256) {
     const float d = frame_depth(f, (size_t)r * cp.cols + c);
-    cnt += !(d < cp.minD || d > cp.maxD);
+    cnt += depth_in_range(d, cp.minD, cp.maxD);
   }
   __shared__ int s[4];
   float t = wave_sum((float)cnt);           // <= 64*N small ints: exact in fp32
@@ -343,6 +342,20 @@ __global__ void k_gather_counts(const FrameDesc* __restrict__ frames, int n, int
   if (i < n) out[i] = *frames[i].cloud.count;
   if (i == n) out[n] = *fault;      // time-out flag of k_unproject_integral rides along with the counts
 }
+// Ordered compaction of one 256-pixel step of an image row, block = 256: the point index of this thread's pixel = base + valid pixels
+// left of it in the step (meaningful when `valid`); tot = the step's valid pixels.  wcount: the block's 4 per-wave counts, free again after
+// the caller's next __syncthreads().
+__device__ __forceinline__ int row_compact(bool valid, int (&wcount)[4], int wave, int lane, int base, int& tot) {
+  const unsigned long long bal = __ballot(valid);
+  const int rank = __popcll(bal & ((1ull << lane) - 1ull));
+  if (lane == 0) wcount[wave] = __popcll(bal);
+  __syncthreads();
+  int woff = 0;
+  tot = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) { const int n = wcount[w]; if (w < wave) woff += n; tot += n; }
+  return base + woff + rank;
+}
 // step 3: PinholePointProjector::unProject (pwn_core/pinholepointprojector.cpp:93-133) + projectIntervals (:135-147).
 // Point index = row-major rank of the valid pixel.  grid = (rows, frames), block = 256.
 __global__ void __launch_bounds__(256) k_unproject(const FrameDesc* __restrict__ frames, ConvertParams cp) {
@@ -355,31 +368,17 @@ __global__ void __launch_bounds__(256) k_unproject(const FrameDesc* __restrict__
     const int c = c0 + threadIdx.x;
     const bool in = c < cp.cols;
     const float d = in ? frame_depth(f, (size_t)r * cp.cols + c) : 0.f;
-    const bool valid = in && !(d < cp.minD || d > cp.maxD);
-    const unsigned long long bal = __ballot(valid);
-    const int rank = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wcount[wave] = __popcll(bal);
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { const int n = wcount[w]; if (w < wave) woff += n; tot += n; }
+    const bool valid = in && depth_in_range(d, cp.minD, cp.maxD);
+    int tot;
+    const int slot = row_compact(valid, wcount, wave, lane, base, tot);
     if (in) {
       const size_t pix = (size_t)r * cp.cols + c;
       int idx = -1, itv = -1;
       if (valid) {
-        idx = base + woff + rank;
-        // _unProject: p = iKRt * (x*d, y*d, d, 1)
-        const float a = (float)c * d, b = (float)r * d;
-        float4 p;
-        p.x = dot4seq(cp.iKRt(0,0), a, cp.iKRt(0,1), b, cp.iKRt(0,2), d, cp.iKRt(0,3), 1.0f);
-        p.y = dot4seq(cp.iKRt(1,0), a, cp.iKRt(1,1), b, cp.iKRt(1,2), d, cp.iKRt(1,3), 1.0f);
-        p.z = dot4seq(cp.iKRt(2,0), a, cp.iKRt(2,1), b, cp.iKRt(2,2), d, cp.iKRt(2,3), 1.0f);
-        p.w = 0.f;
+        idx = slot;
+        const Vec3 p = unproject_pixel(cp.iKRt, c, r, d);
         if (f.cloud.P3 && idx < f.cloud.capacity) store_xyz(f.cloud.P3, idx, p.x, p.y, p.z);
-        // _projectInterval: int(max(fx*R/d, fy*R/d))
-        const float inv = 1.0f / d;
-        const float px = cp.ivx * inv, py = cp.ivy * inv;
-        itv = (px > py) ? (int)px : (int)py;
+        itv = depth_interval(cp.ivx, cp.ivy, d);
       }
       f.index[pix] = idx;
       f.interval[pix] = itv;
@@ -399,6 +398,12 @@ __global__ void __launch_bounds__(256) k_unproject(const FrameDesc* __restrict__
 // wavefront of the strip kernel fills and drains in half the time with 8-row bands: -7 % against 16
 constexpr int kIR_Rows = 8, kIR_Cols = 64, kIR_Stride = kIR_Cols + 1;
 static_assert(kIR_Rows % 4 == 0 && (kIR_Rows & (kIR_Rows - 1)) == 0 && kIR_Rows <= 64, "band height");
+// the ten integral-image channel values of a point (PointAccumulator::operator+=(Point), pointaccumulator.h:56-59): p, 1, the upper triangle of p p^T
+__device__ __forceinline__ void point_channels(float (&v)[kIntegralChannels], float x, float y, float z) {
+  v[0] = x; v[1] = y; v[2] = z; v[3] = 1.0f;
+  v[4] = x * x; v[5] = x * y; v[6] = x * z;
+  v[7] = y * y; v[8] = y * z; v[9] = z * z;
+}
 __global__ void __launch_bounds__(256) k_integral_rows(const FrameDesc* __restrict__ frames, int rows, int cols) {
   const FrameDesc& f = frames[blockIdx.y];
   const int r0 = blockIdx.x * kIR_Rows;
@@ -422,9 +427,7 @@ __global__ void __launch_bounds__(256) k_integral_rows(const FrameDesc* __restri
         const int idx = f.index[(size_t)r * cols + c];
         if (idx >= 0 && idx < f.cloud.capacity) {
           const float4 p = load_xyz(f.cloud.P3, idx);
-          v[0] = p.x; v[1] = p.y; v[2] = p.z; v[3] = 1.0f;
-          v[4] = p.x * p.x; v[5] = p.x * p.y; v[6] = p.x * p.z;
-          v[7] = p.y * p.y; v[8] = p.y * p.z; v[9] = p.z * p.z;
+          point_channels(v, p.x, p.y, p.z);
         }
       }
 #pragma unroll
@@ -468,7 +471,7 @@ __global__ void __launch_bounds__(256) k_integral_rows(const FrameDesc* __restri
 // r0 + w + 4j (j = 0..3): one wave instruction covers the 64 columns of one row, the point index of a valid pixel = row offset +
 // valid pixels of the row left of the tile (counted here) + popcount(ballot below the lane).
 // grid = (8 * ceil(bands/8) * strips, frames), block = 256.
-constexpr int kII_ChainsRows = kIntegralChannels * kIR_Rows;     // 160
+constexpr int kII_Chains = kIntegralChannels * kIR_Rows;     // 160 (channel, row) chains of a band
 __global__ void __launch_bounds__(256) k_unproject_integral_rows(const FrameDesc* __restrict__ frames, ConvertParams cp, unsigned epoch, int* __restrict__ fault) {
   const FrameDesc& f = frames[blockIdx.y];
   const int rows = cp.rows, cols = cp.cols;
@@ -491,11 +494,11 @@ __global__ void __launch_bounds__(256) k_unproject_integral_rows(const FrameDesc
       base = f.rowoff[r];
       for (int t = 0; t < s; ++t) {                           // full strips left of this one
         const float dl = frame_depth(f, (size_t)r * cols + t * kIR_Cols + lane);
-        base += __popcll(__ballot(!(dl < cp.minD || dl > cp.maxD)));
+        base += __popcll(__ballot(depth_in_range(dl, cp.minD, cp.maxD)));
       }
     }
     const float d = in ? frame_depth(f, (size_t)r * cols + c) : 0.f;
-    const bool valid = in && !(d < cp.minD || d > cp.maxD);
+    const bool valid = in && depth_in_range(d, cp.minD, cp.maxD);
     const unsigned long long bal = __ballot(valid);
     float v[kIntegralChannels];
 #pragma unroll
@@ -504,23 +507,12 @@ __global__ void __launch_bounds__(256) k_unproject_integral_rows(const FrameDesc
       int idx = -1, itv = -1;
       if (valid) {
         idx = base + __popcll(bal & ((1ull << lane) - 1ull));
-        const float a = (float)c * d, b = (float)r * d;
-        float4 p;
-        p.x = dot4seq(cp.iKRt(0,0), a, cp.iKRt(0,1), b, cp.iKRt(0,2), d, cp.iKRt(0,3), 1.0f);
-        p.y = dot4seq(cp.iKRt(1,0), a, cp.iKRt(1,1), b, cp.iKRt(1,2), d, cp.iKRt(1,3), 1.0f);
-        p.z = dot4seq(cp.iKRt(2,0), a, cp.iKRt(2,1), b, cp.iKRt(2,2), d, cp.iKRt(2,3), 1.0f);
-        p.w = 0.f;
+        const Vec3 p = unproject_pixel(cp.iKRt, c, r, d);
         if (idx < f.cloud.capacity) {
           if (!cp.lean) store_xyz(f.cloud.P3, idx, p.x, p.y, p.z);
-          v[0] = p.x; v[1] = p.y; v[2] = p.z; v[3] = 1.0f;
-          v[4] = p.x * p.x; v[5] = p.x * p.y; v[6] = p.x * p.z;
-          v[7] = p.y * p.y; v[8] = p.y * p.z; v[9] = p.z * p.z;
+          point_channels(v, p.x, p.y, p.z);
         }
-        if (!cp.lean) {
-          const float inv = 1.0f / d;
-          const float px = cp.ivx * inv, py = cp.ivy * inv;
-          itv = (px > py) ? (int)px : (int)py;
-        }
+        if (!cp.lean) itv = depth_interval(cp.ivx, cp.ivy, d);
       }
       f.index[(size_t)r * cols + c] = idx;
       if (!cp.lean) f.interval[(size_t)r * cols + c] = itv;
@@ -530,10 +522,10 @@ __global__ void __launch_bounds__(256) k_unproject_integral_rows(const FrameDesc
   }
   __syncthreads();
   // 2. the 160 (channel, row) chains of the tile, continued from the tile to the left
-  if (tid < kII_ChainsRows) {
+  if (tid < kII_Chains) {
     float carry = 0.f;
     if (s > 0) {
-      const unsigned long long* src = f.carry + ((size_t)(s - 1) * NB + band) * kII_ChainsRows + tid;
+      const unsigned long long* src = f.carry + ((size_t)(s - 1) * NB + band) * kII_Chains + tid;
       unsigned long long w = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       int spins = 0;
       while ((unsigned)(w >> 32) != epoch) {
@@ -555,8 +547,8 @@ __global__ void __launch_bounds__(256) k_unproject_integral_rows(const FrameDesc
 #pragma unroll
       for (int c = 0; c < 16; ++c) t[c0 + c] = vals[c];
     }
-    if (s + 1 < S && (s * NB + band) * kII_ChainsRows + tid != cp.dbgWithhold)
-      __hip_atomic_store(f.carry + ((size_t)s * NB + band) * kII_ChainsRows + tid,
+    if (s + 1 < S && (s * NB + band) * kII_Chains + tid != cp.dbgWithhold)
+      __hip_atomic_store(f.carry + ((size_t)s * NB + band) * kII_Chains + tid,
                          ((unsigned long long)epoch << 32) | (unsigned long long)__float_as_uint(carry), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();
@@ -591,7 +583,6 @@ __global__ void __launch_bounds__(256) k_unproject_integral_rows(const FrameDesc
 // bounded (kSpinLimit), a starved chain raises *fault and finishes with garbage instead of hanging the device.
 // Workgroup -> (frame, strip) puts all strips of a frame on one XCD (ids are dealt round-robin over the 8 XCDs), so the
 // hand-over words stay in that XCD's L2.  grid = 8 * ceil(frames/8) * strips, block = 256.
-constexpr int kII_Chains = kII_ChainsRows;                   // 10 planes x band rows: the same hand-over word layout in both kernels that hand over
 constexpr int kSpinLimit = 1 << 20;      // polls of >= 64 cycles + one L2 round trip each: ~1 s, against hand-over waits of microseconds
 __host__ __device__ __forceinline__ int strips_of(int cols) { return (cols + kIR_Cols - 1) / kIR_Cols; }
 __host__ __device__ __forceinline__ int bands_of(int rows) { return (rows + kIR_Rows - 1) / kIR_Rows; }
@@ -621,14 +612,14 @@ __global__ void __launch_bounds__(256) k_strip_count(const FrameDesc* __restrict
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const unsigned lo = u[k] & 0xFFFFu, hi = u[k] >> 16;
-          d[2 * k] = lo ? scale * (float)lo : 0.0f; d[2 * k + 1] = hi ? scale * (float)hi : 0.0f;      // pwn_static.cpp:54-68
+          d[2 * k] = raw_to_metres(lo, scale); d[2 * k + 1] = raw_to_metres(hi, scale);
         }
       } else {
         const v4f w = *(gptr<const v4f>)(as_global(f.depth) + ((size_t)r * cp.cols + c));
         d[0] = w.x; d[1] = w.y; d[2] = w.z; d[3] = w.w;
       }
 #pragma unroll
-      for (int k = 0; k < PX; ++k) cnt += !(d[k] < cp.minD || d[k] > cp.maxD);
+      for (int k = 0; k < PX; ++k) cnt += depth_in_range(d[k], cp.minD, cp.maxD);
     }
 #pragma unroll
     for (int off = 1; off < LPS; off <<= 1) cnt += __shfl_xor(cnt, off, 64);
@@ -644,7 +635,7 @@ __global__ void __launch_bounds__(256) k_strip_count_any(const FrameDesc* __rest
   for (int s = wave; s < S; s += 4) {
     const int c = s * kIR_Cols + lane;
     const float d = (c < cp.cols) ? frame_depth(f, (size_t)r * cp.cols + c) : 0.f;
-    const bool valid = c < cp.cols && !(d < cp.minD || d > cp.maxD);
+    const bool valid = c < cp.cols && depth_in_range(d, cp.minD, cp.maxD);
     const unsigned long long bal = __ballot(valid);
     if (lane == 0) f.rowoff[r * S + s] = __popcll(bal);
   }
@@ -718,7 +709,7 @@ __device__ __forceinline__ void unproject_integral_body(const FrameDesc& f, cons
 #pragma unroll
     for (int i = 0; i < kIR_Rows; ++i) {
       float d;
-      if (is_raw) d = bits[i] ? raw_scale * (float)bits[i] : 0.0f;      // DepthImage_convert_16UC1_to_32FC1 (pwn_static.cpp:54-68)
+      if (is_raw) d = raw_to_metres(bits[i], raw_scale);
       else d = __uint_as_float(bits[i]);
       stage[b & 1][i * kIR_Cols + lane] = (r0 + i < rows && c < cols) ? d : 0.f;
     }
@@ -758,7 +749,7 @@ __device__ __forceinline__ void unproject_integral_body(const FrameDesc& f, cons
         const int r = r0 + lr;
         const bool in = r < rows && c < cols;
         const float dd = stage[band & 1][lr * kIR_Cols + lane];
-        const bool valid = in && !(dd < cp.minD || dd > cp.maxD);
+        const bool valid = in && depth_in_range(dd, cp.minD, cp.maxD);
         const unsigned long long bal = __ballot(valid);
         float v[kIntegralChannels];
 #pragma unroll
@@ -767,23 +758,12 @@ __device__ __forceinline__ void unproject_integral_body(const FrameDesc& f, cons
           int idx = -1, itv = -1;
           if (valid) {
             idx = sbase[band & 1][lr] + __popcll(bal & ((1ull << lane) - 1ull));
-            const float a = (float)c * dd, b = (float)r * dd;
-            float4 p;
-            p.x = dot4seq(cp.iKRt(0,0), a, cp.iKRt(0,1), b, cp.iKRt(0,2), dd, cp.iKRt(0,3), 1.0f);
-            p.y = dot4seq(cp.iKRt(1,0), a, cp.iKRt(1,1), b, cp.iKRt(1,2), dd, cp.iKRt(1,3), 1.0f);
-            p.z = dot4seq(cp.iKRt(2,0), a, cp.iKRt(2,1), b, cp.iKRt(2,2), dd, cp.iKRt(2,3), 1.0f);
-            p.w = 0.f;
+            const Vec3 p = unproject_pixel(cp.iKRt, c, r, dd);
             if (idx < capacity) {
               if (!lean) store_xyz(gP3, idx, p.x, p.y, p.z);
-              v[0] = p.x; v[1] = p.y; v[2] = p.z; v[3] = 1.0f;
-              v[4] = p.x * p.x; v[5] = p.x * p.y; v[6] = p.x * p.z;
-              v[7] = p.y * p.y; v[8] = p.y * p.z; v[9] = p.z * p.z;
+              point_channels(v, p.x, p.y, p.z);
             }
-            if (!lean) {
-              const float inv = 1.0f / dd;
-              const float px = cp.ivx * inv, py = cp.ivy * inv;
-              itv = (px > py) ? (int)px : (int)py;
-            }
+            if (!lean) itv = depth_interval(cp.ivx, cp.ivy, dd);
           }
           __builtin_nontemporal_store(idx, gindex + (unsigned)(r * cols + c));
           if (!lean) __builtin_nontemporal_store(itv, ginterval + (unsigned)(r * cols + c));
@@ -911,18 +891,13 @@ __device__ __forceinline__ void stats_pixel(const FrameDesc& f, const ConvertPar
   int itv;
   float4 P;
   if (cp.lean) {
-    // the front end kept the point and the interval to itself: the same expressions on the same depth (pinholepointprojector.h:246-251,264-274)
+    // the front end kept the point and the interval to itself: recomputed from the same depth by the same helpers
     float d;
-    if (f.raw) { const unsigned sv = stream_load(as_global(f.raw) + upix); d = sv ? f.raw_scale * (float)sv : 0.0f; }
+    if (f.raw) d = raw_to_metres(stream_load(as_global(f.raw) + upix), f.raw_scale);
     else d = stream_load(as_global(f.depth) + upix);
-    const float a = (float)c * d, b = (float)r * d;
-    P.x = dot4seq(cp.iKRt(0,0), a, cp.iKRt(0,1), b, cp.iKRt(0,2), d, cp.iKRt(0,3), 1.0f);
-    P.y = dot4seq(cp.iKRt(1,0), a, cp.iKRt(1,1), b, cp.iKRt(1,2), d, cp.iKRt(1,3), 1.0f);
-    P.z = dot4seq(cp.iKRt(2,0), a, cp.iKRt(2,1), b, cp.iKRt(2,2), d, cp.iKRt(2,3), 1.0f);
-    P.w = 0.f;
-    const float inv = 1.0f / d;
-    const float px = cp.ivx * inv, py = cp.ivy * inv;
-    itv = (px > py) ? (int)px : (int)py;
+    const Vec3 p = unproject_pixel(cp.iKRt, c, r, d);
+    P.x = p.x; P.y = p.y; P.z = p.z; P.w = 0.f;
+    itv = depth_interval(cp.ivx, cp.ivy, d);
   } else {
     itv = stream_load(ginterval + upix);
     const v3f_raw pv = stream_load3((gptr<const float>)gP + 3u * (unsigned)idx); P.x = pv.x; P.y = pv.y; P.z = pv.z; P.w = 0.f;      // one 12-byte load
@@ -1113,37 +1088,32 @@ __global__ void __launch_bounds__(256) k_cloud_transform(CloudDev cl, Mat4 m) {
 // PinholePointProjector::project (pwn_core/pinholepointprojector.cpp:33-66): z-buffer by 64-bit atomicMin on
 // (depth bits, point index): nearest point wins, ties keep the lowest index (the reference's strict '>' in a
 // sequential loop).  grid = (ceil(capacity/256), pairs), block = 256.  which: 0 = reference cloud, 1 = current.
+// _project of the aligner's projections: false when the depth is out of range or the pixel (x, y) outside the image
+__device__ __forceinline__ bool project_to_pixel(const Mat4& KRt, float minD, float maxD, int rows, int cols, const float4 p, float& d, int& x, int& y) {
+  const Vec3 ip = project_plane(KRt, p.x, p.y, p.z);
+  d = ip.z;
+  if (!depth_in_range(d, minD, maxD)) return false;
+  float fx, fy;
+  round_to_pixel(ip, fx, fy);
+  if (!in_image(fx, fy, rows, cols)) return false;
+  x = (int)fx; y = (int)fy;
+  return true;
+}
 __device__ __forceinline__ void project_point(const Mat4& KRt, float minD, float maxD, int rows, int cols,
                                               const float4 p, int i, unsigned long long* z, unsigned tag) {
-  const float ix = dot4seq(KRt(0,0), p.x, KRt(0,1), p.y, KRt(0,2), p.z, KRt(0,3), 1.0f);
-  const float iy = dot4seq(KRt(1,0), p.x, KRt(1,1), p.y, KRt(1,2), p.z, KRt(1,3), 1.0f);
-  const float d  = dot4seq(KRt(2,0), p.x, KRt(2,1), p.y, KRt(2,2), p.z, KRt(2,3), 1.0f);
-  if (d < minD || d > maxD) return;
-  const float inv = 1.0f / d;
-  const float fx = roundf(ix * inv), fy = roundf(iy * inv);
-  // int conversion of out-of-range floats is undefined on the CPU; such points are rejected by the bounds test
-  if (!(fx >= 0.f && fx < (float)cols && fy >= 0.f && fy < (float)rows)) return;
-  const int x = (int)fx, y = (int)fy;
-  atomicMin(&z[(size_t)y * cols + x], zkey(tag, d, i));
+  float d; int x, y;
+  if (project_to_pixel(KRt, minD, maxD, rows, cols, p, d, x, y)) atomicMin(&z[(size_t)y * cols + x], zkey(tag, d, i));
 }
-// depth of a point under a projector matrix: the third row of _project (pinholepointprojector.h:224-233), same expression as project_point
-__device__ __forceinline__ float point_depth(const Mat4& KRt, const float4 p) {
-  return dot4seq(KRt(2,0), p.x, KRt(2,1), p.y, KRt(2,2), p.z, KRt(2,3), 1.0f);
-}
+// depth of a point under a projector matrix: the third row of _project
+__device__ __forceinline__ float point_depth(const Mat4& KRt, const float4 p) { return affine_row(KRt, 2, p.x, p.y, p.z); }
 // 32-bit z-buffer insert (see kZ32Tag0) in two steps, so that a thread with several points has all its atomics in flight before it
 // looks at the first returned word.  z32_insert: the projection and the atomicMin; w = nullptr when the point is rejected.
 struct Z32Pending { unsigned* w; unsigned key, old; float d; };
 __device__ __forceinline__ Z32Pending z32_insert(const Mat4& KRt, float minD, float maxD, int rows, int cols, const float4 p, int i, unsigned* z, unsigned tag) {
   Z32Pending r; r.w = nullptr; r.key = 0u; r.old = ~0u; r.d = 0.f;
-  const float ix = dot4seq(KRt(0,0), p.x, KRt(0,1), p.y, KRt(0,2), p.z, KRt(0,3), 1.0f);
-  const float iy = dot4seq(KRt(1,0), p.x, KRt(1,1), p.y, KRt(1,2), p.z, KRt(1,3), 1.0f);
-  const float d  = dot4seq(KRt(2,0), p.x, KRt(2,1), p.y, KRt(2,2), p.z, KRt(2,3), 1.0f);
-  if (d < minD || d > maxD) return r;
-  const float inv = 1.0f / d;
-  const float fx = roundf(ix * inv), fy = roundf(iy * inv);
-  // int conversion of out-of-range floats is undefined on the CPU; such points are rejected by the bounds test
-  if (!(fx >= 0.f && fx < (float)cols && fy >= 0.f && fy < (float)rows)) return r;
-  r.w = &z[(size_t)(int)fy * cols + (int)fx];
+  float d; int x, y;
+  if (!project_to_pixel(KRt, minD, maxD, rows, cols, p, d, x, y)) return r;
+  r.w = &z[(size_t)y * cols + x];
   r.key = z32key(tag, i); r.d = d;
   r.old = atomicMin(r.w, r.key);
   return r;
@@ -1209,18 +1179,6 @@ __global__ void __launch_bounds__(256) k_project(const PairDesc* __restrict__ pa
 // is checked by the host, so the patterns order like the values; -0 counts as 0) in the pair's own depth image PairDesc::zdepth, cleared to ~0
 // by the host before the launch.  Pass 2: every point that has its pixel's nearest depth enters the 32-bit word by atomicMin on tag | index:
 // the nearest point, ties to the lowest index -- the reference's sequential strict '>' (pinholepointprojector.cpp:61), the word k_project leaves.
-__device__ __forceinline__ bool project_pixel(const Mat4& KRt, const AlignParams& ap, const float4 p, int& pix, unsigned& dbits) {
-  const float ix = dot4seq(KRt(0,0), p.x, KRt(0,1), p.y, KRt(0,2), p.z, KRt(0,3), 1.0f);
-  const float iy = dot4seq(KRt(1,0), p.x, KRt(1,1), p.y, KRt(1,2), p.z, KRt(1,3), 1.0f);
-  const float d  = dot4seq(KRt(2,0), p.x, KRt(2,1), p.y, KRt(2,2), p.z, KRt(2,3), 1.0f);
-  if (d < ap.minD || d > ap.maxD) return false;
-  const float inv = 1.0f / d;
-  const float fx = roundf(ix * inv), fy = roundf(iy * inv);
-  if (!(fx >= 0.f && fx < (float)ap.cols && fy >= 0.f && fy < (float)ap.rows)) return false;
-  pix = (int)fy * ap.cols + (int)fx;
-  dbits = __float_as_uint(d) & 0x7fffffffu;
-  return true;
-}
 __global__ void __launch_bounds__(256) k_project_robust(const PairDesc* __restrict__ pairs, AlignParams ap, int which, unsigned tag, int pass) {
   const PairDesc& pd = pairs[blockIdx.y];
   const CloudDev& cl = which ? pd.cur : pd.ref;
@@ -1228,8 +1186,10 @@ __global__ void __launch_bounds__(256) k_project_robust(const PairDesc* __restri
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const Mat4 KRt = uniform_iso(which ? pd.state->KRtCur : pd.state->KRt);
-  int pix; unsigned dbits;
-  if (!project_pixel(KRt, ap, load_xyz(cl.P3, i), pix, dbits)) return;
+  float d; int x, y;
+  if (!project_to_pixel(KRt, ap.minD, ap.maxD, ap.rows, ap.cols, load_xyz(cl.P3, i), d, x, y)) return;
+  const int pix = y * ap.cols + x;
+  const unsigned dbits = __float_as_uint(d) & 0x7fffffffu;
   if (pass == 0) atomicMin(&pd.zdepth[pix], dbits);
   else if (pd.zdepth[pix] == dbits) atomicMin(&(which ? pd.zcur : pd.zref)[pix], z32key(tag, i));
 }

@@ -118,6 +118,45 @@ PWN_HD void projector_matrices(const Mat3& K, const Mat4& T, Mat4& KRt, Mat4& iK
   iKRt(0,3) = T(0,3); iKRt(1,3) = T(1,3); iKRt(2,3) = T(2,3);
 }
 
+// ---- PinholePointProjector's per-point arithmetic (reference pwn_core/pinholepointprojector.h:224-274) ----------------
+// The one definition of each expression: the converter kernels, the stats pass that recomputes points, the stand-alone stage and
+// scene kernels and the host helpers of the C-ABI all call these, so that their results agree bit for bit.
+
+// the projector's depth range, as _project / _unProject / _projectInterval test it (a NaN depth passes, as there)
+PWN_HD bool depth_in_range(float d, float minD, float maxD) { return !(d < minD || d > maxD); }
+// DepthImage_convert_16UC1_to_32FC1 (pwn_core/pwn_static.cpp:54-68): raw 0 stays 0 metres
+PWN_HD float raw_to_metres(unsigned s, float scale) { return s ? scale * (float)s : 0.0f; }
+// row i of M * (x, y, z, 1)
+PWN_HD float affine_row(const Mat4& M, int i, float x, float y, float z) { return dot4seq(M(i,0), x, M(i,1), y, M(i,2), z, M(i,3), 1.0f); }
+// _unProject (pinholepointprojector.h:246-251) of pixel (column c, row r) at depth d: iKRt * (c d, r d, d, 1)
+PWN_HD Vec3 unproject_pixel(const Mat4& iKRt, int c, int r, float d) {
+  const float a = (float)c * d, b = (float)r * d;
+  const Vec3 p = { affine_row(iKRt, 0, a, b, d), affine_row(iKRt, 1, a, b, d), affine_row(iKRt, 2, a, b, d) };
+  return p;
+}
+// _projectInterval (pinholepointprojector.h:264-274): K * (R, R, 0), the image extent of the world radius R at unit depth ...
+PWN_HD void interval_scale(const Mat3& K, float R, float& ivx, float& ivy) {
+  ivx = dot3seq(K(0,0), R, K(0,1), R, K(0,2), 0.f);
+  ivy = dot3seq(K(1,0), R, K(1,1), R, K(1,2), 0.f);
+}
+// ... and at depth d, the larger of x, y truncated: int(max(ivx / d, ivy / d))
+PWN_HD int depth_interval(float ivx, float ivy, float d) {
+  const float inv = 1.0f / d;
+  const float px = ivx * inv, py = ivy * inv;
+  return (px > py) ? (int)px : (int)py;
+}
+// _project (pinholepointprojector.h:224-233), first half: ip = KRt * p = (image x, image y, depth), before the division by the depth
+PWN_HD Vec3 project_plane(const Mat4& KRt, float x, float y, float z) {
+  const Vec3 ip = { affine_row(KRt, 0, x, y, z), affine_row(KRt, 1, x, y, z), affine_row(KRt, 2, x, y, z) };
+  return ip;
+}
+// second half: ip *= 1 / d, rounded to the pixel (still float: the int conversion of an out-of-range value is undefined on the CPU)
+PWN_HD void round_to_pixel(const Vec3& ip, float& fx, float& fy) {
+  const float inv = 1.0f / ip.z;
+  fx = roundf(ip.x * inv); fy = roundf(ip.y * inv);
+}
+PWN_HD bool in_image(float fx, float fy, int rows, int cols) { return fx >= 0.f && fx < (float)cols && fy >= 0.f && fy < (float)rows; }
+
 // pwn_core/bm_se3.h:9-22
 PWN_HD Mat3 quat2mat(float qx, float qy, float qz) {
   const float qw = sqrtf(1.f - dot3seq(qx, qx, qy, qy, qz, qz));

@@ -72,22 +72,14 @@ __global__ void __launch_bounds__(256) k_gaussians(const FrameDesc* __restrict__
     const int c = c0 + threadIdx.x;
     const bool in = c < cp.cols;
     const float d = in ? frame_depth(f, (size_t)r * cp.cols + c) : 0.f;
-    const bool valid = in && !(d < cp.minD || d > cp.maxD);
-    const unsigned long long bal = __ballot(valid);
-    const int rank = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wcount[wave] = __popcll(bal);
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { const int n = wcount[w]; if (w < wave) woff += n; tot += n; }
+    const bool valid = in && depth_in_range(d, cp.minD, cp.maxD);
+    int tot;
+    const int idx = row_compact(valid, wcount, wave, lane, base, tot);
     if (valid) {
-      const int idx = base + woff + rank;
       if (idx < f.cloud.capacity) {
         GaussD g;
-        const float a = (float)c * d, b = (float)r * d;
-        g.mean[0] = dot4seq(cp.iKRt(0,0), a, cp.iKRt(0,1), b, cp.iKRt(0,2), d, cp.iKRt(0,3), 1.0f);
-        g.mean[1] = dot4seq(cp.iKRt(1,0), a, cp.iKRt(1,1), b, cp.iKRt(1,2), d, cp.iKRt(1,3), 1.0f);
-        g.mean[2] = dot4seq(cp.iKRt(2,0), a, cp.iKRt(2,1), b, cp.iKRt(2,2), d, cp.iKRt(2,3), 1.0f);
+        const Vec3 mean = unproject_pixel(cp.iKRt, c, r, d);
+        g.mean[0] = mean.x; g.mean[1] = mean.y; g.mean[2] = mean.z;
         const float z = d;
         const float zVariation = (alpha * z * z) / (fB + z * alpha);
         Mat3 J;
@@ -228,15 +220,14 @@ __global__ void __launch_bounds__(256) k_merge_classify(CloudDev cl, int n, Mat4
   if (i >= n) return;
   const float4 p = load_xyz(cl.P3, i);
   int res = -1;
-  // PinholePointProjector::_project (pinholepointprojector.h:224-233): x, y stay -1 when the depth is out of the projector's range
-  const float ix = dot4seq(KRt(0,0), p.x, KRt(0,1), p.y, KRt(0,2), p.z, KRt(0,3), 1.0f);
-  const float iy = dot4seq(KRt(1,0), p.x, KRt(1,1), p.y, KRt(1,2), p.z, KRt(1,3), 1.0f);
-  const float d  = dot4seq(KRt(2,0), p.x, KRt(2,1), p.y, KRt(2,2), p.z, KRt(2,3), 1.0f);
-  bool ok = !(d < minD || d > maxD);
+  // PinholePointProjector::_project: x, y stay -1 when the depth is out of the projector's range
+  const Vec3 ip = project_plane(KRt, p.x, p.y, p.z);
+  const float d = ip.z;
+  const bool ok = depth_in_range(d, minD, maxD);
   float fx = -1.f, fy = -1.f;
-  if (ok) { const float inv = 1.0f / d; fx = roundf(ix * inv); fy = roundf(iy * inv); }
+  if (ok) round_to_pixel(ip, fx, fy);
   // merger.cpp:49-54
-  if (ok && !(d < 0 || d > maxPointDepth) && fx >= 0.f && fx < (float)cols && fy >= 0.f && fy < (float)rows) {
+  if (ok && !(d < 0 || d > maxPointDepth) && in_image(fx, fy, rows, cols)) {
     const int x = (int)fx, y = (int)fy;
     const unsigned long long key = z[(size_t)y * cols + x];
     const int targetIndex = zkey_index(key, tag);

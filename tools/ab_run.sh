@@ -3,7 +3,7 @@
 O=$(mktemp -d); trap 'rm -rf "$O"' EXIT
 for rep in 1 2; do
 for lib in build/variants/*.so; do
-  PWN_HIP_LIB=$PWD/$lib timeout 300 python bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-latency --no-extras $AB_ARGS > $O/b.json 2>$O/b.err || { echo "$lib FAILED"; tail -3 $O/b.err; continue; }
+  PWN_HIP_LIB=$PWD/$lib timeout -k 10 300 python bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-latency --no-extras $AB_ARGS > $O/b.json 2>$O/b.err || { echo "$lib FAILED"; tail -3 $O/b.err; exit 1; }
   python -c "
 import json; d=json.load(open('$O/b.json')); s=d['stage_ms_per_step']; print('$lib', round(d['value']), 'ms/step', round(d['ms_per_step'],2), {k: round(v,2) for k,v in s.items() if v}, 'chi2', round(d['counters_mean']['chi2_final'],3))"
 done
