@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include "../../include/pwn_hip.h"
 #include "../../include/pwn_hip_testing.h"
+#include "pwn_buffers.h"
 #include "pwn_kernels.h"
 #include "pwn_scene_kernels.h"
 #include "pwn_stats.h"
@@ -70,7 +71,7 @@ struct pwn_hip_cloud {
   // it was made from.  Projecting a cloud with the very projector it was unprojected with (same K, size, range, identity pose) returns
   // this image: every point falls back on its own pixel (the round trip moves it by < 0.01 pixel and its depth not at all), so batch
   // alignments take it as the current index image and skip that projection.  Anything that changes the points invalidates it.
-  int* idximg = nullptr; size_t idx_cap = 0; bool idx_valid = false;
+  DevBuf<int> idximg; bool idx_valid = false;
   int idx_rows = 0, idx_cols = 0; float idx_K[9] = { 0 }; float idx_minD = 0.f, idx_maxD = 0.f;
 };
 
@@ -93,28 +94,28 @@ struct pwn_hip_ctx {
   int concurrency = 4;
   int omega_sym = 1;                       // pwn_hip_ctx_set_omega_storage: storage of the point information matrices of clouds created from now on (default: sym6)
   // convert workspaces (per slot)
-  float* depth_ws = nullptr; int* index_ws = nullptr; int* interval_ws = nullptr; float* integral_ws = nullptr; int* rowoff_ws = nullptr;
-  uint16_t* raw_ws = nullptr;
-  unsigned long long* carry_ws = nullptr; size_t carry_slot = 0; size_t rowoff_slot = 0;   // single-pass integral image: hand-over words, strip offsets
-  unsigned convert_epoch = 0; int* fault_dev = nullptr;
+  DevBuf<float> depth_ws; DevBuf<int> index_ws, interval_ws; DevBuf<float> integral_ws; DevBuf<int> rowoff_ws;
+  DevBuf<uint16_t> raw_ws;
+  DevBuf<unsigned long long> carry_ws; size_t carry_slot = 0; size_t rowoff_slot = 0;   // single-pass integral image: hand-over words, strip offsets
+  unsigned convert_epoch = 0; DevBuf<int> fault_dev;
   int last_convert_fault = 0;              // fault word of the last converter launch of the CURRENT call (1 = a bounded poll timed out); reset when a call starts
   int spin_limit = kSpinLimit; int dbg_withhold = -1;        // pwn_hip_debug_withhold_carry (test hook)
   int dbg_withhold_once = 0;                                 // the hook switches itself off after the first launch that timed out
   int convert_retries = 0;                                   // conversions repeated after a hand-over time-out (pwn_hip_debug_convert_retries)
   // align workspaces (per slot)
-  unsigned long long* zref_ws = nullptr;        // 64-bit z-buffer of the stand-alone projection and of Merger::merge (one image)
-  unsigned* z32ref_ws = nullptr; unsigned* z32cur_ws = nullptr;      // the aligner's 32-bit z-buffers (tag | index), one image per slot
-  int* curidx_ws = nullptr; double* partials_ws = nullptr; PairState* state_ws = nullptr;
+  DevBuf<unsigned long long> zref_ws;           // 64-bit z-buffer of the stand-alone projection and of Merger::merge (one image)
+  DevBuf<unsigned> z32ref_ws, z32cur_ws;        // the aligner's 32-bit z-buffers (tag | index), one image per slot
+  DevBuf<int> curidx_ws; DevBuf<double> partials_ws; DevBuf<PairState> state_ws;
   int nblocks_max = 0;
   // descriptors (one entry per frame / pair of a batch call; grown on demand)
   int desc_cap = 0;
-  FrameDesc* frames_dev = nullptr; PairDesc* pairs_dev = nullptr; RawDesc* raw_dev = nullptr; int* counts_dev = nullptr;
-  FrameDesc* frames_host = nullptr; PairDesc* pairs_host = nullptr; RawDesc* raw_host = nullptr; PairState* state_host = nullptr; int* counts_host = nullptr;
+  DevBuf<FrameDesc> frames_dev; DevBuf<PairDesc> pairs_dev; DevBuf<RawDesc> raw_dev; DevBuf<int> counts_dev;
+  HostBuf<FrameDesc> frames_host; HostBuf<PairDesc> pairs_host; HostBuf<RawDesc> raw_host; HostBuf<PairState> state_host; HostBuf<int> counts_host;
+  DevBuf<MatchAcc> match_dev; HostBuf<MatchAcc> match_host;
+  DevBuf<SolveOut> stats_dev; HostBuf<SolveOut> stats_host;
   // misc scratch
-  MatchAcc* match_dev = nullptr; MatchAcc* match_host = nullptr; int match_cap = 0;
-  SolveOut* stats_dev = nullptr; SolveOut* stats_host = nullptr;
-  SolveOut* solve_dev = nullptr; int* counters_dev = nullptr; int2* corr_ws = nullptr; int* scratch_count = nullptr;
-  float* io_ws = nullptr;   // N*16 floats staging for cloud up/download
+  DevBuf<SolveOut> solve_dev; DevBuf<int> counters_dev; DevBuf<int2> corr_ws; DevBuf<int> scratch_count;
+  DevBuf<float> io_ws;      // N*16 floats staging for cloud up/download
   // images of the last single align
   int img_rows = 0, img_cols = 0; bool img_valid = false; unsigned img_ref_tag = kZ32Tag0, img_cur_tag = kZ32Tag0;
   int img_pair = 0;                         // descriptor (pairs_host / pairs_dev entry) of the pair whose images sit in workspace slot 0
@@ -134,22 +135,22 @@ struct pwn_hip_ctx {
   std::vector<hipEvent_t> event_pool;
   hipEvent_t t0 = nullptr, t1 = nullptr;
   // scene-stage scratch (grown on demand)
-  int* scene_i[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr }; size_t scene_icap = 0;
-  unsigned long long* scene_k[3] = { nullptr, nullptr, nullptr }; size_t scene_kcap = 0;
-  int* scene_total = nullptr;
+  DevBuf<int> scene_i[8];
+  DevBuf<unsigned long long> scene_k[3];
+  DevBuf<int> scene_total;
   // Retired clouds kept for reuse: pwn_hip_cloud_create / _destroy are called once per frame by makeCloud-style callers (the reference
   // returns a `new Cloud` per depth image, pwn_matcher_base.cpp:77-85), and hipMalloc / hipFree of the point arrays cost more than the
   // conversion of a frame.  Bounded by kCloudPoolBytes.
   std::vector<pwn_hip_cloud*> cloud_pool; size_t cloud_pool_bytes = 0;
   AsyncConvert* async = nullptr;           // pwn_hip_convert_scaled_begin: created on first use
-  void* flat_hdr_host = nullptr;           // page-locked staging of a flat cloud's 256-byte header (pwn_hip_cloud_export / _import)
-  float* records_ws = nullptr; int records_cap = 0;      // result records of a batch on their way to host memory (k_pack_records)
-  int* ids_dev = nullptr; int ids_cap = 0;               // the caller's pair ids of those records
+  HostBuf<char> flat_hdr_host;             // page-locked staging of a flat cloud's 256-byte header (pwn_hip_cloud_export / _import)
+  DevBuf<float> records_ws;                              // result records of a batch on their way to host memory (k_pack_records)
+  DevBuf<int> ids_dev;                                   // the caller's pair ids of those records
   // Projection fault path (z32_settle): a page-locked word the projection kernels raise when a pixel's settle loop gave up; the call is then
   // repeated with the two-pass projection (k_project_robust) and its depth images (allocated on first use)
   void (*enqueued_cb)(void*) = nullptr; void* enqueued_user = nullptr;      // pwn_hip_ctx_set_enqueued_callback
-  int* align_fault_host = nullptr;
-  unsigned* zdepth_ws = nullptr;
+  HostBuf<int> align_fault_host;
+  DevBuf<unsigned> zdepth_ws;
   int settle_guard = kSettleGuard;                       // pwn_hip_debug_set_settle_guard (test hook)
   int last_align_fault = 0;                              // the last alignment call ended with the fault word raised
   int projection_fallbacks = 0;                          // calls repeated with the two-pass projection so far (pwn_hip_debug_projection_fallbacks)
@@ -159,12 +160,12 @@ namespace {
 
 constexpr size_t kCloudPoolBytes = 1ull << 30;
 size_t om_floats(const CloudDev& d) { return (size_t)d.capacity * 3 * (size_t)om_planes(d.omSym); }      // floats of the Om planes (9 or 6 per point)
-size_t cloud_core_bytes(const pwn_hip_cloud* c) { return (size_t)c->d.capacity * (3 * sizeof(float) + sizeof(float4)) + om_floats(c->d) * sizeof(float) + c->idx_cap * sizeof(int); }
+size_t cloud_core_bytes(const pwn_hip_cloud* c) { return (size_t)c->d.capacity * (3 * sizeof(float) + sizeof(float4)) + om_floats(c->d) * sizeof(float) + c->idximg.cap * sizeof(int); }
 void cloud_free(pwn_hip_cloud* c) {
   void* p[] = { c->d.P3, c->d.Nc, c->d.Om, c->d.OmN, c->d.St, c->d.count, c->sb.G, c->sb.Gf,
-                c->back.P3, c->back.Nc, c->back.Om, c->back.OmN, c->back.St, c->sback.G, c->sback.Gf, c->idximg };
+                c->back.P3, c->back.Nc, c->back.Om, c->back.OmN, c->back.St, c->sback.G, c->sback.Gf };
   for (void* q : p) if (q) (void)hipFree(q);
-  delete c;
+  delete c;                                   // and with it the index image
 }
 
 // the fused correspondence + linearize pass: the throughput shape, or the latency shape (same sums bit for bit, see k_corr_linearize_lat)
@@ -448,7 +449,7 @@ int take_tags32(pwn_hip_ctx* ctx, unsigned need, unsigned* first) {
 }
 // the two-pass projection's depth images: one per workspace slot, allocated when a call first needs them
 int ensure_zdepth(pwn_hip_ctx* ctx) {
-  if (!ctx->zdepth_ws) HIPCHK(ctx, hipMalloc((void**)&ctx->zdepth_ws, (size_t)ctx->max_batch * ctx->N * sizeof(unsigned)), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->zdepth_ws.ensure((size_t)ctx->max_batch * ctx->N), PWN_HIP_ERR_ALLOCATION);
   return PWN_HIP_OK;
 }
 // An alignment attempt starts here and ends in take_align_fault; a robust one (the repeat) runs every projection with the two-pass kernels
@@ -481,35 +482,23 @@ int align_nblocks(int N) { return (N + kAlignBlock * kPixPerThread - 1) / (kAlig
 int ensure_desc(pwn_hip_ctx* ctx, int n) {
   if (n <= ctx->desc_cap) return PWN_HIP_OK;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
-  void* dev[] = { ctx->frames_dev, ctx->pairs_dev, ctx->raw_dev, ctx->counts_dev, ctx->state_ws };
-  for (void* p : dev) if (p) (void)hipFree(p);
-  void* host[] = { ctx->frames_host, ctx->pairs_host, ctx->raw_host, ctx->state_host, ctx->counts_host };
-  for (void* p : host) if (p) (void)hipHostFree(p);
-  ctx->frames_dev = nullptr; ctx->pairs_dev = nullptr; ctx->raw_dev = nullptr; ctx->counts_dev = nullptr; ctx->state_ws = nullptr;
-  ctx->frames_host = nullptr; ctx->pairs_host = nullptr; ctx->raw_host = nullptr; ctx->state_host = nullptr; ctx->counts_host = nullptr;
   ctx->desc_cap = 0;
   ctx->img_valid = false;                    // the descriptor of the last alignment's pair goes with the old arrays
   const size_t B = (size_t)std::max(n, 16);
-  HIPCHK(ctx, hipMalloc((void**)&ctx->frames_dev, B * sizeof(FrameDesc)), PWN_HIP_ERR_ALLOCATION);
-  HIPCHK(ctx, hipMalloc((void**)&ctx->pairs_dev, B * sizeof(PairDesc)), PWN_HIP_ERR_ALLOCATION);
-  HIPCHK(ctx, hipMalloc((void**)&ctx->raw_dev, B * sizeof(RawDesc)), PWN_HIP_ERR_ALLOCATION);
-  HIPCHK(ctx, hipMalloc((void**)&ctx->counts_dev, (B + 1) * sizeof(int)), PWN_HIP_ERR_ALLOCATION);
-  HIPCHK(ctx, hipMalloc((void**)&ctx->state_ws, B * sizeof(PairState)), PWN_HIP_ERR_ALLOCATION);
-  HIPCHK(ctx, hipHostMalloc((void**)&ctx->frames_host, B * sizeof(FrameDesc)), PWN_HIP_ERR_ALLOCATION);
-  HIPCHK(ctx, hipHostMalloc((void**)&ctx->pairs_host, B * sizeof(PairDesc)), PWN_HIP_ERR_ALLOCATION);
-  HIPCHK(ctx, hipHostMalloc((void**)&ctx->raw_host, B * sizeof(RawDesc)), PWN_HIP_ERR_ALLOCATION);
-  HIPCHK(ctx, hipHostMalloc((void**)&ctx->state_host, B * sizeof(PairState)), PWN_HIP_ERR_ALLOCATION);
-  HIPCHK(ctx, hipHostMalloc((void**)&ctx->counts_host, (B + 1) * sizeof(int)), PWN_HIP_ERR_ALLOCATION);
-  if (ctx->match_dev) (void)hipFree(ctx->match_dev);
-  if (ctx->match_host) (void)hipHostFree(ctx->match_host);
-  ctx->match_dev = nullptr; ctx->match_host = nullptr;
-  HIPCHK(ctx, hipMalloc((void**)&ctx->match_dev, B * sizeof(MatchAcc)), PWN_HIP_ERR_ALLOCATION);
-  HIPCHK(ctx, hipHostMalloc((void**)&ctx->match_host, B * sizeof(MatchAcc)), PWN_HIP_ERR_ALLOCATION);
-  if (ctx->stats_dev) (void)hipFree(ctx->stats_dev);
-  if (ctx->stats_host) (void)hipHostFree(ctx->stats_host);
-  ctx->stats_dev = nullptr; ctx->stats_host = nullptr;
-  HIPCHK(ctx, hipMalloc((void**)&ctx->stats_dev, B * sizeof(SolveOut)), PWN_HIP_ERR_ALLOCATION);
-  HIPCHK(ctx, hipHostMalloc((void**)&ctx->stats_host, B * sizeof(SolveOut)), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->frames_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->pairs_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->raw_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->counts_dev.ensure(B + 1), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->state_ws.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->frames_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->pairs_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->raw_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->state_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->counts_host.ensure(B + 1), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->match_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->match_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->stats_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->stats_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
   ctx->desc_cap = (int)B;
   return PWN_HIP_OK;
 }
@@ -519,6 +508,12 @@ int ensure_desc(pwn_hip_ctx* ctx, int n) {
 // launches of at least this many frames take the single-pass strip kernel; measured on MI355X at VGA, three kernels vs single pass: 8 frames 0.20 vs
 // 0.27 ms, 16 frames 0.38 vs 0.35, 32 frames 0.74 vs 0.58
 constexpr int kSinglePassMinFrames = 16;
+// the stats pass over n frames
+void launch_stats(const ConvertParams& cp, const FrameDesc* fr, int n, hipStream_t st) {
+  const unsigned perFrame = (unsigned)cp.rows * (unsigned)((cp.cols + 255) / 256);
+  const unsigned nblk = (n >= 8 ? 8u * (unsigned)((n + 7) / 8) : (unsigned)n) * perFrame;      // see k_stats: XCD-aware placement from 8 frames on
+  hipLaunchKernelGGL(k_stats, dim3(nblk), dim3(256), 0, st, fr, cp, n);
+}
 int launch_convert(pwn_hip_ctx* ctx, const ConvertParams& cp, int base, int n, hipStream_t st, int* fault_out = nullptr) {
   const FrameDesc* fr = ctx->frames_dev + base;
   if (n >= kSinglePassMinFrames) {
@@ -556,19 +551,16 @@ int launch_convert(pwn_hip_ctx* ctx, const ConvertParams& cp, int base, int n, h
                          (const int*)ctx->fault_dev, fault_out); }
   }
   { StageTimer t(ctx, "stats", st);
-    const unsigned perFrame = (unsigned)cp.rows * (unsigned)((cp.cols + 255) / 256);
-    const unsigned nblk = (n >= 8 ? 8u * (unsigned)((n + 7) / 8) : (unsigned)n) * perFrame;      // see k_stats: XCD-aware placement from 8 frames on
-    hipLaunchKernelGGL(k_stats, dim3(nblk), dim3(256), 0, st, fr, cp, n); }
+    launch_stats(cp, fr, n, st); }
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
 }
-void fill_frame(pwn_hip_ctx* ctx, int entry, int slot, const float* depth_dev, const CloudDev& cl, int rows) {
+void fill_frame(pwn_hip_ctx* ctx, int entry, int slot, const float* depth_dev, const CloudDev& cl) {
   FrameDesc& f = ctx->frames_host[entry];
   f.depth = depth_dev; f.raw = nullptr; f.raw_scale = 0.f;
   f.index = ctx->index_ws + (size_t)slot * ctx->N;
   f.interval = ctx->interval_ws + (size_t)slot * ctx->N;
   f.integral = ctx->integral_ws + (size_t)slot * ctx->N * kIntegralChannels;
-  (void)rows;
   f.rowoff = ctx->rowoff_ws + (size_t)slot * ctx->rowoff_slot;
   f.carry = ctx->carry_ws + (size_t)slot * ctx->carry_slot;
   f.cloud = cl;
@@ -577,6 +569,15 @@ void fill_frame(pwn_hip_ctx* ctx, int entry, int slot, const float* depth_dev, c
 int ensure_stats(pwn_hip_ctx* ctx, pwn_hip_cloud* c) {
   if (!c->d.St) HIPCHK(ctx, hipMalloc(&c->d.St, sizeof(float) * 16 * (size_t)c->d.capacity), PWN_HIP_ERR_ALLOCATION);
   return PWN_HIP_OK;
+}
+// explicit Omega_n planes of a cloud (uploaded, imported and scene clouds; converted clouds keep the two class matrices only).  Dropping
+// them is for a caller that knows no stream still reads them.
+int ensure_omega_n(pwn_hip_ctx* ctx, pwn_hip_cloud* c) {
+  if (!c->d.OmN) HIPCHK(ctx, hipMalloc((void**)&c->d.OmN, (size_t)c->d.capacity * 9 * sizeof(float)), PWN_HIP_ERR_ALLOCATION);
+  return PWN_HIP_OK;
+}
+void drop_omega_n(pwn_hip_cloud* c) {
+  if (c->d.OmN) { (void)hipFree(c->d.OmN); c->d.OmN = nullptr; }
 }
 // direct: the kernels of the call have written counts and fault flag into counts_host themselves (FrameDesc::count_out, launch_convert's fault_out)
 // the two halves of sync_and_counts for callers that wait for the stream themselves: queue the copy back of counts + fault flag; digest them
@@ -644,18 +645,15 @@ int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const S
     if (keep_stats) { if (int rc = ensure_stats(ctx, c)) return rc; }
     c->has_stats = keep_stats != 0;
     c->n_gauss = 0;                              // the cloud's Gaussians (if any) belonged to its previous content
-    if (c->d.OmN) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH); (void)hipFree(c->d.OmN); c->d.OmN = nullptr; }
+    if (c->d.OmN) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH); drop_omega_n(c); }
     make_omega_n_classes(p, c->d);
     job.src[i] = frames[i];
     const float* depth_dev = nullptr;
     if (!raw) depth_dev = reinterpret_cast<const float*>(frames[i]);         // patched below if it is a host pointer
-    fill_frame(ctx, i, slot[i], depth_dev, c->d, rows);
-    if (c->idx_cap < N) {
+    fill_frame(ctx, i, slot[i], depth_dev, c->d);
+    if (c->idximg.cap < N) {
       HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
-      if (c->idximg) (void)hipFree(c->idximg);
-      c->idximg = nullptr; c->idx_cap = 0;
-      HIPCHK(ctx, hipMalloc((void**)&c->idximg, N * sizeof(int)), PWN_HIP_ERR_ALLOCATION);
-      c->idx_cap = N;
+      HIPCHK(ctx, c->idximg.ensure(N), PWN_HIP_ERR_ALLOCATION);
     }
     ctx->frames_host[i].index = c->idximg;                    // the index image stays with the cloud
     c->idx_valid = cp.hasOffset == 0;
@@ -859,6 +857,39 @@ static hipError_t make_stream(hipStream_t* s, bool high_priority) {
   }
   return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
 }
+// the workspaces of a context for max_batch images of N pixels; a failure leaves a half-built context that pwn_hip_ctx_destroy takes as it is
+static int ctx_alloc(pwn_hip_ctx* ctx) {
+  const size_t N = ctx->N, B = (size_t)ctx->max_batch;
+  HIPCHK(ctx, ctx->depth_ws.alloc(B * N), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->raw_ws.alloc(B * N), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->index_ws.alloc(B * N), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->interval_ws.alloc(B * N), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->integral_ws.alloc(B * N * kIntegralChannels), PWN_HIP_ERR_ALLOCATION);
+  {   // any rows x cols image with rows*cols <= N and rows, cols <= M: rows*strips <= N/64 + M, strips*bands <= N/1024 + M/64 + M/16 + 1
+    const size_t M = (size_t)std::max(ctx->max_rows, ctx->max_cols);
+    ctx->rowoff_slot = N / 64 + M + 64;
+    ctx->carry_slot = (N / ((size_t)kIR_Cols * kIR_Rows) + M / kIR_Cols + M / kIR_Rows + 2) * (size_t)kII_Chains;
+  }
+  HIPCHK(ctx, ctx->rowoff_ws.alloc(B * ctx->rowoff_slot), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->carry_ws.alloc(B * ctx->carry_slot), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->fault_dev.alloc(1), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->align_fault_host.alloc(1), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->flat_hdr_host.alloc(256), PWN_HIP_ERR_ALLOCATION);
+  *ctx->align_fault_host = 0;
+  if (hipMemset(ctx->carry_ws, 0, B * ctx->carry_slot * sizeof(unsigned long long)) != hipSuccess || hipMemset(ctx->fault_dev, 0, sizeof(int)) != hipSuccess)
+    return fail(ctx, PWN_HIP_ERR_ALLOCATION, "hipMemset of the hand-over workspace failed");
+  HIPCHK(ctx, ctx->zref_ws.alloc(N), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->z32ref_ws.alloc(B * N), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->z32cur_ws.alloc(B * N), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->curidx_ws.alloc(B * N), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->partials_ws.alloc(B * (size_t)ctx->nblocks_max * kAccN), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->solve_dev.alloc(1), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->counters_dev.alloc(16), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->corr_ws.alloc(N), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->scratch_count.alloc(1), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->io_ws.alloc(N * 16), PWN_HIP_ERR_ALLOCATION);
+  return ensure_desc(ctx, std::max(16, ctx->max_batch));
+}
 static int ctx_create(pwn_hip_ctx** out, int device, int max_rows, int max_cols, int max_batch, bool high_priority) {
   if (!out || max_rows <= 0 || max_cols <= 0 || max_batch <= 0) return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, "bad ctx_create argument");
   *out = nullptr;
@@ -870,10 +901,7 @@ static int ctx_create(pwn_hip_ctx** out, int device, int max_rows, int max_cols,
   ctx->device = device; ctx->max_rows = max_rows; ctx->max_cols = max_cols; ctx->max_batch = max_batch;
   ctx->N = (size_t)max_rows * max_cols;
   { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) ctx->num_cus = cus; }
-  const size_t N = ctx->N, B = (size_t)max_batch;
-  ctx->nblocks_max = align_nblocks((int)N);
-#define ALLOC(ptr, bytes) do { hipError_t e_ = hipMalloc((void**)&(ptr), (bytes)); if (e_ != hipSuccess) { std::string m = std::string("hipMalloc ") + #ptr + ": " + hipGetErrorString(e_); pwn_hip_ctx_destroy(ctx); return fail(nullptr, PWN_HIP_ERR_ALLOCATION, m); } } while (0)
-#define HALLOC(ptr, bytes) do { hipError_t e_ = hipHostMalloc((void**)&(ptr), (bytes)); if (e_ != hipSuccess) { std::string m = std::string("hipHostMalloc ") + #ptr + ": " + hipGetErrorString(e_); pwn_hip_ctx_destroy(ctx); return fail(nullptr, PWN_HIP_ERR_ALLOCATION, m); } } while (0)
+  ctx->nblocks_max = align_nblocks((int)ctx->N);
   if (make_stream(&ctx->own_stream, high_priority) != hipSuccess) { delete ctx; return fail(nullptr, PWN_HIP_ERR_ALLOCATION, "hipStreamCreate failed"); }
   ctx->stream = ctx->own_stream;
   (void)make_stream(&ctx->stream2, high_priority);
@@ -882,38 +910,8 @@ static int ctx_create(pwn_hip_ctx** out, int device, int max_rows, int max_cols,
   (void)hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking);
   (void)hipEventCreateWithFlags(&ctx->copy_ev, hipEventDisableTiming);
   (void)hipEventCreateWithFlags(&ctx->foreign_ev, hipEventDisableTiming);
-  ALLOC(ctx->depth_ws, B * N * sizeof(float));
-  ALLOC(ctx->raw_ws, B * N * sizeof(uint16_t));
-  ALLOC(ctx->index_ws, B * N * sizeof(int));
-  ALLOC(ctx->interval_ws, B * N * sizeof(int));
-  ALLOC(ctx->integral_ws, B * N * kIntegralChannels * sizeof(float));
-  {   // any rows x cols image with rows*cols <= N and rows, cols <= M: rows*strips <= N/64 + M, strips*bands <= N/1024 + M/64 + M/16 + 1
-    const size_t M = (size_t)std::max(max_rows, max_cols);
-    ctx->rowoff_slot = N / 64 + M + 64;
-    ctx->carry_slot = (N / ((size_t)kIR_Cols * kIR_Rows) + M / kIR_Cols + M / kIR_Rows + 2) * (size_t)kII_Chains;
-  }
-  ALLOC(ctx->rowoff_ws, B * ctx->rowoff_slot * sizeof(int));
-  ALLOC(ctx->carry_ws, B * ctx->carry_slot * sizeof(unsigned long long));
-  ALLOC(ctx->fault_dev, sizeof(int));
-  HALLOC(ctx->align_fault_host, sizeof(int));
-  HALLOC(ctx->flat_hdr_host, 256);
-  *ctx->align_fault_host = 0;
-  if (hipMemset(ctx->carry_ws, 0, B * ctx->carry_slot * sizeof(unsigned long long)) != hipSuccess || hipMemset(ctx->fault_dev, 0, sizeof(int)) != hipSuccess) {
-    pwn_hip_ctx_destroy(ctx); return fail(nullptr, PWN_HIP_ERR_ALLOCATION, "hipMemset of the hand-over workspace failed"); }
-  ALLOC(ctx->zref_ws, N * sizeof(unsigned long long));
-  ALLOC(ctx->z32ref_ws, B * N * sizeof(unsigned));
-  ALLOC(ctx->z32cur_ws, B * N * sizeof(unsigned));
-  ALLOC(ctx->curidx_ws, B * N * sizeof(int));
-  ALLOC(ctx->partials_ws, B * (size_t)ctx->nblocks_max * kAccN * sizeof(double));
-  ALLOC(ctx->solve_dev, sizeof(SolveOut));
-  ALLOC(ctx->counters_dev, 16 * sizeof(int));
-  ALLOC(ctx->corr_ws, N * sizeof(int2));
-  ALLOC(ctx->scratch_count, sizeof(int));
-  ALLOC(ctx->io_ws, N * 16 * sizeof(float));
-#undef ALLOC
-#undef HALLOC
   (void)hipEventCreateWithFlags(&ctx->t0, hipEventDisableSystemFence); (void)hipEventCreateWithFlags(&ctx->t1, hipEventDisableSystemFence);
-  if (int rc = ensure_desc(ctx, std::max(16, max_batch))) { std::string m = ctx->err; pwn_hip_ctx_destroy(ctx); return fail(nullptr, rc, m); }
+  if (int rc = ctx_alloc(ctx)) { std::string m = ctx->err; pwn_hip_ctx_destroy(ctx); return fail(nullptr, rc, m); }
   *out = ctx;
   return PWN_HIP_OK;
 }
@@ -930,29 +928,12 @@ int pwn_hip_ctx_destroy(pwn_hip_ctx* ctx) {
   }
   if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);      // pwn_hip_copy_async transfers still in flight
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  void* dev[] = { ctx->depth_ws, ctx->raw_ws, ctx->index_ws, ctx->interval_ws, ctx->integral_ws, ctx->rowoff_ws, ctx->carry_ws, ctx->fault_dev, ctx->zref_ws, ctx->z32ref_ws, ctx->z32cur_ws, ctx->curidx_ws,
-                  ctx->partials_ws, ctx->state_ws, ctx->frames_dev, ctx->pairs_dev, ctx->raw_dev, ctx->counts_dev, ctx->solve_dev, ctx->counters_dev,
-                  ctx->corr_ws, ctx->scratch_count, ctx->io_ws };
-  for (void* p : dev) if (p) (void)hipFree(p);
-  void* host[] = { ctx->frames_host, ctx->pairs_host, ctx->raw_host, ctx->state_host, ctx->counts_host, ctx->match_host };
-  for (void* p : host) if (p) (void)hipHostFree(p);
-  if (ctx->match_dev) (void)hipFree(ctx->match_dev);
-  if (ctx->stats_dev) (void)hipFree(ctx->stats_dev);
-  if (ctx->stats_host) (void)hipHostFree(ctx->stats_host);
   collect_stage_times(ctx);
   for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
   if (ctx->t0) (void)hipEventDestroy(ctx->t0);
   if (ctx->t1) (void)hipEventDestroy(ctx->t1);
   for (pwn_hip_cloud* r : ctx->cloud_pool) cloud_free(r);
   ctx->cloud_pool.clear();
-  for (int k = 0; k < 8; ++k) if (ctx->scene_i[k]) (void)hipFree(ctx->scene_i[k]);
-  for (int k = 0; k < 3; ++k) if (ctx->scene_k[k]) (void)hipFree(ctx->scene_k[k]);
-  if (ctx->scene_total) (void)hipFree(ctx->scene_total);
-  if (ctx->records_ws) (void)hipFree(ctx->records_ws);
-  if (ctx->ids_dev) (void)hipFree(ctx->ids_dev);
-  if (ctx->zdepth_ws) (void)hipFree(ctx->zdepth_ws);
-  if (ctx->align_fault_host) (void)hipHostFree(ctx->align_fault_host);
-  if (ctx->flat_hdr_host) (void)hipHostFree(ctx->flat_hdr_host);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   for (int k = 0; k < 2; ++k) { if (ctx->extra[k]) (void)hipStreamDestroy(ctx->extra[k]); if (ctx->join_extra[k]) (void)hipEventDestroy(ctx->join_extra[k]); }
@@ -963,6 +944,8 @@ int pwn_hip_ctx_destroy(pwn_hip_ctx* ctx) {
   ctx->sync_events.clear();
   if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
   if (ctx->join_ev) (void)hipEventDestroy(ctx->join_ev);
+  // every workspace, descriptor array and mirror is a member that frees itself here: the context's device is current (set above; the helper
+  // contexts live on the same one) and both streams were synchronised above, so nothing queued still uses them
   delete ctx;
   return PWN_HIP_OK;
 }
@@ -1088,9 +1071,9 @@ int pwn_hip_debug_stats_from_integral(pwn_hip_ctx* ctx, const pwn_hip_converter_
     c->has_stats = keep_stats != 0;
     c->n_gauss = 0;
     c->idx_valid = false;
-    if (c->d.OmN) { (void)hipFree(c->d.OmN); c->d.OmN = nullptr; }
+    drop_omega_n(c);
     make_omega_n_classes(p, c->d);
-    fill_frame(ctx, i, i, nullptr, c->d, rows);
+    fill_frame(ctx, i, i, nullptr, c->d);
     const FrameDesc& f = ctx->frames_host[i];
     HIPCHK(ctx, hipMemcpyAsync(f.index, index_image + (size_t)i * N, N * sizeof(int), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
     HIPCHK(ctx, hipMemcpyAsync(f.interval, interval_image + (size_t)i * N, N * sizeof(int), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
@@ -1098,9 +1081,7 @@ int pwn_hip_debug_stats_from_integral(pwn_hip_ctx* ctx, const pwn_hip_converter_
                                ctx->stream), PWN_HIP_ERR_COPY);
   }
   HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev, ctx->frames_host, sizeof(FrameDesc) * nframes, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
-  const unsigned perFrame = (unsigned)cp.rows * (unsigned)((cp.cols + 255) / 256);
-  const unsigned nblk = (nframes >= 8 ? 8u * (unsigned)((nframes + 7) / 8) : (unsigned)nframes) * perFrame;      // launch_convert's grid
-  hipLaunchKernelGGL(k_stats, dim3(nblk), dim3(256), 0, ctx->stream, ctx->frames_dev, cp, nframes);
+  launch_stats(cp, ctx->frames_dev, nframes, ctx->stream);      // launch_convert's grid
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
@@ -1116,9 +1097,9 @@ __global__ void __launch_bounds__(256) k_debug_trig(int n, const float* __restri
 int pwn_hip_debug_trig_eval(pwn_hip_ctx* ctx, int n, const float* y, const float* x, float* theta, float* cos_theta, float* sin_theta) {
   if (!ctx || n < 0 || (n > 0 && (!y || !x || !theta || !cos_theta || !sin_theta))) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (n == 0) return PWN_HIP_OK;
-  float* d = nullptr;
+  DevBuf<float> d;
   const size_t bytes = (size_t)n * sizeof(float);
-  HIPCHK(ctx, hipMalloc((void**)&d, 5 * bytes), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, d.alloc(5 * (size_t)n), PWN_HIP_ERR_ALLOCATION);
   hipError_t e = hipMemcpy(d, y, bytes, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d + n, x, bytes, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
@@ -1129,7 +1110,6 @@ int pwn_hip_debug_trig_eval(pwn_hip_ctx* ctx, int n, const float* y, const float
   if (e == hipSuccess) e = hipMemcpy(theta, d + 2 * (size_t)n, bytes, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(cos_theta, d + 3 * (size_t)n, bytes, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(sin_theta, d + 4 * (size_t)n, bytes, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
   if (e != hipSuccess) return fail(ctx, PWN_HIP_ERR_LAUNCH, std::string("trig eval: ") + hipGetErrorString(e));
   return PWN_HIP_OK;
 }
@@ -1167,16 +1147,16 @@ int pwn_hip_measure_hbm(pwn_hip_ctx* ctx, size_t bytes, float* read_gbps, float*
   if (!ctx || bytes < (1u << 20)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null ctx or fewer than 1 MiB");
   HIPCHK(ctx, hipSetDevice(ctx->device), PWN_HIP_ERR_NO_DEVICE);
   const size_t n4 = bytes / sizeof(float4);
-  float4 *src = nullptr, *dst = nullptr;
-  HIPCHK(ctx, hipMalloc(&src, n4 * sizeof(float4)), PWN_HIP_ERR_ALLOCATION);
-  if (hipMalloc(&dst, n4 * sizeof(float4)) != hipSuccess) { (void)hipFree(src); return fail(ctx, PWN_HIP_ERR_ALLOCATION, "hipMalloc (probe)"); }
+  DevBuf<float4> src, dst;
+  HIPCHK(ctx, src.alloc(n4), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, dst.alloc(n4), PWN_HIP_ERR_ALLOCATION);
   hipStream_t st = ctx->stream;
   (void)hipMemsetAsync(src, 0, n4 * sizeof(float4), st); (void)hipMemsetAsync(dst, 0, n4 * sizeof(float4), st);
   float best_r = 1e30f, best_c = 1e30f;
   for (int rep = 0; rep < 6; ++rep) {
     float ms = 0.f;
     (void)hipEventRecord(ctx->t0, st);
-    hipLaunchKernelGGL(k_probe_read, dim3(2048), dim3(256), 0, st, (const v4f*)src, n4, (float*)dst);
+    hipLaunchKernelGGL(k_probe_read, dim3(2048), dim3(256), 0, st, (const v4f*)src.p, n4, (float*)dst.p);
     (void)hipEventRecord(ctx->t1, st); (void)hipEventSynchronize(ctx->t1); (void)hipEventElapsedTime(&ms, ctx->t0, ctx->t1);
     if (rep > 0 && ms < best_r) best_r = ms;
     (void)hipEventRecord(ctx->t0, st);
@@ -1185,7 +1165,6 @@ int pwn_hip_measure_hbm(pwn_hip_ctx* ctx, size_t bytes, float* read_gbps, float*
     if (rep > 0 && ms < best_c) best_c = ms;
   }
   const hipError_t e = hipGetLastError();
-  (void)hipFree(src); (void)hipFree(dst);
   if (e != hipSuccess) return fail(ctx, PWN_HIP_ERR_LAUNCH, hipGetErrorString(e));
   const double b = (double)n4 * sizeof(float4);
   if (read_gbps) *read_gbps = (float)(b / (best_r * 1e-3) / 1e9);
@@ -1277,7 +1256,7 @@ int pwn_hip_cloud_upload(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int n, const float*
       OmN[om_at(cap, i, 3 * r + q)] = hon[(size_t)16 * i + r + 4 * q];
     }
   }
-  if (!c->d.OmN) HIPCHK(ctx, hipMalloc((void**)&c->d.OmN, cap * 9 * sizeof(float)), PWN_HIP_ERR_ALLOCATION);
+  if (int rc = ensure_omega_n(ctx, c)) return rc;
   if (int rc = cloud_store_records(ctx, c->d, n, P, Nm)) return rc;
   HIPCHK(ctx, hipMemcpy(c->d.Om, Om.data(), Om.size() * 4, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipMemcpy(c->d.OmN, OmN.data(), OmN.size() * 4, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
@@ -1411,10 +1390,10 @@ int pwn_hip_cloud_export(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, void* dst, si
   const size_t n = (size_t)std::min(c->n_host, c->d.capacity), cap = (size_t)c->d.capacity;
   // the header is staged in page-locked memory of the context: the copy below is asynchronous, and an error return further down must not
   // leave it reading a dead stack frame
-  CloudFlatHeader& h = *(CloudFlatHeader*)ctx->flat_hdr_host; std::memset(&h, 0, sizeof(h));
+  CloudFlatHeader& h = *(CloudFlatHeader*)ctx->flat_hdr_host.p; std::memset(&h, 0, sizeof(h));
   h.magic = kFlatMagic; h.version = 1; h.n = (int32_t)n; h.omSym = c->d.omSym; h.hasOmN = c->d.OmN ? 1 : 0;
   h.clsThr = c->d.clsThr; std::memcpy(h.omN, c->d.omN, sizeof(h.omN));
-  const bool idx = c->idx_valid && c->idximg && (size_t)c->idx_rows * c->idx_cols <= c->idx_cap;
+  const bool idx = c->idx_valid && c->idximg && (size_t)c->idx_rows * c->idx_cols <= c->idximg.cap;
   h.idxValid = idx ? 1 : 0; h.idxRows = idx ? c->idx_rows : 0; h.idxCols = idx ? c->idx_cols : 0;
   h.idxMinD = c->idx_minD; h.idxMaxD = c->idx_maxD; std::memcpy(h.idxK, c->idx_K, sizeof(h.idxK));
   const size_t npx = idx ? (size_t)c->idx_rows * c->idx_cols : 0;
@@ -1461,15 +1440,10 @@ int pwn_hip_cloud_import(pwn_hip_ctx* ctx, pwn_hip_cloud* c, const void* src, si
   // has arrived, so that a copy that fails half way leaves an empty cloud behind, not a mixture with the old sizes
   c->n_host = 0;
   HIPCHK(ctx, hipMemsetAsync(c->d.count, 0, sizeof(int), st), PWN_HIP_ERR_COPY);
-  CloudFlatHeader& hp = *(CloudFlatHeader*)ctx->flat_hdr_host; hp = h;      // page-locked copy: source of the asynchronous count copy below
-  if (h.hasOmN && !c->d.OmN) HIPCHK(ctx, hipMalloc((void**)&c->d.OmN, cap * 9 * sizeof(float)), PWN_HIP_ERR_ALLOCATION);
-  if (!h.hasOmN && c->d.OmN) { (void)hipFree(c->d.OmN); c->d.OmN = nullptr; }      // the stream is idle (synchronised above)
-  if (idx && c->idx_cap < npx) {
-    if (c->idximg) (void)hipFree(c->idximg);
-    c->idximg = nullptr; c->idx_cap = 0;
-    HIPCHK(ctx, hipMalloc((void**)&c->idximg, npx * sizeof(int)), PWN_HIP_ERR_ALLOCATION);
-    c->idx_cap = npx;
-  }
+  CloudFlatHeader& hp = *(CloudFlatHeader*)ctx->flat_hdr_host.p; hp = h;      // page-locked copy: source of the asynchronous count copy below
+  if (h.hasOmN) { if (int rc = ensure_omega_n(ctx, c)) return rc; }
+  else drop_omega_n(c);                                                         // the stream is idle (synchronised above)
+  if (idx) HIPCHK(ctx, c->idximg.ensure(npx), PWN_HIP_ERR_ALLOCATION);
   const char* in = (const char*)src;
   if (n > 0) {
     HIPCHK(ctx, copy_section(c->d.P3, in + h.offP3, n * 12, st), PWN_HIP_ERR_COPY);
@@ -1555,7 +1529,7 @@ int pwn_hip_unproject(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const
   if (int rc = stage_depth(ctx, depth, N, &d)) return rc;
   HIPCHK(ctx, hipMemsetAsync(cloud->d.Nc, 0, sizeof(float4) * (size_t)cloud->d.capacity, ctx->stream), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipMemsetAsync(cloud->d.Om, 0, sizeof(float) * om_floats(cloud->d), ctx->stream), PWN_HIP_ERR_COPY);
-  fill_frame(ctx, 0, 0, d, cloud->d, rows);
+  fill_frame(ctx, 0, 0, d, cloud->d);
   HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev, ctx->frames_host, sizeof(FrameDesc), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
   hipLaunchKernelGGL(k_row_count, dim3(rows, 1), dim3(256), 0, ctx->stream, ctx->frames_dev, cp);
   hipLaunchKernelGGL(k_row_offsets, dim3(1), dim3(1024), 0, ctx->stream, ctx->frames_dev, rows);
@@ -1574,7 +1548,7 @@ int pwn_hip_project_intervals(pwn_hip_ctx* ctx, const pwn_hip_converter_params* 
   const float* d = nullptr;
   if (int rc = stage_depth(ctx, depth, N, &d)) return rc;
   CloudDev none; std::memset(&none, 0, sizeof(none)); none.count = ctx->scratch_count; none.capacity = 0;
-  fill_frame(ctx, 0, 0, d, none, rows);
+  fill_frame(ctx, 0, 0, d, none);
   HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev, ctx->frames_host, sizeof(FrameDesc), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
   hipLaunchKernelGGL(k_row_count, dim3(rows, 1), dim3(256), 0, ctx->stream, ctx->frames_dev, cp);
   hipLaunchKernelGGL(k_row_offsets, dim3(1), dim3(1024), 0, ctx->stream, ctx->frames_dev, rows);
@@ -1589,7 +1563,7 @@ int pwn_hip_integral_image(pwn_hip_ctx* ctx, const int* index_image, const pwn_h
   if (int rc = check_image(ctx, rows, cols)) return rc;
   if (int rc = absorb_copies(ctx)) return rc;      // caller pointers may be the destination of a queued pwn_hip_copy_async
   const size_t N = (size_t)rows * cols;
-  fill_frame(ctx, 0, 0, nullptr, cloud->d, rows);
+  fill_frame(ctx, 0, 0, nullptr, cloud->d);
   HIPCHK(ctx, copy_any(ctx->frames_host[0].index, index_image, N * 4, ctx->stream), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev, ctx->frames_host, sizeof(FrameDesc), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
   hipLaunchKernelGGL(k_integral_rows, dim3((rows + kIR_Rows - 1) / kIR_Rows, 1), dim3(256), 0, ctx->stream, ctx->frames_dev, rows, cols);
@@ -2018,19 +1992,9 @@ static int align_batch_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, i
     // context's own buffer into host memory
     const bool dev = is_device_ptr(records);
     const int rlen = match_records ? kMatchRecordFloats : kRecordFloats;
-    if (!dev && ctx->records_cap < n) {
-      if (ctx->records_ws) (void)hipFree(ctx->records_ws);
-      ctx->records_ws = nullptr; ctx->records_cap = 0;
-      HIPCHK(ctx, hipMalloc((void**)&ctx->records_ws, (size_t)std::max(n, 64) * kMatchRecordFloats * sizeof(float)), PWN_HIP_ERR_ALLOCATION);
-      ctx->records_cap = std::max(n, 64);
-    }
+    if (!dev) HIPCHK(ctx, ctx->records_ws.ensure((size_t)std::max(n, 64) * kMatchRecordFloats), PWN_HIP_ERR_ALLOCATION);
     if (pair_ids) {
-      if (ctx->ids_cap < n) {
-        if (ctx->ids_dev) (void)hipFree(ctx->ids_dev);
-        ctx->ids_dev = nullptr; ctx->ids_cap = 0;
-        HIPCHK(ctx, hipMalloc((void**)&ctx->ids_dev, (size_t)std::max(n, 64) * sizeof(int)), PWN_HIP_ERR_ALLOCATION);
-        ctx->ids_cap = std::max(n, 64);
-      }
+      HIPCHK(ctx, ctx->ids_dev.ensure((size_t)std::max(n, 64)), PWN_HIP_ERR_ALLOCATION);
       HIPCHK(ctx, copy_any(ctx->ids_dev, pair_ids, sizeof(int) * n, ctx->stream), PWN_HIP_ERR_COPY);
     }
     float* dst = dev ? records : ctx->records_ws;

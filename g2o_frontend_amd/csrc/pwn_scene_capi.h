@@ -72,21 +72,10 @@ void swap_back(pwn_hip_cloud* c) {
 }
 // context scratch of the scene stage: int arrays of n entries and 64-bit arrays
 int scene_scratch(pwn_hip_ctx* ctx, size_t n_int, size_t n_u64) {
-  if (n_int > ctx->scene_icap) {
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
-    for (int k = 0; k < 8; ++k) { if (ctx->scene_i[k]) (void)hipFree(ctx->scene_i[k]); ctx->scene_i[k] = nullptr; }
-    ctx->scene_icap = 0;
-    for (int k = 0; k < 8; ++k) HIPCHK(ctx, hipMalloc((void**)&ctx->scene_i[k], (n_int + 1024) * sizeof(int)), PWN_HIP_ERR_ALLOCATION);
-    ctx->scene_icap = n_int;
-  }
-  if (n_u64 > ctx->scene_kcap) {
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
-    for (int k = 0; k < 3; ++k) { if (ctx->scene_k[k]) (void)hipFree(ctx->scene_k[k]); ctx->scene_k[k] = nullptr; }
-    ctx->scene_kcap = 0;
-    for (int k = 0; k < 3; ++k) HIPCHK(ctx, hipMalloc((void**)&ctx->scene_k[k], n_u64 * sizeof(unsigned long long)), PWN_HIP_ERR_ALLOCATION);
-    ctx->scene_kcap = n_u64;
-  }
-  if (!ctx->scene_total) HIPCHK(ctx, hipMalloc((void**)&ctx->scene_total, 4 * sizeof(int)), PWN_HIP_ERR_ALLOCATION);
+  if (n_int + 1024 > ctx->scene_i[0].cap || n_u64 > ctx->scene_k[0].cap) HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  for (auto& b : ctx->scene_i) HIPCHK(ctx, b.ensure(n_int + 1024), PWN_HIP_ERR_ALLOCATION);
+  for (auto& b : ctx->scene_k) HIPCHK(ctx, b.ensure(n_u64), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->scene_total.ensure(4), PWN_HIP_ERR_ALLOCATION);
   return PWN_HIP_OK;
 }
 // out[i] = sum of in[0..i), *total = sum of all; sums: scratch of >= n/1024 + 1 ints
@@ -119,7 +108,7 @@ int pwn_hip_cloud_gaussians(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p,
   projector_matrices(mat3_from(p->K), mat4_identity(), KRt, iKRt, iK);
   const float* d = nullptr;
   if (int rc = stage_depth(ctx, depth, N, &d)) return rc;
-  fill_frame(ctx, 0, 0, d, cloud->d, rows);
+  fill_frame(ctx, 0, 0, d, cloud->d);
   HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev, ctx->frames_host, sizeof(FrameDesc), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
   hipLaunchKernelGGL(k_row_count, dim3(rows, 1), dim3(256), 0, ctx->stream, ctx->frames_dev, cp);
   hipLaunchKernelGGL(k_row_offsets, dim3(1), dim3(1024), 0, ctx->stream, ctx->frames_dev, rows);

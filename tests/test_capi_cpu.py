@@ -328,6 +328,31 @@ def test_product_sources_carry_no_compile_time_or_environment_switches():
     assert not [x for x in build.FLAGS if x.startswith("-D")]
 
 
+def test_runtime_allocation_calls_live_in_the_buffer_type_and_the_cloud_code_only():
+    """The library's own device and page-locked memory is owned by pwn_buffers.h's buffer type (a member that frees itself: no list in
+    pwn_hip_ctx_destroy to forget it in).  The runtime's four allocation / free calls may appear only there, in the four entry points that
+    hand memory to the caller, and in the functions that own a cloud's CloudDev arrays; a raw call anywhere else fails here."""
+    allowed = {"pwn_hip_device_alloc", "pwn_hip_device_free", "pwn_hip_host_alloc", "pwn_hip_host_free",
+               "pwn_hip_cloud_create", "cloud_free", "ensure_stats", "ensure_omega_n", "drop_omega_n", "scene_alloc"}
+    call = re.compile(r"\bhip(Malloc|Free|HostMalloc|HostFree)\s*\(")
+    d = os.path.join(ROOT, "g2o_frontend_amd", "csrc")
+    seen = set()
+    for f in sorted(os.listdir(d)):
+        text = re.sub(r"//[^\n]*", "", open(os.path.join(d, f)).read())
+        if f == "pwn_buffers.h":
+            assert len(call.findall(text)) == 4, "the buffer type calls each of the four once"
+            continue
+        fn = None
+        for n, line in enumerate(text.splitlines(), 1):
+            m = re.match(r"(?![#}])\S.*?(\w+)\s*\(", line)                    # a definition starts in column 0 and does not end in ';'
+            if m and not line.rstrip().endswith(";"):
+                fn = m.group(1)
+            if call.search(line):
+                assert fn in allowed, (f, n, fn, line.strip())
+                seen.add(fn)
+    assert seen == allowed, sorted(allowed - seen)
+
+
 def test_single_point_projector_forms_against_the_numpy_model():
     """PinholePointProjector::project(x, y, f, p) / unProject(p, x, y, d) / projectInterval (pinholepointprojector.h:174,187,200) are host code of the
     library (no GPU): against the numpy statement of the reference's lines (tests/numpy_reference_model.py), point by point, bit for bit."""

@@ -90,6 +90,25 @@ def test_records_on_the_device_and_without_results():
     assert np.array_equal(_bits(h), _bits(shard.pack_results_raw(r0, np.arange(n)))) and (h[:, 16:19] == 0).all()
     rec.free()
     ctx.close()
+    # A batch with more items than the context's descriptor arrays were created for (max(16, max_batch) entries) and than its record and
+    # pair-id buffers hold after a first use (64): all of them grow inside the call, after a single alignment and a small batch have used
+    # the old ones.  Its records are those of the same pairs aligned in batches that fit.
+    n = 70
+    ctx, converter, aligner, pairs, refs, curs = _rig("small", n, 8)
+    for k in range(0, n, 8):
+        converter.computeBatch(refs[k:k + 8] + curs[k:k + 8], [p[0] for p in pairs[k:k + 8]] + [p[1] for p in pairs[k:k + 8]], raw_scale=0.001)
+    aligner.setReferenceCloud(refs[0]); aligner.setCurrentCloud(curs[0])
+    one = aligner.align()
+    ids = np.arange(500, 500 + n, dtype=np.int32)
+    fit = np.zeros((n, shard.RECORD_FLOATS), np.float32)
+    aligner.alignBatchRecords(refs[:10], curs[:10], fit[:10], pair_ids=ids[:10])
+    big = np.zeros((n, shard.RECORD_FLOATS), np.float32)
+    got = aligner.alignBatchRecords(refs, curs, big, pair_ids=ids)
+    for k in range(10, n, 10):
+        aligner.alignBatchRecords(refs[k:k + 10], curs[k:k + 10], fit[k:k + 10], pair_ids=ids[k:k + 10])
+    assert np.array_equal(_bits(big), _bits(fit)) and np.array_equal(_bits(big), _bits(shard.pack_results_raw(got, ids)))
+    assert np.array_equal(_bits(one["chi2"]), _bits(got["chi2"][0][:10]))
+    ctx.close()
 
 
 def test_fused_step_vga_against_oracle_sym6(oracle):
