@@ -43,21 +43,45 @@ def _iso(T, p, w):
     return np.stack([((T[k, 0] * p[:, 0] + T[k, 1] * p[:, 1]) + T[k, 2] * p[:, 2]) + T[k, 3] * f32(w) for k in range(3)], 1)
 
 
-def correspondences(ref, cur, ref_index, cur_index, T, normal_thr, dist_thr, flat_thr, ratio_thr):
-    """CorrespondenceFinder::compute (correspondencefinder.cpp:45-106), one thread: (list [C,2] in row-major pixel order, K)"""
+def correspondence_terms(ref, cur, ref_index, cur_index, T, flat_thr):
+    """the quantities CorrespondenceFinder::compute (correspondencefinder.cpp:60-99) tests, per candidate in row-major pixel order, each in the
+    reference's fp32 operation order: squared norms of both normals, cN . rn, the squared distance, the clamped curvatures and the
+    double-evaluated, float-rounded curvature ratio"""
     r_i, c_i = ref_index.reshape(-1), cur_index.reshape(-1)
     cand = (r_i >= 0) & (c_i >= 0)
     rI, cI = r_i[cand], c_i[cand]
     rP, rN, cP, cN = ref["points"][rI], ref["normals"][rI], cur["points"][cI], cur["normals"][cI]
-    ok = (_sq3(cN) != 0) & (_sq3(rN) != 0)
     rp, rn = _iso(T, rP, 1.0), _iso(T, rN, 0.0)
-    ok &= ~(((cN[:, 0] * rn[:, 0] + cN[:, 1] * rn[:, 1]) + cN[:, 2] * rn[:, 2]) < f32(normal_thr))
-    ok &= ~(_sq3(cP[:, :3] - rp) > f32(dist_thr) * f32(dist_thr))
     rc = np.maximum(ref["curvature"][rI], f32(flat_thr)); cc = np.maximum(cur["curvature"][cI], f32(flat_thr))
     ratio = ((rc.astype(np.float64) + 1e-5) / (cc.astype(np.float64) + 1e-5)).astype(np.float32)
+    return dict(pixel=np.nonzero(cand)[0], ri=rI, ci=cI, sq_cn=_sq3(cN), sq_rn=_sq3(rN),
+                dot=(cN[:, 0] * rn[:, 0] + cN[:, 1] * rn[:, 1]) + cN[:, 2] * rn[:, 2], sqdist=_sq3(cP[:, :3] - rp), rc=rc, cc=cc, ratio=ratio)
+
+
+def correspondences(ref, cur, ref_index, cur_index, T, normal_thr, dist_thr, flat_thr, ratio_thr):
+    """CorrespondenceFinder::compute (correspondencefinder.cpp:45-106), one thread: (list [C,2] in row-major pixel order, K)"""
+    t = correspondence_terms(ref, cur, ref_index, cur_index, T, flat_thr)
+    ok = (t["sq_cn"] != 0) & (t["sq_rn"] != 0)
+    ok &= ~(t["dot"] < f32(normal_thr))
+    ok &= ~(t["sqdist"] > f32(dist_thr) * f32(dist_thr))
     mx = f32(ratio_thr); mn = f32(1.0) / mx
-    ok &= ~((ratio < mn) | (ratio > mx))
-    return np.stack([rI[ok], cI[ok]], 1).astype(np.int32), int(cand.sum())
+    ok &= ~((t["ratio"] < mn) | (t["ratio"] > mx))
+    return np.stack([t["ri"][ok], t["ci"][ok]], 1).astype(np.int32), len(t["ri"])
+
+
+def local_error_f32(ref, cur, corr, invT):
+    """localError of Linearizer::update (linearizer.cpp:52-62) per correspondence, every operation fp32 in the reference's order: what is
+    compared with inlierMaxChi2"""
+    T = np.asarray(invT, np.float32)
+    ri, ci = corr[:, 0], corr[:, 1]
+    rp, rn = _iso(T, ref["points"][ri], 1.0), _iso(T, ref["normals"][ri], 0.0)
+    pe = rp - cur["points"][ci, :3]; ne = rn - cur["normals"][ci, :3]
+    oP = cur["omega_p"][ci].reshape(-1, 4, 4).transpose(0, 2, 1)[:, :3, :3]
+    oN = cur["omega_n"][ci].reshape(-1, 4, 4).transpose(0, 2, 1)[:, :3, :3]
+    def mv(o, v): return np.stack([(o[:, k, 0] * v[:, 0] + o[:, k, 1] * v[:, 1]) + o[:, k, 2] * v[:, 2] for k in range(3)], 1)
+    def dot(a, b): return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+    with np.errstate(over="ignore", invalid="ignore"):
+        return (dot(pe, mv(oP, pe)) + dot(ne, mv(oN, ne))).astype(np.float32)
 
 
 def _skew(v):
@@ -69,8 +93,9 @@ def _skew(v):
     return S
 
 
-def linearize(ref, cur, corr, invT, max_chi2, robust=True):
-    """Linearizer::update (linearizer.cpp:33-114) in float64 from the fp32 clouds: H, b, chi2, inliers"""
+def linearize(ref, cur, corr, invT, max_chi2, robust=True, abs_sums=False):
+    """Linearizer::update (linearizer.cpp:33-114) in float64 from the fp32 clouds: H, b, chi2, inliers.  abs_sums: also the sums of the absolute
+    values of the per-correspondence terms of every entry of H and b (Habs [6,6], babs [6]): the scale a summation error is measured against."""
     T = np.asarray(invT, np.float64)
     ri, ci = corr[:, 0], corr[:, 1]
     rp = ref["points"][ri, :3].astype(np.float64) @ T[:3, :3].T + T[:3, 3]
@@ -87,13 +112,21 @@ def linearize(ref, cur, corr, invT, max_chi2, robust=True):
     else:
         keep = ~over
     Sp, Sn = _skew(rp), _skew(rn)
-    Htt = oP[keep].sum(0)
-    Htr = np.einsum("nij,njk->ik", oP[keep], Sp[keep])
-    Hrr = np.einsum("nji,njk,nkl->il", Sp[keep], oP[keep], Sp[keep]) + np.einsum("nji,njk,nkl->il", Sn[keep], oN[keep], Sn[keep])
-    bt = (k[keep, None] * ep[keep]).sum(0)
-    br = (k[keep, None] * (np.einsum("nji,nj->ni", Sp[keep], ep[keep]) + np.einsum("nji,nj->ni", Sn[keep], en[keep]))).sum(0)
-    H = np.zeros((6, 6)); H[:3, :3] = Htt; H[:3, 3:] = Htr; H[3:, 3:] = Hrr; H[3:, :3] = Htr.T
-    return H, np.concatenate([bt, br]), float((k[keep] * le[keep]).sum()), int(keep.sum())
+    tHtt = oP[keep]
+    tHtr = np.einsum("nij,njk->nik", oP[keep], Sp[keep])
+    tHrr = np.einsum("nji,njk,nkl->nil", Sp[keep], oP[keep], Sp[keep]) + np.einsum("nji,njk,nkl->nil", Sn[keep], oN[keep], Sn[keep])
+    tbt = k[keep, None] * ep[keep]
+    tbr = k[keep, None] * (np.einsum("nji,nj->ni", Sp[keep], ep[keep]) + np.einsum("nji,nj->ni", Sn[keep], en[keep]))
+
+    def assemble(f):
+        Htr = f(tHtr)
+        H = np.zeros((6, 6)); H[:3, :3] = f(tHtt); H[:3, 3:] = Htr; H[3:, 3:] = f(tHrr); H[3:, :3] = Htr.T
+        return H, np.concatenate([f(tbt), f(tbr)])
+    H, b = assemble(lambda t: t.sum(0))
+    out = (H, b, float((k[keep] * le[keep]).sum()), int(keep.sum()))
+    if abs_sums:
+        out += assemble(lambda t: np.abs(t).sum(0))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------- projector matrices, converter
