@@ -514,9 +514,10 @@ void launch_stats(const ConvertParams& cp, const FrameDesc* fr, int n, hipStream
   const unsigned nblk = (n >= 8 ? 8u * (unsigned)((n + 7) / 8) : (unsigned)n) * perFrame;      // see k_stats: XCD-aware placement from 8 frames on
   hipLaunchKernelGGL(k_stats, dim3(nblk), dim3(256), 0, st, fr, cp, n);
 }
-int launch_convert(pwn_hip_ctx* ctx, const ConvertParams& cp, int base, int n, hipStream_t st, int* fault_out = nullptr) {
+// the front end of a convert call (everything before the stats pass): counts, offsets, points, index / interval images, integral planes
+int launch_front_end(pwn_hip_ctx* ctx, const ConvertParams& cp, int base, int n, hipStream_t st, bool single_pass, int* fault_out) {
   const FrameDesc* fr = ctx->frames_dev + base;
-  if (n >= kSinglePassMinFrames) {
+  if (single_pass) {
     // throughput path: the integral planes are written once; a frame is a chain of strips * bands hand-over steps, so it
     // needs several frames in flight to fill the device
     { StageTimer t(ctx, "unproject", st);          // ordered compaction: valid pixels per (row, strip) and their offsets
@@ -550,8 +551,12 @@ int launch_convert(pwn_hip_ctx* ctx, const ConvertParams& cp, int base, int n, h
       hipLaunchKernelGGL(k_integral_cols, dim3((cp.cols + kIC_Block - 1) / kIC_Block, kIntegralChannels, n), dim3(kIC_Block), 0, st, fr, cp.rows, cp.cols,
                          (const int*)ctx->fault_dev, fault_out); }
   }
+  return PWN_HIP_OK;
+}
+int launch_convert(pwn_hip_ctx* ctx, const ConvertParams& cp, int base, int n, hipStream_t st, int* fault_out = nullptr) {
+  if (int rc = launch_front_end(ctx, cp, base, n, st, n >= kSinglePassMinFrames, fault_out)) return rc;
   { StageTimer t(ctx, "stats", st);
-    launch_stats(cp, fr, n, st); }
+    launch_stats(cp, ctx->frames_dev + base, n, st); }
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
 }
@@ -747,6 +752,40 @@ int convert_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, cons
     if (int rc = plan_join(ctx, plan)) return rc;
     return convert_finish(ctx, job, clouds);
   });
+}
+
+// pwn_hip_debug_front_end: one launch of launch_front_end over n frames prepared as a convert call prepares them (frame i in workspace slot i),
+// and what it wrote copied back per frame.  No stats pass, no repeat after a time-out.
+template <typename SRC>
+int debug_front_end_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n, int rows, int cols,
+                         bool single_pass, int lean, pwn_hip_cloud* const* clouds, float* integral_out, int* index_out, int* interval_out, int* rowoff_out) {
+  ctx->stages.clear();
+  std::vector<int> slot((size_t)n);
+  for (int i = 0; i < n; ++i) slot[i] = i;
+  const bool direct = !single_pass && n < kSinglePassMinFrames;      // as convert_batch_impl decides for a call of n frames in one launch
+  ConvertJob job;
+  if (int rc = convert_prepare<SRC>(ctx, p, frames, depth_scale, n, rows, cols, clouds, 0, lean == 0, slot, direct, job)) return rc;
+  if (job.host_input) { if (int rc = convert_stage_frames(ctx, job, 0, n, ctx->stream)) return rc; }
+  // The one thing queued here that a convert call does not queue (there k_stats writes normals and matrices): with lean = 0 the clouds get points
+  // only, so their previous normals and matrices are cleared instead of staying readable next to the new points.  Two memsets per cloud ahead of
+  // the kernels; the kernels, their grids and their arguments are the convert call's.
+  if (!lean) for (int i = 0; i < n; ++i) {
+    HIPCHK(ctx, hipMemsetAsync(clouds[i]->d.Nc, 0, sizeof(float4) * (size_t)clouds[i]->d.capacity, ctx->stream), PWN_HIP_ERR_COPY);
+    HIPCHK(ctx, hipMemsetAsync(clouds[i]->d.Om, 0, sizeof(float) * om_floats(clouds[i]->d), ctx->stream), PWN_HIP_ERR_COPY);
+  }
+  if (int rc = launch_front_end(ctx, job.cp, 0, n, ctx->stream, single_pass, direct ? ctx->counts_host + n : nullptr)) return rc;
+  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  const size_t N = job.N, noff = (size_t)rows * (size_t)(single_pass ? strips_of(cols) : 1);
+  for (int i = 0; i < n; ++i) {
+    const FrameDesc& f = ctx->frames_host[i];
+    HIPCHK(ctx, copy_any(integral_out + (size_t)i * N * kIntegralChannels, f.integral, N * kIntegralChannels * sizeof(float), ctx->stream), PWN_HIP_ERR_COPY);
+    HIPCHK(ctx, copy_any(index_out + (size_t)i * N, f.index, N * sizeof(int), ctx->stream), PWN_HIP_ERR_COPY);
+    HIPCHK(ctx, copy_any(rowoff_out + (size_t)i * noff, f.rowoff, noff * sizeof(int), ctx->stream), PWN_HIP_ERR_COPY);
+    if (!lean) HIPCHK(ctx, copy_any(interval_out + (size_t)i * N, f.interval, N * sizeof(int), ctx->stream), PWN_HIP_ERR_COPY);
+  }
+  if (int rc = convert_finish(ctx, job, clouds)) return rc;
+  if (lean) for (int i = 0; i < n; ++i) { clouds[i]->n_host = 0; clouds[i]->idx_valid = false; }      // a lean front end stores no points
+  return PWN_HIP_OK;
 }
 
 }  // namespace
@@ -1085,6 +1124,26 @@ int pwn_hip_debug_stats_from_integral(pwn_hip_ctx* ctx, const pwn_hip_converter_
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
+}
+// Test hook: the front end of a convert call (launch_front_end, the function launch_convert itself calls) on the caller's frames, the path chosen
+// by the caller instead of by the frame count, and everything it wrote handed back: planes, index images, offsets, and with lean = 0 the
+// interval images and (in the clouds) the points.  k_stats is not launched.
+int pwn_hip_debug_front_end(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const void* const* frames, float depth_scale, int nframes, int rows, int cols,
+                            int path, int lean, pwn_hip_cloud* const* clouds, float* integral_out, int* index_out, int* interval_out, int* rowoff_out) {
+  if (!ctx || !p || !frames || !clouds || !integral_out || !index_out || !rowoff_out) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (nframes < 1 || nframes > ctx->max_batch) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "nframes must be 1..max_batch");
+  if (path != PWN_HIP_FRONT_END_LATENCY && path != PWN_HIP_FRONT_END_SINGLE_PASS) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "path must be 0 (latency) or 1 (single pass)");
+  if (lean ? interval_out != nullptr : interval_out == nullptr)
+    return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, lean ? "a lean front end writes no interval image (and no points): interval_out must be null" : "null argument");
+  if (depth_scale < 0.f) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "negative depth scale");
+  if (int rc = check_image(ctx, rows, cols)) return rc;
+  if (int rc = absorb_copies(ctx)) return rc;
+  const bool single = path == PWN_HIP_FRONT_END_SINGLE_PASS;
+  if (depth_scale > 0.f)
+    return debug_front_end_impl<uint16_t>(ctx, p, reinterpret_cast<const uint16_t* const*>(frames), depth_scale, nframes, rows, cols, single, lean, clouds,
+                                          integral_out, index_out, interval_out, rowoff_out);
+  return debug_front_end_impl<float>(ctx, p, reinterpret_cast<const float* const*>(frames), 0.f, nframes, rows, cols, single, lean, clouds,
+                                     integral_out, index_out, interval_out, rowoff_out);
 }
 __global__ void __launch_bounds__(256) k_debug_trig(int n, const float* __restrict__ y, const float* __restrict__ x, float* __restrict__ theta,
                                                     float* __restrict__ c, float* __restrict__ s) {

@@ -41,6 +41,21 @@ int pwn_hip_debug_projection_fallbacks(pwn_hip_ctx* ctx, int* calls);
  * 1 <= nframes <= max_batch; from 8 frames on the kernel takes its XCD-aware placement, as in a convert call. */
 int pwn_hip_debug_stats_from_integral(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, int rows, int cols, int nframes, const float* integral,
                                       const int* index_image, const int* interval_image, pwn_hip_cloud* const* clouds, int keep_stats);
+/* The converter's front end (everything a convert call launches before its stats pass) on the caller's frames, and what it wrote:
+ * frames[i] = rows x cols float32 metres (depth_scale == 0) or uint16 raw values (depth_scale > 0: metres = depth_scale * raw), host or device
+ * pointers, all of one kind.  path chooses the launch sequence whatever nframes is: PWN_HIP_FRONT_END_LATENCY (k_row_count, k_row_offsets,
+ * k_unproject_integral_rows, k_integral_cols: what a call of fewer than 16 frames per launch takes) or PWN_HIP_FRONT_END_SINGLE_PASS (k_strip_count
+ * or k_strip_count_any, k_row_offsets, k_unproject_integral) -- the function a convert call runs, with its grids, its choice of the counting
+ * kernel by width and pointer alignment and its hand-over epoch; the stats pass is not launched.  1 <= nframes <= max_batch (frame i uses
+ * workspace slot i).  Per frame: integral_out nframes x [10][rows][cols], index_out nframes x [rows][cols], rowoff_out nframes x [rows]
+ * (latency: first point index of every row) or nframes x [rows][strips of 64 columns] (single pass: of every (row, strip)).  lean = 0: the
+ * interval images go to interval_out and clouds[i] holds the points (normals, curvature and matrices zero).  lean = 1, the setting of a batch
+ * call: the front end stores neither; interval_out must be NULL and the clouds hold 0 points afterwards.  A hand-over time-out returns
+ * PWN_HIP_ERR_LAUNCH with a convert call's message (the call is not repeated). */
+enum { PWN_HIP_FRONT_END_LATENCY = 0, PWN_HIP_FRONT_END_SINGLE_PASS = 1 };
+int pwn_hip_debug_front_end(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const void* const* frames, float depth_scale, int nframes, int rows,
+                            int cols, int path, int lean, pwn_hip_cloud* const* clouds, float* integral_out, int* index_out, int* interval_out,
+                            int* rowoff_out);
 /* The eigensolver's three trig values (theta = atan2(y, x) / 3, cos theta, sin theta as floats) evaluated on the device for n host arguments
  * y = sqrt(q) >= 0, x = half_b: the lines of the stats kernel's eigensolver that compute them (one macro, expanded in both places). */
 int pwn_hip_debug_trig_eval(pwn_hip_ctx* ctx, int n, const float* y, const float* x, float* theta, float* cos_theta, float* sin_theta);

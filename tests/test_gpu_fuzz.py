@@ -47,7 +47,7 @@ def rigs():
     def get(name):
         if name not in made:
             rows, cols, _, _, _ = case_params(name)
-            ctx = api.Context(0, rows, cols, 4, omega_storage="exact9")
+            ctx = api.Context(0, rows, cols, 16, omega_storage="exact9")      # holds the 16-frame batch of the converter test in one launch
             _, converter, aligner = gpu_objects(ctx, name)
             made[name] = (ctx, converter, aligner)
         return made[name]
@@ -76,11 +76,13 @@ def test_converter_bit_exact_on_disturbed_frames(rigs, oracle, name, seed):
         assert np.array_equal(o["eigenvalues"].view(np.uint32), g["eigenvalues"].view(np.uint32))
         ok = o["npoints"] > 0
         assert np.array_equal(o["stats"][ok].view(np.uint32), g["stats"][ok].view(np.uint32))
-        # the raw uint16 batch path (conversion fused into the kernels, single-pass front end needs >= 16 frames: repeat the frame)
+        # the raw uint16 batch path (conversion fused into the kernels, single-pass front end needs >= 16 frames in one launch: repeat the frame)
         many = [api.Cloud(ctx, rows * cols) for _ in range(16)]
-        ctx.set_subbatch(4, 4)
+        ctx.set_profiling(True)
         converter.computeBatch(many, [mm] * 16, raw_scale=0.001)
-        ctx.set_subbatch(64, 64)
+        ran = {s: ctx.stage_ms(s)[1] for s in ("integral", "integral_rows", "integral_cols")}
+        ctx.set_profiling(False)
+        assert ran == dict(integral=1, integral_rows=0, integral_cols=0), f"the single-pass kernel did not run: {ran}"
         for c in (many[0], many[7], many[15]):
             _compare_clouds(o, c.arrays(), name)
 
