@@ -56,6 +56,35 @@ struct AsyncConvert {
   int rc = 0; std::string err;
 };
 
+// What an index image was made with.  Projecting a cloud returns the index image the converter kept for it exactly when the projector's key equals the
+// image's (and the pose is the identity): the aligner's shortcut compares keys, so a field the projection depends on is added here and nowhere else.
+struct IndexKey {
+  int rows = 0, cols = 0; float K[9] = { 0 }; float minD = 0.f, maxD = 0.f;
+  IndexKey() = default;
+  IndexKey(int r, int c, const float* k, float mn, float mx) : rows(r), cols(c), minD(mn), maxD(mx) { std::memcpy(K, k, sizeof(K)); }
+  bool operator==(const IndexKey& o) const { return rows == o.rows && cols == o.cols && minD == o.minD && maxD == o.maxD && std::memcmp(K, o.K, sizeof(K)) == 0; }
+};
+IndexKey index_key(const pwn_hip_converter_params* p, int rows, int cols) { return IndexKey(rows, cols, p->K, p->min_distance, p->max_distance); }
+IndexKey index_key(const pwn_hip_aligner_params* p) { return IndexKey(p->rows, p->cols, p->K, p->min_distance, p->max_distance); }
+// The pair whose images sit in workspace slot 0 after an alignment: its descriptor (pairs_host / pairs_dev entry), its clouds (the depth images are
+// recomputed from their points) and the z-buffer epochs of its last reference projection and of its current projection
+struct Slot0Pair {
+  int pair = 0; const pwn_hip_cloud* ref_cloud = nullptr; const pwn_hip_cloud* cur_cloud = nullptr; unsigned ref_tag = kZ32Tag0, cur_tag = kZ32Tag0;
+};
+// The finder's images of the last alignment, as pwn_hip_align_images / pwn_hip_match_score read them.  Written by its own functions only: set()
+// after a finished call, invalidate() by whatever touches slot 0 or the descriptors, drop_clouds() when one of its clouds changes or goes.
+struct FinderImages : Slot0Pair {
+  bool valid = false;
+  AlignParams ap = {};                       // of the call (the images are ap.rows x ap.cols)
+  // A single alignment whose current cloud carries its own index image (pwn_hip_cloud::idximg) does not project that cloud at all; its
+  // z-buffer is filled in only when pwn_hip_align_images asks for the finder's current images (pwn_hip_match_score reads the depths off the cloud)
+  bool cur_lazy = false;
+  void invalidate() { valid = false; }
+  void drop_clouds() { valid = false; ref_cloud = nullptr; cur_cloud = nullptr; }
+  void set(const AlignParams& a, const Slot0Pair& s, bool is_valid, bool lazy) { Slot0Pair::operator=(s); ap = a; valid = is_valid; cur_lazy = lazy; }
+  void cur_projected() { cur_lazy = false; }      // pwn_hip_align_images has made the projection the alignment skipped
+};
+
 }  // namespace
 
 struct pwn_hip_cloud {
@@ -71,8 +100,7 @@ struct pwn_hip_cloud {
   // it was made from.  Projecting a cloud with the very projector it was unprojected with (same K, size, range, identity pose) returns
   // this image: every point falls back on its own pixel (the round trip moves it by < 0.01 pixel and its depth not at all), so batch
   // alignments take it as the current index image and skip that projection.  Anything that changes the points invalidates it.
-  DevBuf<int> idximg; bool idx_valid = false;
-  int idx_rows = 0, idx_cols = 0; float idx_K[9] = { 0 }; float idx_minD = 0.f, idx_maxD = 0.f;
+  DevBuf<int> idximg; bool idx_valid = false; IndexKey idx_key;
 };
 
 struct pwn_hip_ctx {
@@ -116,14 +144,8 @@ struct pwn_hip_ctx {
   // misc scratch
   DevBuf<SolveOut> solve_dev; DevBuf<int> counters_dev; DevBuf<int2> corr_ws; DevBuf<int> scratch_count;
   DevBuf<float> io_ws;      // N*16 floats staging for cloud up/download
-  // images of the last single align
-  int img_rows = 0, img_cols = 0; bool img_valid = false; unsigned img_ref_tag = kZ32Tag0, img_cur_tag = kZ32Tag0;
-  int img_pair = 0;                         // descriptor (pairs_host / pairs_dev entry) of the pair whose images sit in workspace slot 0
-  // A single alignment whose current cloud carries its own index image (pwn_hip_cloud::idximg) does not project that cloud at all; its
-  // z-buffer is filled in only when pwn_hip_align_images asks for the finder's current images (pwn_hip_match_score reads the depths off the cloud)
-  bool img_cur_lazy = false; AlignParams img_ap; int img_cur_capacity = 0;
+  FinderImages img;                         // images of the last alignment
   int index_shortcut = 1;                   // pwn_hip_debug_set_index_shortcut (test hook): 0 = always project
-  const pwn_hip_cloud* img_ref_cloud = nullptr; const pwn_hip_cloud* img_cur_cloud = nullptr;      // its clouds: the depth images are recomputed from their points
   // z-buffer epoch tags are handed out in descending order ACROSS batch calls (a smaller tag wins, so whatever earlier calls left in
   // the buffers reads as empty): the buffers are cleared only when the 12-bit tag space is used up, not once per alignment
   unsigned ztag_next = 0;                   // 64-bit buffer (scene stage)
@@ -168,19 +190,22 @@ void cloud_free(pwn_hip_cloud* c) {
   delete c;                                   // and with it the index image
 }
 
+// What the aligner's launches for one sub-batch share: the call's parameters and grid (nb workgroups per pair; sym: storage of the current clouds' point
+// information matrices, CloudDev::omSym, the same for every pair), the m consecutive pair descriptors, their stream, and -- when the call runs the
+// two-pass projection, else nullptr -- the depth images of their workspace slots (contiguous, ctx->N words each)
+struct PairLaunch { const AlignParams* ap; int nb, sym; int m; hipStream_t st; const PairDesc* pr; unsigned* zd; };
 // the fused correspondence + linearize pass: the throughput shape, or the latency shape (same sums bit for bit, see k_corr_linearize_lat)
 // when all workgroups of the launch find a CU of their own -- its 1024-thread workgroups fit one per CU, a second round costs more than
 // the shape saves: one VGA pair is 150 workgroups, two pairs or one 1280x960 pair are not worth it on 256 CUs
-// sym: storage of the current clouds' point information matrices (CloudDev::omSym; the same for every pair of the launch)
 template <bool SAME_T, bool FULL_H, bool SYM>
-void launch_corr_linearize_s(const pwn_hip_ctx* ctx, int nb, int m, hipStream_t st, const PairDesc* pr, const AlignParams& ap, unsigned tag, int usePrevTc, int ownRef) {
-  if ((long long)nb * m <= ctx->num_cus) hipLaunchKernelGGL((k_corr_linearize_lat<SAME_T, FULL_H, SYM>), dim3(nb, m), dim3(kLatBlock), 0, st, pr, ap, tag, usePrevTc, ownRef);
-  else hipLaunchKernelGGL((k_corr_linearize<SAME_T, FULL_H, SYM>), dim3(nb, m), dim3(kAlignBlock), 0, st, pr, ap, tag, usePrevTc, ownRef);
+void launch_corr_linearize_s(const pwn_hip_ctx* ctx, const PairLaunch& L, unsigned tag, int usePrevTc, int ownRef) {
+  if ((long long)L.nb * L.m <= ctx->num_cus) hipLaunchKernelGGL((k_corr_linearize_lat<SAME_T, FULL_H, SYM>), dim3(L.nb, L.m), dim3(kLatBlock), 0, L.st, L.pr, *L.ap, tag, usePrevTc, ownRef);
+  else hipLaunchKernelGGL((k_corr_linearize<SAME_T, FULL_H, SYM>), dim3(L.nb, L.m), dim3(kAlignBlock), 0, L.st, L.pr, *L.ap, tag, usePrevTc, ownRef);
 }
 template <bool SAME_T, bool FULL_H>
-void launch_corr_linearize(const pwn_hip_ctx* ctx, int sym, int nb, int m, hipStream_t st, const PairDesc* pr, const AlignParams& ap, unsigned tag, int usePrevTc, int ownRef) {
-  if (sym) launch_corr_linearize_s<SAME_T, FULL_H, true>(ctx, nb, m, st, pr, ap, tag, usePrevTc, ownRef);
-  else launch_corr_linearize_s<SAME_T, FULL_H, false>(ctx, nb, m, st, pr, ap, tag, usePrevTc, ownRef);
+void launch_corr_linearize(const pwn_hip_ctx* ctx, const PairLaunch& L, unsigned tag, int usePrevTc, int ownRef) {
+  if (L.sym) launch_corr_linearize_s<SAME_T, FULL_H, true>(ctx, L, tag, usePrevTc, ownRef);
+  else launch_corr_linearize_s<SAME_T, FULL_H, false>(ctx, L, tag, usePrevTc, ownRef);
 }
 
 int fail(pwn_hip_ctx* ctx, int code, const std::string& msg) {
@@ -191,7 +216,7 @@ int fail(pwn_hip_ctx* ctx, int code, const std::string& msg) {
 // The finder's depth images of the last alignment are recomputed from the clouds' points (the z-buffer keeps indices only): anything
 // that changes or frees one of those clouds ends the validity of pwn_hip_align_images / pwn_hip_match_score for that alignment.
 void cloud_changes(pwn_hip_ctx* ctx, const pwn_hip_cloud* c) {
-  if (ctx && c && (c == ctx->img_ref_cloud || c == ctx->img_cur_cloud)) { ctx->img_valid = false; ctx->img_ref_cloud = nullptr; ctx->img_cur_cloud = nullptr; }
+  if (ctx && c && (c == ctx->img.ref_cloud || c == ctx->img.cur_cloud)) ctx->img.drop_clouds();
 }
 #define HIPCHK(ctx, call, code)                                                                               \
   do {                                                                                                        \
@@ -199,19 +224,32 @@ void cloud_changes(pwn_hip_ctx* ctx, const pwn_hip_cloud* c) {
     if (e_ != hipSuccess) return fail(ctx, code, std::string(#call) + ": " + hipGetErrorString(e_));           \
   } while (0)
 
-// projection of one cloud of each of the m pairs (which: 0 = reference, 1 = current): four points per thread when the launch is large
+// projection of one cloud of each of the launch's pairs (which: 0 = reference, 1 = current; capacity: the largest of those clouds): four
+// points per thread when the launch is large
 constexpr int kProjectPPT = 4;
-// zd: the depth images of the m pairs' workspace slots (contiguous, ctx->N words each) when the call runs the two-pass projection, else nullptr
-int launch_project(pwn_hip_ctx* ctx, int capacity, int m, hipStream_t st, const PairDesc* pr, const AlignParams& ap, int which, unsigned tag, unsigned* zd = nullptr) {
-  if (zd) {
-    HIPCHK(ctx, hipMemsetAsync(zd, 0xFF, (size_t)m * ctx->N * sizeof(unsigned), st), PWN_HIP_ERR_COPY);
+int launch_project(pwn_hip_ctx* ctx, const PairLaunch& L, int capacity, int which, unsigned tag) {
+  if (L.zd) {
+    HIPCHK(ctx, hipMemsetAsync(L.zd, 0xFF, (size_t)L.m * ctx->N * sizeof(unsigned), L.st), PWN_HIP_ERR_COPY);
     for (int pass = 0; pass < 2; ++pass)
-      hipLaunchKernelGGL(k_project_robust, dim3((capacity + 255) / 256, m), dim3(256), 0, st, pr, ap, which, tag, pass);
+      hipLaunchKernelGGL(k_project_robust, dim3((capacity + 255) / 256, L.m), dim3(256), 0, L.st, L.pr, *L.ap, which, tag, pass);
     return PWN_HIP_OK;
   }
-  if (m >= 8) hipLaunchKernelGGL((k_project<kProjectPPT>), dim3((capacity + 256 * kProjectPPT - 1) / (256 * kProjectPPT), m), dim3(256), 0, st, pr, ap, which, tag);
-  else hipLaunchKernelGGL((k_project<1>), dim3((capacity + 255) / 256, m), dim3(256), 0, st, pr, ap, which, tag);
+  if (L.m >= 8) hipLaunchKernelGGL((k_project<kProjectPPT>), dim3((capacity + 256 * kProjectPPT - 1) / (256 * kProjectPPT), L.m), dim3(256), 0, L.st, L.pr, *L.ap, which, tag);
+  else hipLaunchKernelGGL((k_project<1>), dim3((capacity + 255) / 256, L.m), dim3(256), 0, L.st, L.pr, *L.ap, which, tag);
   return PWN_HIP_OK;
+}
+// the current clouds projected with epoch `tag` and resolved into the pairs' current index images
+int launch_project_cur(pwn_hip_ctx* ctx, const PairLaunch& L, int capacity, unsigned tag) {
+  if (int rc = launch_project(ctx, L, capacity, 1, tag)) return rc;
+  const int N = L.ap->rows * L.ap->cols;
+  hipLaunchKernelGGL(k_resolve_cur, dim3(std::min((N + 255) / 256, 1024), L.m), dim3(256), 0, L.st, L.pr, N, tag);
+  return PWN_HIP_OK;
+}
+// Aligner::_computeStatistics' extra Linearizer::update: the finder's correspondences of the last outer iteration (epoch lastRefTag, tests with
+// that iteration's transform) re-linearized at the final transform with the full H (aligner.cpp:165-170), and its sums reduced into out[0..m)
+void launch_statistics(const pwn_hip_ctx* ctx, const PairLaunch& L, unsigned lastRefTag, SolveOut* out) {
+  launch_corr_linearize<false, true>(ctx, L, lastRefTag, 1, 0);
+  hipLaunchKernelGGL(k_reduce_pairs, dim3(L.m), dim3(256), 0, L.st, L.pr, L.nb, out);
 }
 
 bool is_device_ptr(const void* p) {
@@ -483,7 +521,7 @@ int ensure_desc(pwn_hip_ctx* ctx, int n) {
   if (n <= ctx->desc_cap) return PWN_HIP_OK;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
   ctx->desc_cap = 0;
-  ctx->img_valid = false;                    // the descriptor of the last alignment's pair goes with the old arrays
+  ctx->img.invalidate();                     // the descriptor of the last alignment's pair goes with the old arrays
   const size_t B = (size_t)std::max(n, 16);
   HIPCHK(ctx, ctx->frames_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
   HIPCHK(ctx, ctx->pairs_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
@@ -662,7 +700,7 @@ int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const S
     }
     ctx->frames_host[i].index = c->idximg;                    // the index image stays with the cloud
     c->idx_valid = cp.hasOffset == 0;
-    c->idx_rows = rows; c->idx_cols = cols; std::memcpy(c->idx_K, p->K, sizeof(c->idx_K)); c->idx_minD = p->min_distance; c->idx_maxD = p->max_distance;
+    c->idx_key = index_key(p, rows, cols);
     if (raw) {                                                                // uint16 frames are converted on the fly by the kernels
       ctx->frames_host[i].raw = reinterpret_cast<const uint16_t*>(frames[i]); // patched below if it is a host pointer
       ctx->frames_host[i].raw_scale = depth_scale;
@@ -1063,7 +1101,7 @@ int pwn_hip_debug_convert_retries(pwn_hip_ctx* ctx, int* retries) {
   return PWN_HIP_OK;
 }
 // Test hook: 0 makes every alignment project both clouds in every iteration, also where a cloud's own index image is known to be that
-// projection's result (the shortcut of align_batch_impl) -- so that tests can hold the shortcut against the projection it replaces.
+// projection's result (the shortcut of align_describe_pairs) -- so that tests can hold the shortcut against the projection it replaces.
 int pwn_hip_debug_set_index_shortcut(pwn_hip_ctx* ctx, int enabled) {
   if (!ctx) return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, "null ctx");
   ctx->index_shortcut = enabled ? 1 : 0;
@@ -1452,10 +1490,11 @@ int pwn_hip_cloud_export(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, void* dst, si
   CloudFlatHeader& h = *(CloudFlatHeader*)ctx->flat_hdr_host.p; std::memset(&h, 0, sizeof(h));
   h.magic = kFlatMagic; h.version = 1; h.n = (int32_t)n; h.omSym = c->d.omSym; h.hasOmN = c->d.OmN ? 1 : 0;
   h.clsThr = c->d.clsThr; std::memcpy(h.omN, c->d.omN, sizeof(h.omN));
-  const bool idx = c->idx_valid && c->idximg && (size_t)c->idx_rows * c->idx_cols <= c->idximg.cap;
-  h.idxValid = idx ? 1 : 0; h.idxRows = idx ? c->idx_rows : 0; h.idxCols = idx ? c->idx_cols : 0;
-  h.idxMinD = c->idx_minD; h.idxMaxD = c->idx_maxD; std::memcpy(h.idxK, c->idx_K, sizeof(h.idxK));
-  const size_t npx = idx ? (size_t)c->idx_rows * c->idx_cols : 0;
+  const IndexKey& key = c->idx_key;
+  const bool idx = c->idx_valid && c->idximg && (size_t)key.rows * key.cols <= c->idximg.cap;
+  h.idxValid = idx ? 1 : 0; h.idxRows = idx ? key.rows : 0; h.idxCols = idx ? key.cols : 0;
+  h.idxMinD = key.minD; h.idxMaxD = key.maxD; std::memcpy(h.idxK, key.K, sizeof(h.idxK));
+  const size_t npx = idx ? (size_t)key.rows * key.cols : 0;
   flat_layout(h, n, c->d.omSym, c->d.OmN != nullptr, npx);
   if (written) *written = (size_t)h.total;
   if (!dst) return PWN_HIP_OK;                                   // size query
@@ -1517,10 +1556,7 @@ int pwn_hip_cloud_import(pwn_hip_ctx* ctx, pwn_hip_cloud* c, const void* src, si
   HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_COPY);
   c->d.clsThr = h.clsThr; std::memcpy(c->d.omN, h.omN, sizeof(h.omN));
   c->n_host = h.n;
-  if (idx) {
-    c->idx_valid = true; c->idx_rows = h.idxRows; c->idx_cols = h.idxCols; c->idx_minD = h.idxMinD; c->idx_maxD = h.idxMaxD;
-    std::memcpy(c->idx_K, h.idxK, sizeof(h.idxK));
-  }
+  if (idx) { c->idx_valid = true; c->idx_key = IndexKey(h.idxRows, h.idxCols, h.idxK, h.idxMinD, h.idxMaxD); }
   return PWN_HIP_OK;
 }
 
@@ -1787,7 +1823,7 @@ int pwn_hip_project(pwn_hip_ctx* ctx, const float K[9], const float T[16], float
   if (index_image && di != index_image) HIPCHK(ctx, hipMemcpyAsync(index_image, di, N * 4, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
   if (depth_image && dd != depth_image) HIPCHK(ctx, hipMemcpyAsync(depth_image, dd, N * 4, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
-  ctx->img_valid = false;
+  ctx->img.invalidate();
   collect_stage_times(ctx);
   return PWN_HIP_OK;
 }
@@ -1839,18 +1875,39 @@ int pwn_hip_linearize(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, const p
   return PWN_HIP_OK;
 }
 
-static void finish_match(const MatchAcc& a, pwn_hip_match_result* r) {
-  r->image_non_zeros = (int)a.nonZeros;
-  r->image_inliers = (int)a.inliers;
-  r->image_outliers = (int)a.nonZeros - (int)a.inliers;
-  r->image_reprojection_distance = match_reprojection_distance(a);               // the expression k_pack_records evaluates for the score words of a record
-}
 // What a caller may weave into a batch alignment (pwn_hip_convert_align_batch_u16: the conversion of a sub-batch's frames goes in front of its
 // alignment on the same stream, so that one sub-batch converts while the other aligns and nothing waits for the host in between).
 struct AlignHooks {
   std::function<int(int base, int m, int k, hipStream_t st)> pre_sub;      // before the kernels of pairs [base, base + m) (sub-batch k) are enqueued on st
   std::function<int()> before_sync;                                        // on ctx->stream, after the streams have joined
   std::function<int()> after_sync;                                         // after the final wait, before the results are filled in
+};
+// What a caller asks of a batch alignment; every member defaults to "not asked for", an entry point names the ones it uses.
+struct AlignCall {
+  const pwn_hip_aligner_params* p = nullptr;
+  int n = 0;                                                   // pairs: refs[i] against curs[i]
+  pwn_hip_cloud* const* refs = nullptr; pwn_hip_cloud* const* curs = nullptr;
+  const float* guesses = nullptr;                              // n initial transforms (16 floats each); nullptr: p->initial_guess for every pair
+  pwn_hip_align_result* results = nullptr;                     // may be nullptr when records are asked for
+  pwn_hip_match_result* scores = nullptr; float match_threshold = 0.f;      // the matchClouds score of every pair
+  pwn_hip_align_statistics* statistics = nullptr;              // Aligner::_computeStatistics of every pair
+  const AlignHooks* hooks = nullptr;
+  float* records = nullptr;                                    // n records, device or host, written by k_pack_records: PWN_HIP_RECORD_FLOATS floats each,
+  bool match_records = false;                                  // or the long form with the score words
+  const int* pair_ids = nullptr; int first_pair_id = 0;        // record word 19: pair_ids[i] (host), else first_pair_id + i
+};
+// What the phases of one attempt at a call share (on align_batch_once's stack)
+struct AlignRun {
+  bool robust = false;                   // every projection by the two-pass kernels (the repeat of a call whose k_project gave up on a pixel)
+  bool want_scores = false;              // the score accumulators are needed: for `scores`, or for the score words of the long records
+  bool direct_state = false;             // a few pairs: k_solve_update keeps state_host up to date itself, no copy back
+  StreamPlan plan;
+  AlignParams ap;
+  int N = 0, nb = 0, omSym = 0;          // pixels; workgroups per pair of the linearize pass; storage of the current clouds' information matrices
+  std::vector<char> sub_own, sub_ownref; // per sub-batch: every pair of it takes the current cloud's own index image / the reference cloud's in iteration 0
+  bool any_own = false;
+  bool rolling = false; unsigned tagBase = kZ32Tag0, tagsPerSub = 1;      // sub-batch k draws the tags tagBase - k * tagsPerSub downwards; fixed tags: kZ32Tag0 for all
+  Slot0Pair slot0;                       // the sub-batch that owns workspace slot 0 (what the finder's images will show)
 };
 // the parameter checks of every alignment call (each entry point checks its own pointer arguments first)
 static int check_align_params(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p) {
@@ -1891,6 +1948,173 @@ static void set_pose(PairState& st, const Mat4& T, const AlignParams& ap, const 
   st.KRtLast = st.KRt;
   st.KRtCur = KRtCur;
 }
+
+// ---- one attempt at a batch alignment, phase by phase (align_batch_once calls them in this order) ----
+// Check and plan.  On the streams: the start event.  A call refused for its image size keeps the last alignment's images; from there on they are gone.
+static int align_check_and_plan(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& run) {
+  if (!ctx || !c.p || !c.refs || !c.curs || (!c.results && !c.records) || c.n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (int rc = check_image(ctx, c.p->rows, c.p->cols)) return rc;
+  ctx->img.invalidate();                  // whatever happens below (set again on success)
+  if (int rc = check_align_params(ctx, c.p)) return rc;
+  if (int rc = start_align_attempt(ctx, run.robust)) return rc;
+  run.want_scores = c.scores != nullptr || (c.records && c.match_records);
+  run.ap = make_align_params(ctx, c.p); run.N = c.p->rows * c.p->cols; run.nb = align_nblocks(run.N);
+  ctx->stages.clear();
+  run.plan = make_plan(ctx, ctx->sub_pairs, c.n);
+  if (int rc = ensure_desc(ctx, c.n)) return rc;
+  HIPCHK(ctx, hipEventRecord(ctx->t0, ctx->stream), PWN_HIP_ERR_LAUNCH);
+  return PWN_HIP_OK;
+}
+// Describe the pairs.  On ctx->stream: the uploads of all descriptors and initial states, and the score accumulators cleared.
+static int align_describe_pairs(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& run) {
+  const pwn_hip_aligner_params* p = c.p;
+  const int n = c.n, sub = run.plan.sub;
+  // A cloud's own index image (the converter's) is what projecting it with these parameters and an identity pose would give (see
+  // pwn_hip_cloud::idximg): the current cloud's projection is skipped, and the matchClouds score then reads the current depth image off the
+  // cloud itself (k_match_score, curOwn); a single alignment's current z-buffer is made on demand (FinderImages::cur_lazy).  The reference
+  // cloud's FIRST projection is skipped when guess and reference offset are the identity too; later iterations (and the last one, whose
+  // z-buffer the statistics pass re-reads) project as usual.
+  const IndexKey key = index_key(p);
+  const bool shortcut = n >= 1 && ctx->index_shortcut && is_identity(forced(p->current_sensor_offset));
+  const bool shortcut_ref = shortcut && p->outer_iterations > 1 && is_identity(forced(p->reference_sensor_offset));
+  // a few pairs (latency path): k_solve_update writes the pose and the traces into the page-locked host copy itself, no copy back at the end;
+  // batches copy the states back in one transfer (64 workgroups storing across PCIe in every solve launch cost more than that: 16 against 11 us per launch)
+  run.direct_state = n <= 4;
+  run.omSym = (n > 0 && c.curs[0]) ? c.curs[0]->d.omSym : 0;      // the linearizer reads the CURRENT cloud's information matrices (linearizer.cpp:52-53)
+  // The loop runs with the device idle (the call's first launch comes after it): what does not depend on the pair is computed once, and only the
+  // head of a state is cleared (the traces behind `it` are written before they are read: k_solve_update stores entry `it`, every reader stops at `it`).
+  // Workspace slots are reused round-robin across sub-batches; a sub-batch skips the projection kernels only if every pair of it can.
+  run.sub_own.assign((size_t)(n + sub - 1) / sub + 1, 1); run.sub_ownref.assign(run.sub_own.size(), 1);
+  Mat4 KRtCur0;
+  { Mat4 iKRt0; Mat3 iK0; projector_matrices(run.ap.K, mat4_from(p->current_sensor_offset), KRtCur0, iKRt0, iK0); }
+  for (int i = 0; i < n; ++i) {
+    const pwn_hip_cloud* r = c.refs[i]; const pwn_hip_cloud* cu = c.curs[i];
+    if (!r || !cu) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null cloud in batch");
+    if (cu->d.omSym != run.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "current clouds of one batch must share one omega storage (exact9 / sym6)");
+    if (int rc = check_pair_points(ctx, r, cu)) return rc;
+    fill_pair(ctx, i, run.plan.slot0(i / sub) + i % sub, r, cu, run.direct_state ? ctx->state_host + i : nullptr, run.robust);
+    // initial state: aligner.cpp:60-64,72-73,79,84
+    PairState& st = ctx->state_host[i];
+    std::memset(&st, 0, offsetof(PairState, chi2));
+    Mat4 T = mat4_from(c.guesses ? c.guesses + 16 * (size_t)i : p->initial_guess);
+    set_last_row(T);
+    if (!(shortcut && cu->idx_valid && cu->idx_key == key)) run.sub_own[i / sub] = 0;
+    if (!(shortcut_ref && is_identity(T) && r->idx_valid && r->idx_key == key)) run.sub_ownref[i / sub] = 0;
+    set_pose(st, T, run.ap, KRtCur0);
+  }
+  for (int i = 0; i < n; ++i) {
+    if (run.sub_own[i / sub]) { ctx->pairs_host[i].curidx = c.curs[i]->idximg; run.any_own = true; }
+    if (run.sub_ownref[i / sub]) ctx->pairs_host[i].refidx0 = c.refs[i]->idximg;
+  }
+  if (n > 0) {
+    HIPCHK(ctx, hipMemcpyAsync(ctx->pairs_dev, ctx->pairs_host, sizeof(PairDesc) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->state_ws, ctx->state_host, sizeof(PairState) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+    if (run.want_scores) HIPCHK(ctx, hipMemsetAsync(ctx->match_dev, 0, sizeof(MatchAcc) * n, ctx->stream), PWN_HIP_ERR_COPY);
+  }
+  return PWN_HIP_OK;
+}
+// Draw the tags.  On ctx->stream: the clearing of all z-buffer slots if the tag space had to start over, else nothing.
+// Every sub-batch takes its own block of tags (workspace slots are reused from sub-batch to sub-batch): its first for the current-cloud
+// projection (its own buffer) and that minus i for the reference projection of outer iteration i.  A call with more sub-batches than the tag
+// space holds falls back to the fixed tags and clears the slots of every sub-batch.
+static int align_draw_tags(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& run) {
+  run.tagsPerSub = (unsigned)std::max(1, c.p->outer_iterations);
+  const unsigned nsub = (unsigned)((c.n + run.plan.sub - 1) / run.plan.sub);
+  if (run.tagsPerSub > kZ32Tag0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "more projections per alignment than z-buffer epoch tags");
+  run.rolling = (unsigned long long)nsub * run.tagsPerSub <= kZ32Tag0;
+  if (run.rolling && nsub > 0) { if (int rc = take_tags32(ctx, nsub * run.tagsPerSub, &run.tagBase)) return rc; }
+  // fixed tags leave words in the buffers that could beat (smaller tag wins) the tags a later rolling call draws: make that call clear first
+  if (!run.rolling) ctx->z32tag_next = 0;
+  run.slot0.cur_tag = run.tagBase; run.slot0.ref_tag = run.tagBase - (run.tagsPerSub - 1);
+  return PWN_HIP_OK;
+}
+// Enqueue sub-batch k, the pairs [base, base + m).  On its stream: what the pre_sub hook put there, then all its kernels up to the final states, statistics sums and scores.
+static int align_enqueue_sub(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& run, int base, int k) {
+  const pwn_hip_aligner_params* p = c.p;
+  const int m = std::min(run.plan.sub, c.n - base), N = run.N;
+  hipStream_t st = run.plan.stream(k);
+  const size_t s0 = (size_t)run.plan.slot0(k);
+  const PairLaunch L = { &run.ap, run.nb, run.omSym, m, st, ctx->pairs_dev + base, run.robust ? ctx->zdepth_ws + s0 * ctx->N : nullptr };
+  int maxcap_ref = 0, maxcap_cur = 0;
+  for (int i = 0; i < m; ++i) { maxcap_ref = std::max(maxcap_ref, c.refs[base + i]->d.capacity); maxcap_cur = std::max(maxcap_cur, c.curs[base + i]->d.capacity); }
+  const unsigned tag0 = run.rolling ? run.tagBase - (unsigned)k * run.tagsPerSub : kZ32Tag0, lastRefTag = tag0 - (run.tagsPerSub - 1);
+  if (!run.rolling) {      // z-buffers start empty; slots are contiguous
+    HIPCHK(ctx, hipMemsetAsync(ctx->z32ref_ws + s0 * ctx->N, 0xFF, (size_t)m * ctx->N * 4, st), PWN_HIP_ERR_COPY);
+    HIPCHK(ctx, hipMemsetAsync(ctx->z32cur_ws + s0 * ctx->N, 0xFF, (size_t)m * ctx->N * 4, st), PWN_HIP_ERR_COPY);
+  }
+  if (s0 == 0 || k == 0) {      // slot 0: what pwn_hip_align_images / pwn_hip_match_score read
+    run.slot0.pair = base; run.slot0.ref_cloud = c.refs[base]; run.slot0.cur_cloud = c.curs[base];
+    run.slot0.cur_tag = tag0; run.slot0.ref_tag = lastRefTag;
+  }
+  if (c.hooks && c.hooks->pre_sub) { if (int rc = c.hooks->pre_sub(base, m, k, st)) return rc; }
+  if (!run.sub_own[k]) {
+    StageTimer t(ctx, "project_cur", st);
+    if (int rc = launch_project_cur(ctx, L, maxcap_cur, tag0)) return rc; }
+  for (int i = 0; i < p->outer_iterations; ++i) {
+    const unsigned tag = tag0 - (unsigned)i;      // epoch of this outer iteration's reference projection
+    const int ownRef = (i == 0 && run.sub_ownref[k]) ? 1 : 0;
+    if (!ownRef) { StageTimer t(ctx, "project_ref", st);
+      if (int rc = launch_project(ctx, L, maxcap_ref, 0, tag)) return rc; }
+    for (int j = 0; j < p->inner_iterations; ++j) {
+      const bool lastInner = (j == p->inner_iterations - 1);
+      { StageTimer t(ctx, "corr_linearize", st);
+        // first inner pass: the linearizer's transform is bitwise the finder's (aligner.cpp:79,84)
+        if (j == 0) launch_corr_linearize<true, false>(ctx, L, tag, 0, ownRef);
+        else launch_corr_linearize<false, false>(ctx, L, tag, 0, ownRef); }
+      { StageTimer t(ctx, "solve", st);
+        hipLaunchKernelGGL(k_solve_update, dim3(m), dim3(256), 0, st, L.pr, run.ap, run.nb, lastInner ? 1 : 0, (lastInner && i == p->outer_iterations - 1) ? 1 : 0); }
+    }
+  }
+  if (c.statistics && p->outer_iterations > 0) {
+    StageTimer t(ctx, "statistics", st);
+    launch_statistics(ctx, L, lastRefTag, ctx->stats_dev + base);
+  }
+  if (run.want_scores && p->outer_iterations > 0) {
+    StageTimer t(ctx, "match_score", st);     // the z-buffers of this sub-batch still hold the finder's last depth images
+    // blocks per pair: enough to fill the device together with the other pairs of the launch, few enough that the per-block atomics on the
+    // pair's one record stay rare
+    hipLaunchKernelGGL(k_match_score, dim3(std::min((N + 255) / 256, m >= 8 ? 64 : 256), m), dim3(256), 0, st, L.pr, N, lastRefTag, tag0, 1000.0f,
+                       c.match_threshold, ctx->match_dev + base, run.sub_own[k] ? 1 : 0);
+  }
+  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  return PWN_HIP_OK;
+}
+// Enqueue the records.  On ctx->stream (the streams have joined): the pair ids up, k_pack_records, and the records on their way to the caller -- as the kernel
+// wrote them: straight into the caller's device buffer (what an all-gather sends), or through the context's own buffer into host memory.
+static int align_enqueue_records(pwn_hip_ctx* ctx, const AlignCall& c) {
+  const int n = c.n;
+  if (n <= 0 || !c.records) return PWN_HIP_OK;
+  const bool dev = is_device_ptr(c.records);
+  const int rlen = c.match_records ? kMatchRecordFloats : kRecordFloats;
+  if (!dev) HIPCHK(ctx, ctx->records_ws.ensure((size_t)std::max(n, 64) * kMatchRecordFloats), PWN_HIP_ERR_ALLOCATION);
+  if (c.pair_ids) {
+    HIPCHK(ctx, ctx->ids_dev.ensure((size_t)std::max(n, 64)), PWN_HIP_ERR_ALLOCATION);
+    HIPCHK(ctx, copy_any(ctx->ids_dev, c.pair_ids, sizeof(int) * n, ctx->stream), PWN_HIP_ERR_COPY);
+  }
+  float* dst = dev ? c.records : ctx->records_ws;
+  hipLaunchKernelGGL(k_pack_records, dim3(n), dim3(c.match_records ? 128 : 64), 0, ctx->stream, ctx->pairs_dev, c.pair_ids ? (const int*)ctx->ids_dev : nullptr, c.first_pair_id, dst,
+                     c.match_records ? (const MatchAcc*)ctx->match_dev : nullptr);
+  if (!dev) HIPCHK(ctx, hipMemcpyAsync(c.records, ctx->records_ws, sizeof(float) * rlen * n, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
+  return PWN_HIP_OK;
+}
+// Enqueue the copy-backs and the end event.  On ctx->stream: everything of the call; nothing has been waited for.
+static int align_enqueue_copybacks(pwn_hip_ctx* ctx, const AlignCall& c, const AlignRun& run) {
+  const int n = c.n;
+  if (n > 0 && c.scores) HIPCHK(ctx, hipMemcpyAsync(ctx->match_host, ctx->match_dev, sizeof(MatchAcc) * n, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
+  if (n > 0 && c.statistics) HIPCHK(ctx, hipMemcpyAsync(ctx->stats_host, ctx->stats_dev, sizeof(SolveOut) * n, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
+  // direct_state: T, it and the traces of state_host[i] were written by the last k_solve_update of each pair (PairDesc::state_out); with no
+  // iterations it still holds the initial state
+  if (n > 0 && !run.direct_state && c.results) HIPCHK(ctx, hipMemcpyAsync(ctx->state_host, ctx->state_ws, sizeof(PairState) * n, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipEventRecord(ctx->t1, ctx->stream), PWN_HIP_ERR_LAUNCH);      // before the wait: recording it afterwards costs a second round trip per call
+  return PWN_HIP_OK;
+}
+
+static void finish_match(const MatchAcc& a, pwn_hip_match_result* r) {
+  r->image_non_zeros = (int)a.nonZeros;
+  r->image_inliers = (int)a.inliers;
+  r->image_outliers = (int)a.nonZeros - (int)a.inliers;
+  r->image_reprojection_distance = match_reprojection_distance(a);               // the expression k_pack_records evaluates for the score words of a record
+}
 // a pair's result from its final state (transform, iterations, traces)
 static void fill_result(pwn_hip_align_result& r, const PairState& st, const pwn_hip_cloud* ref, const pwn_hip_cloud* cur, float ms) {
   std::memset(&r, 0, sizeof(r));
@@ -1910,211 +2134,71 @@ static void fill_statistics(pwn_hip_align_statistics& q, const SolveOut* so, con
   std::memcpy(q.H, so->H, sizeof(q.H)); std::memcpy(q.b, so->b, sizeof(q.b)); q.error = so->chi2; q.inliers = so->inliers;
   compute_statistics(so->H, T, q.mean, q.omega, &q.translational_eigen_ratio, &q.rotational_eigen_ratio);
 }
-// records (optional): n * PWN_HIP_RECORD_FLOATS floats, device or host, written by k_pack_records; pair_ids (optional, host): the id in
-// record word 19 (else first_pair_id + i).  results may be NULL when records are asked for.
-// robust: every projection of the call by the two-pass kernels (what align_batch_impl repeats a call with whose k_project gave up on a pixel)
-static int align_batch_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs,
-                            const float* guesses, pwn_hip_align_result* results, pwn_hip_match_result* scores, float match_threshold,
-                            pwn_hip_align_statistics* statistics, const AlignHooks* hooks, float* records,
-                            const int* pair_ids, int first_pair_id, bool match_records, bool robust) {
-  if (!ctx || !p || !refs || !curs || (!results && !records) || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  if (int rc = check_image(ctx, p->rows, p->cols)) return rc;      // (first: a call refused for its image size keeps the last alignment's images)
-  ctx->img_valid = false;                 // whatever happens below, the finder images of an earlier alignment are gone (set again on success)
-  if (int rc = check_align_params(ctx, p)) return rc;
-  if (int rc = start_align_attempt(ctx, robust)) return rc;
-  const bool want_scores = scores != nullptr || (records && match_records);      // the score words of the long records come from the same accumulators
-  const int N = p->rows * p->cols;
-  const AlignParams ap = make_align_params(ctx, p);
-  const int nb = align_nblocks(N);
-  ctx->stages.clear();
-  const StreamPlan plan = make_plan(ctx, ctx->sub_pairs, n);
-  const int sub = plan.sub;
-  if (int rc = ensure_desc(ctx, n)) return rc;
-  HIPCHK(ctx, hipEventRecord(ctx->t0, ctx->stream), PWN_HIP_ERR_LAUNCH);
-  // Batch calls (the finder's images belong to single alignments) skip the projection of a current cloud whose own index image is that
-  // projection's result; the matchClouds score then reads the current depth image off the cloud itself (k_match_score, curOwn).
-  // (single alignments too: the finder's current images are then made on demand, see img_cur_lazy)
-  const bool batch_shortcut = n >= 1 && ctx->index_shortcut && is_identity(forced(p->current_sensor_offset));
-  std::vector<char> own_index((size_t)std::max(n, 1), 0), own_ref((size_t)std::max(n, 1), 0);
-  const bool ident_ref = is_identity(forced(p->reference_sensor_offset));
-  const bool direct_state = n <= 4;
-  const int omSym = (n > 0 && curs[0]) ? curs[0]->d.omSym : 0;      // the linearizer reads the CURRENT cloud's information matrices (linearizer.cpp:52-53)
-  // descriptors + initial states of all pairs; workspace slots are reused round-robin across sub-batches.  This loop runs with the device
-  // idle (the call's first launch comes after it): what does not depend on the pair is computed once, and only the head of a state is cleared
-  // (the traces behind `it` are written before they are read: k_solve_update stores entry `it`, every reader stops at `it`)
-  Mat4 KRtCur0;
-  { Mat4 iKRt0; Mat3 iK0; projector_matrices(ap.K, mat4_from(p->current_sensor_offset), KRtCur0, iKRt0, iK0); }
-  for (int i = 0; i < n; ++i) {
-    const pwn_hip_cloud* r = refs[i]; const pwn_hip_cloud* c = curs[i];
-    if (!r || !c) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null cloud in batch");
-    if (c->d.omSym != omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "current clouds of one batch must share one omega storage (exact9 / sym6)");
-    if (int rc = check_pair_points(ctx, r, c)) return rc;
-    // a few pairs (latency path): k_solve_update writes the pose and the traces into the page-locked host copy itself, no copy back at the end;
-    // batches copy the states back in one transfer (64 workgroups storing across PCIe in every solve launch cost more than that: 16 against 11 us per launch)
-    fill_pair(ctx, i, plan.slot0(i / sub) + i % sub, r, c, direct_state ? ctx->state_host + i : nullptr, robust);
-    // the converter's own index image is what projecting the current cloud would give (see pwn_hip_cloud::idximg)
-    own_index[i] = batch_shortcut && c->idx_valid && c->idx_rows == p->rows && c->idx_cols == p->cols && c->idx_minD == p->min_distance &&
-                   c->idx_maxD == p->max_distance && std::memcmp(c->idx_K, p->K, sizeof(c->idx_K)) == 0;
-    // initial state: aligner.cpp:60-64,72-73,79,84
-    PairState& st = ctx->state_host[i];
-    std::memset(&st, 0, offsetof(PairState, chi2));
-    Mat4 T = mat4_from(guesses ? guesses + 16 * (size_t)i : p->initial_guess);
-    set_last_row(T);
-    // first reference projection with an identity pose (identity guess and reference offset): it returns the reference cloud's own index
-    // image, like the current cloud's; later iterations (and the last one, whose z-buffer the statistics pass re-reads) project as usual
-    own_ref[i] = batch_shortcut && p->outer_iterations > 1 && ident_ref && is_identity(T) && r->idx_valid && r->idx_rows == p->rows &&
-                 r->idx_cols == p->cols && r->idx_minD == p->min_distance && r->idx_maxD == p->max_distance && std::memcmp(r->idx_K, p->K, sizeof(r->idx_K)) == 0;
-    set_pose(st, T, ap, KRtCur0);
-  }
-  // a sub-batch skips the projection kernels only if every pair of it can
-  std::vector<char> sub_own((size_t)(n + sub - 1) / sub + 1, 1);
-  for (int i = 0; i < n; ++i) if (!own_index[i]) sub_own[i / sub] = 0;
-  bool any_own = false;
-  for (int i = 0; i < n; ++i) if (sub_own[i / sub]) { ctx->pairs_host[i].curidx = curs[i]->idximg; any_own = true; }
-  std::vector<char> sub_ownref(sub_own.size(), 1);
-  for (int i = 0; i < n; ++i) if (!own_ref[i]) sub_ownref[i / sub] = 0;
-  for (int i = 0; i < n; ++i) if (sub_ownref[i / sub]) ctx->pairs_host[i].refidx0 = refs[i]->idximg;
-  if (n > 0) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->pairs_dev, ctx->pairs_host, sizeof(PairDesc) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->state_ws, ctx->state_host, sizeof(PairState) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
-    if (want_scores) HIPCHK(ctx, hipMemsetAsync(ctx->match_dev, 0, sizeof(MatchAcc) * n, ctx->stream), PWN_HIP_ERR_COPY);
-  }
-  // Every sub-batch takes its own block of tags (workspace slots are reused from sub-batch to sub-batch): tag0 for the
-  // current-cloud projection (its own buffer) and tag0 - i for the reference projection of outer iteration i.  A call with
-  // more sub-batches than the tag space holds falls back to the fixed tags and clears the slots of every sub-batch.
-  const unsigned tagsPerSub = (unsigned)std::max(1, p->outer_iterations);
-  const unsigned nsub = (unsigned)((n + sub - 1) / sub);
-  if (tagsPerSub > kZ32Tag0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "more projections per alignment than z-buffer epoch tags");
-  const bool rolling = (unsigned long long)nsub * tagsPerSub <= kZ32Tag0;
-  unsigned tagBase = kZ32Tag0;
-  if (rolling && nsub > 0) { if (int rc = take_tags32(ctx, nsub * tagsPerSub, &tagBase)) return rc; }
-  // fixed tags leave words in the buffers that could beat (smaller tag wins) the tags a later rolling call draws: make that call clear first
-  if (!rolling) ctx->z32tag_next = 0;
-  unsigned tag0 = tagBase, lastRefTag = tag0 - (tagsPerSub - 1);
-  if (int rc = plan_fork(ctx, plan)) return rc;
-  for (int base = 0, kk = 0; base < n; base += sub, ++kk) {
-    const int m = std::min(sub, n - base);
-    const PairDesc* pr = ctx->pairs_dev + base;
-    hipStream_t st = plan.stream(kk);
-    const size_t s0 = (size_t)plan.slot0(kk);
-    int maxcap_ref = 0, maxcap_cur = 0;
-    for (int i = 0; i < m; ++i) { maxcap_ref = std::max(maxcap_ref, refs[base + i]->d.capacity); maxcap_cur = std::max(maxcap_cur, curs[base + i]->d.capacity); }
-    const unsigned subTag0 = rolling ? tagBase - (unsigned)kk * tagsPerSub : kZ32Tag0;
-    if (!rolling) {      // z-buffers start empty; slots are contiguous
-      HIPCHK(ctx, hipMemsetAsync(ctx->z32ref_ws + s0 * ctx->N, 0xFF, (size_t)m * ctx->N * 4, st), PWN_HIP_ERR_COPY);
-      HIPCHK(ctx, hipMemsetAsync(ctx->z32cur_ws + s0 * ctx->N, 0xFF, (size_t)m * ctx->N * 4, st), PWN_HIP_ERR_COPY);
-    }
-    if (s0 == 0 || kk == 0) {      // slot 0: what pwn_hip_align_images / pwn_hip_match_score read
-      tag0 = subTag0; lastRefTag = subTag0 - (tagsPerSub - 1); ctx->img_pair = base;
-      ctx->img_ref_cloud = refs[base]; ctx->img_cur_cloud = curs[base];
-    }
-    const unsigned subLastRefTag = subTag0 - (tagsPerSub - 1);
-    if (hooks && hooks->pre_sub) { if (int rc = hooks->pre_sub(base, m, kk, st)) return rc; }
-    if (!sub_own[kk]) {
-      StageTimer t(ctx, "project_cur", st);
-      if (int rc = launch_project(ctx, maxcap_cur, m, st, pr, ap, 1, subTag0, robust ? ctx->zdepth_ws + s0 * ctx->N : nullptr)) return rc;
-      hipLaunchKernelGGL(k_resolve_cur, dim3(std::min((N + 255) / 256, 1024), m), dim3(256), 0, st, pr, N, subTag0); }
-    for (int i = 0; i < p->outer_iterations; ++i) {
-      const unsigned tag = subTag0 - (unsigned)i;      // epoch of this outer iteration's reference projection
-      const int ownRef = (i == 0 && sub_ownref[kk]) ? 1 : 0;
-      if (!ownRef) { StageTimer t(ctx, "project_ref", st);
-        if (int rc = launch_project(ctx, maxcap_ref, m, st, pr, ap, 0, tag, robust ? ctx->zdepth_ws + s0 * ctx->N : nullptr)) return rc; }
-      for (int k = 0; k < p->inner_iterations; ++k) {
-        const bool lastInner = (k == p->inner_iterations - 1);
-        { StageTimer t(ctx, "corr_linearize", st);
-          // first inner pass: the linearizer's transform is bitwise the finder's (aligner.cpp:79,84)
-          if (k == 0) launch_corr_linearize<true, false>(ctx, omSym, nb, m, st, pr, ap, tag, 0, ownRef);
-          else launch_corr_linearize<false, false>(ctx, omSym, nb, m, st, pr, ap, tag, 0, ownRef); }
-        { StageTimer t(ctx, "solve", st);
-          hipLaunchKernelGGL(k_solve_update, dim3(m), dim3(256), 0, st, pr, ap, nb, lastInner ? 1 : 0, (lastInner && i == p->outer_iterations - 1) ? 1 : 0); }
-      }
-    }
-    if (statistics && p->outer_iterations > 0) {
-      // Aligner::_computeStatistics' extra Linearizer::update: the finder's correspondences of the last outer iteration
-      // (tests with that iteration's transform) re-linearized at the final transform (aligner.cpp:165-170)
-      StageTimer t(ctx, "statistics", st);
-      launch_corr_linearize<false, true>(ctx, omSym, nb, m, st, pr, ap, subLastRefTag, 1, 0);   // full H for _computeStatistics
-      hipLaunchKernelGGL(k_reduce_pairs, dim3(m), dim3(256), 0, st, pr, nb, ctx->stats_dev + base);
-    }
-    if (want_scores && p->outer_iterations > 0) {
-      StageTimer t(ctx, "match_score", st);     // the z-buffers of this sub-batch still hold the finder's last depth images
-      // blocks per pair: enough to fill the device together with the other pairs of the launch, few enough that the per-block atomics on the
-      // pair's one record stay rare
-      hipLaunchKernelGGL(k_match_score, dim3(std::min((N + 255) / 256, m >= 8 ? 64 : 256), m), dim3(256), 0, st, pr, N, subLastRefTag, subTag0, 1000.0f,
-                         match_threshold, ctx->match_dev + base, sub_own[kk] ? 1 : 0);
-    }
-    HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
-  }
-  if (int rc = plan_join(ctx, plan)) return rc;
-  if (n > 0 && records) {
-    // the records leave the device as the kernel wrote them: straight into the caller's device buffer (what an all-gather sends), or through the
-    // context's own buffer into host memory
-    const bool dev = is_device_ptr(records);
-    const int rlen = match_records ? kMatchRecordFloats : kRecordFloats;
-    if (!dev) HIPCHK(ctx, ctx->records_ws.ensure((size_t)std::max(n, 64) * kMatchRecordFloats), PWN_HIP_ERR_ALLOCATION);
-    if (pair_ids) {
-      HIPCHK(ctx, ctx->ids_dev.ensure((size_t)std::max(n, 64)), PWN_HIP_ERR_ALLOCATION);
-      HIPCHK(ctx, copy_any(ctx->ids_dev, pair_ids, sizeof(int) * n, ctx->stream), PWN_HIP_ERR_COPY);
-    }
-    float* dst = dev ? records : ctx->records_ws;
-    hipLaunchKernelGGL(k_pack_records, dim3(n), dim3(match_records ? 128 : 64), 0, ctx->stream, ctx->pairs_dev, pair_ids ? (const int*)ctx->ids_dev : nullptr, first_pair_id, dst,
-                       match_records ? (const MatchAcc*)ctx->match_dev : nullptr);
-    if (!dev) HIPCHK(ctx, hipMemcpyAsync(records, ctx->records_ws, sizeof(float) * rlen * n, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
-  }
-  if (hooks && hooks->before_sync) { if (int rc = hooks->before_sync()) return rc; }
-  if (n > 0 && scores) HIPCHK(ctx, hipMemcpyAsync(ctx->match_host, ctx->match_dev, sizeof(MatchAcc) * n, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
-  if (n > 0 && statistics) HIPCHK(ctx, hipMemcpyAsync(ctx->stats_host, ctx->stats_dev, sizeof(SolveOut) * n, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
-  // direct_state: T, it and the traces of state_host[i] were written by the last k_solve_update of each pair (PairDesc::state_out); with no
-  // iterations it still holds the initial state
-  if (n > 0 && !direct_state && results) HIPCHK(ctx, hipMemcpyAsync(ctx->state_host, ctx->state_ws, sizeof(PairState) * n, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipEventRecord(ctx->t1, ctx->stream), PWN_HIP_ERR_LAUNCH);      // before the wait: recording it afterwards costs a second round trip per call
-  // everything of the call is queued, nothing has been waited for: the caller's moment to queue what depends on it on other streams, or to prepare
-  // the next call, while the device works (pwn_hip_ctx_set_enqueued_callback)
-  if (ctx->enqueued_cb && n > 0) ctx->enqueued_cb(ctx->enqueued_user);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
-  if (hooks && hooks->after_sync) { if (int rc = hooks->after_sync()) return rc; }
+// Finish after the wait.  The streams are idle: the fault word is digested, scores, results and statistics are filled in, the finder's images are this call's.
+static int align_finish(pwn_hip_ctx* ctx, const AlignCall& c, const AlignRun& run) {
+  const int n = c.n;
+  if (c.hooks && c.hooks->after_sync) { if (int rc = c.hooks->after_sync()) return rc; }
   if (int rc = take_align_fault(ctx)) return rc;
-  for (int i = 0; i < n && scores; ++i) finish_match(ctx->match_host[i], &scores[i]);      // with or without `results` (pwn_hip_match_batch_records)
+  for (int i = 0; i < n && c.scores; ++i) finish_match(ctx->match_host[i], &c.scores[i]);      // with or without `results` (pwn_hip_match_batch_records)
   float ms = 0.f; (void)hipEventElapsedTime(&ms, ctx->t0, ctx->t1);
-  for (int i = 0; i < n && results; ++i) {
-    fill_result(results[i], ctx->state_host[i], refs[i], curs[i], ms / n);
-    if (statistics) fill_statistics(statistics[i], p->outer_iterations > 0 ? ctx->stats_host + i : nullptr, ctx->state_host[i].T);
+  for (int i = 0; i < n && c.results; ++i) {
+    fill_result(c.results[i], ctx->state_host[i], c.refs[i], c.curs[i], ms / n);
+    if (c.statistics) fill_statistics(c.statistics[i], c.p->outer_iterations > 0 ? ctx->stats_host + i : nullptr, ctx->state_host[i].T);
   }
   // batches: no current z-buffer after a skipped projection; a single alignment makes it on demand
-  ctx->img_rows = p->rows; ctx->img_cols = p->cols; ctx->img_valid = n > 0 && (!any_own || n == 1);
-  ctx->img_cur_lazy = n == 1 && any_own; ctx->img_ap = ap; ctx->img_cur_capacity = n == 1 ? curs[0]->d.capacity : 0;
-  ctx->img_ref_tag = lastRefTag; ctx->img_cur_tag = tag0;
+  ctx->img.set(run.ap, run.slot0, n > 0 && (!run.any_own || n == 1), n == 1 && run.any_own);
   collect_stage_times(ctx);
   return PWN_HIP_OK;
+}
+// One attempt at the call; robust: every projection by the two-pass kernels
+static int align_batch_once(pwn_hip_ctx* ctx, const AlignCall& call, bool robust) {
+  AlignRun run; run.robust = robust;
+  if (int rc = align_check_and_plan(ctx, call, run)) return rc;
+  if (int rc = align_describe_pairs(ctx, call, run)) return rc;
+  if (int rc = align_draw_tags(ctx, call, run)) return rc;
+  if (int rc = plan_fork(ctx, run.plan)) return rc;
+  for (int base = 0, k = 0; base < call.n; base += run.plan.sub, ++k) { if (int rc = align_enqueue_sub(ctx, call, run, base, k)) return rc; }
+  if (int rc = plan_join(ctx, run.plan)) return rc;
+  if (int rc = align_enqueue_records(ctx, call)) return rc;
+  if (call.hooks && call.hooks->before_sync) { if (int rc = call.hooks->before_sync()) return rc; }
+  if (int rc = align_enqueue_copybacks(ctx, call, run)) return rc;
+  // everything of the call is queued, nothing has been waited for: the caller's moment to queue what depends on it on other streams, or to prepare
+  // the next call, while the device works (pwn_hip_ctx_set_enqueued_callback)
+  if (ctx->enqueued_cb && call.n > 0) ctx->enqueued_cb(ctx->enqueued_user);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  return align_finish(ctx, call, run);
 }
 // The call; and once more with the two-pass projection if one of its projections gave up on a pixel (z32_settle): nothing of the failed
 // attempt is kept (states and descriptors are rebuilt, z-buffer tags move on; the hooks of a fused step convert the same frames into the same
 // clouds again).  A fault in the repeat cannot happen (k_project_robust has no loop) and would be reported.
-static int align_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs,
-                            const float* guesses, pwn_hip_align_result* results, pwn_hip_match_result* scores, float match_threshold,
-                            pwn_hip_align_statistics* statistics = nullptr, const AlignHooks* hooks = nullptr, float* records = nullptr,
-                            const int* pair_ids = nullptr, int first_pair_id = 0, bool match_records = false) {
-  return repeat_once(ctx, kSettleFault, [&](bool robust) {
-    return align_batch_once(ctx, p, n, refs, curs, guesses, results, scores, match_threshold, statistics, hooks, records, pair_ids, first_pair_id, match_records, robust);
-  });
+static int align_batch_impl(pwn_hip_ctx* ctx, const AlignCall& call) {
+  return repeat_once(ctx, kSettleFault, [&](bool robust) { return align_batch_once(ctx, call, robust); });
+}
+// the members every batch entry point fills
+static AlignCall align_call(const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs, const float* guesses,
+                            pwn_hip_align_result* results) {
+  AlignCall c; c.p = p; c.n = n; c.refs = refs; c.curs = curs; c.guesses = guesses; c.results = results;
+  return c;
 }
 int pwn_hip_align_batch(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs,
                         const float* guesses, pwn_hip_align_result* results) {
-  return align_batch_impl(ctx, p, n, refs, curs, guesses, results, nullptr, 0.f);
+  return align_batch_impl(ctx, align_call(p, n, refs, curs, guesses, results));
 }
 int pwn_hip_match_batch(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs,
                         const float* guesses, float threshold, pwn_hip_align_result* results, pwn_hip_match_result* scores) {
   if (!scores) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null scores");
-  return align_batch_impl(ctx, p, n, refs, curs, guesses, results, scores, threshold);
+  AlignCall call = align_call(p, n, refs, curs, guesses, results);
+  call.scores = scores; call.match_threshold = threshold;
+  return align_batch_impl(ctx, call);
 }
 int pwn_hip_align_with_priors(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, const pwn_hip_cloud* ref, const pwn_hip_cloud* cur, int n_priors,
                               const pwn_hip_prior* priors, pwn_hip_align_result* result) {
   return pwn_hip_align_with_priors_ex(ctx, p, ref, cur, n_priors, priors, result, nullptr);
 }
-// n_priors > 0 (pwn_hip_align_with_priors_ex); robust: see align_batch_once
-static int align_with_priors_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, const pwn_hip_cloud* ref, const pwn_hip_cloud* cur, int n_priors,
-                                  const pwn_hip_prior* priors, pwn_hip_align_result* result, pwn_hip_align_statistics* statistics, bool robust) {
-  if (!ctx || !p || !ref || !cur || !priors || !result) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+// n_priors > 0 (pwn_hip_align_with_priors_ex): the one pair of `call` with its result and (optional) statistics, the loop driven from the host; robust: see align_batch_once
+static int align_with_priors_once(pwn_hip_ctx* ctx, const AlignCall& call, int n_priors, const pwn_hip_prior* priors, bool robust) {
+  const pwn_hip_aligner_params* p = call.p; const pwn_hip_cloud* ref = call.refs[0]; const pwn_hip_cloud* cur = call.curs[0];
+  if (!ctx || !p || !ref || !cur || !priors || !call.results) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (int rc = check_align_params(ctx, p)) return rc;
   std::vector<PriorHost> pr(n_priors);
   for (int i = 0; i < n_priors; ++i) {
@@ -2123,15 +2207,12 @@ static int align_with_priors_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params
     std::memcpy(pr[i].information, priors[i].information, sizeof(pr[i].information));
   }
   if (int rc = check_pair_points(ctx, ref, cur)) return rc;
-  const int N = p->rows * p->cols;
   const AlignParams ap = make_align_params(ctx, p);
-  const int nb = align_nblocks(N);
   hipStream_t st = ctx->stream;
   if (int rc = start_align_attempt(ctx, robust)) return rc;
   fill_pair(ctx, 0, 0, ref, cur, nullptr, robust);
-  const PairDesc& pd = ctx->pairs_host[0];
-  ctx->img_valid = false;
-  ctx->img_pair = 0; ctx->img_ref_cloud = ref; ctx->img_cur_cloud = cur;
+  const PairLaunch L = { &ap, align_nblocks(p->rows * p->cols), cur->d.omSym, 1, st, ctx->pairs_dev, ctx->pairs_host[0].zdepth };
+  ctx->img.invalidate();
   PairState& hs = ctx->state_host[0];
   std::memset(&hs, 0, sizeof(hs));
   Mat4 T = mat4_from(p->initial_guess); set_last_row(T);
@@ -2143,10 +2224,10 @@ static int align_with_priors_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params
   HIPCHK(ctx, hipMemcpyAsync(ctx->state_ws, &hs, sizeof(PairState), hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
   // z-buffer tags come from the context's running supply like the batch path's (a smaller tag wins atomicMin: fixed tags would
   // leave words behind that beat a later call's)
-  unsigned tag0 = kZ32Tag0;
-  if (int rc = take_tags32(ctx, (unsigned)std::max(1, p->outer_iterations), &tag0)) return rc;
-  if (int rc = launch_project(ctx, cur->d.capacity, 1, st, ctx->pairs_dev, ap, 1, tag0, pd.zdepth)) return rc;
-  hipLaunchKernelGGL(k_resolve_cur, dim3(std::min((N + 255) / 256, 1024), 1), dim3(256), 0, st, ctx->pairs_dev, N, tag0);
+  Slot0Pair slot0; slot0.ref_cloud = ref; slot0.cur_cloud = cur;
+  if (int rc = take_tags32(ctx, (unsigned)std::max(1, p->outer_iterations), &slot0.cur_tag)) return rc;
+  const unsigned tag0 = slot0.cur_tag; slot0.ref_tag = tag0 - (unsigned)std::max(0, p->outer_iterations - 1);
+  if (int rc = launch_project_cur(ctx, L, cur->d.capacity, tag0)) return rc;
   int it = 0;
   for (int i = 0; i < p->outer_iterations; ++i) {
     const unsigned tag = tag0 - (unsigned)i;
@@ -2157,10 +2238,10 @@ static int align_with_priors_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params
       set_last_row(invT);                                                            // :86
       hs.invT = invT;
       HIPCHK(ctx, hipMemcpyAsync(ctx->state_ws, &hs, sizeof(PairState), hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
-      if (k == 0) { if (int rc = launch_project(ctx, ref->d.capacity, 1, st, ctx->pairs_dev, ap, 0, tag, pd.zdepth)) return rc; }
-      if (k == 0) launch_corr_linearize<true, true>(ctx, cur->d.omSym, nb, 1, st, ctx->pairs_dev, ap, tag, 0, 0);
-      else launch_corr_linearize<false, true>(ctx, cur->d.omSym, nb, 1, st, ctx->pairs_dev, ap, tag, 0, 0);
-      hipLaunchKernelGGL(k_reduce_pairs, dim3(1), dim3(256), 0, st, ctx->pairs_dev, nb, ctx->stats_dev);
+      if (k == 0) { if (int rc = launch_project(ctx, L, ref->d.capacity, 0, tag)) return rc; }
+      if (k == 0) launch_corr_linearize<true, true>(ctx, L, tag, 0, 0);
+      else launch_corr_linearize<false, true>(ctx, L, tag, 0, 0);
+      hipLaunchKernelGGL(k_reduce_pairs, dim3(1), dim3(256), 0, st, ctx->pairs_dev, L.nb, ctx->stats_dev);
       HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
       HIPCHK(ctx, hipMemcpyAsync(ctx->stats_host, ctx->stats_dev, sizeof(SolveOut), hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
       HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
@@ -2179,15 +2260,12 @@ static int align_with_priors_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params
     T = iso_inverse(invT);                                                           // :115-117
     float v[6]; t2v(T, v); T = v2t(v); set_last_row(T);
   }
-  const unsigned lastRefTag = tag0 - (unsigned)std::max(0, p->outer_iterations - 1);
-  if (statistics && p->outer_iterations > 0) {
-    // Aligner::_computeStatistics (aligner.cpp:127,152-199) runs after the loop whether or not priors exist: one more
-    // Linearizer::update at the final transform on the finder's last correspondences, H + I without the prior terms (:168-170)
+  if (call.statistics && p->outer_iterations > 0) {
+    // Aligner::_computeStatistics (aligner.cpp:127,152-199) runs after the loop whether or not priors exist: H + I without the prior terms (:168-170)
     hs.invTcorrPrev = hs.invTcorr;
     hs.invT = iso_inverse(T); set_last_row(hs.invT);                                  // :165-167
     HIPCHK(ctx, hipMemcpyAsync(ctx->state_ws, &hs, sizeof(PairState), hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
-    launch_corr_linearize<false, true>(ctx, cur->d.omSym, nb, 1, st, ctx->pairs_dev, ap, lastRefTag, 1, 0);
-    hipLaunchKernelGGL(k_reduce_pairs, dim3(1), dim3(256), 0, st, ctx->pairs_dev, nb, ctx->stats_dev);
+    launch_statistics(ctx, L, slot0.ref_tag, ctx->stats_dev);
     HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
     HIPCHK(ctx, hipMemcpyAsync(ctx->stats_host, ctx->stats_dev, sizeof(SolveOut), hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
     HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
@@ -2197,38 +2275,41 @@ static int align_with_priors_once(pwn_hip_ctx* ctx, const pwn_hip_aligner_params
   if (int rc = take_align_fault(ctx)) return rc;
   float ms = 0.f; (void)hipEventElapsedTime(&ms, ctx->t0, ctx->t1);
   hs.T = T; hs.it = it;
-  fill_result(*result, hs, ref, cur, ms);
-  if (statistics) fill_statistics(*statistics, p->outer_iterations > 0 ? ctx->stats_host : nullptr, T);
-  ctx->img_rows = p->rows; ctx->img_cols = p->cols; ctx->img_valid = true; ctx->img_cur_lazy = false;
-  ctx->img_ref_tag = lastRefTag; ctx->img_cur_tag = tag0;
+  fill_result(*call.results, hs, ref, cur, ms);
+  if (call.statistics) fill_statistics(*call.statistics, p->outer_iterations > 0 ? ctx->stats_host : nullptr, T);
+  ctx->img.set(ap, slot0, true, false);
   return PWN_HIP_OK;
 }
 int pwn_hip_align_with_priors_ex(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, const pwn_hip_cloud* ref, const pwn_hip_cloud* cur, int n_priors,
                                  const pwn_hip_prior* priors, pwn_hip_align_result* result, pwn_hip_align_statistics* statistics) {
-  if (n_priors <= 0) {
-    pwn_hip_cloud* r[1] = { const_cast<pwn_hip_cloud*>(ref) };
-    pwn_hip_cloud* c[1] = { const_cast<pwn_hip_cloud*>(cur) };
-    return align_batch_impl(ctx, p, 1, r, c, nullptr, result, nullptr, 0.f, statistics);
-  }
-  return repeat_once(ctx, kSettleFault, [&](bool robust) {
-    return align_with_priors_once(ctx, p, ref, cur, n_priors, priors, result, statistics, robust);
-  });
+  pwn_hip_cloud* r[1] = { const_cast<pwn_hip_cloud*>(ref) };
+  pwn_hip_cloud* c[1] = { const_cast<pwn_hip_cloud*>(cur) };
+  AlignCall call = align_call(p, 1, r, c, nullptr, result);
+  call.statistics = statistics;
+  if (n_priors <= 0) return align_batch_impl(ctx, call);
+  return repeat_once(ctx, kSettleFault, [&](bool robust) { return align_with_priors_once(ctx, call, n_priors, priors, robust); });
 }
 int pwn_hip_align_batch_ex(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs,
                            const float* guesses, pwn_hip_align_result* results, float threshold, pwn_hip_match_result* scores,
                            pwn_hip_align_statistics* statistics) {
-  return align_batch_impl(ctx, p, n, refs, curs, guesses, results, scores, threshold, statistics);
+  AlignCall call = align_call(p, n, refs, curs, guesses, results);
+  call.scores = scores; call.match_threshold = threshold; call.statistics = statistics;
+  return align_batch_impl(ctx, call);
 }
 int pwn_hip_align_batch_records(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs,
                                 const float* guesses, const int* pair_ids, int first_pair_id, pwn_hip_align_result* results, float* records) {
   if (!records) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null records");
-  return align_batch_impl(ctx, p, n, refs, curs, guesses, results, nullptr, 0.f, nullptr, nullptr, records, pair_ids, first_pair_id);
+  AlignCall call = align_call(p, n, refs, curs, guesses, results);
+  call.records = records; call.pair_ids = pair_ids; call.first_pair_id = first_pair_id;
+  return align_batch_impl(ctx, call);
 }
 int pwn_hip_match_batch_records(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs,
                                 const float* guesses, float threshold, const int* pair_ids, int first_pair_id, pwn_hip_align_result* results,
                                 pwn_hip_match_result* scores, float* records) {
   if (!records) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null records");
-  return align_batch_impl(ctx, p, n, refs, curs, guesses, results, scores, threshold, nullptr, nullptr, records, pair_ids, first_pair_id, true);
+  AlignCall call = align_call(p, n, refs, curs, guesses, results);
+  call.scores = scores; call.match_threshold = threshold; call.records = records; call.match_records = true; call.pair_ids = pair_ids; call.first_pair_id = first_pair_id;
+  return align_batch_impl(ctx, call);
 }
 int pwn_hip_convert_align_batch_u16(pwn_hip_ctx* ctx, const pwn_hip_converter_params* cp, const pwn_hip_aligner_params* ap, int n,
                                     const uint16_t* const* ref_frames, const uint16_t* const* cur_frames, float depth_scale, int rows, int cols,
@@ -2280,7 +2361,9 @@ int pwn_hip_convert_align_batch_u16(pwn_hip_ctx* ctx, const pwn_hip_converter_pa
     };
     hooks.before_sync = [&]() -> int { return counts_enqueue(ctx, 2 * n); };
     hooks.after_sync = [&]() -> int { return counts_apply(ctx, clouds.data(), 2 * n); };
-    return align_batch_impl(ctx, ap, n, refs, curs, guesses, results, nullptr, 0.f, nullptr, &hooks, records, pair_ids, first_pair_id);
+    AlignCall call = align_call(ap, n, refs, curs, guesses, results);
+    call.hooks = &hooks; call.records = records; call.pair_ids = pair_ids; call.first_pair_id = first_pair_id;
+    return align_batch_impl(ctx, call);
   });
 }
 void pwn_hip_compute_statistics(const float H[36], const float T[16], float mean[6], float omega[36], float* tr, float* rr) {
@@ -2288,12 +2371,12 @@ void pwn_hip_compute_statistics(const float H[36], const float T[16], float mean
 }
 int pwn_hip_match_score(pwn_hip_ctx* ctx, float threshold, pwn_hip_match_result* out) {
   if (!ctx || !out) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  if (!ctx->img_valid) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "no alignment has run on this context");
-  const int N = ctx->img_rows * ctx->img_cols;
+  if (!ctx->img.valid) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "no alignment has run on this context");
+  const int N = ctx->img.ap.rows * ctx->img.ap.cols;
   // the descriptor of the pair in slot 0 is still in pairs_dev (clouds, z-buffers, state with the projection matrices)
   HIPCHK(ctx, hipMemsetAsync(ctx->match_dev, 0, sizeof(MatchAcc), ctx->stream), PWN_HIP_ERR_COPY);
-  hipLaunchKernelGGL(k_match_score, dim3(std::min((N + 255) / 256, 256), 1), dim3(256), 0, ctx->stream, ctx->pairs_dev + ctx->img_pair, N, ctx->img_ref_tag,
-                     ctx->img_cur_tag, 1000.0f, threshold, ctx->match_dev, ctx->img_cur_lazy ? 1 : 0);
+  hipLaunchKernelGGL(k_match_score, dim3(std::min((N + 255) / 256, 256), 1), dim3(256), 0, ctx->stream, ctx->pairs_dev + ctx->img.pair, N, ctx->img.ref_tag,
+                     ctx->img.cur_tag, 1000.0f, threshold, ctx->match_dev, ctx->img.cur_lazy ? 1 : 0);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   HIPCHK(ctx, hipMemcpyAsync(ctx->match_host, ctx->match_dev, sizeof(MatchAcc), hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
@@ -2307,25 +2390,26 @@ int pwn_hip_align(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, const pwn_h
 }
 int pwn_hip_align_images(pwn_hip_ctx* ctx, int* ref_index, float* ref_depth, int* cur_index, float* cur_depth) {
   if (!ctx) return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, "null ctx");
-  if (!ctx->img_valid) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "no alignment has run on this context");
-  const size_t N = (size_t)ctx->img_rows * ctx->img_cols;
-  if (ctx->img_cur_lazy && (cur_index || cur_depth)) {      // the projection the alignment skipped, with the tag it had reserved for it
+  if (!ctx->img.valid) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "no alignment has run on this context");
+  const size_t N = (size_t)ctx->img.ap.rows * ctx->img.ap.cols;
+  if (ctx->img.cur_lazy && (cur_index || cur_depth)) {      // the projection the alignment skipped, with the tag it had reserved for it
     // two-pass form straight away: one projection of one cloud, off the hot path, and no repeat to arrange (the pair's descriptor on the device
     // gets the depth image's address first)
     if (int rc = ensure_zdepth(ctx)) return rc;
-    ctx->pairs_host[ctx->img_pair].zdepth = ctx->zdepth_ws;
-    HIPCHK(ctx, hipMemcpyAsync(&ctx->pairs_dev[ctx->img_pair].zdepth, &ctx->pairs_host[ctx->img_pair].zdepth, sizeof(unsigned*), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
-    if (int rc = launch_project(ctx, ctx->img_cur_capacity, 1, ctx->stream, ctx->pairs_dev + ctx->img_pair, ctx->img_ap, 1, ctx->img_cur_tag, ctx->zdepth_ws)) return rc;
+    ctx->pairs_host[ctx->img.pair].zdepth = ctx->zdepth_ws;
+    HIPCHK(ctx, hipMemcpyAsync(&ctx->pairs_dev[ctx->img.pair].zdepth, &ctx->pairs_host[ctx->img.pair].zdepth, sizeof(unsigned*), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+    const PairLaunch L = { &ctx->img.ap, 0, 0, 1, ctx->stream, ctx->pairs_dev + ctx->img.pair, ctx->zdepth_ws };
+    if (int rc = launch_project(ctx, L, ctx->img.cur_cloud->d.capacity, 1, ctx->img.cur_tag)) return rc;
     HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
-    ctx->img_cur_lazy = false;
+    ctx->img.cur_projected();
   }
   for (int pass = 0; pass < 2; ++pass) {
     int* oi = pass == 0 ? ref_index : cur_index; float* od = pass == 0 ? ref_depth : cur_depth;
     if (!oi && !od) continue;
     int* di = oi ? (is_device_ptr(oi) ? oi : ctx->index_ws) : nullptr;
     float* dd = od ? (is_device_ptr(od) ? od : ctx->depth_ws) : nullptr;
-    hipLaunchKernelGGL(k_pair_images, dim3((unsigned)std::min<size_t>((N + 255) / 256, 2048)), dim3(256), 0, ctx->stream, ctx->pairs_dev + ctx->img_pair, pass,
-                       pass == 0 ? ctx->img_ref_tag : ctx->img_cur_tag, (int)N, di, dd);
+    hipLaunchKernelGGL(k_pair_images, dim3((unsigned)std::min<size_t>((N + 255) / 256, 2048)), dim3(256), 0, ctx->stream, ctx->pairs_dev + ctx->img.pair, pass,
+                       pass == 0 ? ctx->img.ref_tag : ctx->img.cur_tag, (int)N, di, dd);
     HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
     if (oi && di != oi) HIPCHK(ctx, hipMemcpyAsync(oi, di, N * 4, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
     if (od && dd != od) HIPCHK(ctx, hipMemcpyAsync(od, dd, N * 4, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);

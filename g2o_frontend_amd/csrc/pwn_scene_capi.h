@@ -213,7 +213,7 @@ int pwn_hip_merge(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, const float K[9], cons
   HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
   swap_back(cloud);
   cloud->n_host = k; cloud->idx_valid = false;
-  ctx->img_valid = false;                 // slot 0 of the z-buffer was used
+  ctx->img.invalidate();                  // slot 0 of the z-buffer was used
   if (new_size) *new_size = k;
   return PWN_HIP_OK;
 }

@@ -282,6 +282,49 @@ def test_index_shortcut_is_the_projection_it_replaces(world):
     assert np.array_equal(conv.indexImage(), on["images"][1]["cur_index"])
 
 
+def test_index_shortcut_is_not_taken_when_the_key_differs(world):
+    """The negative case of the shortcut: clouds converted with the fixture's converter parameters, aligned with a projector that differs from
+    them in ONE field of the index-image key (one K entry in its last bit, the minimum / maximum distance so that valid pixels of the frames
+    fall outside, the image rows / cols).  Such a cloud's own index image is not what the projection gives and every projection must run: a
+    batch of 3 pairs and the single alignment of pair 0 are bitwise what they are with the shortcut switched off
+    (pwn_hip_debug_set_index_shortcut).  With all five fields equal the same holds (the positive case, asserted once more)."""
+    ctx, aligner = world["ctx"], world["aligner"]
+    refs, curs, rows, cols = world["refs"][:3], world["curs"][:3], world["rows"], world["cols"]
+    proj = aligner.projector()
+    keys = ("T", "chi2", "C", "K", "iter_inliers")
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint32) if np.asarray(a).dtype.itemsize == 4 else np.ascontiguousarray(a)
+    K0, min0, max0 = proj.cameraMatrix().copy(), proj.minDistance(), proj.maxDistance()
+    # valid depths of the six frames as the converter saw them (raw 0 stays 0 metres; valid = not outside [min, max])
+    depths = [np.asarray(f, np.float32) * np.float32(0.001) for p in world["pairs"][:3] for f in p[:2]]
+    valid = [d[(d != 0) & ~((d < np.float32(min0)) | (d > np.float32(max0)))] for d in depths]
+    new_min = float(np.float32(max(v.min() for v in valid) + 0.05)); new_max = float(np.float32(min(v.max() for v in valid) - 0.05))
+    assert min0 < new_min < new_max < max0
+    for v in valid:                                   # every frame loses valid pixels at the moved bound
+        assert (v < np.float32(new_min)).sum() >= 1 and (v > np.float32(new_max)).sum() >= 1
+    K1 = K0.copy(); K1[0, 0] = np.nextafter(K0[0, 0], np.float32(np.inf)); assert K1[0, 0] != K0[0, 0]
+    cases = dict(equal=lambda: None, K=lambda: proj.setCameraMatrix(K1), min_distance=lambda: proj.setMinDistance(new_min),
+                 max_distance=lambda: proj.setMaxDistance(new_max), rows=lambda: proj.setImageSize(rows - 2, cols),
+                 cols=lambda: proj.setImageSize(rows, cols - 2))
+
+    def run(enabled):
+        ctx.check(ctx._L.pwn_hip_debug_set_index_shortcut(ctx.h, enabled))
+        aligner.setReferenceCloud(refs[0]); aligner.setCurrentCloud(curs[0])
+        return aligner.alignBatch(refs, curs) + [aligner.align()]
+
+    try:
+        for name, change in cases.items():
+            change()
+            on, off = run(1), run(0)
+            for j, (a, b) in enumerate(zip(on, off)):
+                assert a["iterations"] == b["iterations"] == 10, (name, j)
+                for k in keys:
+                    assert np.array_equal(bits(a[k]), bits(b[k])), (name, j, k)
+            proj.setCameraMatrix(K0); proj.setMinDistance(min0); proj.setMaxDistance(max0); proj.setImageSize(rows, cols)
+    finally:
+        proj.setCameraMatrix(K0); proj.setMinDistance(min0); proj.setMaxDistance(max0); proj.setImageSize(rows, cols)
+        ctx.check(ctx._L.pwn_hip_debug_set_index_shortcut(ctx.h, 1))
+
+
 def test_single_point_projector_forms_are_the_kernels_expressions():
     """PinholePointProjector::project(x, y, f, p) / unProject(p, x, y, d) / projectInterval (host code of the library) against what the kernels wrote for
     the same pixels and points: the converter's points and interval image, and the index / depth images of a projection under a non-identity camera pose."""
