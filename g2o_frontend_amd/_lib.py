@@ -100,6 +100,8 @@ PROTOTYPES = {
     "pwn_hip_depth_u16_to_f32": (_I, [_VP, _VP, _VP, _I, _F]),
     "pwn_hip_depth_f32_to_u16": (_I, [_VP, _VP, _VP, _I, _F]),
     "pwn_hip_depth_scale": (_I, [_VP, _VP, _I, _I, _I, _F, _VP]),
+    "pwn_hip_depth_scale_batch": (_I, [_VP, _VP, _I, _I, _I, _I, _F, _VP]),
+    "pwn_hip_depth_scale_batch_u16": (_I, [_VP, _VP, _F, _I, _I, _I, _I, _F, _VP]),
     "pwn_hip_unproject": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP, _VP]),
     "pwn_hip_project_intervals": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
     "pwn_hip_integral_image": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
@@ -111,6 +113,8 @@ PROTOTYPES = {
     "pwn_hip_convert_export_end": (_I, [_VP, _VP, C.POINTER(C.c_size_t), C.POINTER(_F)]),
     "pwn_hip_convert_batch": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP]),
     "pwn_hip_convert_batch_u16": (_I, [_VP, _VP, _VP, _F, _I, _I, _I, _VP]),
+    "pwn_hip_convert_batch_scaled": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _F, _VP]),
+    "pwn_hip_convert_batch_u16_scaled": (_I, [_VP, _VP, _VP, _F, _I, _I, _I, _I, _F, _VP]),
     "pwn_hip_project": (_I, [_VP, _VP, _VP, _F, _F, _I, _I, _VP, _VP, _VP]),
     "pwn_hip_correspondences": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(_I), C.POINTER(_I)]),
     "pwn_hip_linearize": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, C.POINTER(_F), C.POINTER(_I)]),
@@ -122,6 +126,7 @@ PROTOTYPES = {
     "pwn_hip_align_batch_ex": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _F, _VP, _VP]),
     "pwn_hip_align_batch_records": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
     "pwn_hip_convert_align_batch_u16": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _F, _I, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
+    "pwn_hip_convert_align_batch_u16_scaled": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _F, _I, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _I, _F]),
     "pwn_hip_compute_statistics": (None, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_match_score": (_I, [_VP, _F, _VP]),
     "pwn_hip_match_batch": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _F, _VP, _VP]),

@@ -345,6 +345,27 @@ class Context:
         self.check(self._L.pwn_hip_depth_scale(self.h, _ptr(src), src.shape[0], src.shape[1], step, maxDepthCov, _ptr(dst)))
         return dst
 
+    def DepthImage_scale_batch(self, srcs, step, maxDepthCov=0.01, raw_scale=None, out=None):
+        """pwn_core/pwn_static.cpp:5-36 of n frames of one size in one call (pwn_hip_depth_scale_batch[_u16]).  srcs: float32 arrays / CUDA
+        tensors, or uint16 frames when raw_scale is given (DepthImage_convert_16UC1_to_32FC1 in front, :54-68).  out: optional destinations
+        (float32 [rows/step, cols/step] arrays or CUDA tensors), else numpy arrays are returned."""
+        dt = np.float32 if raw_scale is None else np.uint16
+        srcs = [d if hasattr(d, "data_ptr") else np.ascontiguousarray(d, dt) for d in srcs]
+        n = len(srcs)
+        if n == 0:
+            return []
+        rows, cols = srcs[0].shape
+        if any(tuple(d.shape) != (rows, cols) for d in srcs):
+            raise ValueError("DepthImage_scale_batch: frames of one call share one size")
+        if out is None:
+            out = [np.empty((rows // max(step, 1), cols // max(step, 1)), np.float32) for _ in range(n)]
+        sp = (C.c_void_p * n)(*[_ptr(d) for d in srcs]); dp = (C.c_void_p * n)(*[_ptr(d) for d in out])
+        if raw_scale is None:
+            self.check(self._L.pwn_hip_depth_scale_batch(self.h, sp, n, rows, cols, step, maxDepthCov, dp))
+        else:
+            self.check(self._L.pwn_hip_depth_scale_batch_u16(self.h, sp, raw_scale, n, rows, cols, step, maxDepthCov, dp))
+        return out
+
 
 class Cloud:
     """Device-resident pwn::Cloud (pwn_core/cloud.h:20-187): points, normals, curvature (of Stats) and the
@@ -1014,14 +1035,18 @@ class Aligner:
         return np.frombuffer(res, dtype=ALIGN_RESULT_DTYPE, count=n) if want_results else None
 
     def convertAlignBatch(self, converter, references, currents, refFrames, curFrames, raw_scale=0.001, records=None, pair_ids=None, first_pair_id=0,
-                          initialGuesses=None, want_results=True, prepared=None):
+                          initialGuesses=None, want_results=True, prepared=None, step=1, max_depth_cov=0.01):
         """One candidate batch from raw uint16 frames as one submission (pwn_hip_convert_align_batch_u16): per pair makeCloud of both frames, then
-        align; sub-batch k converts while sub-batch k-1 aligns.  prepared = (refs, curs, ref frame ptrs, cur frame ptrs, n, (rows, cols))."""
+        align; sub-batch k converts while sub-batch k-1 aligns.  prepared = (refs, curs, ref frame ptrs, cur frame ptrs, n, (rows, cols)).
+        step != 1: the step at 1/step resolution (pwn_hip_convert_align_batch_u16_scaled: DepthImage_scale(frame, step, max_depth_cov) in front
+        of every conversion); the frames keep their size, the converter's and this aligner's projectors describe the scaled image."""
         if prepared is None:
             prepared = self.convertAlignHandles(references, currents, refFrames, curFrames)
         refs, curs, rf, cf, n, (rows, cols) = prepared[:6]
+        if len(prepared) > 7:
+            step, max_depth_cov = prepared[7]
         # the two parameter structs cost ~35 us of Python per call: a caller that repeats a call with unchanged objects passes them along
-        cp, p = prepared[6] if len(prepared) > 6 else (converter.params(None), self.params())
+        cp, p = prepared[6] if len(prepared) > 6 and prepared[6] is not None else (converter.params(None), self.params())
         res = (AlignResult * n)() if want_results else None
         g = None
         if initialGuesses is not None:
@@ -1030,16 +1055,22 @@ class Aligner:
         _check_records(records, n, RECORD_FLOATS, self.ctx)
         if ids is not None and ids.size < n:
             raise ValueError("pair_ids shorter than the batch")
-        self.ctx.check(self.ctx._L.pwn_hip_convert_align_batch_u16(self.ctx.h, C.byref(cp), C.byref(p), n, rf, cf, raw_scale, rows, cols, refs, curs, _ptr(g),
-                                                                   _ptr(ids), int(first_pair_id), res, _ptr(records)))
+        if step != 1:
+            self.ctx.check(self.ctx._L.pwn_hip_convert_align_batch_u16_scaled(self.ctx.h, C.byref(cp), C.byref(p), n, rf, cf, raw_scale, rows, cols, refs, curs,
+                                                                              _ptr(g), _ptr(ids), int(first_pair_id), res, _ptr(records), int(step), max_depth_cov))
+        else:
+            self.ctx.check(self.ctx._L.pwn_hip_convert_align_batch_u16(self.ctx.h, C.byref(cp), C.byref(p), n, rf, cf, raw_scale, rows, cols, refs, curs, _ptr(g),
+                                                                       _ptr(ids), int(first_pair_id), res, _ptr(records)))
         return np.frombuffer(res, dtype=ALIGN_RESULT_DTYPE, count=n) if want_results else None
 
-    def convertAlignHandles(self, references, currents, refFrames, curFrames, converter=None):
+    def convertAlignHandles(self, references, currents, refFrames, curFrames, converter=None, step=1, max_depth_cov=0.01):
         """handle / pointer arrays for convertAlignBatch(..., prepared=...); with `converter`, the parameter structs of both objects as they
-        are NOW ride along (rebuild after changing a parameter)"""
+        are NOW ride along (rebuild after changing a parameter); with step != 1, the step and its variance bound ride along too"""
         n = len(references)
         out = ((C.c_void_p * n)(*[c.h for c in references]), (C.c_void_p * n)(*[c.h for c in currents]),
                (C.c_void_p * n)(*[_ptr(d) for d in refFrames]), (C.c_void_p * n)(*[_ptr(d) for d in curFrames]), n, tuple(refFrames[0].shape))
+        if step != 1:
+            return out + ((converter.params(None), self.params()) if converter is not None else None, (int(step), float(max_depth_cov)))
         return out + ((converter.params(None), self.params()),) if converter is not None else out
 
     # stage-level entry points (CorrespondenceFinder::compute / Linearizer::update with explicit inputs)
@@ -1106,6 +1137,39 @@ class PwnMatcherBase:
         ctx.check(ctx._L.pwn_hip_convert_scaled(ctx.h, C.byref(p), _ptr(depth), rows, cols, self._scale, 0.01, cloud.h))
         self.numCalls += 1
         return cloud, projector.imageRows(), projector.imageCols(), projector.cameraMatrix().copy()
+
+    def makeCloudBatch(self, cameraMatrix, sensorOffset, depthImages, raw_scale=None, clouds=None, ctx: Context = None):
+        """makeCloud (pwn_matcher_base.cpp:57-86) of n frames of one size, camera matrix and sensor offset in one call
+        (pwn_hip_convert_batch[_u16]_scaled) -> (clouds, r, c, scaledCameraMatrix).  depthImages: float32 arrays / CUDA tensors, or uint16
+        frames when raw_scale is given; clouds: optional clouds to fill instead of new ones.  The projector ends as n makeCloud calls leave
+        it; numCalls advances by n."""
+        ctx = ctx or self._aligner.ctx
+        projector = self._converter.projector()
+        invScale = np.float32(1.0) / np.float32(self._scale)
+        scaled = (np.asarray(cameraMatrix, np.float32).reshape(3, 3) * invScale).astype(np.float32)
+        scaled[2, 2] = 1.0
+        projector.setCameraMatrix(scaled)
+        dt = np.float32 if raw_scale is None else np.uint16
+        frames = [d if hasattr(d, "data_ptr") else np.ascontiguousarray(d, dt) for d in depthImages]
+        n = len(frames)
+        if n == 0:
+            return [], projector.imageRows(), projector.imageCols(), projector.cameraMatrix().copy()
+        rows, cols = frames[0].shape
+        if any(tuple(d.shape) != (rows, cols) for d in frames):
+            raise ValueError("makeCloudBatch: frames of one call share one size")
+        r, c = rows // self._scale, cols // self._scale
+        projector.setImageSize(r, c)
+        if clouds is None:
+            clouds = [Cloud(ctx, max(1, r * c)) for _ in range(n)]
+        projector.setTransform(np.eye(4, dtype=np.float32))
+        p = self._converter.params(sensorOffset)
+        handles = (C.c_void_p * n)(*[cl.h for cl in clouds]); ptrs = (C.c_void_p * n)(*[_ptr(d) for d in frames])
+        if raw_scale is None:
+            ctx.check(ctx._L.pwn_hip_convert_batch_scaled(ctx.h, C.byref(p), ptrs, n, rows, cols, self._scale, 0.01, handles))
+        else:
+            ctx.check(ctx._L.pwn_hip_convert_batch_u16_scaled(ctx.h, C.byref(p), ptrs, raw_scale, n, rows, cols, self._scale, 0.01, handles))
+        self.numCalls += n
+        return list(clouds), projector.imageRows(), projector.imageCols(), projector.cameraMatrix().copy()
 
     def makeCloudBegin(self, cameraMatrix, sensorOffset, depthImage, ctx: Context = None):
         """makeCloud in two halves (pwn_hip_convert_scaled_begin / pwn_hip_convert_end): returns at once with a ticket, the frame is
@@ -1281,6 +1345,40 @@ class CloudCache:
         c, _, _, _ = self._matcher.makeCloud(K, off, depth)    # pwn_tracker_cache.cpp:38-44
         self._insert(key, c)
         return c
+
+    def getBatch(self, keys):
+        """get(key) for every key, in order, with the misses converted by makeCloudBatch: one call per group of frames of one shape, camera
+        matrix and sensor offset.  Clouds, LRU order and hit / miss counts are those of the per-key gets."""
+        # the gets replayed on the keys alone: which of them miss (a resident cloud can be evicted before its key comes up)
+        order, missing = list(self._clouds), []
+        for key in keys:
+            if key in order:
+                order.remove(key)
+            elif key not in missing:
+                missing.append(key)
+            order.append(key)
+            del order[:max(0, len(order) - self._capacity)]
+        groups = {}
+        for key in missing:
+            depth, K, off = self._frames[key]
+            groups.setdefault((depth.shape, K.tobytes(), off.tobytes()), []).append(key)
+        made = {}
+        for members in groups.values():
+            _, K, off = self._frames[members[0]]
+            clouds = self._matcher.makeCloudBatch(K, off, [self._frames[k][0] for k in members])[0]
+            made.update(zip(members, clouds))
+        out = []
+        for key in keys:
+            c = self._clouds.pop(key, None)
+            if c is not None:
+                self.hits += 1
+                self._clouds[key] = c
+            else:
+                self.misses += 1
+                c = made[key]
+                self._insert(key, c)
+            out.append(c)
+        return out
 
 
 class PwnTracker(PwnMatcherBase):

@@ -59,6 +59,13 @@ def build_tools(force: bool = False) -> str:
     if force or (not os.path.exists(out4)) or any(os.path.getmtime(d) > os.path.getmtime(out4) for d in deps4):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src4, "-o", out4, "-L", _HERE, "-lpwn_hip",
                                "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
+    # PwnMatcherBase::makeCloudBatch against makeCloud per frame, every downloaded array compared (exit status 0 = no difference)
+    src6 = os.path.join(root, "tools", "pwn_hip_scaled_batch_check.cpp")
+    out6 = os.path.join(root, "tools", "pwn_hip_scaled_batch_check")
+    deps6 = [src6] + deps[1:]
+    if force or (not os.path.exists(out6)) or any(os.path.getmtime(d) > os.path.getmtime(out6) for d in deps6):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src6, "-o", out6, "-L", _HERE, "-lpwn_hip",
+                               "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
     # PwnCloser::processPartition over the GPUs of a node in native code: the mirror + RCCL (broadcast of the flat `current` cloud, all-gather of the
     # match records); the program's own streams and events come from the HIP runtime
     src5 = os.path.join(root, "tools", "pwn_hip_partition_app.cpp")

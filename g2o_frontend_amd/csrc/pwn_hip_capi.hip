@@ -124,6 +124,9 @@ struct pwn_hip_ctx {
   // convert workspaces (per slot)
   DevBuf<float> depth_ws; DevBuf<int> index_ws, interval_ws; DevBuf<float> integral_ws; DevBuf<int> rowoff_ws;
   DevBuf<uint16_t> raw_ws;
+  // the *_scaled batch calls (allocated by the first of them): the down-sampled frame of every slot, which its front end reads, and the box
+  // kernel's descriptors (one per frame of a call)
+  DevBuf<float> scaled_ws; DevBuf<ScaleDesc> scale_dev; HostBuf<ScaleDesc> scale_host;
   DevBuf<unsigned long long> carry_ws; size_t carry_slot = 0; size_t rowoff_slot = 0;   // single-pass integral image: hand-over words, strip offsets
   unsigned convert_epoch = 0; DevBuf<int> fault_dev;
   int last_convert_fault = 0;              // fault word of the last converter launch of the CURRENT call (1 = a bounded poll timed out); reset when a call starts
@@ -658,18 +661,66 @@ int counts_apply(pwn_hip_ctx* ctx, pwn_hip_cloud* const* clouds, int n) {
 // frames, uploaded on ctx->stream), convert_enqueue (the kernels of frames [base, base + m) on one stream) and convert_finish (counts and
 // fault flag back, clouds' host-side sizes).  slot[i] = workspace slot of frame i: frames that are in flight at the same time on different
 // streams must not share one; a stream reuses its slots from launch to launch (stream order serialises the reuse).
+// DepthImage_scale in front of a conversion (PwnMatcherBase::makeCloud, pwn_matcher_base.cpp:57-86): the source size, the step and what it leaves
+struct ScaleSpec {
+  int step = 0;                          // 0: the frames are converted as they are
+  int srows = 0, scols = 0, orows = 0, ocols = 0; float maxCov = 0.f;
+};
+// the argument checks the *_scaled calls share: the step, a source frame the context holds, a scaled image that is not empty
+int make_scale_spec(pwn_hip_ctx* ctx, int rows, int cols, int step, float max_depth_cov, ScaleSpec& sc) {
+  if (step < 1) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "DepthImage_scale: step < 1");
+  if (int rc = check_image(ctx, rows, cols)) return rc;
+  sc.step = step; sc.srows = rows; sc.scols = cols; sc.orows = rows / step; sc.ocols = cols / step; sc.maxCov = max_depth_cov;
+  if (sc.orows <= 0 || sc.ocols <= 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "scaled image has zero size");
+  return PWN_HIP_OK;
+}
+// the scaled frames' workspace (one frame per slot, as depth_ws) and box descriptors for n frames (grown after a wait for the stream, as
+// ensure_desc grows its arrays)
+int ensure_scale(pwn_hip_ctx* ctx, int n) {
+  HIPCHK(ctx, ctx->scaled_ws.ensure((size_t)ctx->max_batch * ctx->N), PWN_HIP_ERR_ALLOCATION);
+  if ((size_t)n > ctx->scale_dev.cap) HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  const size_t B = (size_t)std::max(n, 16);
+  HIPCHK(ctx, ctx->scale_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->scale_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  return PWN_HIP_OK;
+}
+// DepthImage_scale of the frames [base, base + n) of the uploaded box descriptors (scale_host / scale_dev) on st.  The 16-byte form for the
+// three (type, step) pairs it exists for, when every frame and every source row starts 16-byte aligned; else one thread per pixel.
+int launch_depth_scale(pwn_hip_ctx* ctx, const ScaleSpec& sc, bool raw, float raw_scale, int base, int n, hipStream_t st) {
+  if (n <= 0) return PWN_HIP_OK;
+  StageTimer t(ctx, "depth_scale", st);
+  const ScaleDesc* fr = ctx->scale_dev + base;
+  bool aligned = ((size_t)sc.scols * (raw ? sizeof(uint16_t) : sizeof(float))) % 16 == 0 && (raw ? (sc.step == 2 || sc.step == 4) : sc.step == 2);
+  for (int i = 0; i < n && aligned; ++i) aligned = ((uintptr_t)ctx->scale_host[base + i].src & 15u) == 0;
+  if (aligned) {
+    const int dpl = (raw ? 8 : 4) / sc.step;
+    const dim3 grid((unsigned)(((size_t)sc.orows * (size_t)((sc.ocols + dpl - 1) / dpl) + 255) / 256), (unsigned)n);
+    if (!raw) hipLaunchKernelGGL((k_depth_scale_batch<float, 2>), grid, dim3(256), 0, st, fr, sc.srows, sc.scols, raw_scale, sc.maxCov);
+    else if (sc.step == 2) hipLaunchKernelGGL((k_depth_scale_batch<uint16_t, 2>), grid, dim3(256), 0, st, fr, sc.srows, sc.scols, raw_scale, sc.maxCov);
+    else hipLaunchKernelGGL((k_depth_scale_batch<uint16_t, 4>), grid, dim3(256), 0, st, fr, sc.srows, sc.scols, raw_scale, sc.maxCov);
+  } else {
+    const dim3 grid((unsigned)(((size_t)sc.orows * sc.ocols + 255) / 256), (unsigned)n);
+    if (raw) hipLaunchKernelGGL(k_depth_scale_batch_any<uint16_t>, grid, dim3(256), 0, st, fr, sc.srows, sc.scols, sc.step, raw_scale, sc.maxCov);
+    else hipLaunchKernelGGL(k_depth_scale_batch_any<float>, grid, dim3(256), 0, st, fr, sc.srows, sc.scols, sc.step, raw_scale, sc.maxCov);
+  }
+  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  return PWN_HIP_OK;
+}
 struct ConvertJob {
   ConvertParams cp;
   int n = 0, rows = 0, cols = 0;
   size_t N = 0;
-  bool raw = false, host_input = false, direct = false;
+  size_t srcN = 0;                       // pixels of a frame as the caller hands it over (= N unless the job down-samples)
+  ScaleSpec scale;
+  bool raw = false, host_input = false, direct = false;      // raw: the caller's frames are uint16
   float depth_scale = 0.f;
   std::vector<const void*> src;          // the caller's frame pointers (host frames are staged by convert_enqueue)
   std::vector<int> slot;
 };
 template <typename SRC>
 int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n, int rows, int cols,
-                    pwn_hip_cloud* const* clouds, int keep_stats, bool want_interval, const std::vector<int>& slot, bool direct, ConvertJob& job) {
+                    pwn_hip_cloud* const* clouds, int keep_stats, bool want_interval, const std::vector<int>& slot, bool direct, ConvertJob& job,
+                    const ScaleSpec& sc = ScaleSpec()) {
   const size_t N = (size_t)rows * cols;
   ctx->last_convert_fault = 0;            // the fault word belongs to this call from here on (a stale 1 would make an unrelated failure look like a time-out)
   ConvertParams cp = make_convert_params(ctx, p, nullptr, rows, cols, keep_stats);
@@ -677,6 +728,7 @@ int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const S
   if (int rc = ensure_desc(ctx, n)) return rc;
   const bool raw = std::is_same<SRC, uint16_t>::value;
   job.n = n; job.rows = rows; job.cols = cols; job.N = N; job.raw = raw; job.depth_scale = depth_scale; job.slot = slot; job.direct = direct;
+  job.scale = sc; job.srcN = sc.step ? (size_t)sc.srows * sc.scols : N;
   job.src.assign(n, nullptr);
   // every frame gets a descriptor; workspace slots are reused round-robin (stream order serialises the reuse)
   for (int i = 0; i < n; ++i) {
@@ -692,7 +744,8 @@ int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const S
     make_omega_n_classes(p, c->d);
     job.src[i] = frames[i];
     const float* depth_dev = nullptr;
-    if (!raw) depth_dev = reinterpret_cast<const float*>(frames[i]);         // patched below if it is a host pointer
+    if (sc.step) depth_dev = ctx->scaled_ws + (size_t)slot[i] * ctx->N;      // the front end reads the down-sampled frame of its slot
+    else if (!raw) depth_dev = reinterpret_cast<const float*>(frames[i]);    // patched below if it is a host pointer
     fill_frame(ctx, i, slot[i], depth_dev, c->d);
     if (c->idximg.cap < N) {
       HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
@@ -701,7 +754,10 @@ int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const S
     ctx->frames_host[i].index = c->idximg;                    // the index image stays with the cloud
     c->idx_valid = cp.hasOffset == 0;
     c->idx_key = index_key(p, rows, cols);
-    if (raw) {                                                                // uint16 frames are converted on the fly by the kernels
+    if (sc.step) {                                                            // ... by the box kernel, which reads the caller's frame
+      ctx->scale_host[i].src = frames[i];                                     // patched below if it is a host pointer
+      ctx->scale_host[i].dst = ctx->scaled_ws + (size_t)slot[i] * ctx->N;
+    } else if (raw) {                                                         // uint16 frames are converted on the fly by the kernels
       ctx->frames_host[i].raw = reinterpret_cast<const uint16_t*>(frames[i]); // patched below if it is a host pointer
       ctx->frames_host[i].raw_scale = depth_scale;
     }
@@ -710,10 +766,13 @@ int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const S
   job.host_input = n > 0 && !is_device_ptr(frames[0]);
   if (job.host_input) {
     for (int i = 0; i < n; ++i) {
-      if (raw) ctx->frames_host[i].raw = ctx->raw_ws + (size_t)slot[i] * ctx->N;
-      else ctx->frames_host[i].depth = ctx->depth_ws + (size_t)slot[i] * ctx->N;
+      const void* staged = raw ? (const void*)(ctx->raw_ws + (size_t)slot[i] * ctx->N) : (const void*)(ctx->depth_ws + (size_t)slot[i] * ctx->N);
+      if (sc.step) ctx->scale_host[i].src = staged;
+      else if (raw) ctx->frames_host[i].raw = (const uint16_t*)staged;
+      else ctx->frames_host[i].depth = (const float*)staged;
     }
   }
+  if (sc.step) HIPCHK(ctx, hipMemcpyAsync(ctx->scale_dev, ctx->scale_host, sizeof(ScaleDesc) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
   // a call of a few frames (latency path, one launch): counts and fault flag land in page-locked host words straight from the kernels
   if (direct) for (int i = 0; i < n; ++i) ctx->frames_host[i].count_out = ctx->counts_host + i;
   HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev, ctx->frames_host, sizeof(FrameDesc) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
@@ -725,11 +784,11 @@ int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const S
 int convert_stage_frames(pwn_hip_ctx* ctx, const ConvertJob& job, int base, int m, hipStream_t cs) {
   // frames that follow each other in host memory (a ring buffer, one block for the batch) go in one transfer -- only when the frame
   // fills its staging slot (N == ctx->N), so that the slots are contiguous too
-  const size_t fbytes = job.N * (job.raw ? sizeof(uint16_t) : sizeof(float));
+  const size_t fbytes = job.srcN * (job.raw ? sizeof(uint16_t) : sizeof(float));
   const int s0 = job.slot[base];
   for (int i = 0; i < m;) {
     int run = 1;
-    if (job.N == ctx->N)
+    if (job.srcN == ctx->N)
       while (i + run < m && (const char*)job.src[base + i + run] == (const char*)job.src[base + i] + (size_t)run * fbytes) ++run;
     void* dst = job.raw ? (void*)(ctx->raw_ws + (size_t)(s0 + i) * ctx->N) : (void*)(ctx->depth_ws + (size_t)(s0 + i) * ctx->N);
     HIPCHK(ctx, hipMemcpyAsync(dst, job.src[base + i], fbytes * run, hipMemcpyHostToDevice, cs), PWN_HIP_ERR_COPY);
@@ -737,11 +796,25 @@ int convert_stage_frames(pwn_hip_ctx* ctx, const ConvertJob& job, int base, int 
   }
   return PWN_HIP_OK;
 }
+// what convert_prepare would refuse, looked at before it touches a cloud (the *_scaled calls leave the clouds of a refused call as they were)
+template <typename SRC>
+int check_frames_and_clouds(pwn_hip_ctx* ctx, const SRC* const* frames, pwn_hip_cloud* const* clouds, int n) {
+  for (int i = 0; i < n; ++i) {
+    if (!clouds[i] || !frames[i]) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null frame or cloud");
+    if (clouds[i]->d.omSym != clouds[0]->d.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds of one convert batch must share one omega storage (exact9 / sym6)");
+  }
+  return PWN_HIP_OK;
+}
+// the kernels of frames [base, base + m) of the job on st: the box mean into the frames' slots first when the job down-samples
+int convert_enqueue(pwn_hip_ctx* ctx, const ConvertJob& job, int base, int m, hipStream_t st, int* fault_out = nullptr) {
+  if (job.scale.step) { if (int rc = launch_depth_scale(ctx, job.scale, job.raw, job.depth_scale, base, m, st)) return rc; }
+  return launch_convert(ctx, job.cp, base, m, st, fault_out);
+}
 int convert_finish(pwn_hip_ctx* ctx, const ConvertJob& job, pwn_hip_cloud* const* clouds) { return sync_and_counts(ctx, clouds, job.n, job.direct); }
 
 template <typename SRC>
 int convert_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n,
-                       int rows, int cols, pwn_hip_cloud* const* clouds, int keep_stats, bool want_interval = false) {
+                       int rows, int cols, pwn_hip_cloud* const* clouds, int keep_stats, bool want_interval = false, const ScaleSpec& sc = ScaleSpec()) {
   if (!ctx || !p || !frames || !clouds || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (int rc = check_image(ctx, rows, cols)) return rc;
   if (int rc = absorb_copies(ctx)) return rc;
@@ -756,7 +829,7 @@ int convert_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, cons
     for (int i = 0; i < n; ++i) slot[i] = plan.slot0(i / sub) + i % sub;
     const bool direct = n > 0 && n < kSinglePassMinFrames && n <= sub;
     ConvertJob job;
-    if (int rc = convert_prepare<SRC>(ctx, p, frames, depth_scale, n, rows, cols, clouds, keep_stats, want_interval, slot, direct, job)) return rc;
+    if (int rc = convert_prepare<SRC>(ctx, p, frames, depth_scale, n, rows, cols, clouds, keep_stats, want_interval, slot, direct, job, sc)) return rc;
     if (int rc = plan_fork(ctx, plan)) return rc;
     // Host frames travel on the copy stream, ahead of the kernels: the frames of sub-batch k are copied while sub-batches k-1, k-2 ... are
     // being converted (with the copies on the sub-batch's own stream the two streams copy at the same time and then compute at the same
@@ -784,7 +857,7 @@ int convert_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, cons
           HIPCHK(ctx, hipStreamWaitEvent(st, ctx->sync_events[2 * k], 0), PWN_HIP_ERR_LAUNCH);
         }
       }
-      if (int rc = launch_convert(ctx, job.cp, base, m, st, direct ? ctx->counts_host + n : nullptr)) return rc;
+      if (int rc = convert_enqueue(ctx, job, base, m, st, direct ? ctx->counts_host + n : nullptr)) return rc;
       if (ahead) HIPCHK(ctx, hipEventRecord(ctx->sync_events[2 * k + 1], st), PWN_HIP_ERR_LAUNCH);
     }
     if (int rc = plan_join(ctx, plan)) return rc;
@@ -824,6 +897,81 @@ int debug_front_end_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, co
   if (int rc = convert_finish(ctx, job, clouds)) return rc;
   if (lean) for (int i = 0; i < n; ++i) { clouds[i]->n_host = 0; clouds[i]->idx_valid = false; }      // a lean front end stores no points
   return PWN_HIP_OK;
+}
+
+// DepthImage_scale of n equal-sized frames: chunks of at most max_batch frames, one box launch each; host sources are staged in the slots'
+// source-size workspaces, host destinations leave through the slots' scaled frames.  dst == nullptr (check_scaled_capacities): the images stay
+// in the slots and only valid[i], the pixels of image i inside [min_d, max_d], comes back.
+template <typename SRC>
+int depth_scale_batch_impl(pwn_hip_ctx* ctx, const SRC* const* src, float depth_scale, int n, int rows, int cols, int step, float max_depth_cov,
+                           float* const* dst, float min_d = 0.f, float max_d = 0.f, int* valid = nullptr) {
+  if (!ctx || !src || (!dst && !valid) || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  ScaleSpec sc;
+  if (int rc = make_scale_spec(ctx, rows, cols, step, max_depth_cov, sc)) return rc;
+  for (int i = 0; i < n; ++i) if (!src[i] || (dst && !dst[i])) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null frame");
+  if (int rc = absorb_copies(ctx)) return rc;
+  if (int rc = ensure_scale(ctx, std::min(n, ctx->max_batch))) return rc;
+  ctx->stages.clear();
+  const bool raw = std::is_same<SRC, uint16_t>::value;
+  const size_t sbytes = (size_t)rows * cols * sizeof(SRC), obytes = (size_t)sc.orows * sc.ocols * sizeof(float);
+  for (int base = 0; base < n; base += ctx->max_batch) {
+    const int m = std::min(ctx->max_batch, n - base);
+    for (int j = 0; j < m; ++j) {
+      ScaleDesc& d = ctx->scale_host[j];
+      d.src = src[base + j]; d.dst = dst ? dst[base + j] : nullptr;
+      if (!is_device_ptr(d.src)) {
+        void* ws = raw ? (void*)(ctx->raw_ws + (size_t)j * ctx->N) : (void*)(ctx->depth_ws + (size_t)j * ctx->N);
+        HIPCHK(ctx, hipMemcpyAsync(ws, d.src, sbytes, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+        d.src = ws;
+      }
+      if (!is_device_ptr(d.dst)) d.dst = ctx->scaled_ws + (size_t)j * ctx->N;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->scale_dev, ctx->scale_host, sizeof(ScaleDesc) * m, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+    if (int rc = launch_depth_scale(ctx, sc, raw, depth_scale, 0, m, ctx->stream)) return rc;
+    for (int j = 0; j < m && dst; ++j)
+      if (ctx->scale_host[j].dst != dst[base + j]) HIPCHK(ctx, hipMemcpyAsync(dst[base + j], ctx->scale_host[j].dst, obytes, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
+    if (valid) {
+      HIPCHK(ctx, hipMemsetAsync(ctx->counts_dev, 0, sizeof(int) * m, ctx->stream), PWN_HIP_ERR_COPY);
+      const int on = sc.orows * sc.ocols;
+      hipLaunchKernelGGL(k_count_in_range, dim3((unsigned)std::min((on + 255) / 256, 1024), (unsigned)m), dim3(256), 0, ctx->stream, ctx->scale_dev, on, min_d, max_d,
+                         ctx->counts_dev);
+      HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+      HIPCHK(ctx, hipMemcpyAsync(ctx->counts_host, ctx->counts_dev, sizeof(int) * m, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);      // the descriptors and the slots are reused by the next chunk
+    if (valid) std::copy(ctx->counts_host.p, ctx->counts_host.p + m, valid + base);
+  }
+  collect_stage_times(ctx);
+  return PWN_HIP_OK;
+}
+// A cloud too small for its frame's valid pixels is otherwise found when the kernels have written into it.  The *_scaled calls refuse before they
+// touch a cloud: where a cloud holds fewer points than the scaled image has pixels, the frames are down-sampled and counted first (a pass of its
+// own, only then).
+template <typename SRC>
+int check_scaled_capacities(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n, const ScaleSpec& sc,
+                            pwn_hip_cloud* const* clouds) {
+  bool tight = false;
+  for (int i = 0; i < n; ++i) tight = tight || (size_t)clouds[i]->d.capacity < (size_t)sc.orows * sc.ocols;
+  if (!tight) return PWN_HIP_OK;
+  std::vector<int> valid((size_t)n);
+  if (int rc = depth_scale_batch_impl<SRC>(ctx, frames, depth_scale, n, sc.srows, sc.scols, sc.step, sc.maxCov, nullptr, p->min_distance, p->max_distance, valid.data()))
+    return rc;
+  for (int i = 0; i < n; ++i)
+    if (valid[i] > clouds[i]->d.capacity) return fail(ctx, PWN_HIP_ERR_CAPACITY, "cloud capacity smaller than the number of valid depth pixels");
+  return PWN_HIP_OK;
+}
+// n x makeCloud's data path (DepthImage_scale, then the conversion of the small image) inside the batch plan.  Everything that can refuse the
+// call is looked at before a cloud is touched.
+template <typename SRC>
+int convert_batch_scaled_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n, int rows, int cols,
+                                     int step, float max_depth_cov, pwn_hip_cloud* const* clouds) {
+  if (!ctx || !p || !frames || !clouds || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  ScaleSpec sc;
+  if (int rc = make_scale_spec(ctx, rows, cols, step, max_depth_cov, sc)) return rc;
+  if (int rc = check_frames_and_clouds(ctx, frames, clouds, n)) return rc;
+  if (int rc = check_scaled_capacities<SRC>(ctx, p, frames, depth_scale, n, sc, clouds)) return rc;
+  if (int rc = ensure_scale(ctx, n)) return rc;
+  return convert_batch_impl<SRC>(ctx, p, frames, depth_scale, n, sc.orows, sc.ocols, clouds, 0, false, sc);
 }
 
 }  // namespace
@@ -1603,6 +1751,13 @@ int pwn_hip_depth_scale(pwn_hip_ctx* ctx, const float* src, int rows, int cols, 
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
 }
+int pwn_hip_depth_scale_batch(pwn_hip_ctx* ctx, const float* const* src, int n, int rows, int cols, int step, float max_depth_cov, float* const* dst) {
+  return depth_scale_batch_impl<float>(ctx, src, 0.f, n, rows, cols, step, max_depth_cov, dst);
+}
+int pwn_hip_depth_scale_batch_u16(pwn_hip_ctx* ctx, const uint16_t* const* src, float depth_scale, int n, int rows, int cols, int step, float max_depth_cov,
+                                  float* const* dst) {
+  return depth_scale_batch_impl<uint16_t>(ctx, src, depth_scale, n, rows, cols, step, max_depth_cov, dst);
+}
 
 // ---------------------------------------------------------------------------------------------- converter stages
 static int stage_depth(pwn_hip_ctx* ctx, const float* depth, size_t N, const float** out) {
@@ -1798,6 +1953,14 @@ int pwn_hip_convert_end(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud) {
 int pwn_hip_convert_batch(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const float* const* depth_frames, int n, int rows, int cols,
                           pwn_hip_cloud* const* clouds) {
   return convert_batch_impl<float>(ctx, p, depth_frames, 0.f, n, rows, cols, clouds, 0);
+}
+int pwn_hip_convert_batch_scaled(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const float* const* depth_frames, int n, int rows, int cols, int step,
+                                 float max_depth_cov, pwn_hip_cloud* const* clouds) {
+  return convert_batch_scaled_impl<float>(ctx, p, depth_frames, 0.f, n, rows, cols, step, max_depth_cov, clouds);
+}
+int pwn_hip_convert_batch_u16_scaled(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const uint16_t* const* raw_frames, float depth_scale, int n,
+                                     int rows, int cols, int step, float max_depth_cov, pwn_hip_cloud* const* clouds) {
+  return convert_batch_scaled_impl<uint16_t>(ctx, p, raw_frames, depth_scale, n, rows, cols, step, max_depth_cov, clouds);
 }
 int pwn_hip_convert_batch_u16(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const uint16_t* const* raw_frames, float depth_scale, int n,
                               int rows, int cols, pwn_hip_cloud* const* clouds) {
@@ -2311,11 +2474,11 @@ int pwn_hip_match_batch_records(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* 
   call.scores = scores; call.match_threshold = threshold; call.records = records; call.match_records = true; call.pair_ids = pair_ids; call.first_pair_id = first_pair_id;
   return align_batch_impl(ctx, call);
 }
-int pwn_hip_convert_align_batch_u16(pwn_hip_ctx* ctx, const pwn_hip_converter_params* cp, const pwn_hip_aligner_params* ap, int n,
+// the one-submission step; sc.step != 0: every frame is down-sampled in front of its conversion (rows, cols: the size that is converted and aligned)
+static int convert_align_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* cp, const pwn_hip_aligner_params* ap, int n,
                                     const uint16_t* const* ref_frames, const uint16_t* const* cur_frames, float depth_scale, int rows, int cols,
                                     pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs, const float* guesses, const int* pair_ids, int first_pair_id,
-                                    pwn_hip_align_result* results, float* records) {
-  if (!ctx || !cp || !ap || !ref_frames || !cur_frames || !refs || !curs || (!results && !records) || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+                                    pwn_hip_align_result* results, float* records, const ScaleSpec& sc) {
   if (int rc = check_image(ctx, rows, cols)) return rc;
   if (ap->rows != rows || ap->cols != cols) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "aligner image size differs from the frames'");
   // the clouds' host-side sizes are those of their PREVIOUS content while the step is being queued: bound what the conversion can produce instead
@@ -2349,13 +2512,13 @@ int pwn_hip_convert_align_batch_u16(pwn_hip_ctx* ctx, const pwn_hip_converter_pa
       for (int f = 0; f < 2 * m; ++f) slot[2 * base + f] = (k % plan.ns) * fslots + f % fslots;
     }
     ConvertJob job;
-    if (int rc = convert_prepare<uint16_t>(ctx, cp, frames.data(), depth_scale, 2 * n, rows, cols, clouds.data(), 0, false, slot, false, job)) return rc;
+    if (int rc = convert_prepare<uint16_t>(ctx, cp, frames.data(), depth_scale, 2 * n, rows, cols, clouds.data(), 0, false, slot, false, job, sc)) return rc;
     AlignHooks hooks;
     hooks.pre_sub = [&](int base, int m, int, hipStream_t st) -> int {
       for (int f = 0; f < 2 * m; f += fslots) {
         const int cnt = std::min(fslots, 2 * m - f);
         if (job.host_input) { if (int rc = convert_stage_frames(ctx, job, 2 * base + f, cnt, st)) return rc; }
-        if (int rc = launch_convert(ctx, job.cp, 2 * base + f, cnt, st)) return rc;
+        if (int rc = convert_enqueue(ctx, job, 2 * base + f, cnt, st)) return rc;
       }
       return PWN_HIP_OK;
     };
@@ -2365,6 +2528,31 @@ int pwn_hip_convert_align_batch_u16(pwn_hip_ctx* ctx, const pwn_hip_converter_pa
     call.hooks = &hooks; call.records = records; call.pair_ids = pair_ids; call.first_pair_id = first_pair_id;
     return align_batch_impl(ctx, call);
   });
+}
+int pwn_hip_convert_align_batch_u16(pwn_hip_ctx* ctx, const pwn_hip_converter_params* cp, const pwn_hip_aligner_params* ap, int n,
+                                    const uint16_t* const* ref_frames, const uint16_t* const* cur_frames, float depth_scale, int rows, int cols,
+                                    pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs, const float* guesses, const int* pair_ids, int first_pair_id,
+                                    pwn_hip_align_result* results, float* records) {
+  if (!ctx || !cp || !ap || !ref_frames || !cur_frames || !refs || !curs || (!results && !records) || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  return convert_align_batch_impl(ctx, cp, ap, n, ref_frames, cur_frames, depth_scale, rows, cols, refs, curs, guesses, pair_ids, first_pair_id, results, records,
+                                  ScaleSpec());
+}
+int pwn_hip_convert_align_batch_u16_scaled(pwn_hip_ctx* ctx, const pwn_hip_converter_params* cp, const pwn_hip_aligner_params* ap, int n,
+                                           const uint16_t* const* ref_frames, const uint16_t* const* cur_frames, float depth_scale, int rows, int cols,
+                                           pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs, const float* guesses, const int* pair_ids, int first_pair_id,
+                                           pwn_hip_align_result* results, float* records, int step, float max_depth_cov) {
+  if (!ctx || !cp || !ap || !ref_frames || !cur_frames || !refs || !curs || (!results && !records) || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  ScaleSpec sc;
+  if (int rc = make_scale_spec(ctx, rows, cols, step, max_depth_cov, sc)) return rc;
+  // what the conversions would refuse, before a cloud is touched
+  if (int rc = check_frames_and_clouds(ctx, ref_frames, refs, n)) return rc;
+  if (int rc = check_frames_and_clouds(ctx, cur_frames, curs, n)) return rc;
+  if (n > 0 && refs[0]->d.omSym != curs[0]->d.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds of one convert batch must share one omega storage (exact9 / sym6)");
+  if (int rc = check_scaled_capacities<uint16_t>(ctx, cp, ref_frames, depth_scale, n, sc, refs)) return rc;
+  if (int rc = check_scaled_capacities<uint16_t>(ctx, cp, cur_frames, depth_scale, n, sc, curs)) return rc;
+  if (int rc = ensure_scale(ctx, 2 * n)) return rc;
+  return convert_align_batch_impl(ctx, cp, ap, n, ref_frames, cur_frames, depth_scale, sc.orows, sc.ocols, refs, curs, guesses, pair_ids, first_pair_id, results,
+                                  records, sc);
 }
 void pwn_hip_compute_statistics(const float H[36], const float T[16], float mean[6], float omega[36], float* tr, float* rr) {
   compute_statistics(H, mat4_from(T), mean, omega, tr, rr);

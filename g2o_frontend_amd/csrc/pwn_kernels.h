@@ -264,29 +264,105 @@ __global__ void k_f32_to_u16(const float* __restrict__ src, uint16_t* __restrict
     dst[i] = (f < FLT_MAX) ? (uint16_t)(scale * f) : (uint16_t)0;
   }
 }
-// DepthImage_scale (pwn_core/pwn_static.cpp:5-36): one thread per destination pixel
+// DepthImage_scale (pwn_core/pwn_static.cpp:5-36), the arithmetic of one destination pixel, stated once: the sums over its step x step block
+// in the loop's order (block row outer, block column inner); every pixel enters the sums, the positive ones are counted; the pixel is the
+// mean unless nothing was counted or the variance exceeds maxCov
+struct BoxAcc {
+  float acc = 0.f, acc2 = 0.f; int np = 0;
+  __device__ __forceinline__ void add(float f) { acc += f; acc2 += f * f; np += f > 0; }
+  __device__ __forceinline__ float pixel(float maxCov) const {
+    if (!np) return 0.f;
+    const float mu = acc / np;
+    const float sigma = acc2 / np - mu * mu;
+    return (sigma > maxCov) ? 0.f : mu;
+  }
+};
+// a source pixel in metres: float frames as they are, raw uint16 as DepthImage_convert_16UC1_to_32FC1 makes them (pwn_static.cpp:54-68)
+__device__ __forceinline__ float metres_of(float v, float) { return v; }
+__device__ __forceinline__ float metres_of(uint16_t v, float scale) { return raw_to_metres(v, scale); }
+// the destination pixel whose block starts at p (rows `pitch` elements apart)
+template <typename SRC> __device__ __forceinline__ float box_pixel(gptr<const SRC> p, int pitch, int step, float rawScale, float maxCov) {
+  BoxAcc s;
+  for (int a = 0; a < step; ++a)
+    for (int b = 0; b < step; ++b) s.add(metres_of(p[(size_t)a * pitch + b], rawScale));
+  return s.pixel(maxCov);
+}
+// one frame, one thread per destination pixel (pwn_hip_depth_scale, pwn_hip_convert_scaled)
 __global__ void k_depth_scale(const float* __restrict__ src, int srows, int scols, int step, float maxCov, float* __restrict__ dst) {
   const int rows = srows / step, cols = scols / step;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= rows * cols) return;
   const int r = i / cols, c = i % cols;
-  float acc = 0, acc2 = 0; int np = 0;
-  const int sr = r * step, sc = c * step;
-  for (int a = 0; a < step; ++a)
-    for (int b = 0; b < step; ++b)
-      if (sr + a < srows && sc + b < scols) {
-        const float f = src[(size_t)(sr + a) * scols + sc + b];
-        acc += f; acc2 += f * f; np += f > 0;
-      }
-  float out = 0.f;
-  if (np) {
-    const float mu = acc / np;
-    const float sigma = acc2 / np - mu * mu;
-    if (!(sigma > maxCov)) out = mu;
+  dst[i] = box_pixel(as_global(src) + ((size_t)r * step * scols + (size_t)c * step), scols, step, 0.f, maxCov);
+}
+// DepthImage_scale of the frames of a sub-batch in one launch (grid.y = frame), float or raw uint16 source.  The kernel only streams -- 2 or 4
+// bytes in per source pixel, 4 / step^2 out -- so a lane owns DPL adjacent destination pixels and reads one 16-byte word per source row of
+// their blocks: uint16 step 2: 4 pixels, uint16 step 4: 2, float step 2: 2.  Every destination pixel keeps sums of its own, filled in the
+// reference's order.  Needs frames and source rows that start 16-byte aligned; the last lane of a destination row takes the pixels that do
+// not fill a word with box_pixel.  Source rows and columns past rows * STEP, cols * STEP are not read.
+// grid = (ceil(rows * ceil(cols / DPL) / 256), frames), block = 256
+struct ScaleDesc { const void* src; float* dst; };
+__device__ __forceinline__ void unpack_word(const v4u w, float (&f)[8], float scale) {
+  const unsigned u[4] = { w.x, w.y, w.z, w.w };
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { f[2 * k] = raw_to_metres(u[k] & 0xFFFFu, scale); f[2 * k + 1] = raw_to_metres(u[k] >> 16, scale); }
+}
+__device__ __forceinline__ void unpack_word(const v4u w, float (&f)[4], float) {
+  f[0] = __uint_as_float(w.x); f[1] = __uint_as_float(w.y); f[2] = __uint_as_float(w.z); f[3] = __uint_as_float(w.w);
+}
+template <typename SRC, int STEP>
+__global__ void __launch_bounds__(256) k_depth_scale_batch(const ScaleDesc* __restrict__ frames, int srows, int scols, float rawScale, float maxCov) {
+  constexpr int PX = 16 / (int)sizeof(SRC);            // source pixels per 16-byte word
+  constexpr int DPL = PX / STEP;                       // destination pixels per lane
+  static_assert(DPL >= 1 && DPL * STEP == PX, "a word holds whole blocks");
+  const ScaleDesc sd = frames[blockIdx.y];
+  const int rows = srows / STEP, cols = scols / STEP;
+  const int full = cols / DPL, slots = (cols + DPL - 1) / DPL;
+  const unsigned t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= (unsigned)rows * (unsigned)slots) return;
+  const int r = (int)(t / (unsigned)slots), s = (int)(t % (unsigned)slots);
+  const gptr<const SRC> src = as_global((const SRC*)sd.src) + ((size_t)r * STEP * scols + (size_t)s * PX);
+  const gptr<float> dst = as_global(sd.dst) + ((size_t)r * cols + (size_t)s * DPL);
+  if (s < full) {
+    v4u w[STEP];
+#pragma unroll
+    for (int a = 0; a < STEP; ++a) w[a] = *(gptr<const v4u>)(src + (size_t)a * scols);
+    BoxAcc acc[DPL];
+#pragma unroll
+    for (int a = 0; a < STEP; ++a) {
+      float f[PX];
+      unpack_word(w[a], f, rawScale);
+#pragma unroll
+      for (int j = 0; j < DPL; ++j)
+#pragma unroll
+        for (int b = 0; b < STEP; ++b) acc[j].add(f[j * STEP + b]);
+    }
+#pragma unroll
+    for (int j = 0; j < DPL; ++j) dst[j] = acc[j].pixel(maxCov);
+  } else {
+    for (int j = 0; j < cols - full * DPL; ++j) dst[j] = box_pixel(src + j * STEP, scols, STEP, rawScale, maxCov);
   }
-  dst[i] = out;
+}
+// any step, any alignment: one thread per destination pixel.  grid = (ceil(rows * cols / 256), frames), block = 256
+template <typename SRC>
+__global__ void __launch_bounds__(256) k_depth_scale_batch_any(const ScaleDesc* __restrict__ frames, int srows, int scols, int step, float rawScale, float maxCov) {
+  const ScaleDesc sd = frames[blockIdx.y];
+  const int rows = srows / step, cols = scols / step;
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= (unsigned)rows * (unsigned)cols) return;
+  const int r = (int)(i / (unsigned)cols), c = (int)(i % (unsigned)cols);
+  as_global(sd.dst)[i] = box_pixel(as_global((const SRC*)sd.src) + ((size_t)r * step * scols + (size_t)c * step), scols, step, rawScale, maxCov);
 }
 
+// valid pixels (the range test of PinholePointProjector::_unProject, pinholepointprojector.h:246-248) of each frame's down-sampled image: the
+// points a conversion of it will ask of its cloud.  out[frame] starts at 0.  grid = (<= 1024, frames), block = 256
+__global__ void __launch_bounds__(256) k_count_in_range(const ScaleDesc* __restrict__ frames, int n, float minD, float maxD, int* __restrict__ out) {
+  const gptr<const float> d = as_global((const float*)frames[blockIdx.y].dst);
+  int cnt = 0;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) cnt += depth_in_range(d[i], minD, maxD);
+  const int t = (int)wave_sum((float)cnt);      // small integers: exact in fp32
+  if (lane_id() == 0 && t) atomicAdd(out + blockIdx.y, t);
+}
 // depth of pixel i of a frame: the float image, or the raw uint16 image converted on the fly
 __device__ __forceinline__ float frame_depth(const FrameDesc& f, size_t i) {
   if (f.raw) return raw_to_metres(f.raw[i], f.raw_scale);

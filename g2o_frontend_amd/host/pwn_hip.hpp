@@ -117,6 +117,18 @@ inline void DepthImage_scale(Context& ctx, DepthImage& dest, const DepthImage& s
   dest.create(src.rows / step, src.cols / step);
   ctx.check(pwn_hip_depth_scale(ctx.handle(), src.data.data(), src.rows, src.cols, step, maxDepthCov, dest.data.data()));
 }
+// the same for a run of images of one size, in one call (pwn_hip_depth_scale_batch)
+inline void DepthImage_scale(Context& ctx, std::vector<DepthImage>& dest, const std::vector<DepthImage>& src, int step, float maxDepthCov = 0.01f) {
+  dest.resize(src.size());
+  if (src.empty()) return;
+  std::vector<const float*> s(src.size()); std::vector<float*> d(src.size());
+  for (size_t i = 0; i < src.size(); ++i) {
+    if (src[i].rows != src[0].rows || src[i].cols != src[0].cols) throw Error(PWN_HIP_ERR_INVALID_ARGUMENT, "DepthImage_scale: images of one call share one size");
+    dest[i].create(src[i].rows / (step > 0 ? step : 1), src[i].cols / (step > 0 ? step : 1));
+    s[i] = src[i].data.data(); d[i] = dest[i].data.data();
+  }
+  ctx.check(pwn_hip_depth_scale_batch(ctx.handle(), s.data(), (int)src.size(), src[0].rows, src[0].cols, step, maxDepthCov, d.data()));
+}
 
 // cloud.h:20-187
 class Cloud {
@@ -617,6 +629,34 @@ struct PwnMatcherBase {
     if (rc) { delete cloud; _ctx->check(rc); }
     ++numCalls;
     return cloud;
+  }
+  // makeCloud of n depth images of one size, camera matrix and sensor offset in one call (pwn_hip_convert_batch_scaled; not in the reference):
+  // the clouds are new and owned by the caller, the same bits as n makeCloud calls; r, c, cameraMatrix and the projector as those leave them
+  std::vector<Cloud*> makeCloudBatch(int& r, int& c, Matrix3f& cameraMatrix, const Isometry3f& sensorOffset, const std::vector<const DepthImage*>& depthImages) {
+    std::vector<Cloud*> clouds;
+    if (depthImages.empty()) return clouds;
+    const int rows = depthImages[0]->rows, cols = depthImages[0]->cols;
+    std::vector<const float*> frames(depthImages.size());
+    for (size_t i = 0; i < depthImages.size(); ++i) {
+      if (depthImages[i]->rows != rows || depthImages[i]->cols != cols) throw Error(PWN_HIP_ERR_INVALID_ARGUMENT, "makeCloudBatch: images of one call share one size");
+      frames[i] = depthImages[i]->data.data();
+    }
+    PinholePointProjector* projector = _converter->projector();
+    const float invScale = 1.0f / _scale;
+    Matrix3f scaled = cameraMatrix;
+    for (int i = 0; i < 9; ++i) scaled.m[i] = scaled.m[i] * invScale;
+    scaled(2,2) = 1.0f;
+    projector->setCameraMatrix(scaled);
+    projector->setImageSize(rows / _scale, cols / _scale);
+    projector->setTransform(Isometry3f::Identity());
+    cameraMatrix = projector->cameraMatrix(); r = projector->imageRows(); c = projector->imageCols();
+    std::vector<pwn_hip_cloud*> h(frames.size());
+    for (size_t i = 0; i < frames.size(); ++i) { clouds.push_back(new Cloud(*_ctx, r * c > 0 ? r * c : 1)); h[i] = clouds.back()->handle(); }
+    const pwn_hip_converter_params p = _converter->params(sensorOffset);
+    const int rc = pwn_hip_convert_batch_scaled(_ctx->handle(), &p, frames.data(), (int)frames.size(), rows, cols, _scale, 0.01f, h.data());
+    if (rc) { for (Cloud* cl : clouds) delete cl; _ctx->check(rc); }
+    numCalls += (int)frames.size();
+    return clouds;
   }
   // makeCloud in two halves (pwn_hip_convert_scaled_begin / _end; not in the reference): makeCloudBegin returns at once, the frame is
   // converted by the library's helper thread next to whatever runs on the context meanwhile; makeCloudEnd returns the cloud makeCloud would

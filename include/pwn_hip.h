@@ -267,6 +267,14 @@ int pwn_hip_depth_u16_to_f32(pwn_hip_ctx* ctx, const uint16_t* src, float* dst, 
 int pwn_hip_depth_f32_to_u16(pwn_hip_ctx* ctx, const float* src, uint16_t* dst, int n, float scale);
 /* DepthImage_scale (pwn_static.cpp:5-36); dst holds (rows/step)*(cols/step) floats */
 int pwn_hip_depth_scale(pwn_hip_ctx* ctx, const float* src, int rows, int cols, int step, float max_depth_cov, float* dst);
+/* DepthImage_scale (pwn_static.cpp:5-36) of n frames of equal size in one call: src[i] (rows*cols floats) -> dst[i] ((rows/step)*(cols/step)
+ * floats); src / dst: n pointers (host arrays), each frame host or device.  step = 1 is the reference's copy that zeroes non-positive pixels.
+ * Waits for the results. */
+int pwn_hip_depth_scale_batch(pwn_hip_ctx* ctx, const float* const* src, int n, int rows, int cols, int step, float max_depth_cov,
+                              float* const* dst);
+/* Same, from raw uint16 frames: DepthImage_convert_16UC1_to_32FC1 (pwn_static.cpp:54-68, depth = depth_scale * raw) fused in front. */
+int pwn_hip_depth_scale_batch_u16(pwn_hip_ctx* ctx, const uint16_t* const* src, float depth_scale, int n, int rows, int cols, int step,
+                                  float max_depth_cov, float* const* dst);
 
 /* ------------------------------------------------------------------ converter stages --------- */
 /* PinholePointProjector::unProject(points, gaussians, indexImage, depthImage) (pinholepointprojector.cpp:93-133)
@@ -319,6 +327,18 @@ int pwn_hip_convert_batch(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, c
 /* Same, from raw uint16 millimetre frames: fuses DepthImage_convert_16UC1_to_32FC1 (scale) in front. */
 int pwn_hip_convert_batch_u16(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const uint16_t* const* raw_frames,
                               float depth_scale, int n, int rows, int cols, pwn_hip_cloud* const* clouds);
+/* n x PwnMatcherBase::makeCloud's data path (pwn_tracker/pwn_matcher_base.cpp:57-86) in one call: DepthImage_scale(frame i, step,
+ * max_depth_cov) and the converter on the (rows/step) x (cols/step) image -> clouds[i], inside the batch plan (the box mean of a
+ * sub-batch's frames is queued on its stream in front of its conversion).  rows, cols: the SOURCE size; p->K must already be the scaled
+ * camera matrix.  clouds[i] holds the bits pwn_hip_convert_scaled gives for frame i, index image included.  A refused call leaves the
+ * clouds as they were: PWN_HIP_ERR_INVALID_ARGUMENT for step < 1, an empty scaled image, a null frame or cloud, mixed omega storages;
+ * PWN_HIP_ERR_CAPACITY for a context smaller than the source frame or a cloud smaller than its number of valid scaled pixels. */
+int pwn_hip_convert_batch_scaled(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const float* const* depth_frames, int n, int rows,
+                                 int cols, int step, float max_depth_cov, pwn_hip_cloud* const* clouds);
+/* Same, from raw uint16 frames (DepthImage_convert_16UC1_to_32FC1, pwn_static.cpp:54-68, in front of DepthImage_scale, :5-36). */
+int pwn_hip_convert_batch_u16_scaled(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const uint16_t* const* raw_frames,
+                                     float depth_scale, int n, int rows, int cols, int step, float max_depth_cov,
+                                     pwn_hip_cloud* const* clouds);
 
 /* ------------------------------------------------------------------ aligner stages ----------- */
 /* PinholePointProjector::project(indexImage, depthImage, points) (pinholepointprojector.cpp:33-66) with
@@ -407,6 +427,15 @@ int pwn_hip_convert_align_batch_u16(pwn_hip_ctx* ctx, const pwn_hip_converter_pa
                                     const uint16_t* const* ref_frames, const uint16_t* const* cur_frames, float depth_scale, int rows, int cols,
                                     pwn_hip_cloud* const* references, pwn_hip_cloud* const* currents, const float* initial_guesses,
                                     const int* pair_ids, int first_pair_id, pwn_hip_align_result* results, float* records);
+/* The same step at 1/step resolution, as the reference's callers run it (PwnMatcherBase::makeCloud, pwn_matcher_base.cpp:57-86: _scale is 2
+ * by default, :12): every frame goes through DepthImage_scale(frame, step, max_depth_cov) in front of its conversion.  rows, cols: the
+ * SOURCE size; converter->K and aligner->K the scaled camera matrix; aligner->rows / cols must equal rows/step, cols/step.  Results are bit
+ * for bit those of pwn_hip_convert_batch_u16_scaled followed by pwn_hip_align_batch_records. */
+int pwn_hip_convert_align_batch_u16_scaled(pwn_hip_ctx* ctx, const pwn_hip_converter_params* converter, const pwn_hip_aligner_params* aligner,
+                                           int n, const uint16_t* const* ref_frames, const uint16_t* const* cur_frames, float depth_scale,
+                                           int rows, int cols, pwn_hip_cloud* const* references, pwn_hip_cloud* const* currents,
+                                           const float* initial_guesses, const int* pair_ids, int first_pair_id,
+                                           pwn_hip_align_result* results, float* records, int step, float max_depth_cov);
 /* Aligner::align with priors (aligner.cpp:96-108).  The prior terms (numeric Jacobians, se3_prior.cpp:8-52) are 6x6 host math
  * that changes the normal equations of every iteration, so this entry point keeps the reference's host-driven loop: per
  * iteration the GPU projects, finds correspondences and reduces H, b; the host adds damping + priors, solves and updates.
