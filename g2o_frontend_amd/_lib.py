@@ -83,6 +83,7 @@ PROTOTYPES = {
     "pwn_hip_host_free": (_I, [_VP]),
     "pwn_hip_device_alloc": (_I, [_VP, C.POINTER(C.c_void_p), C.c_size_t]),
     "pwn_hip_device_free": (_I, [_VP, _VP]),
+    "pwn_hip_device_memset": (_I, [_VP, _VP, _I, C.c_size_t]),
     "pwn_hip_copy": (_I, [_VP, _VP, _VP, C.c_size_t]),
     "pwn_hip_copy_async": (_I, [_VP, _VP, _VP, C.c_size_t]),
     "pwn_hip_default_converter_params": (None, [_VP]),
@@ -116,6 +117,8 @@ PROTOTYPES = {
     "pwn_hip_convert_batch_scaled": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _F, _VP]),
     "pwn_hip_convert_batch_u16_scaled": (_I, [_VP, _VP, _VP, _F, _I, _I, _I, _I, _F, _VP]),
     "pwn_hip_project": (_I, [_VP, _VP, _VP, _F, _F, _I, _I, _VP, _VP, _VP]),
+    "pwn_hip_merge_depth_images": (_I, [_VP, _I, _VP, _I, _I, _VP, _VP, _VP, _VP]),
+    "pwn_hip_project_merge_batch": (_I, [_VP, _VP, _I, _VP, _VP, _F, _F, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_correspondences": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(_I), C.POINTER(_I)]),
     "pwn_hip_linearize": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, C.POINTER(_F), C.POINTER(_I)]),
     "pwn_hip_align": (_I, [_VP, _VP, _VP, _VP, _VP]),

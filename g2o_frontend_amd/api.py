@@ -54,6 +54,10 @@ class DeviceBuffer:
         assert array.nbytes == self.nbytes and array.flags["C_CONTIGUOUS"]
         self.ctx.check(self.ctx._L.pwn_hip_copy_async(self.ctx.h, self._p, array.ctypes.data_as(C.c_void_p), array.nbytes))
 
+    def zero(self):
+        """all bytes 0, on the device (pwn_hip_device_memset): ordered before every later call on the context"""
+        self.ctx.check(self.ctx._L.pwn_hip_device_memset(self.ctx.h, self._p, 0, self.nbytes))
+
     def numpy(self):
         out = np.empty(self.shape, self.dtype)
         self.ctx.check(self.ctx._L.pwn_hip_copy(self.ctx.h, out.ctypes.data_as(C.c_void_p), self._p, self.nbytes))
@@ -1309,6 +1313,227 @@ def _mul3(A, B):
             s = np.float32(A[i, 0] * B[0, j]); s = np.float32(s + np.float32(A[i, 1] * B[1, j])); s = np.float32(s + np.float32(A[i, 2] * B[2, j]))
             R[i, j] = s
     return R
+
+
+# ---- 4x4 isometries in double, as the closers compose them (Eigen::Isometry3d products): plain loops in a fixed order, so that the C++ mirror
+# (host/pwn_hip.hpp), which runs the same loops, arrives at the same bits before the cast to float
+def _iso_mul_d(A, B):
+    A = np.asarray(A, np.float64); B = np.asarray(B, np.float64)
+    out = np.zeros((4, 4)); out[3, 3] = 1.0
+    for i in range(3):
+        for j in range(4):
+            s = float(A[i, 0]) * float(B[0, j])
+            s = s + float(A[i, 1]) * float(B[1, j])
+            s = s + float(A[i, 2]) * float(B[2, j])
+            out[i, j] = s + float(A[i, 3]) if j == 3 else s
+    return out
+
+
+def _iso_inverse_d(T):
+    T = np.asarray(T, np.float64)
+    out = np.zeros((4, 4)); out[3, 3] = 1.0
+    for i in range(3):
+        for j in range(3):
+            out[i, j] = T[j, i]
+        s = float(T[0, i]) * float(T[0, 3])
+        s = s + float(T[1, i]) * float(T[1, 3])
+        s = s + float(T[2, i]) * float(T[2, 3])
+        out[i, 3] = -s
+    return out
+
+
+class Merger2:
+    """pwn_tracker2/merger2.{h,cpp}: the depth-image half of the merger -- clear (:36-43), mergeDepthImage (:75-101) and matchWithPartition
+    (:185-203).  The fused image, the weight image (_image_pesi) and the projected planes stay on the device.  Not mirrored: merge (the
+    cloud-level fusion with stats and Gaussians, :106-183), init and scale (:45-73)."""
+
+    def __init__(self, ctx: Context, depthImageConverter: DepthImageConverterIntegralImage, matcher: "PwnMatcherBase"):
+        self.ctx, self._depthImageConverter, self._matcher = ctx, depthImageConverter, matcher
+        self._r = depthImageConverter.projector().imageRows()              # deserialize, :216-217
+        self._c = depthImageConverter.projector().imageCols()
+        self._image_points_count = 0
+        self._image_overlapping_points_count = 0
+        self._image_pesi = DeviceBuffer(ctx, np.zeros((self._r, self._c), np.float32))
+        self._bigCloud = Cloud(ctx, max(1, self._r * self._c))
+        self._currentBigCloud = Cloud(ctx, max(1, self._r * self._c))
+        self._result = None
+        self.overlaps = []                   # _image_overlapping_points_count after each image of the last call
+
+    def depthImageConverter(self): return self._depthImageConverter
+    def matcher(self): return self._matcher
+
+    def zeros(self):
+        """DepthImage::zeros(_r, _c) on the device: what the closer starts a partition image from"""
+        return DeviceBuffer(self.ctx, np.zeros((self._r, self._c), np.float32))
+
+    def clear(self):
+        """:36-43"""
+        self._image_points_count = 0
+        self._image_overlapping_points_count = 0
+        self._image_pesi.zero()
+
+    def _counted(self, n, overlap, points):
+        self.overlaps = [int(v) for v in overlap[:n]]
+        if n:
+            self._image_overlapping_points_count = self.overlaps[-1]
+        self._image_points_count = int(points.value)
+
+    def mergeDepthImage(self, out, images):
+        """mergeDepthImage(out, image) (:75-101) for one image or a list of them, in order (pwn_hip_merge_depth_images).  out: float32
+        [_r, _c], in / out -- a DeviceBuffer / CUDA tensor, or a numpy array.  Returns the overlap count per image."""
+        if hasattr(images, "shape") and len(images.shape) == 2:
+            images = [images]
+        imgs = [d if hasattr(d, "data_ptr") else np.ascontiguousarray(d, np.float32) for d in images]
+        n = len(imgs)
+        for d in imgs:
+            if tuple(d.shape) != (self._r, self._c):
+                raise ValueError("mergeDepthImage: an image is not %d x %d" % (self._r, self._c))
+        ptrs = (C.c_void_p * max(1, n))(*[_ptr(d) for d in imgs])
+        overlap = (C.c_int * max(1, n))(); points = C.c_int(self._image_points_count)
+        self.ctx.check(self.ctx._L.pwn_hip_merge_depth_images(self.ctx.h, n, ptrs, self._r, self._c, _ptr(out), _ptr(self._image_pesi), overlap, C.byref(points)))
+        self._counted(n, overlap, points)
+        return list(self.overlaps)
+
+    def projectMerge(self, out, clouds, transforms, planes=None):
+        """PwnCloserWithMerger::mergeNode (pwn_closer_with_merger.cpp:210-224) for n clouds in one submission (pwn_hip_project_merge_batch):
+        cloud i projected by the converter's projector under transforms[i] (float 4x4) and merged into `out` in order.  planes (optional,
+        float32 [n, _r, _c], host or device) receives the projected depth images.  Returns the overlap count per cloud."""
+        pp = self._depthImageConverter.projector()
+        n = len(clouds)
+        handles = (C.c_void_p * max(1, n))(*[c.h for c in clouds])
+        tr = np.ascontiguousarray(np.stack([_colmajor(T, 4) for T in transforms]), np.float32) if n else np.zeros((1, 16), np.float32)
+        overlap = (C.c_int * max(1, n))(); points = C.c_int(self._image_points_count)
+        self.ctx.check(self.ctx._L.pwn_hip_project_merge_batch(self.ctx.h, _ptr(_colmajor(pp.cameraMatrix(), 3)), n, handles, _ptr(tr), pp.minDistance(),
+                                                               pp.maxDistance(), self._r, self._c, _ptr(out), _ptr(self._image_pesi), overlap,
+                                                               C.byref(points), _ptr(planes)))
+        self._counted(n, overlap, points)
+        return list(self.overlaps)
+
+    def matchWithPartition(self, currentPartitionImage, offset, partitionMerged):
+        """:185-203: both images converted (one pwn_hip_convert_batch of the two device frames), then
+        matchClouds(from = cloud of currentPartitionImage, to = cloud of partitionMerged, offset, offset, K, rows, cols, identity)"""
+        pp = self._depthImageConverter.projector()
+        pp.setImageSize(self._r, self._c); pp.setTransform(np.eye(4, dtype=np.float32))      # what two compute() calls leave behind
+        self._depthImageConverter.computeBatch([self._bigCloud, self._currentBigCloud], [partitionMerged, currentPartitionImage], sensorOffset=offset)
+        self._matcher.aligner().clearPriors()
+        self._result = self._matcher.matchClouds(self._currentBigCloud, self._bigCloud, offset, offset, pp.cameraMatrix().copy(), pp.imageRows(),
+                                                 pp.imageCols(), np.eye(4))
+        return self._result
+
+
+class MapNode:
+    """What the merged closer needs of a SyncSensorDataNode: transform() (double), the sensor offset of its depth camera, and the key its
+    frame has in the cloud cache"""
+
+    def __init__(self, key, transform, sensorOffset=None):
+        self.key = key
+        self._transform = np.asarray(transform, np.float64).reshape(4, 4).copy()
+        self.sensorOffset = np.asarray(np.eye(4) if sensorOffset is None else sensorOffset, np.float64).reshape(4, 4).copy()
+
+    def transform(self): return self._transform
+
+
+class PwnCloserWithMerger:
+    """pwn_tracker2/pwn_closer_with_merger.{h,cpp}: one alignment per partition -- the clouds of every som-th node of the other partition
+    projected into the view of `current` and fused (mergeNode, :210-224), the fused image aligned with the image of `current`
+    (Merger2::matchWithPartition), the one result fanned out to a relation per contributing node (processPartition, :108-208).
+    The reference walks a std::set of pointers, whose order is not defined; here the order is the caller's list.  Quirks kept: the integer
+    divisions of som and of the rejection rule, every visited node merged but only those with more than 4000 overlapping pixels related,
+    the sensor offset of the LAST visited node handed to the matcher."""
+
+    OVERLAP_MIN = 4000                                                         # :151
+    INFORMATION = np.diag([100.0, 100.0, 100.0, 1000.0, 1000.0, 1000.0])       # :196-198
+
+    def __init__(self, merger: Merger2, cache: "CloudCache", frameMinNonZeroThreshold=3000, frameMaxOutliersThreshold=100, frameMinInliersThreshold=1000):
+        self._merger, self._cache = merger, cache
+        self._frameMinNonZeroThreshold, self._frameMaxOutliersThreshold = int(frameMinNonZeroThreshold), int(frameMaxOutliersThreshold)
+        self._frameMinInliersThreshold = int(frameMinInliersThreshold)
+        self._current = None
+        self._currentPartitionActive, self._nodeList = [], []
+        self._currentPartitionImage = self._otherPartitionImage = None
+        self.accepted = None                 # of the last processPartition that got as far as the match; None when it did not
+
+    def merger(self): return self._merger
+
+    @staticmethod
+    def som(size: int) -> int:
+        """(int)round(size / 8) with the integer division of :134; 0 becomes 1 (:135)"""
+        return max(1, int(size) // 8)
+
+    def rejects(self, result) -> bool:
+        """:167-169, with its integer halves and eighths"""
+        return (result["image_nonZeros"] < self._frameMinNonZeroThreshold // 2 or result["image_outliers"] > result["image_inliers"] // 8
+                or result["image_inliers"] < self._frameMinInliersThreshold // 2)
+
+    @staticmethod
+    def projectorTransform(other: MapNode, current: MapNode, offset):
+        """tr = other.T^-1 * current.T * offset in double (:149), then convertScalar to float (mergeNode, :216-217)"""
+        return _iso_mul_d(_iso_mul_d(_iso_inverse_d(other.transform()), current.transform()), offset).astype(np.float32)
+
+    @staticmethod
+    def relationTransform(nodo2: MapNode, current: MapNode, result, nodo: MapNode):
+        """nodo2.T^-1 * ((current.T * result * current.T^-1) * nodo.T) in double (:175-188)"""
+        current_ris_iT = _iso_mul_d(_iso_mul_d(current.transform(), result), _iso_inverse_d(current.transform()))
+        return _iso_mul_d(_iso_inverse_d(nodo2.transform()), _iso_mul_d(current_ris_iT, nodo.transform()))
+
+    def mergeNode(self, out, other: MapNode, T):
+        """:210-224 -- the cached cloud of `other` projected under T (float 4x4) and merged into `out`"""
+        return self.mergeNodes(out, [other], [T])
+
+    def mergeNodes(self, out, others, transforms, planes=None):
+        """mergeNode for a run of nodes in one submission; returns Merger2::_image_overlapping_points_count after each"""
+        clouds = self._cache.getBatch([o.key for o in others])
+        return self._merger.projectMerge(out, clouds, [np.asarray(T, np.float64).astype(np.float32) for T in transforms], planes=planes)
+
+    def _zeroed(self, image):
+        """DepthImage::zeros(_r, _c) (:72, :129): the closer's device image, allocated once and cleared on the device from then on"""
+        if image is None:
+            return self._merger.zeros()
+        image.zero()
+        return image
+
+    def processCurrentPartition(self, current: MapNode):
+        """:70-106 -- the image of `current` itself (tr = its sensor offset); the loop over the current partition is commented out there"""
+        self._merger.clear()
+        self._currentPartitionImage = self._zeroed(self._currentPartitionImage)
+        self.mergeNode(self._currentPartitionImage, current, current.sensorOffset)
+        self._currentPartitionActive.append(current)
+
+    def processPartition(self, otherPartition, current: MapNode):
+        """:108-208 -> the new relations: dicts of nodes (nodo2, nodo), transform (double 4x4), informationMatrix and the MatcherResult fields"""
+        relations = []
+        self.accepted = None
+        if any(o is current for o in otherPartition):                          # :113-114
+            return relations
+        if self._current is not current:                                       # :123-127
+            self._current = current
+            self._currentPartitionActive = []
+            self.processCurrentPartition(current)
+        self._merger.clear()
+        self._otherPartitionImage = self._zeroed(self._otherPartitionImage)
+        self._nodeList = []
+        som = self.som(len(otherPartition))
+        visited = [o for it, o in enumerate(otherPartition) if it % som == 0 and o is not current]       # :137-144
+        if not visited:
+            return relations
+        trs = [self.projectorTransform(o, current, o.sensorOffset) for o in visited]
+        overlaps = self.mergeNodes(self._otherPartitionImage, visited, trs)
+        self._nodeList = [o for o, c in zip(visited, overlaps) if c > self.OVERLAP_MIN]                   # :151-153
+        if not self._nodeList:                                                 # :160
+            return relations
+        transformation = visited[-1].sensorOffset.astype(np.float32)          # :163-164: otherOffset_ of the last node visited
+        result = self._merger.matchWithPartition(self._currentPartitionImage, transformation, self._otherPartitionImage)
+        self.accepted = not self.rejects(result)
+        if not self.accepted:
+            return relations
+        for nodo in self._nodeList:                                            # :178-203
+            for nodo2 in self._currentPartitionActive:
+                r = dict(result)
+                r["nodes"] = (nodo2, nodo)
+                r["transform"] = self.relationTransform(nodo2, current, result["transform"], nodo)
+                r["informationMatrix"] = self.INFORMATION.copy()
+                relations.append(r)
+        return relations
 
 
 class CloudCache:

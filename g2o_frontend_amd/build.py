@@ -66,6 +66,13 @@ def build_tools(force: bool = False) -> str:
     if force or (not os.path.exists(out6)) or any(os.path.getmtime(d) > os.path.getmtime(out6) for d in deps6):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src6, "-o", out6, "-L", _HERE, "-lpwn_hip",
                                "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
+    # PwnCloserWithMerger::processPartition of the C++ mirror against the relations the Python mirror wrote to a file (exit status 0 = no difference)
+    src7 = os.path.join(root, "tools", "pwn_hip_merged_closure_check.cpp")
+    out7 = os.path.join(root, "tools", "pwn_hip_merged_closure_check")
+    deps7 = [src7] + deps[1:]
+    if force or (not os.path.exists(out7)) or any(os.path.getmtime(d) > os.path.getmtime(out7) for d in deps7):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src7, "-o", out7, "-L", _HERE, "-lpwn_hip",
+                               "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
     # PwnCloser::processPartition over the GPUs of a node in native code: the mirror + RCCL (broadcast of the flat `current` cloud, all-gather of the
     # match records); the program's own streams and events come from the HIP runtime
     src5 = os.path.join(root, "tools", "pwn_hip_partition_app.cpp")

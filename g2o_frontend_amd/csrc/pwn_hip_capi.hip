@@ -101,6 +101,7 @@ struct pwn_hip_cloud {
   // this image: every point falls back on its own pixel (the round trip moves it by < 0.01 pixel and its depth not at all), so batch
   // alignments take it as the current index image and skip that projection.  Anything that changes the points invalidates it.
   DevBuf<int> idximg; bool idx_valid = false; IndexKey idx_key;
+  const pwn_hip_ctx* owner = nullptr;    // the context it was created on (pwn_hip_project_merge_batch refuses another context's cloud)
 };
 
 struct pwn_hip_ctx {
@@ -179,6 +180,15 @@ struct pwn_hip_ctx {
   int settle_guard = kSettleGuard;                       // pwn_hip_debug_set_settle_guard (test hook)
   int last_align_fault = 0;                              // the last alignment call ended with the fault word raised
   int projection_fallbacks = 0;                          // calls repeated with the two-pass projection so far (pwn_hip_debug_projection_fallbacks)
+  // The merged closure (pwn_hip_merge_depth_images, pwn_hip_project_merge_batch), allocated by the first such call: the staging images of
+  // host-side `merged` / `weights` ([0, N) and [N, 2N)) and behind them merge_planes = min(max_batch, kMergePlanesMax) depth planes of N words;
+  // a call with more images runs in chunks of that many.  Per image of a call: its plane's address, its cloud, its projector matrix; the
+  // counters (overlap[n], then points) on their way to the host.
+  DevBuf<float> merge_ws; int merge_planes = 0;
+  DevBuf<const float*> plane_ptrs_dev; HostBuf<const float*> plane_ptrs_host;
+  DevBuf<DepthCloudDesc> depth_clouds_dev; HostBuf<DepthCloudDesc> depth_clouds_host;
+  DevBuf<Mat4> krt_dev; HostBuf<Mat4> krt_host;
+  DevBuf<int> merge_counts_dev; HostBuf<int> merge_counts_host;
 };
 
 namespace {
@@ -1030,6 +1040,14 @@ int pwn_hip_copy(pwn_hip_ctx* ctx, void* dst, const void* src, size_t bytes) {
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_COPY);
   return PWN_HIP_OK;
 }
+int pwn_hip_device_memset(pwn_hip_ctx* ctx, void* ptr, int value, size_t bytes) {
+  if (!ctx || (!ptr && bytes)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (!bytes) return PWN_HIP_OK;
+  if (!is_device_ptr(ptr)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "pwn_hip_device_memset: not a device pointer");
+  HIPCHK(ctx, hipSetDevice(ctx->device), PWN_HIP_ERR_NO_DEVICE);
+  HIPCHK(ctx, hipMemsetAsync(ptr, value, bytes, ctx->stream), PWN_HIP_ERR_COPY);
+  return PWN_HIP_OK;
+}
 int pwn_hip_copy_async(pwn_hip_ctx* ctx, void* dst, const void* src, size_t bytes) {
   if (!ctx || !dst || !src) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "bad copy argument");
   if (bytes == 0) return PWN_HIP_OK;
@@ -1435,6 +1453,7 @@ int pwn_hip_cloud_create(pwn_hip_ctx* ctx, int capacity, pwn_hip_cloud** out) {
     ctx->cloud_pool.erase(ctx->cloud_pool.begin() + (long)k);
     ctx->cloud_pool_bytes -= cloud_core_bytes(r);
     HIPCHK(ctx, hipMemsetAsync(r->d.count, 0, sizeof(int), ctx->stream), PWN_HIP_ERR_COPY);      // stream order: after whatever used the retired cloud
+    r->owner = ctx;
     *out = r;
     return PWN_HIP_OK;
   }
@@ -1442,6 +1461,7 @@ int pwn_hip_cloud_create(pwn_hip_ctx* ctx, int capacity, pwn_hip_cloud** out) {
   std::memset(&c->d, 0, sizeof(c->d));
   c->d.capacity = capacity;
   c->d.omSym = ctx->omega_sym;
+  c->owner = ctx;
   const size_t cap = (size_t)capacity;
   hipError_t e = hipMalloc((void**)&c->d.P3, cap * 3 * sizeof(float));
   if (e == hipSuccess) e = hipMalloc((void**)&c->d.Nc, cap * sizeof(float4));
@@ -1989,6 +2009,122 @@ int pwn_hip_project(pwn_hip_ctx* ctx, const float K[9], const float T[16], float
   ctx->img.invalidate();
   collect_stage_times(ctx);
   return PWN_HIP_OK;
+}
+// ------------------------------------------------------------------------------------------------ merged closure
+// What the two entry points of the merged closure share.  A call is checked completely before anything is written; then: the caller's `merged`
+// and weight image are used in place (device) or staged (host), the counters cleared, the images fused in chunks of ctx->merge_planes in call
+// order on the context's stream -- the per-pixel chain of a later chunk continues from what the earlier one left in `merged` / `weights`, so the
+// chunking does not show in the bits -- and everything that has to reach the host copied back before the one wait of the call.
+struct MergeRun { float* merged; float* weights; float* planes; int N; };
+static int merge_check(pwn_hip_ctx* ctx, int n, int rows, int cols, const float* merged, const float* weights) {
+  if (!ctx || !merged || !weights) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "negative number of images");
+  if (merged == weights) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "merged and weights are the same image");
+  return check_image(ctx, rows, cols);
+}
+static int merge_begin(pwn_hip_ctx* ctx, int n, int rows, int cols, float* merged, float* weights, MergeRun& r) {
+  HIPCHK(ctx, hipSetDevice(ctx->device), PWN_HIP_ERR_NO_DEVICE);
+  if (int rc = absorb_copies(ctx)) return rc;
+  if (!ctx->merge_planes) ctx->merge_planes = std::min(ctx->max_batch, kMergePlanesMax);
+  HIPCHK(ctx, ctx->merge_ws.ensure((size_t)(ctx->merge_planes + 2) * ctx->N), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->plane_ptrs_dev.ensure((size_t)n), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->plane_ptrs_host.ensure((size_t)n), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->merge_counts_dev.ensure((size_t)n + 1), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->merge_counts_host.ensure((size_t)n + 1), PWN_HIP_ERR_ALLOCATION);
+  ctx->stages.clear();
+  r.N = rows * cols;
+  r.planes = ctx->merge_ws + 2 * ctx->N;
+  r.merged = is_device_ptr(merged) ? merged : ctx->merge_ws.p;
+  r.weights = is_device_ptr(weights) ? weights : ctx->merge_ws + ctx->N;
+  if (r.merged != merged) HIPCHK(ctx, hipMemcpyAsync(r.merged, merged, (size_t)r.N * 4, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+  if (r.weights != weights) HIPCHK(ctx, hipMemcpyAsync(r.weights, weights, (size_t)r.N * 4, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipMemsetAsync(ctx->merge_counts_dev, 0, sizeof(int) * ((size_t)n + 1), ctx->stream), PWN_HIP_ERR_COPY);
+  return PWN_HIP_OK;
+}
+// images [base, base + m) of the call, whose addresses sit in plane_ptrs_dev
+static int merge_chunk(pwn_hip_ctx* ctx, const MergeRun& r, int n, int base, int m) {
+  StageTimer t(ctx, "merge_depth_images");
+  hipLaunchKernelGGL(k_merge_depth_images, dim3((unsigned)((r.N + 255) / 256)), dim3(256), 0, ctx->stream, ctx->plane_ptrs_dev + base, m, r.N, r.merged, r.weights,
+                     ctx->merge_counts_dev + base, ctx->merge_counts_dev + n);
+  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  return PWN_HIP_OK;
+}
+static int merge_end(pwn_hip_ctx* ctx, const MergeRun& r, int n, float* merged, float* weights, int* overlap, int* points) {
+  if (r.merged != merged) HIPCHK(ctx, hipMemcpyAsync(merged, r.merged, (size_t)r.N * 4, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
+  if (r.weights != weights) HIPCHK(ctx, hipMemcpyAsync(weights, r.weights, (size_t)r.N * 4, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->merge_counts_host, ctx->merge_counts_dev, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  if (overlap) std::copy(ctx->merge_counts_host.p, ctx->merge_counts_host.p + n, overlap);
+  if (points) *points += ctx->merge_counts_host[n];
+  collect_stage_times(ctx);
+  return PWN_HIP_OK;
+}
+int pwn_hip_merge_depth_images(pwn_hip_ctx* ctx, int n, const float* const* depth_images, int rows, int cols, float* merged, float* weights, int* overlap,
+                               int* points) {
+  if (int rc = merge_check(ctx, n, rows, cols, merged, weights)) return rc;
+  if (n > 0 && !depth_images) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  for (int i = 0; i < n; ++i) if (!depth_images[i]) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null image");
+  if (n == 0) return PWN_HIP_OK;
+  MergeRun r;
+  if (int rc = merge_begin(ctx, n, rows, cols, merged, weights, r)) return rc;
+  const int P = ctx->merge_planes;
+  std::vector<char> staged((size_t)n);                 // host images pass through the plane of their place in the chunk
+  for (int i = 0; i < n; ++i) {
+    staged[i] = !is_device_ptr(depth_images[i]);
+    ctx->plane_ptrs_host[i] = staged[i] ? r.planes + (size_t)(i % P) * r.N : depth_images[i];
+  }
+  HIPCHK(ctx, hipMemcpyAsync(ctx->plane_ptrs_dev, ctx->plane_ptrs_host, sizeof(float*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+  for (int base = 0; base < n; base += P) {
+    const int m = std::min(P, n - base);
+    for (int j = 0; j < m; ++j)
+      if (staged[base + j]) HIPCHK(ctx, hipMemcpyAsync(r.planes + (size_t)j * r.N, depth_images[base + j], (size_t)r.N * 4, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+    if (int rc = merge_chunk(ctx, r, n, base, m)) return rc;
+  }
+  return merge_end(ctx, r, n, merged, weights, overlap, points);
+}
+int pwn_hip_project_merge_batch(pwn_hip_ctx* ctx, const float K[9], int n, pwn_hip_cloud* const* clouds, const float* transforms, float min_distance,
+                                float max_distance, int rows, int cols, float* merged, float* weights, int* overlap, int* points, float* planes) {
+  if (int rc = merge_check(ctx, n, rows, cols, merged, weights)) return rc;
+  if (!K || (n > 0 && (!clouds || !transforms))) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (min_distance < 0.f) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "min_distance must be >= 0");
+  for (int i = 0; i < n; ++i) {
+    if (!clouds[i]) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null cloud");
+    if (clouds[i]->owner != ctx) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "cloud of another context");
+  }
+  if (n == 0) return PWN_HIP_OK;
+  MergeRun r;
+  if (int rc = merge_begin(ctx, n, rows, cols, merged, weights, r)) return rc;
+  HIPCHK(ctx, ctx->depth_clouds_dev.ensure((size_t)n), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->depth_clouds_host.ensure((size_t)n), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->krt_dev.ensure((size_t)n), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->krt_host.ensure((size_t)n), PWN_HIP_ERR_ALLOCATION);
+  const int P = ctx->merge_planes;
+  const Mat3 Km = mat3_from(K);
+  for (int i = 0; i < n; ++i) {
+    Mat4 iKRt; Mat3 iK;
+    projector_matrices(Km, mat4_from(transforms + 16 * (size_t)i), ctx->krt_host[i], iKRt, iK);      // as pwn_hip_project builds its KRt
+    DepthCloudDesc& d = ctx->depth_clouds_host[i];
+    d.P3 = clouds[i]->d.P3; d.count = clouds[i]->d.count; d.capacity = clouds[i]->d.capacity;
+    ctx->plane_ptrs_host[i] = r.planes + (size_t)(i % P) * r.N;
+  }
+  HIPCHK(ctx, hipMemcpyAsync(ctx->plane_ptrs_dev, ctx->plane_ptrs_host, sizeof(float*) * (size_t)n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->depth_clouds_dev, ctx->depth_clouds_host, sizeof(DepthCloudDesc) * (size_t)n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->krt_dev, ctx->krt_host, sizeof(Mat4) * (size_t)n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+  for (int base = 0; base < n; base += P) {
+    const int m = std::min(P, n - base);
+    int capacity = 1;
+    for (int j = 0; j < m; ++j) capacity = std::max(capacity, clouds[base + j]->d.capacity);
+    HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)r.planes, (int)kDepthPlaneEmpty, (size_t)m * r.N, ctx->stream), PWN_HIP_ERR_COPY);
+    // one point per thread: the atomics return nothing, so a thread has nothing to wait for between its points (what k_project's four points per
+    // thread buy); more points per thread stay unbuilt until a measurement asks for them
+    { StageTimer t(ctx, "project_depth_batch");
+      hipLaunchKernelGGL((k_project_depth_batch<1>), dim3((unsigned)((capacity + 255) / 256), (unsigned)m), dim3(256), 0, ctx->stream, ctx->depth_clouds_dev + base,
+                         ctx->krt_dev + base, min_distance, max_distance, rows, cols, (unsigned*)r.planes); }
+    HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+    if (int rc = merge_chunk(ctx, r, n, base, m)) return rc;
+    if (planes) HIPCHK(ctx, copy_any(planes + (size_t)base * r.N, r.planes, (size_t)m * r.N * 4, ctx->stream), PWN_HIP_ERR_COPY);
+  }
+  return merge_end(ctx, r, n, merged, weights, overlap, points);
 }
 int pwn_hip_correspondences(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, const pwn_hip_cloud* ref, const pwn_hip_cloud* cur,
                             const int* ref_index, const int* cur_index, const float T[16], int* corr, int* n_corr, int* n_cand) {

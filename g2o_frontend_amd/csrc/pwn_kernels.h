@@ -1307,6 +1307,81 @@ __global__ void k_zbuf_resolve(const unsigned long long* __restrict__ z, int n, 
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// PwnCloserWithMerger::mergeNode (pwn_tracker2/pwn_closer_with_merger.cpp:210-224) for the nodes of a partition in one launch: the depth
+// images of n clouds, each under its own projector, and their pixel-wise fusion (Merger2::mergeDepthImage, pwn_tracker2/merger2.cpp:75-101).
+//
+// k_project_depth_batch: PinholePointProjector::project's depth image (pinholepointprojector.cpp:33-66) of cloud blockIdx.y under
+// KRt[blockIdx.y] into plane blockIdx.y (rows * cols words).  Only the depths are wanted, so a point that passes _project does one atomicMin
+// on its depth's bit pattern (the sign bit masked as in k_project_robust: min_distance >= 0 is the host's check, so the patterns order like
+// the values) and nothing else: no index, no settle loop, no second pass.  The planes are cleared to the bit pattern of FLT_MAX; afterwards
+// a plane read as floats is the projector's depth image: FLT_MAX where nothing landed (:41-42), else the nearest depth.
+// grid = (ceil(largest capacity / (256 * PPT)), n), block = 256
+struct DepthCloudDesc { const float* P3; const int* count; int capacity; };
+constexpr unsigned kDepthPlaneEmpty = 0x7f7fffffu;      // FLT_MAX
+template <int PPT>
+__global__ void __launch_bounds__(256) k_project_depth_batch(const DepthCloudDesc* __restrict__ clouds, const Mat4* __restrict__ KRts, float minD, float maxD,
+                                                             int rows, int cols, unsigned* __restrict__ planes) {
+  const DepthCloudDesc cl = clouds[blockIdx.y];
+  const int n = min(*cl.count, cl.capacity);
+  const int i0 = blockIdx.x * 256 * PPT + threadIdx.x;
+  if (i0 >= n) return;
+  const Mat4 KRt = uniform_iso_global(as_global((const float*)(KRts + blockIdx.y)));
+  unsigned* plane = planes + (size_t)blockIdx.y * ((size_t)rows * cols);
+  float4 p[PPT];
+#pragma unroll
+  for (int j = 0; j < PPT; ++j) { const int i = i0 + 256 * j; if (i < n) p[j] = load_xyz(cl.P3, i); }
+#pragma unroll
+  for (int j = 0; j < PPT; ++j) {
+    float d; int x, y;
+    if (i0 + 256 * j < n && project_to_pixel(KRt, minD, maxD, rows, cols, p[j], d, x, y))
+      atomicMin(&plane[(size_t)y * cols + x], __float_as_uint(d) & 0x7fffffffu);
+  }
+}
+// k_merge_depth_images: one thread per pixel walks the m planes in call order with Merger2::mergeDepthImage's arithmetic, literally: the
+// range test and the two thresholds in double against the double literals, the weight an IEEE division, the weighted mean from separately
+// rounded products (dot2seq), `out` and the weight image in / out -- m planes in one launch are m successive mergeDepthImage calls.
+// overlap[k] += pixels of plane k inside (0.1, 10000) (_image_overlapping_points_count, which the reference resets per image: the host
+// clears the words), *points += pixels replaced (_image_points_count): a ballot per wave, an LDS word per counter, one global atomic per
+// workgroup and non-zero counter.  grid = ceil(N / 256), block = 256, m <= kMergePlanesMax
+constexpr int kMergePlanesMax = 256;
+__global__ void __launch_bounds__(256) k_merge_depth_images(const float* const* __restrict__ planes, int m, int N, float* __restrict__ out,
+                                                            float* __restrict__ weights, int* __restrict__ overlap, int* __restrict__ points) {
+  __shared__ int s_cnt[kMergePlanesMax + 1];
+  for (int t = threadIdx.x; t <= m; t += 256) s_cnt[t] = 0;
+  __syncthreads();
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  const bool live = i < (unsigned)N;
+  float o = 0.f, w = 0.f;
+  if (live) { o = out[i]; w = weights[i]; }
+  int replaced = 0;
+  for (int k = 0; k < m; ++k) {
+    bool selected = false;
+    if (live) {
+      const float d = as_global(planes[k])[i];
+      selected = (double)d > 0.1 && (double)d < 10000;                   // merger2.cpp:80
+      if (selected) {
+        const float peso = 1.0f / d;                                     // :82
+        if (o == 0.f || (double)(d - o) < -.00003) {                     // :84
+          ++replaced; o = d; w = peso;                                   // :86-89
+        } else if ((double)fabsf(d - o) < .2) {                          // :91
+          const float somma = w + peso;                                  // :93
+          o = dot2seq(o, w, d, peso) / somma;                            // :94
+          w = somma;                                                     // :95
+        }
+      }
+    }
+    const int c = __popcll(__ballot(selected));
+    if (lane_id() == 0 && c) atomicAdd(&s_cnt[k], c);
+  }
+  if (live) { out[i] = o; weights[i] = w; }
+  const int r = (int)wave_sum((float)replaced);      // <= 64 * kMergePlanesMax: exact in fp32
+  if (lane_id() == 0 && r) atomicAdd(&s_cnt[m], r);
+  __syncthreads();
+  for (int t = threadIdx.x; t <= m; t += 256)
+    if (s_cnt[t]) atomicAdd(t < m ? overlap + t : points, s_cnt[t]);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // One correspondence's contribution to the normal equations: Linearizer::update loop body
 // (pwn_core/linearizer.cpp:57-88).  oP / oN: row-major 3x3 information matrices of the CURRENT point.
 // The 4x4 products of the reference are written out for the non-zero 3x3 part; dropped terms are exact zeros.

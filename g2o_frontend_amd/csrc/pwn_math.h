@@ -37,7 +37,10 @@ PWN_HD Mat4 mat4_from(const float* p) { Mat4 r; for (int i = 0; i < 16; ++i) r.m
 PWN_HD Mat3 mat3_from(const float* p) { Mat3 r; for (int i = 0; i < 9; ++i) r.m[i] = p[i]; return r; }
 PWN_HD void set_last_row(Mat4& T) { T(3,0) = 0.f; T(3,1) = 0.f; T(3,2) = 0.f; T(3,3) = 1.f; }
 
-// 3-term / 4-term inner products, strictly left to right
+// 2-term / 3-term / 4-term inner products, strictly left to right
+PWN_HD float dot2seq(float a0, float b0, float a1, float b1) {
+  float s = a0 * b0; s = s + a1 * b1; return s;
+}
 PWN_HD float dot3seq(float a0, float b0, float a1, float b1, float a2, float b2) {
   float s = a0 * b0; s = s + a1 * b1; s = s + a2 * b2; return s;
 }

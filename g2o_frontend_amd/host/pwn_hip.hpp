@@ -14,6 +14,7 @@
 #include <cstring>
 #include <list>
 #include <map>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -792,7 +793,7 @@ class CloudCache {
     insert(key, cloud);
     return cloud;
   }
-  size_t resident() const { return _lru.size(); }
+  size_t resident() const { return _lru.size(); }  size_t capacity() const { return _capacity; }
   int hits = 0, misses = 0;
  private:
   struct Frame { DepthImage depth; Matrix3f cameraMatrix; Isometry3f sensorOffset; };
@@ -879,6 +880,176 @@ class PwnTracker : public PwnMatcherBase {
   Isometry3f _globalT, _previousCloudTransform, _previousCloudOffset;
   float _newFrameInliersFraction = 0.4f;     // pwn_tracker.cpp:36
   int _counter = 0, _numKeyframes = 0;
+};
+
+// ---- the merged closure (pwn_tracker2) --------------------------------------------------------------------------------------------------
+// Eigen::Isometry3d as the closers compose it: row-major 4x4 doubles, products and inverse as plain loops in a fixed order (api.py runs the
+// same loops: the two mirrors arrive at the same bits before the cast to float)
+struct Isometry3d {
+  double m[16];                                    // row-major
+  Isometry3d() { for (int i = 0; i < 16; ++i) m[i] = (i % 5 == 0) ? 1.0 : 0.0; }
+  double& operator()(int r, int c) { return m[4 * r + c]; }
+  double operator()(int r, int c) const { return m[4 * r + c]; }
+  Isometry3d operator*(const Isometry3d& b) const {
+    Isometry3d o;
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 4; ++j) {
+        double s = (*this)(i,0) * b(0,j); s = s + (*this)(i,1) * b(1,j); s = s + (*this)(i,2) * b(2,j);
+        o(i,j) = (j == 3) ? s + (*this)(i,3) : s;
+      }
+    return o;
+  }
+  Isometry3d inverse() const {
+    Isometry3d o;
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) o(i,j) = (*this)(j,i);
+      double s = (*this)(0,i) * (*this)(0,3); s = s + (*this)(1,i) * (*this)(1,3); s = s + (*this)(2,i) * (*this)(2,3);
+      o(i,3) = -s;
+    }
+    return o;
+  }
+  Isometry3f toFloat() const { Isometry3f f; for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) f(r,c) = (float)(*this)(r,c); return f; }      // convertScalar
+  static Isometry3d fromColumnMajor(const double* a) { Isometry3d o; for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) o(r,c) = a[r + 4 * c]; return o; }
+};
+
+// a depth image in device memory (pwn_hip_device_alloc): what the merged closure fuses into and converts from
+class DeviceImage {
+ public:
+  DeviceImage(Context& ctx, int rows, int cols) : _ctx(&ctx), _rows(rows), _cols(cols) {
+    ctx.check(pwn_hip_device_alloc(ctx.handle(), (void**)&_p, sizeof(float) * (size_t)(rows * cols > 0 ? rows * cols : 1)));
+    try { setZero(); } catch (...) { pwn_hip_device_free(ctx.handle(), _p); throw; }
+  }
+  ~DeviceImage() { pwn_hip_device_free(_ctx->handle(), _p); }
+  DeviceImage(const DeviceImage&) = delete;
+  DeviceImage& operator=(const DeviceImage&) = delete;
+  void setZero() { _ctx->check(pwn_hip_device_memset(_ctx->handle(), _p, 0, sizeof(float) * (size_t)_rows * _cols)); }      // on the device
+  void download(DepthImage& out) const { out.create(_rows, _cols); if (!out.data.empty()) _ctx->check(pwn_hip_copy(_ctx->handle(), out.data.data(), _p, out.data.size() * sizeof(float))); }
+  float* data() const { return _p; }
+  int rows() const { return _rows; }  int cols() const { return _cols; }
+ private:
+  Context* _ctx; int _rows, _cols; float* _p = nullptr;
+};
+
+// pwn_tracker2/merger2.{h,cpp}: the depth-image half of the merger -- clear (:36-43), mergeDepthImage (:75-101), matchWithPartition (:185-203).
+// The fused image, the weight image (_image_pesi) and the projected planes stay on the device.  Not mirrored: merge (:106-183), init and
+// scale (:45-73).
+class Merger2 {
+ public:
+  Merger2(Context* ctx, DepthImageConverterIntegralImage* converter, PwnMatcherBase* matcher)
+      : _r(converter->projector()->imageRows()), _c(converter->projector()->imageCols()), _ctx(ctx), _depthImageConverter(converter), _matcher(matcher),
+        _image_pesi(*ctx, _r, _c), _bigCloud(*ctx, _r * _c > 0 ? _r * _c : 1), _currentBigCloud(*ctx, _r * _c > 0 ? _r * _c : 1) {}      // deserialize, :216-217
+  DepthImageConverterIntegralImage* depthImageConverter() { return _depthImageConverter; }
+  void clear() { _image_points_count = 0; _image_overlapping_points_count = 0; _image_pesi.setZero(); }        // :36-43
+  // mergeDepthImage(out, image) (:75-101) for a run of images (host or device pointers, _r x _c floats each) in order; overlaps receives
+  // _image_overlapping_points_count after each
+  void mergeDepthImage(DeviceImage& out, const std::vector<const float*>& images) {
+    overlaps.assign(images.size(), 0);
+    _ctx->check(pwn_hip_merge_depth_images(_ctx->handle(), (int)images.size(), images.data(), _r, _c, out.data(), _image_pesi.data(), overlaps.data(), &_image_points_count));
+    if (!overlaps.empty()) _image_overlapping_points_count = overlaps.back();
+  }
+  // PwnCloserWithMerger::mergeNode (pwn_closer_with_merger.cpp:210-224) for n clouds in one submission (pwn_hip_project_merge_batch)
+  void projectMerge(DeviceImage& out, const std::vector<Cloud*>& clouds, const std::vector<Isometry3f>& transforms, float* planes = nullptr) {
+    if (clouds.size() != transforms.size()) throw Error(PWN_HIP_ERR_INVALID_ARGUMENT, "projectMerge: list sizes differ");
+    PinholePointProjector* pp = _depthImageConverter->projector();
+    std::vector<pwn_hip_cloud*> h(clouds.size()); std::vector<float> tr(clouds.size() * 16);
+    for (size_t i = 0; i < h.size(); ++i) { h[i] = clouds[i]->handle(); std::memcpy(&tr[16 * i], transforms[i].data(), 16 * sizeof(float)); }
+    overlaps.assign(clouds.size(), 0);
+    _ctx->check(pwn_hip_project_merge_batch(_ctx->handle(), pp->cameraMatrix().data(), (int)h.size(), h.data(), tr.data(), pp->minDistance(), pp->maxDistance(), _r, _c,
+                                            out.data(), _image_pesi.data(), overlaps.data(), &_image_points_count, planes));
+    if (!overlaps.empty()) _image_overlapping_points_count = overlaps.back();
+  }
+  // :185-203: both images converted by one pwn_hip_convert_batch of the two device frames, then matchClouds(from = the cloud of
+  // currentPartitionImage, to = the cloud of partitionMerged, offset, offset, K, rows, cols, identity)
+  void matchWithPartition(const DeviceImage& currentPartitionImage, const Isometry3f& offset, const DeviceImage& partitionMerged) {
+    PinholePointProjector* pp = _depthImageConverter->projector();
+    _depthImageConverter->computeBatch({ &_bigCloud, &_currentBigCloud }, { partitionMerged.data(), currentPartitionImage.data() }, _r, _c, offset);
+    _matcher->aligner()->clearPriors();
+    const Matrix3f K = pp->cameraMatrix();
+    _matcher->matchClouds(_result, &_currentBigCloud, &_bigCloud, offset, offset, K, pp->imageRows(), pp->imageCols(), Isometry3f::Identity());
+  }
+  int _r, _c;
+  int _image_points_count = 0, _image_overlapping_points_count = 0;
+  std::vector<int> overlaps;
+  PwnMatcherBase::MatcherResult _result;
+ private:
+  Context* _ctx; DepthImageConverterIntegralImage* _depthImageConverter; PwnMatcherBase* _matcher;
+  DeviceImage _image_pesi;
+  Cloud _bigCloud, _currentBigCloud;
+};
+
+// what the merged closer needs of a SyncSensorDataNode: its transform, the sensor offset of its depth camera, the key of its frame in the cache
+struct MapNode { int key = 0; Isometry3d transform; Isometry3d sensorOffset; };
+
+// pwn_tracker2/pwn_closer_with_merger.{h,cpp}: one alignment per partition (see api.py, PwnCloserWithMerger, for the quirks kept).  The
+// reference walks a std::set of pointers, whose order is not defined; here the order is the caller's vector.
+class PwnCloserWithMerger {
+ public:
+  struct Relation { const MapNode* nodes[2]; Isometry3d transform; double informationMatrix[36]; PwnMatcherBase::MatcherResult result; };
+  PwnCloserWithMerger(Context* ctx, Merger2* merger, CloudCache* cache) : _ctx(ctx), _merger(merger), _cache(cache) {}
+  int frameMinNonZeroThreshold = 3000, frameMaxOutliersThreshold = 100, frameMinInliersThreshold = 1000;
+  static int som(size_t size) { const int s = (int)(size / 8); return s == 0 ? 1 : s; }                     // :134-135
+  bool rejects(const PwnMatcherBase::MatcherResult& r) const {                                            // :167-169
+    return r.image_nonZeros < frameMinNonZeroThreshold / 2 || r.image_outliers > r.image_inliers / 8 || r.image_inliers < frameMinInliersThreshold / 2;
+  }
+  void mergeNodes(DeviceImage& out, const std::vector<const MapNode*>& others, const std::vector<Isometry3f>& transforms) {      // :210-224, n nodes
+    // the cache deletes what it evicts: every cloud of the run has to stay resident until the call has used it
+    if (_cache->capacity() < others.size()) throw Error(PWN_HIP_ERR_CAPACITY, "PwnCloserWithMerger: the cloud cache holds fewer clouds than one merge visits");
+    std::vector<Cloud*> clouds;
+    for (const MapNode* o : others) clouds.push_back(_cache->get(o->key));
+    _merger->projectMerge(out, clouds, transforms);
+  }
+  void processCurrentPartition(const MapNode* current) {                                                  // :70-106
+    _merger->clear();
+    zeroed(_currentPartitionImage);
+    mergeNodes(*_currentPartitionImage, { current }, { current->sensorOffset.toFloat() });
+    _currentPartitionActive.push_back(current);
+  }
+  // :108-208; accepted: -1 = the match was not reached, 0 = rejected, 1 = accepted
+  std::vector<Relation> processPartition(const std::vector<const MapNode*>& otherPartition, const MapNode* current) {
+    std::vector<Relation> relations;
+    accepted = -1;
+    for (const MapNode* o : otherPartition) if (o == current) return relations;                           // :113-114
+    if (_current != current) { _current = current; _currentPartitionActive.clear(); processCurrentPartition(current); }      // :123-127
+    _merger->clear();
+    zeroed(_otherPartitionImage);
+    _nodeList.clear();
+    const int s = som(otherPartition.size());
+    std::vector<const MapNode*> visited; std::vector<Isometry3f> trs;
+    for (size_t it = 0; it < otherPartition.size(); ++it) {                                               // :137-149
+      if ((int)it % s != 0 || otherPartition[it] == current) continue;
+      const MapNode* other = otherPartition[it];
+      visited.push_back(other);
+      trs.push_back((other->transform.inverse() * current->transform * other->sensorOffset).toFloat());
+    }
+    if (visited.empty()) return relations;
+    mergeNodes(*_otherPartitionImage, visited, trs);
+    for (size_t i = 0; i < visited.size(); ++i) if (_merger->overlaps[i] > 4000) _nodeList.push_back(visited[i]);      // :151-153
+    if (_nodeList.empty()) return relations;                                                              // :160
+    _merger->matchWithPartition(*_currentPartitionImage, visited.back()->sensorOffset.toFloat(), *_otherPartitionImage);      // :163-165
+    const PwnMatcherBase::MatcherResult& result = _merger->_result;
+    accepted = rejects(result) ? 0 : 1;
+    if (!accepted) return relations;
+    const Isometry3d current_ris_iT = current->transform * Isometry3d::fromColumnMajor(result.transform) * current->transform.inverse();      // :175
+    for (const MapNode* nodo : _nodeList)                                                                 // :178-203
+      for (const MapNode* nodo2 : _currentPartitionActive) {
+        Relation r; r.nodes[0] = nodo2; r.nodes[1] = nodo; r.result = result;
+        r.transform = nodo2->transform.inverse() * (current_ris_iT * nodo->transform);
+        for (int i = 0; i < 36; ++i) r.informationMatrix[i] = (i % 7 == 0) ? (i < 21 ? 100.0 : 1000.0) : 0.0;      // :196-198
+        relations.push_back(r);
+      }
+    return relations;
+  }
+  int accepted = -1;
+  const std::vector<const MapNode*>& nodeList() const { return _nodeList; }
+  const DeviceImage* otherPartitionImage() const { return _otherPartitionImage.get(); }
+  const DeviceImage* currentPartitionImage() const { return _currentPartitionImage.get(); }
+ private:
+  // DepthImage::zeros(_r, _c) (:72, :129): allocated once, cleared on the device from then on
+  void zeroed(std::unique_ptr<DeviceImage>& image) { if (image) image->setZero(); else image.reset(new DeviceImage(*_ctx, _merger->_r, _merger->_c)); }
+  Context* _ctx; Merger2* _merger; CloudCache* _cache;
+  const MapNode* _current = nullptr;
+  std::vector<const MapNode*> _currentPartitionActive, _nodeList;
+  std::unique_ptr<DeviceImage> _currentPartitionImage, _otherPartitionImage;
 };
 
 }  // namespace pwn_hip

@@ -208,6 +208,9 @@ int pwn_hip_device_alloc(pwn_hip_ctx* ctx, void** ptr, size_t bytes);
 int pwn_hip_device_free(pwn_hip_ctx* ctx, void* ptr);      /* waits for the context's queued work first; ctx may be NULL once the context that
                                                              * allocated the buffer has been destroyed (the buffer is then simply released) */
 int pwn_hip_copy(pwn_hip_ctx* ctx, void* dst, const void* src, size_t bytes);
+/* Fills `bytes` bytes of a device buffer with the byte `value` (0: a DepthImage::zeros that never leaves the device), queued on the context's
+ * stream: every later call on the context sees it; returns at once. */
+int pwn_hip_device_memset(pwn_hip_ctx* ctx, void* ptr, int value, size_t bytes);
 /* The same copy queued on the context's copy stream; returns at once (for page-locked host memory -- pageable memory makes it wait).  The
  * next call on the context that reads data through a caller-supplied pointer -- convert*, unproject, project_intervals, the depth-image
  * helpers, cloud_gaussians, cloud_upload, integral_image, correspondences, linearize -- and pwn_hip_copy, ctx_synchronize, device_free
@@ -345,6 +348,27 @@ int pwn_hip_convert_batch_u16_scaled(pwn_hip_ctx* ctx, const pwn_hip_converter_p
  * projector transform T.  Untouched depth pixels are FLT_MAX, index -1; ties keep the lowest index. */
 int pwn_hip_project(pwn_hip_ctx* ctx, const float K[9], const float T[16], float min_distance, float max_distance,
                     int rows, int cols, const pwn_hip_cloud* cloud, int* index_image, float* depth_image);
+/* ---- the merged closure (pwn_tracker2/pwn_closer_with_merger.cpp:108-224): the clouds of a partition fused into ONE depth image in the view of
+ * `current`, one alignment per partition instead of one per candidate.  merged / weights (rows*cols floats each, in / out), the images and
+ * `planes` may be host or device memory; overlap and points are host memory.  A refused call -- a null argument, n < 0, an image larger than
+ * the context's, min_distance < 0, a cloud of another context -- returns its status and leaves merged, weights and the counters untouched;
+ * n == 0 is a no-op that returns PWN_HIP_OK.  merged, weights, the images and `planes` must not overlap one another (merged == weights is refused; other
+ * overlaps are the caller's to avoid: the kernels read and write them as distinct arrays).  The context keeps min(max_batch, 256) depth planes of max_rows*max_cols words (allocated by the
+ * first call); a call with more images runs in chunks of that many, in order, with the same bits. */
+/* Merger2::mergeDepthImage(out, image) (pwn_tracker2/merger2.cpp:75-101) for depth_images[0..n) in call order: a pixel d inside (0.1, 10000)
+ * replaces `merged` where that is 0 or more than 3e-5 behind d (weight 1/d), else is averaged in with inverse-depth weights when within 0.2
+ * (:84-96); `weights` is Merger2::_image_pesi.  overlap[i] (n ints, may be NULL) = _image_overlapping_points_count after image i (the reference
+ * resets it per image, :77); *points (may be NULL) += the pixels replaced, _image_points_count (:86; Merger2::clear zeroes it, :40). */
+int pwn_hip_merge_depth_images(pwn_hip_ctx* ctx, int n, const float* const* depth_images, int rows, int cols, float* merged, float* weights,
+                               int* overlap, int* points);
+/* PwnCloserWithMerger::mergeNode (pwn_tracker2/pwn_closer_with_merger.cpp:210-224) for n nodes in one submission on the context's stream:
+ * PinholePointProjector::project's depth image (pinholepointprojector.cpp:33-66) of clouds[i] under the projector transform
+ * transforms[16 i .. 16 i + 16) (column-major; camera matrix K, range, image size shared), then Merger2::mergeDepthImage of the n images in
+ * order, without leaving the device.  planes (optional, n*rows*cols floats) receives the projected depth images (FLT_MAX where nothing
+ * landed): what n pwn_hip_project calls return as depth_image, bit for bit. */
+int pwn_hip_project_merge_batch(pwn_hip_ctx* ctx, const float K[9], int n, pwn_hip_cloud* const* clouds, const float* transforms,
+                                float min_distance, float max_distance, int rows, int cols, float* merged, float* weights, int* overlap,
+                                int* points, float* planes);
 /* CorrespondenceFinder::compute (correspondencefinder.cpp:20-118, single-thread canonical order).
  * correspondences: rows*cols pairs (referenceIndex,currentIndex) -- the first *n_correspondences are
  * valid, in row-major pixel order, the rest are (-1,-1) (correspondencefinder.cpp:116-117). */
@@ -503,7 +527,7 @@ void pwn_hip_t2v(const float T[16], float v[6]);
 void pwn_hip_ldlt_solve6(const float H[36], const float b[6], float x[6]);
 /* per-kernel device time (ms) of the stages of the last batch/single call, for bench.py:
  * names: "unproject","integral","integral_rows","integral_cols","stats","project_cur","project_ref","corr_linearize","solve",
- * "statistics","match_score" ("project": the stand-alone pwn_hip_project).  launches = timed launch groups (one per sub-batch). */
+ * "statistics","match_score" ("project": the stand-alone pwn_hip_project; "project_depth_batch","merge_depth_images": the merged closure).  launches = timed launch groups (one per sub-batch). */
 int pwn_hip_last_stage_ms(pwn_hip_ctx* ctx, const char* stage, float* ms, int* launches);
 /* what this GPU's HBM delivers, for the roofline report (SURVEY 8(d) asks for the measured figure next to the 8 TB/s spec):
  * float4 streaming read and device-to-device copy of `bytes` (use >= 1 GiB: the Infinity Cache holds 256 MiB), best of 5,
