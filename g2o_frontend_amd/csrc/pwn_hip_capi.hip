@@ -586,8 +586,9 @@ int launch_front_end(pwn_hip_ctx* ctx, const ConvertParams& cp, int base, int n,
     { StageTimer t(ctx, "integral", st);           // unProject + intervals + the three integral-image passes
       const unsigned epoch = ++ctx->convert_epoch;
       if (epoch == 0) return fail(ctx, PWN_HIP_ERR_LAUNCH, "convert epoch wrapped: recreate the context");
-      hipLaunchKernelGGL(k_unproject_integral, dim3(8u * (unsigned)((n + 7) / 8) * (unsigned)strips_of(cp.cols)), dim3(kII_Threads), 0, st, fr, cp, n,
-                         epoch, ctx->fault_dev); }
+      const dim3 grid(8u * (unsigned)((n + 7) / 8) * (unsigned)strips_of(cp.cols));
+      if (cp.lean == kLeanGrouped) hipLaunchKernelGGL(k_unproject_integral_grouped, grid, dim3(kII_Threads), 0, st, fr, cp, n, epoch, ctx->fault_dev);
+      else hipLaunchKernelGGL(k_unproject_integral, grid, dim3(kII_Threads), 0, st, fr, cp, n, epoch, ctx->fault_dev); }
   } else {
     // latency path (single frames: tracker, makeCloud): three short, fully parallel kernels
     { StageTimer t(ctx, "unproject", st);          // ordered compaction: per-row counts and offsets
@@ -599,8 +600,10 @@ int launch_front_end(pwn_hip_ctx* ctx, const ConvertParams& cp, int base, int n,
       hipLaunchKernelGGL(k_unproject_integral_rows, dim3(8u * (unsigned)((bands_of(cp.rows) + 7) / 8) * (unsigned)strips_of(cp.cols), n), dim3(256), 0, st, fr, cp,
                          epoch, ctx->fault_dev); }
     { StageTimer t(ctx, "integral_cols", st);
-      hipLaunchKernelGGL(k_integral_cols, dim3((cp.cols + kIC_Block - 1) / kIC_Block, kIntegralChannels, n), dim3(kIC_Block), 0, st, fr, cp.rows, cp.cols,
-                         (const int*)ctx->fault_dev, fault_out); }
+      const bool grouped = cp.lean == kLeanGrouped;
+      const dim3 grid = grouped ? dim3((ig_width(0) * cp.cols + kIC_Block - 1) / kIC_Block, kIG_Groups, n)
+                                   : dim3((cp.cols + kIC_Block - 1) / kIC_Block, kIntegralChannels, n);
+      hipLaunchKernelGGL(k_integral_cols, grid, dim3(kIC_Block), 0, st, fr, cp.rows, cp.cols, (const int*)ctx->fault_dev, fault_out, grouped ? 1 : 0); }
   }
   return PWN_HIP_OK;
 }
@@ -734,7 +737,9 @@ int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const S
   const size_t N = (size_t)rows * cols;
   ctx->last_convert_fault = 0;            // the fault word belongs to this call from here on (a stale 1 would make an unrelated failure look like a time-out)
   ConvertParams cp = make_convert_params(ctx, p, nullptr, rows, cols, keep_stats);
-  cp.lean = want_interval ? 0 : 1;      // the interval image leaves the converter only through pwn_hip_convert(..., interval_image)
+  // the interval image leaves the converter only through pwn_hip_convert(..., interval_image); nothing outside the library sees a lean call's
+  // integral image: grouped storage (ig_at)
+  cp.lean = want_interval ? 0 : kLeanGrouped;
   if (int rc = ensure_desc(ctx, n)) return rc;
   const bool raw = std::is_same<SRC, uint16_t>::value;
   job.n = n; job.rows = rows; job.cols = cols; job.N = N; job.raw = raw; job.depth_scale = depth_scale; job.slot = slot; job.direct = direct;
@@ -887,6 +892,7 @@ int debug_front_end_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, co
   ConvertJob job;
   if (int rc = convert_prepare<SRC>(ctx, p, frames, depth_scale, n, rows, cols, clouds, 0, lean == 0, slot, direct, job)) return rc;
   if (job.host_input) { if (int rc = convert_stage_frames(ctx, job, 0, n, ctx->stream)) return rc; }
+  if (lean) job.cp.lean = 1;             // integral_out is ten planes, lean or not
   // The one thing queued here that a convert call does not queue (there k_stats writes normals and matrices): with lean = 0 the clouds get points
   // only, so their previous normals and matrices are cleared instead of staying readable next to the new points.  Two memsets per cloud ahead of
   // the kernels; the kernels, their grids and their arguments are the convert call's.
@@ -1837,7 +1843,7 @@ int pwn_hip_integral_image(pwn_hip_ctx* ctx, const int* index_image, const pwn_h
   HIPCHK(ctx, copy_any(ctx->frames_host[0].index, index_image, N * 4, ctx->stream), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev, ctx->frames_host, sizeof(FrameDesc), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
   hipLaunchKernelGGL(k_integral_rows, dim3((rows + kIR_Rows - 1) / kIR_Rows, 1), dim3(256), 0, ctx->stream, ctx->frames_dev, rows, cols);
-  hipLaunchKernelGGL(k_integral_cols, dim3((cols + kIC_Block - 1) / kIC_Block, kIntegralChannels, 1), dim3(kIC_Block), 0, ctx->stream, ctx->frames_dev, rows, cols, (const int*)nullptr, (int*)nullptr);
+  hipLaunchKernelGGL(k_integral_cols, dim3((cols + kIC_Block - 1) / kIC_Block, kIntegralChannels, 1), dim3(kIC_Block), 0, ctx->stream, ctx->frames_dev, rows, cols, (const int*)nullptr, (int*)nullptr, 0);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   HIPCHK(ctx, copy_any(out, ctx->frames_host[0].integral, N * kIntegralChannels * 4, ctx->stream), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);

@@ -127,7 +127,19 @@ struct ConvertParams {
   int omSym;                 // storage of the clouds' point information matrices (CloudDev::omSym): 1 = k_stats stores the upper triangle as two 12-byte rows
   int lean;                  // 1 = the front end (k_unproject_integral*) stores neither the points nor the interval image and k_stats recomputes
                              // both from the depth (the same expressions, the same bits): 20 bytes per pixel less written and 18 less read back
+                             // kLeanGrouped (2) = lean, and the integral image of a slot is stored as three interleaved arrays (ig_at) instead of ten planes
 };
+constexpr int kLeanGrouped = 2;
+// Grouped storage of the integral image (ConvertParams::lean == kLeanGrouped: the batch and tracker paths, where the image is a temporary between the
+// front end and k_stats): the slot's 10 N floats hold three arrays [rows][cols] of records instead of ten planes [ch][rows][cols] --
+//   group 0: (x, y, z, n)   group 1: (xx, xy, xz, yy)   group 2: (yz, zz)
+// so channel k is component k % 4 of group k / 4, a producer stores one 16-byte (8-byte) record per pixel and group, and k_stats reads a
+// window corner with three loads instead of ten.  Same bytes, same values.  A slot starts 8-byte aligned (40 N bytes per slot), and so
+// does every group (16 N and 32 N bytes in): the record types carry alignment 8.
+constexpr int kIG_Groups = 3;
+__host__ __device__ constexpr int ig_width(int g) { return g < 2 ? 4 : 2; }
+// float offset, inside a slot, of component 0 of pixel pix (= row * cols + col) in group g
+__host__ __device__ __forceinline__ size_t ig_at(size_t N, int g, size_t pix) { return (size_t)4 * (size_t)g * N + pix * (size_t)ig_width(g); }
 
 struct PairState {
   Mat4 T;          // Aligner::_T
@@ -210,6 +222,9 @@ __device__ __forceinline__ void store4(gptr<v4f> p, const float4 v) { v4f t; t.x
 // tests/test_capi_cpu.py disassembles the library and checks that k_stats / k_unproject_integral contain no dwordx4 store)
 typedef float v3f_raw __attribute__((ext_vector_type(3)));
 typedef v3f_raw v3f __attribute__((aligned(4)));
+// records of the grouped integral image (ig_at): 16 and 8 bytes at 8-byte aligned addresses
+typedef v4f ig4 __attribute__((aligned(8)));
+typedef float ig2 __attribute__((ext_vector_type(2)));
 // point i of a packed xyz array as (x, y, z, 0): one 12-byte load
 __device__ __forceinline__ float4 load_xyz(gptr<const float> p3, unsigned i) { const v3f_raw v = *(gptr<const v3f>)(p3 + 3u * i); return make_float4(v.x, v.y, v.z, 0.f); }
 __device__ __forceinline__ float4 load_xyz(const float* p3, int i) { return load_xyz(as_global(p3), (unsigned)i); }
@@ -629,6 +644,19 @@ __global__ void __launch_bounds__(256) k_unproject_integral_rows(const FrameDesc
   }
   __syncthreads();
   // 3. the row-prefixed planes
+  if (cp.lean == kLeanGrouped) {
+    // grouped storage: the tile's 64 columns of a row are 64 * width consecutive floats of a group (column, component): lanes along them
+    for (int g = 0; g < kIG_Groups; ++g) {
+      const int w = ig_width(g), rowlen = kIR_Cols * w;
+      for (int j = tid; j < kIR_Rows * rowlen; j += 256) {
+        const int lr = j / rowlen, e = j % rowlen;
+        const int lc = e / w, k = e % w;
+        const int r = r0 + lr, c = x0 + lc;
+        if (r < rows && c < cols) f.integral[ig_at(N, g, (size_t)r * cols + c) + k] = tile[((4 * g + k) * kIR_Rows + lr) * kIR_Stride + lc];
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int j = 0; j < kIR_Rows / 4; ++j) {
     const int lr = wave + 4 * j, lc = lane;
@@ -729,7 +757,38 @@ __device__ __forceinline__ void lds_barrier() {
 // band, hand-over words of the current one) and passes the values on through LDS; it never stores to global memory.
 // Plane, index and interval stores are non-temporal (measured: strip kernel -5 %, k_stats after it -4 %).
 constexpr int kII_Threads = 320;
-// Body of the single-pass front end for strip s of frame f (planes [10][rows][cols], read back by k_stats).
+// y pass of one group of the grouped integral image: the thread owns column `lane` of the strip and the W chains of the group's channels
+// ch0 .. ch0 + W - 1, continues them over the band's rows and stores one W-float record per row (a wave store covers 64 W floats in a row).
+// Rows go in batches of kIG_RowBatch: W * kIG_RowBatch values in registers at a time.
+constexpr int kIG_RowBatch = 4;
+static_assert(kIR_Rows % kIG_RowBatch == 0, "row batch");
+template <int W>
+__device__ __forceinline__ void ypass_group(const float* tile, const int ch0, const int lane, float (&vc)[4], const bool incol, const gptr<float> dst,
+                                            const unsigned rowFloats, const int r0, const int rows) {
+#pragma unroll
+  for (int rb = 0; rb < kIR_Rows; rb += kIG_RowBatch) {
+    float vals[kIG_RowBatch][W];
+#pragma unroll
+    for (int r = 0; r < kIG_RowBatch; ++r)
+#pragma unroll
+      for (int k = 0; k < W; ++k) vals[r][k] = tile[((ch0 + k) * kIR_Rows + rb + r) * kIR_Stride + lane];
+#pragma unroll
+    for (int r = 0; r < kIG_RowBatch; ++r)
+#pragma unroll
+      for (int k = 0; k < W; ++k) { vc[k] = vals[r][k] + vc[k]; vals[r][k] = vc[k]; }
+    if (incol) {
+#pragma unroll
+      for (int r = 0; r < kIG_RowBatch; ++r) if (r0 + rb + r < rows) {
+        const gptr<float> q = dst + (unsigned)(rb + r) * rowFloats;
+        if (W == 4) { v4f v; v.x = vals[r][0]; v.y = vals[r][1]; v.z = vals[r][2]; v.w = vals[r][3]; __builtin_nontemporal_store(v, (gptr<ig4>)q); }
+        else { ig2 v; v.x = vals[r][0]; v.y = vals[r][W - 1]; __builtin_nontemporal_store(v, (gptr<ig2>)q); }
+      }
+    }
+  }
+}
+// Body of the single-pass front end for strip s of frame f.  GROUPED = false: planes [10][rows][cols] (lean or not, cp.lean); GROUPED = true:
+// the lean front end with the grouped integral image (ig_at), the form k_stats reads back in the batch and tracker paths.
+template <bool GROUPED>
 __device__ __forceinline__ void unproject_integral_body(const FrameDesc& f, const ConvertParams& cp, const int s, const unsigned epoch, int* __restrict__ fault) {
   const int rows = cp.rows, cols = cp.cols;
   const int S = strips_of(cols), NB = bands_of(rows);
@@ -753,8 +812,8 @@ __device__ __forceinline__ void unproject_integral_body(const FrameDesc& f, cons
   float* const gP3 = f.cloud.P3;
   const gptr<unsigned long long> gcarry = as_global(f.carry);
   const int capacity = f.cloud.capacity;
-  const bool lean = cp.lean != 0;
-  float vcarry[3] = { 0.f, 0.f, 0.f };
+  const bool lean = GROUPED || cp.lean != 0;
+  float vcarry[GROUPED ? 4 : 3] = {};      // y-pass running sums: chains tid + 256 jj (planes), the group's channels (grouped)
   bool starved = false;
 
   // loader: request depth + offsets of band b (all loads unconditional and in flight together; pixels outside the image read
@@ -869,8 +928,15 @@ __device__ __forceinline__ void unproject_integral_body(const FrameDesc& f, cons
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     lds_barrier();
-    // 3. y pass, chain q = (channel = q / 64, column = q % 64)
-    if (!loader) {
+    // 3. y pass.  Grouped: compute wave g owns group g (wave 3 has no chain), 64 columns each; one 16-byte (8-byte) store per row.
+    // Planes: chain q = (channel = q / 64, column = q % 64)
+    if constexpr (GROUPED) {
+      if (wave < kIG_Groups) {
+        const gptr<float> dst = gintegral + ig_at(N, wave, (size_t)r0 * cols + c);
+        if (wave < 2) ypass_group<4>(tile, 4 * wave, lane, vcarry, c < cols, dst, 4u * (unsigned)cols, r0, rows);
+        else ypass_group<2>(tile, 8, lane, vcarry, c < cols, dst, 2u * (unsigned)cols, r0, rows);
+      }
+    } else if (!loader) {
 #pragma unroll
       for (int jj = 0; jj < 3; ++jj) {
         const int q = tid + 256 * jj;
@@ -900,7 +966,17 @@ __global__ void __launch_bounds__(kII_Threads) k_unproject_integral(const FrameD
   const unsigned j = blockIdx.x >> 3;
   const int fi = 8 * (int)(j / (unsigned)S) + (int)(blockIdx.x & 7u), s = (int)(j % (unsigned)S);
   if (fi >= nframes) return;
-  unproject_integral_body(frames[fi], cp, s, epoch, fault);
+  unproject_integral_body<false>(frames[fi], cp, s, epoch, fault);
+}
+// the same launch for ConvertParams::lean == kLeanGrouped: a kernel of its own, because it stores 16-byte records where the kernel above must not hold a
+// 16-byte store (its 12-byte point records: see v3f)
+__global__ void __launch_bounds__(kII_Threads) k_unproject_integral_grouped(const FrameDesc* __restrict__ frames, ConvertParams cp, int nframes,
+                                                                            unsigned epoch, int* __restrict__ fault) {
+  const int S = strips_of(cp.cols);
+  const unsigned j = blockIdx.x >> 3;
+  const int fi = 8 * (int)(j / (unsigned)S) + (int)(blockIdx.x & 7u), s = (int)(j % (unsigned)S);
+  if (fi >= nframes) return;
+  unproject_integral_body<true>(frames[fi], cp, s, epoch, fault);
 }
 // pass 3 (pwn_core/pointintegralimage.cpp:38-43): prefix-sum along image y inside each image column, sequential.
 // one thread per (column, channel) chain, lanes along x.  grid = (ceil(cols/64), 10, frames), block = 64: this kernel only runs on the
@@ -908,13 +984,17 @@ __global__ void __launch_bounds__(kII_Threads) k_unproject_integral(const FrameD
 constexpr int kIC_Block = 64;
 // fault / fault_out: the time-out flag of k_unproject_integral_rows (the launch before this one, complete by now) forwarded to a page-locked
 // host word, so that the host reads it without a copy of its own (fault_out may be nullptr).
-__global__ void __launch_bounds__(kIC_Block) k_integral_cols(const FrameDesc* __restrict__ frames, int rows, int cols, const int* __restrict__ fault,
-                                                             int* __restrict__ fault_out) {
+// grouped (ConvertParams::lean == kLeanGrouped): blockIdx.y is a group instead of a plane and a thread owns one float of the group's row -- (column, component),
+// ig_width(group) * cols chains per group; grid = (ceil(4 * cols / 64), 3, frames).
+__global__ void __launch_bounds__(kIC_Block) k_integral_cols(const FrameDesc* __restrict__ frames, int rows, int cols_, const int* __restrict__ fault,
+                                                             int* __restrict__ fault_out, int grouped) {
   if (fault_out && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *fault_out = *fault;
   const FrameDesc& f = frames[blockIdx.z];
+  const size_t N = (size_t)rows * cols_;
+  const int cols = grouped ? ig_width((int)blockIdx.y) * cols_ : cols_;      // floats per row of the array this thread works in
   const int c = blockIdx.x * kIC_Block + threadIdx.x;
   if (c >= cols) return;
-  float* p = f.integral + (size_t)blockIdx.y * rows * cols + c;
+  float* p = f.integral + (grouped ? ig_at(N, (int)blockIdx.y, 0) : (size_t)blockIdx.y * N) + c;
   float carry = 0.f;
   int r = 0;
   constexpr int U = 16;
@@ -998,18 +1078,37 @@ __device__ __forceinline__ void stats_pixel(const FrameDesc& f, const ConvertPar
     const unsigned oA = (unsigned)(ymax * cols + xmax), oB = (unsigned)(ymin * cols + xmin);
     const unsigned oC = (unsigned)(ymax * cols + xmin), oD = (unsigned)(ymin * cols + xmax);
     float a[kIntegralChannels];
+    // group bases of the grouped storage: scalar; lane offsets: 32-bit bytes
+    const gptr<const char> g0 = (gptr<const char>)gintegral, g1 = (gptr<const char>)(gintegral + ig_at(N, 1, 0)), g2 = (gptr<const char>)(gintegral + ig_at(N, 2, 0));
+    if (cp.lean == kLeanGrouped) {
+      // one record per corner holds (x, y, z, n): four loads decide whether the pixel needs the other eight
+      const v4f A = *(gptr<const ig4>)(g0 + 16u * oA), B = *(gptr<const ig4>)(g0 + 16u * oB);
+      const v4f C = *(gptr<const ig4>)(g0 + 16u * oC), D = *(gptr<const ig4>)(g0 + 16u * oD);
+      a[0] = ((A.x + B.x) - C.x) - D.x; a[1] = ((A.y + B.y) - C.y) - D.y; a[2] = ((A.z + B.z) - C.z) - D.z; a[3] = ((A.w + B.w) - C.w) - D.w;
 #pragma unroll
-    for (int k = 0; k < kIntegralChannels; ++k) {
-      const gptr<const char> pl = (gptr<const char>)(gintegral + (size_t)k * N);      // plane base: scalar; lane offsets: 32-bit bytes
-      float v;
-      v = *(gptr<const float>)(pl + 4u * oA);
-      v = v + *(gptr<const float>)(pl + 4u * oB);
-      v = v - *(gptr<const float>)(pl + 4u * oC);
-      v = v - *(gptr<const float>)(pl + 4u * oD);
-      a[k] = v;
+      for (int k = 4; k < kIntegralChannels; ++k) a[k] = 0.f;
+    } else {
+#pragma unroll
+      for (int k = 0; k < kIntegralChannels; ++k) {
+        const gptr<const char> pl = (gptr<const char>)(gintegral + (size_t)k * N);      // plane base: scalar; lane offsets: 32-bit bytes
+        float v;
+        v = *(gptr<const float>)(pl + 4u * oA);
+        v = v + *(gptr<const float>)(pl + 4u * oB);
+        v = v - *(gptr<const float>)(pl + 4u * oC);
+        v = v - *(gptr<const float>)(pl + 4u * oD);
+        a[k] = v;
+      }
     }
     const int n = (int)a[3];
     if (n >= cp.minPoints) {
+      if (cp.lean == kLeanGrouped) {
+        const v4f A = *(gptr<const ig4>)(g1 + 16u * oA), B = *(gptr<const ig4>)(g1 + 16u * oB);
+        const v4f C = *(gptr<const ig4>)(g1 + 16u * oC), D = *(gptr<const ig4>)(g1 + 16u * oD);
+        const ig2 E = *(gptr<const ig2>)(g2 + 8u * oA), F = *(gptr<const ig2>)(g2 + 8u * oB);
+        const ig2 G = *(gptr<const ig2>)(g2 + 8u * oC), H = *(gptr<const ig2>)(g2 + 8u * oD);
+        a[4] = ((A.x + B.x) - C.x) - D.x; a[5] = ((A.y + B.y) - C.y) - D.y; a[6] = ((A.z + B.z) - C.z) - D.z; a[7] = ((A.w + B.w) - C.w) - D.w;
+        a[8] = ((E.x + F.x) - G.x) - H.x; a[9] = ((E.y + F.y) - G.y) - H.y;
+      }
       npts = n;
       // PointAccumulator::mean / covariance (pointaccumulator.h:66-86)
       float d = a[3];

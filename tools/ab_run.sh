@@ -1,7 +1,8 @@
 #!/bin/bash
-# on the GPU box: bench.py (headline step only) once per library variant in build/variants, two rounds; extra bench args via $AB_ARGS
+# on the GPU box: bench.py (headline step only) once per library variant in build/variants, alternating, $AB_ROUNDS rounds (default 2); extra bench
+# args via $AB_ARGS (later arguments win: AB_ARGS="--steps 20 --warmup 3")
 O=$(mktemp -d); trap 'rm -rf "$O"' EXIT
-for rep in 1 2; do
+for rep in $(seq ${AB_ROUNDS:-2}); do
 for lib in build/variants/*.so; do
   PWN_HIP_LIB=$PWD/$lib timeout -k 10 300 python bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-latency --no-extras $AB_ARGS > $O/b.json 2>$O/b.err || { echo "$lib FAILED"; tail -3 $O/b.err; exit 1; }
   python -c "

@@ -21,8 +21,12 @@ KERNELS = ("k_corr_linearize", "k_stats", "k_unproject_integral", "k_project", "
            "k_match_score", "k_pack_records", "k_probe_read", "k_probe_copy")
 
 
+ALIASES = {"k_unproject_integral_grouped": "k_unproject_integral"}      # the strip kernel of the lean calls (grouped integral image): same table row
+
+
 def short(name):
-    return re.sub(r"^void ", "", re.sub(r"[<(].*", "", name)).replace("pwnhip::", "").strip()
+    n = re.sub(r"^void ", "", re.sub(r"[<(].*", "", name)).replace("pwnhip::", "").strip()
+    return ALIASES.get(n, n)
 
 
 def collect_csv(out):
