@@ -892,7 +892,8 @@ int debug_front_end_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, co
   ConvertJob job;
   if (int rc = convert_prepare<SRC>(ctx, p, frames, depth_scale, n, rows, cols, clouds, 0, lean == 0, slot, direct, job)) return rc;
   if (job.host_input) { if (int rc = convert_stage_frames(ctx, job, 0, n, ctx->stream)) return rc; }
-  if (lean) job.cp.lean = 1;             // integral_out is ten planes, lean or not
+  if (lean == PWN_HIP_FRONT_END_LEAN_PLANES) job.cp.lean = 1;      // ten planes; PWN_HIP_FRONT_END_LEAN_GROUPED keeps convert_prepare's kLeanGrouped and
+                                                                   // integral_out receives the slot as stored (three arrays of records, ig_at)
   // The one thing queued here that a convert call does not queue (there k_stats writes normals and matrices): with lean = 0 the clouds get points
   // only, so their previous normals and matrices are cleared instead of staying readable next to the new points.  Two memsets per cloud ahead of
   // the kernels; the kernels, their grids and their arguments are the convert call's.
@@ -1335,6 +1336,65 @@ int pwn_hip_debug_stats_from_integral(pwn_hip_ctx* ctx, const pwn_hip_converter_
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
 }
+// Test hook: the stats pass of a lean convert call (cp.lean = kLeanGrouped) on caller-supplied windows: the integral image arrives in the grouped
+// form (ig_at: three arrays of records per slot), and k_stats recomputes point and interval of every pixel from the staged depth frame, float or
+// raw, as it does behind the grouped front end.  The clouds give capacity only; k_stats writes their points.
+int pwn_hip_debug_stats_from_integral_lean(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, int rows, int cols, int nframes, const float* integral,
+                                           const int* index_image, const void* const* frames, float depth_scale, pwn_hip_cloud* const* clouds, int keep_stats) {
+  if (!ctx || !p || !integral || !index_image || !frames || !clouds) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (nframes < 1 || nframes > ctx->max_batch) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "nframes must be 1..max_batch");
+  if (depth_scale < 0.f) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "negative depth scale");
+  if (int rc = check_image(ctx, rows, cols)) return rc;
+  if (int rc = absorb_copies(ctx)) return rc;
+  if (int rc = ensure_desc(ctx, nframes)) return rc;
+  const size_t N = (size_t)rows * cols;
+  const bool raw = depth_scale > 0.f;
+  ConvertParams cp = make_convert_params(ctx, p, nullptr, rows, cols, keep_stats);
+  cp.lean = kLeanGrouped;
+  std::vector<int> npoints((size_t)nframes, 0);
+  for (int i = 0; i < nframes; ++i) {
+    pwn_hip_cloud* c = clouds[i];
+    if (!c || !frames[i]) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null frame or cloud");
+    if (i == 0) cp.omSym = c->d.omSym;
+    else if (c->d.omSym != cp.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds of one call must share one omega storage (exact9 / sym6)");
+    const int* idx = index_image + (size_t)i * N;
+    for (size_t k = 0; k < N; ++k) {
+      if (idx[k] >= c->d.capacity) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "index image refers to a point beyond the cloud's capacity");
+      if (idx[k] >= npoints[i]) npoints[i] = idx[k] + 1;
+    }
+  }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  for (int i = 0; i < nframes; ++i) {
+    pwn_hip_cloud* c = clouds[i];
+    cloud_changes(ctx, c);
+    if (keep_stats) { if (int rc = ensure_stats(ctx, c)) return rc; }
+    c->has_stats = keep_stats != 0;
+    c->n_gauss = 0;
+    c->idx_valid = false;
+    drop_omega_n(c);
+    make_omega_n_classes(p, c->d);
+    fill_frame(ctx, i, i, nullptr, c->d);
+    FrameDesc& f = ctx->frames_host[i];
+    if (raw) {
+      uint16_t* staged = ctx->raw_ws + (size_t)i * ctx->N;
+      HIPCHK(ctx, hipMemcpyAsync(staged, frames[i], N * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+      f.raw = staged; f.raw_scale = depth_scale;
+    } else {
+      float* staged = ctx->depth_ws + (size_t)i * ctx->N;
+      HIPCHK(ctx, hipMemcpyAsync(staged, frames[i], N * sizeof(float), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+      f.depth = staged;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(f.index, index_image + (size_t)i * N, N * sizeof(int), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+    HIPCHK(ctx, hipMemcpyAsync(f.integral, integral + (size_t)i * N * kIntegralChannels, N * kIntegralChannels * sizeof(float), hipMemcpyHostToDevice,
+                               ctx->stream), PWN_HIP_ERR_COPY);
+  }
+  HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev, ctx->frames_host, sizeof(FrameDesc) * nframes, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+  launch_stats(cp, ctx->frames_dev, nframes, ctx->stream);      // launch_convert's grid
+  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  for (int i = 0; i < nframes; ++i) clouds[i]->n_host = npoints[i];
+  return PWN_HIP_OK;
+}
 // Test hook: the front end of a convert call (launch_front_end, the function launch_convert itself calls) on the caller's frames, the path chosen
 // by the caller instead of by the frame count, and everything it wrote handed back: planes, index images, offsets, and with lean = 0 the
 // interval images and (in the clouds) the points.  k_stats is not launched.
@@ -1343,6 +1403,8 @@ int pwn_hip_debug_front_end(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p,
   if (!ctx || !p || !frames || !clouds || !integral_out || !index_out || !rowoff_out) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (nframes < 1 || nframes > ctx->max_batch) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "nframes must be 1..max_batch");
   if (path != PWN_HIP_FRONT_END_LATENCY && path != PWN_HIP_FRONT_END_SINGLE_PASS) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "path must be 0 (latency) or 1 (single pass)");
+  if (lean != PWN_HIP_FRONT_END_LEAN_OFF && lean != PWN_HIP_FRONT_END_LEAN_PLANES && lean != PWN_HIP_FRONT_END_LEAN_GROUPED)
+    return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "lean must be 0 (off), 1 (ten planes) or 2 (grouped records)");
   if (lean ? interval_out != nullptr : interval_out == nullptr)
     return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, lean ? "a lean front end writes no interval image (and no points): interval_out must be null" : "null argument");
   if (depth_scale < 0.f) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "negative depth scale");

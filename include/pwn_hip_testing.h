@@ -41,6 +41,16 @@ int pwn_hip_debug_projection_fallbacks(pwn_hip_ctx* ctx, int* calls);
  * 1 <= nframes <= max_batch; from 8 frames on the kernel takes its XCD-aware placement, as in a convert call. */
 int pwn_hip_debug_stats_from_integral(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, int rows, int cols, int nframes, const float* integral,
                                       const int* index_image, const int* interval_image, pwn_hip_cloud* const* clouds, int keep_stats);
+/* The same pass as a lean convert call runs it (the batch calls, the tracker, the fused step): the integral image in the grouped form and
+ * no interval image and no points -- the kernel recomputes both from the depth frame.  integral = nframes x 10 N floats, N = rows * cols of
+ * this call (not of the context), per frame three arrays of records: (x y z n) at float 0, (xx xy xz yy) at float 4 N, (yz zz) at float 8 N,
+ * one record per pixel in each array, pixels in row-major order.  frames[i] = rows x cols host image, float32 metres (depth_scale == 0) or
+ * uint16 raw values (depth_scale > 0: metres = depth_scale * raw, raw 0 = 0 metres), as pwn_hip_debug_front_end takes them.  A pixel with
+ * index >= 0 must hold a depth the front end would have accepted: the kernel does not repeat the range test.  The clouds need capacity only
+ * (every index < capacity, else the call is refused); afterwards cloud i reports max(index image i) + 1 points, written by the kernel. */
+int pwn_hip_debug_stats_from_integral_lean(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, int rows, int cols, int nframes, const float* integral,
+                                           const int* index_image, const void* const* frames, float depth_scale, pwn_hip_cloud* const* clouds,
+                                           int keep_stats);
 /* The converter's front end (everything a convert call launches before its stats pass) on the caller's frames, and what it wrote:
  * frames[i] = rows x cols float32 metres (depth_scale == 0) or uint16 raw values (depth_scale > 0: metres = depth_scale * raw), host or device
  * pointers, all of one kind.  path chooses the launch sequence whatever nframes is: PWN_HIP_FRONT_END_LATENCY (k_row_count, k_row_offsets,
@@ -49,10 +59,16 @@ int pwn_hip_debug_stats_from_integral(pwn_hip_ctx* ctx, const pwn_hip_converter_
  * kernel by width and pointer alignment and its hand-over epoch; the stats pass is not launched.  1 <= nframes <= max_batch (frame i uses
  * workspace slot i).  Per frame: integral_out nframes x [10][rows][cols], index_out nframes x [rows][cols], rowoff_out nframes x [rows]
  * (latency: first point index of every row) or nframes x [rows][strips of 64 columns] (single pass: of every (row, strip)).  lean = 0: the
- * interval images go to interval_out and clouds[i] holds the points (normals, curvature and matrices zero).  lean = 1, the setting of a batch
- * call: the front end stores neither; interval_out must be NULL and the clouds hold 0 points afterwards.  A hand-over time-out returns
- * PWN_HIP_ERR_LAUNCH with a convert call's message (the call is not repeated). */
+ * interval images go to interval_out and clouds[i] holds the points (normals, curvature and matrices zero).  lean = 1: the front end stores
+ * neither; interval_out must be NULL and the clouds hold 0 points afterwards; the planes are written as with lean = 0 (a configuration no
+ * shipped call uses any more: it exists for the tests).  lean = 2 (PWN_HIP_FRONT_END_LEAN_GROUPED), the setting of every lean convert call:
+ * as lean = 1, but the launches are the grouped ones (k_unproject_integral_grouped; the grouped write-out of k_unproject_integral_rows and the
+ * grouped mode of k_integral_cols) and integral_out receives each frame's 10 N floats as the slot stores them, nothing rearranged, N = rows *
+ * cols of this call (not of the context): three arrays of records, (x y z n) at float 0, (xx xy xz yy) at float 4 N, (yz zz) at float 8 N,
+ * one record per pixel in each array, pixels in row-major order.  Any other value of lean is refused and the outputs stay untouched.  A
+ * hand-over time-out returns PWN_HIP_ERR_LAUNCH with a convert call's message (the call is not repeated). */
 enum { PWN_HIP_FRONT_END_LATENCY = 0, PWN_HIP_FRONT_END_SINGLE_PASS = 1 };
+enum { PWN_HIP_FRONT_END_LEAN_OFF = 0, PWN_HIP_FRONT_END_LEAN_PLANES = 1, PWN_HIP_FRONT_END_LEAN_GROUPED = 2 };
 int pwn_hip_debug_front_end(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const void* const* frames, float depth_scale, int nframes, int rows,
                             int cols, int path, int lean, pwn_hip_cloud* const* clouds, float* integral_out, int* index_out, int* interval_out,
                             int* rowoff_out);

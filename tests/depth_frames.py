@@ -325,9 +325,47 @@ def reference(O, batch):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ grouped storage of the integral image
+# Written from the sentence in include/pwn_hip_testing.h, not from the library: a frame's 10 N floats (N = rows * cols of the call) are three
+# arrays of records -- (x y z n) at float 0, (xx xy xz yy) at float 4 N, (yz zz) at float 8 N -- one record per pixel in each array, pixels in
+# row-major order.  Channel ch of the ten planes is therefore component ch % 4 of the record array ch // 4.
+GROUPS = ((0, 4), (4, 4), (8, 2))        # (first channel, floats per record) of the three arrays
+LEAN_GROUPED = 2                         # PWN_HIP_FRONT_END_LEAN_GROUPED
+
+
+def _group_positions(N, g):
+    """float positions [N][width] of the records of array g inside a frame's 10 N floats"""
+    width = GROUPS[g][1]
+    return 4 * g * N + np.arange(N)[:, None] * width + np.arange(width)[None, :]
+
+
+def planes_to_grouped(planes):
+    """[..., 10, rows, cols] planes -> [..., 10 * rows * cols] floats in the grouped form (any N, odd ones included)"""
+    planes = np.asarray(planes, F32)
+    lead, N = planes.shape[:-3], planes.shape[-2] * planes.shape[-1]
+    flat = planes.reshape(lead + (10, N))
+    out = np.empty(lead + (10 * N,), F32)
+    for g, (first, width) in enumerate(GROUPS):
+        out[..., _group_positions(N, g)] = np.moveaxis(flat[..., first:first + width, :], -2, -1)
+    return out
+
+
+def grouped_to_planes(buf, rows, cols):
+    """the inverse: [..., 10 * rows * cols] floats in the grouped form -> [..., 10, rows, cols] planes"""
+    buf = np.asarray(buf, F32)
+    N = rows * cols
+    lead = buf.shape[:-1]
+    assert buf.shape[-1] == 10 * N
+    out = np.empty(lead + (10, N), F32)
+    for g, (first, width) in enumerate(GROUPS):
+        out[..., first:first + width, :] = np.moveaxis(buf[..., _group_positions(N, g)], -1, -2)
+    return out.reshape(lead + (10, rows, cols))
+
+
 def run_gpu(ctx, p, batch, frames, path, lean, device_offset=None):
-    """one pwn_hip_debug_front_end call on the given frames of the batch.  device_offset: None = host frames; k = the frames in device memory,
-    each k elements behind a 256-byte boundary"""
+    """one pwn_hip_debug_front_end call on the given frames of the batch.  lean = 0, 1 or 2 as the hook takes it; with 2 the integral image comes
+    back in the grouped form and is handed on as planes (grouped_to_planes).  device_offset: None = host frames; k = the frames in device
+    memory, each k elements behind a 256-byte boundary"""
     from g2o_frontend_amd import api
     n, rows, cols = len(frames), batch.rows, batch.cols
     N = rows * cols
@@ -350,8 +388,10 @@ def run_gpu(ctx, p, batch, frames, path, lean, device_offset=None):
     rowoff = np.full((n, noff), -7, np.int32)
     interval = None if lean else np.full((n, rows, cols), -7, np.int32)
     vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)      # noqa: E731
-    ctx.check(ctx._L.pwn_hip_debug_front_end(ctx.h, C.addressof(p), (C.c_void_p * n)(*ptrs), batch.scale, n, rows, cols, path, 1 if lean else 0,
+    ctx.check(ctx._L.pwn_hip_debug_front_end(ctx.h, C.addressof(p), (C.c_void_p * n)(*ptrs), batch.scale, n, rows, cols, path, int(lean),
                                              (C.c_void_p * n)(*[c.h.value for c in clouds]), vp(integral), vp(index), vp(interval), vp(rowoff)))
+    if lean == LEAN_GROUPED:
+        integral = grouped_to_planes(integral.reshape(n, 10 * N), rows, cols)
     sizes = [c.size() for c in clouds]
     points = None if lean else [c.arrays()["points"] for c in clouds]
     if keep is not None:
@@ -366,7 +406,8 @@ def same_bits(a, b):
 
 
 def compare(batch, frames, ref, got, path, lean):
-    """every output of a front-end call against the oracle's; returns {field: number of differing elements}"""
+    """every output of a front-end call against the oracle's (lean = 2 as lean = 1: neither stores points or intervals); returns {field: number
+    of differing elements}"""
     und = batch.undefined_mask()
     bad = dict(index=0, rowoff=0, planes=0, interval=0, points=0)
     for j, i in enumerate(frames):

@@ -12,6 +12,9 @@ matrix reaches the eigensolver directly.  The "combine" family writes all four c
 
 Dense layouts: "B" the 2-D float32 prefix sums of random points, "R" raw random planes; windows at every pixel, radii 1..60 from the interval
 image clamped at the image border, so corners are shared and clamped.
+
+Lean frames (see "lean frames" below): the same layouts with a depth image under them, for the grouped, lean form of the pass
+(pwn_hip_debug_stats_from_integral_lean): the interval image and the points are the oracle's, derived from that depth.
 """
 from __future__ import annotations
 
@@ -99,7 +102,9 @@ class Frame:
         self.windows = 0           # probes / pixels read by the stats pass (index >= 0 or not)
 
 
-def layout_a(rng, rows, cols, thresholds=(0.2, 0.02, 0.05)):
+def layout_a(rng, rows, cols, thresholds=(0.2, 0.02, 0.05), flip_col=None):
+    """flip_col: None = the flip_zero family is dealt like the others; a probe column = the family is exactly that column's probes (the lean
+    frames, whose points come from the depth: one column where the unprojected x is zero)"""
     fr = Frame(rows, cols)
     ri, ci = np.arange(2, rows, 3), np.arange(2, cols, 3)
     R, Cc = np.meshgrid(ri, ci, indexing="ij")
@@ -108,8 +113,14 @@ def layout_a(rng, rows, cols, thresholds=(0.2, 0.02, 0.05)):
     fr.windows = m
     order = rng.permutation(m)
     fam = np.full(m, "distinct", object)
+    if flip_col is not None:
+        assert flip_col in ci
+        fam[Cc == flip_col] = "flip_zero"
+        order = order[Cc[order] != flip_col]
     start = 0
     for name, frac in FAMILIES.items():
+        if flip_col is not None and name == "flip_zero":
+            continue
         k = max(1, int(round(frac * m)))
         fam[order[start:start + k]] = name
         start += k
@@ -225,6 +236,177 @@ def make_frames(seed, rows, cols, nframes, layouts):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ lean frames
+# A lean frame is a Frame plus a depth image: what k_stats sees behind the grouped front end, where neither points nor intervals are stored and
+# the kernel recomputes both from the depth.  The interval image and the points of a lean frame are the ORACLE's, derived from that depth
+# (lean_frame); the generator only chooses depths that make them what the layouts need.
+#
+# Camera and range.  fx = fy = 512 (a power of two) with the integer principal point (128, 47): in probe column 128 the unprojected x is
+# (c d) / 512 - (128 / 512) d = 0 exactly (held to the oracle by the CPU test, not assumed).  world_radius 0.01 makes the interval int(5.12 / d):
+# 0 beyond 5.12 m, 1 from 2.56 m, 79 at 64 mm -- all of it within uint16 millimetres.  k_stats does not repeat the front end's range test (a
+# pixel with a point has passed it), so the range is opened to everything the generator injects, negative depths included: oracle and kernel
+# then evaluate the same expression at every pixel, and what remains undefined is the float-to-int conversion of an infinite quotient
+# (depth +0 / -0), which LeanFrame.undefined marks.
+LEAN_K = (512.0, 512.0, 128.0, 47.0)
+LEAN_FLIP_COL = 128
+LEAN_CAMERA = dict(K=LEAN_K, world_radius=0.01, min_distance=-3.0e38, max_distance=3.0e38)
+LEAN_RAW_SCALE = 0.001
+LEAN_IV = 512.0 * float(F32(0.01))          # pixels of the world radius at unit depth, both axes (restated: the CPU test checks it with the oracle)
+
+
+# (rows, cols, frames, layouts dealt round-robin, omega storage, sensor offset, raw depth, context).  Every setting is ONE launch.  97 x 300: an
+# even N and two x-blocks per row; 61 x 257: an odd N, so that in a context of exactly 61 x 257 every second slot (40 N bytes each) starts 8 bytes
+# off a 16-byte boundary; "vga": the 97 x 300 call runs in a 480 x 640 context, where the group bases 4 N and 8 N lie inside a larger slot.  1 and
+# 7 frames take the frame-major placement, 8 and 13 the XCD-aware one (13: a ragged last group).  The frame counts of the layout-A frames are
+# what the coverage floor needs at each shape (test_stats_windows_cpu.py holds the generator to it on the CPU).
+LEAN_SETTINGS = [(97, 300, 1, ["B"], "exact9", False, False, "own"),
+                 (97, 300, 7, ["A", "B", "A", "R", "A", "A", "A"], "sym6", True, False, "own"),
+                 (61, 257, 8, ["A", "A", "A", "B", "A", "A", "R", "A"], "sym6", False, True, "own"),
+                 (61, 257, 13, ["A", "A", "A", "B", "A", "A", "A", "R", "A", "A", "A", "A", "A"], "exact9", True, False, "own"),
+                 (97, 300, 13, ["A", "R", "B", "A", "A", "A", "R", "A", "B", "A", "A", "A", "A"], "sym6", True, True, "vga"),
+                 (97, 300, 8, ["A", "A", "B", "A", "R", "A", "A", "A"], "exact9", False, True, "own")]
+MIN_BRANCH = 50      # windows per eig3_direct branch / edge, per setting with layout-A frames (test_gpu_stats_windows.MIN_BRANCH)
+COVERED = ("isotropic", "double_root", "scale_zero", "q_clamped", "half_b_zero", "denormal_cov", "ev0_clamped", "near_threshold", "flip_zero",
+           "n_below", "n_at", "n_above", "itv_neg", "idx_neg")
+
+
+def lean_covered(raw):
+    """the entries of COVERED a setting can meet: a raw frame has no negative depth, so its itv_neg probes hold raw 0 -- an undefined
+    conversion, masked -- and the negative interval is left to the float settings"""
+    return tuple(k for k in COVERED if not (raw and k == "itv_neg"))
+
+
+def lean_params(O, offset=False):
+    return O.converter_params(sensor_offset=SENSOR_OFFSET if offset else None, **dict(CONV, **LEAN_CAMERA))
+
+
+def lean_quotient(depth):
+    """projectInterval before its truncation, in numpy fp32: the larger of ivx * (1 / d) and ivy * (1 / d)"""
+    iv = F32(512.0) * F32(0.01)
+    with np.errstate(all="ignore"):
+        inv = F32(1.0) / np.asarray(depth, F32)
+        px, py = iv * inv, iv * inv
+        return np.where(px > py, px, py).astype(F32)
+
+
+def _depth_for_interval(rng, t, raw):
+    """depths (metres, float64) whose interval int(iv / d) is t: t >= 1 -> iv / (t + u), u in [0.25, 0.75]; 0 -> beyond iv; t < 0 -> -iv / (|t| + u)"""
+    t = np.asarray(t)
+    u = rng.uniform(0.25, 0.75, t.shape)
+    far = LEAN_IV * rng.uniform(1.05, 12.0 if raw else 40.0, t.shape)
+    with np.errstate(divide="ignore"):
+        return np.where(t > 0, LEAN_IV / (t + u), np.where(t == 0, far, -LEAN_IV / (np.abs(t) + u)))
+
+
+def lean_frame(O, p, fr, rng, raw, dense):
+    """Turns a Frame of layout_a(flip_col=LEAN_FLIP_COL) / layout_b into a lean one: chooses the depth image, then replaces fr.interval by
+    oracle.project_intervals of it and fr.points by the oracle's per-pixel unprojection gathered by fr.index.  Adds fr.depth (float32 metres, as
+    both implementations see it), fr.raw (the uint16 image, or None), fr.placed_undefined (where the generator put a zero depth under a point)
+    and fr.undefined (where the quotient does not fit an int)."""
+    rows, cols = fr.rows, fr.cols
+    has = fr.index >= 0
+    want = fr.interval.copy()                            # what the layout drew: 0 / 1 and negatives (A), -3 .. 79 (dense)
+    placed = np.zeros((rows, cols), bool)
+    if dense:
+        if raw:
+            want = np.abs(want)                          # uint16 holds no negative depth
+        # both clamps and (float) the skip at all four borders, whatever the draw gave there
+        for sel in (np.s_[0, :], np.s_[rows - 1, :], np.s_[:, 0], np.s_[:, cols - 1]):
+            at = np.flatnonzero(has[sel])
+            pick = rng.choice(at, 6, replace=False)
+            want[sel][pick] = [0, 0, 70, 75, 2 if raw else -2, 3 if raw else -3]
+        d = _depth_for_interval(rng, want, raw)
+    else:
+        d = _depth_for_interval(rng, np.where(has | (want != 0), want, rng.integers(0, 2, want.shape)), raw)
+        fam_img = np.full((rows, cols), "", object)
+        rr, cc = np.nonzero(has)
+        fam_img[rr, cc] = fr.family[fr.index[rr, cc]]
+        neg = has & (fam_img == "itv_neg")
+        if raw:                                           # no negative raw value: these probes get raw 0, an undefined conversion
+            d[neg] = 0.0; placed |= neg
+        fz = np.flatnonzero((has & (fam_img == "flip_zero")).ravel())
+        assert len(fz) and (fz % cols == LEAN_FLIP_COL).all()
+        fz = rng.permutation(fz)
+        k = max(1, len(fz) // 5)                          # a fifth +0, a fifth -0.0 (raw: +0 both), the rest positive
+        d.ravel()[fz[:k]] = 0.0; d.ravel()[fz[k:2 * k]] = 0.0 if raw else -0.0
+        placed.ravel()[fz[:2 * k]] = True
+    if raw:
+        counts = np.round(d / LEAN_RAW_SCALE)
+        counts = np.where((counts < 1) & ~placed, 1, counts)              # raw 0 only where it was placed
+        fr.raw = np.clip(counts, 0, 65535).astype(np.uint16)
+        fr.depth = O.convert_16u_to_32f(fr.raw, LEAN_RAW_SCALE)
+    else:
+        fr.raw = None
+        fr.depth = d.astype(F32)
+    fr.placed_undefined = placed
+    with np.errstate(invalid="ignore"):
+        fr.undefined = has & ~(np.abs(lean_quotient(fr.depth)) < F32(2.0 ** 31))
+    fr.interval = O.project_intervals(p, fr.depth)
+    every, all_idx = O.unproject(p, fr.depth)            # the range is open: every pixel unprojects, point r * cols + c belongs to pixel (r, c)
+    assert len(every) == rows * cols and np.array_equal(all_idx.ravel(), np.arange(rows * cols))
+    pts = np.zeros((len(fr.points), 4), F32)
+    pts[fr.index[has]] = every.reshape(rows, cols, 4)[has]
+    fr.points = pts
+    return fr
+
+
+def make_lean_frames(O, seed, rows, cols, nframes, layouts, raw, offset=False):
+    p = lean_params(O, offset)
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(nframes):
+        lay = layouts[i % len(layouts)]
+        fr = layout_a(rng, rows, cols, flip_col=LEAN_FLIP_COL) if lay == "A" else layout_b(rng, rows, cols, raw=(lay == "R"))
+        out.append(lean_frame(O, p, fr, rng, raw, dense=(lay != "A")))
+    return out
+
+
+def undefined_points(fr):
+    """per point of the frame: its pixel's float-to-int conversion is undefined"""
+    m = np.zeros(len(fr.points), bool)
+    m[fr.index[fr.undefined]] = True
+    return m
+
+
+def without_points(fr, arrays, drop):
+    """the frame and an implementation's arrays without the points `drop` marks (their pixels lose their index, the others are renumbered)"""
+    keep = ~drop
+    new = np.full(len(keep), -1, np.int32); new[keep] = np.arange(keep.sum(), dtype=np.int32)
+    out = Frame(fr.rows, fr.cols)
+    out.planes, out.interval, out.windows = fr.planes, fr.interval, fr.windows
+    out.index = np.where(fr.index >= 0, new[np.maximum(fr.index, 0)], -1).astype(np.int32)
+    out.points, out.family = fr.points[keep], fr.family[keep]
+    return out, {k: v[keep] for k, v in arrays.items()}
+
+
+def is_layout_a(fr):
+    return fr.family.size == 0 or fr.family[0] not in ("dense", "dense_raw")
+
+
+def coverage(O, fr, a, conv=CONV):
+    """windows of a layout-A frame per eig3_direct branch / edge (test_gpu_stats_windows.COVERED), from the frame and one implementation's
+    arrays `a`; pixels of an undefined conversion (lean frames) are not counted"""
+    und = undefined_points(fr) if hasattr(fr, "undefined") else np.zeros(len(fr.points), bool)
+    n, has, mean, cov = window_cov(fr, conv)
+    has = has & ~und
+    br = eig_branches(O, cov[has])
+    cover = {k: int(br[k].sum()) for k in ("isotropic", "double_root", "scale_zero", "q_clamped", "half_b_zero", "denormal_cov", "ev0_clamped")}
+    assert (a["eigenvalues"][has][br["ev0_clamped"], 0] == 0).all(), "a negative smallest eigenvalue was not clamped to 0"
+    cover["near_threshold"] = 0
+    for key in THRESHOLDS:
+        t = F32(conv[key])
+        cover["near_threshold"] += int((has & (np.abs(a["curvature"].view(np.int32) - t.view(np.int32)) <= 4)).sum())
+    cover["flip_zero"] = int((has & (fr.family == "flip_zero") & (np.abs(a["normals"][:, :3]).sum(1) > 0)).sum())
+    ne = (fr.family == "n_edge") & ~und
+    cnt = fr.planes[3][fr.index >= 0][np.argsort(fr.index[fr.index >= 0])]
+    for name, v in (("n_below", 49), ("n_at", 50), ("n_above", 51)):
+        cover[name] = int((ne & (cnt == v)).sum())
+    und_img = fr.undefined if hasattr(fr, "undefined") else np.zeros(fr.index.shape, bool)
+    cover["itv_neg"] = int(((fr.interval < 0) & (fr.index >= 0) & ~und_img).sum())
+    cover["idx_neg"] = fr.windows - len(fr.points)
+    return cover
+
+
 # ------------------------------------------------------------------------------------------------ the two implementations
 def run_oracle(O, p, fr):
     c = O.stats_from_integral(p, fr.planes, fr.index, fr.interval, fr.points)
@@ -249,6 +431,29 @@ def run_gpu(ctx, p, frames, omega="exact9", keep_stats=True):
     arr = (C.c_void_p * len(clouds))(*[c.h.value for c in clouds])
     ctx.check(ctx._L.pwn_hip_debug_stats_from_integral(ctx.h, C.addressof(p), rows, cols, len(frames), planes.ctypes.data_as(C.c_void_p),
                                                        idx.ctypes.data_as(C.c_void_p), itv.ctypes.data_as(C.c_void_p), arr, int(keep_stats)))
+    return [c.arrays(stats=keep_stats) for c in clouds], clouds
+
+
+def run_gpu_lean(ctx, p, frames, omega="exact9", keep_stats=True):
+    """all lean frames in one call of pwn_hip_debug_stats_from_integral_lean (one k_stats launch with cp.lean = kLeanGrouped): the planes in the
+    grouped form, the depth frames float or raw; the clouds give capacity only"""
+    from depth_frames import planes_to_grouped
+    from g2o_frontend_amd import api
+    rows, cols = frames[0].rows, frames[0].cols
+    raw = frames[0].raw is not None
+    assert all((f.raw is not None) == raw for f in frames), "the frames of a call are all float or all raw"
+    ctx.set_omega_storage(omega)
+    clouds = [api.Cloud(ctx, max(1, len(fr.points))) for fr in frames]
+    grouped = np.ascontiguousarray(np.stack([planes_to_grouped(f.planes) for f in frames]))
+    idx = np.ascontiguousarray(np.stack([f.index for f in frames]))
+    src = [np.ascontiguousarray(f.raw if raw else f.depth) for f in frames]
+    assert src[0].dtype == (np.uint16 if raw else F32)
+    arr = (C.c_void_p * len(clouds))(*[c.h.value for c in clouds])
+    ptrs = (C.c_void_p * len(src))(*[a.ctypes.data for a in src])
+    ctx.check(ctx._L.pwn_hip_debug_stats_from_integral_lean(ctx.h, C.addressof(p), rows, cols, len(frames), grouped.ctypes.data_as(C.c_void_p),
+                                                            idx.ctypes.data_as(C.c_void_p), ptrs, LEAN_RAW_SCALE if raw else 0.0, arr, int(keep_stats)))
+    for c, fr in zip(clouds, frames):
+        assert c.size() == int(fr.index.max()) + 1 == len(fr.points)
     return [c.arrays(stats=keep_stats) for c in clouds], clouds
 
 
@@ -332,9 +537,16 @@ def bits_equal(a, b):
     return (a.view(np.uint32) == b.view(np.uint32)) | ((a == 0) & (b == 0)) | (np.isnan(a) & np.isnan(b))
 
 
-def compare_to_oracle(o, g, sym6=False):
-    """every output field of a frame; returns {field: number of differing points}"""
+def compare_to_oracle(o, g, sym6=False, skip=None):
+    """every output field of a frame; returns {field: number of differing points}.  skip: points left out of every field but the points
+    themselves (lean frames: the pixels of an undefined float-to-int conversion, whose window the two sides choose differently)"""
     bad = {}
+    if skip is not None and skip.any():
+        bad_pts = int((~bits_equal(o["points"], g["points"])).any(1).sum())
+        keep = ~skip
+        bad = compare_to_oracle({k: v[keep] for k, v in o.items()}, {k: v[keep] for k, v in g.items()}, sym6)
+        bad["points"] = bad_pts
+        return bad
     for k in ("points", "normals", "curvature", "omega_n", "eigenvalues"):
         bad[k] = int((~bits_equal(o[k].reshape(len(o[k]), -1), g[k].reshape(len(g[k]), -1))).any(1).sum())
     bad["npoints"] = int((o["npoints"] != g["npoints"]).sum())

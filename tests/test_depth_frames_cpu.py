@@ -224,3 +224,38 @@ def test_oracle_planes_against_float64(batches):
             worst[b.kinds[i]] = max(worst.get(b.kinds[i], 0.0), ratio)
             assert ratio <= 1.0, (b.rows, b.cols, b.kind, i, ratio)
     print("worst |plane - sum64| / (gamma_n sum|term|) per frame kind:", {k: round(v, 4) for k, v in sorted(worst.items())})
+
+
+# ------------------------------------------------------------------------------------------------ the grouped layout, stated a second time
+@pytest.mark.parametrize("shape", [(1, 1), (3, 5), (7, 9), (4, 6), (61, 257)])
+def test_grouped_layout_round_trip(shape):
+    """planes -> grouped -> planes gives the planes back, bit for bit, for odd and even N and with leading frame dimensions"""
+    rng = np.random.default_rng(3)
+    rows, cols = shape
+    planes = rng.standard_normal((2, 3, 10, rows, cols)).astype(F32)
+    planes[0, 0, 3, 0, 0] = np.nan; planes[1, 2, 9, -1, -1] = -0.0
+    buf = D.planes_to_grouped(planes)
+    assert buf.shape == (2, 3, 10 * rows * cols)
+    back = D.grouped_to_planes(buf, rows, cols)
+    assert back.shape == planes.shape and np.array_equal(back.view(np.uint32), planes.view(np.uint32))
+    one = D.planes_to_grouped(planes[1, 2])
+    assert np.array_equal(one.view(np.uint32), buf[1, 2].view(np.uint32))
+    assert np.array_equal(D.grouped_to_planes(one, rows, cols).view(np.uint32), planes[1, 2].view(np.uint32))
+
+
+@pytest.mark.parametrize("shape", [(1, 1), (3, 5), (7, 9), (4, 6)])
+def test_grouped_layout_puts_every_element_where_the_header_says(shape):
+    """the value 1000 * ch + pix lands at float 4 * (ch // 4) * N + pix * width + ch % 4, width = 4, 4, 2 floats per record of the three arrays:
+    (x y z n) at float 0, (xx xy xz yy) at float 4 N, (yz zz) at float 8 N (include/pwn_hip_testing.h)"""
+    rows, cols = shape
+    N = rows * cols
+    ch, pix = np.meshgrid(np.arange(10), np.arange(N), indexing="ij")
+    buf = D.planes_to_grouped((1000 * ch + pix).astype(F32).reshape(10, rows, cols))
+    seen = np.zeros(10 * N, bool)
+    for c in range(10):
+        width = (4, 4, 2)[c // 4]
+        for q in range(N):
+            at = 4 * (c // 4) * N + q * width + c % 4
+            assert buf[at] == 1000 * c + q, (c, q, at, buf[at])
+            seen[at] = True
+    assert seen.all(), "the ten channels of N pixels fill the 10 N floats exactly"

@@ -1,7 +1,9 @@
 """The converter's front end as shipped (k_row_count / k_strip_count<RAW> / k_strip_count_any, k_row_offsets, k_unproject_integral_rows +
 k_integral_cols, k_unproject_integral) through pwn_hip_debug_front_end on the injected frames of tests/depth_frames.py: everything it writes
 -- index image, offsets, the ten integral planes, with lean = 0 the points and the interval image -- against the oracle bit for bit, the planes
-against float64, stale hand-over words across calls of different shapes and paths, and the same frames through the public convert calls."""
+against float64, stale hand-over words across calls of different shapes and paths, and the same frames through the public convert calls.  With
+lean = 2 the same through the grouped kernels every lean convert call launches (k_unproject_integral_grouped, the grouped write-out of
+k_unproject_integral_rows, the grouped mode of k_integral_cols)."""
 import numpy as np
 import pytest
 
@@ -144,6 +146,97 @@ def test_frame_pointer_alignment_chooses_the_counting_kernel(ctx, made, kind):
             assert np.array_equal(outs[0][key], o[key]), key
         assert D.same_bits(outs[0]["planes"], o["planes"]).all()
     run_and_compare(ctx, b, ref, p, frames[:3], D.LATENCY, 0, 1)
+
+
+# ------------------------------------------------------------------------------------------------ the grouped form (lean = 2)
+# What every lean convert call launches: k_unproject_integral_grouped on the single-pass path, the grouped write-out of k_unproject_integral_rows
+# and the grouped mode of k_integral_cols on the latency path.  The hook hands the slot back as stored; depth_frames.grouped_to_planes (the
+# layout stated a second time, from the header's sentence) turns it into planes for the oracle.
+G = D.LEAN_GROUPED
+
+
+def _grouped_counts(case):
+    return D.SINGLE_PASS_COUNTS[(case + 6) % len(D.SINGLE_PASS_COUNTS)], D.LATENCY_COUNTS[(case // 2 + 2) % len(D.LATENCY_COUNTS)]
+
+
+assert {1, 7, 8, 9, 16, 17, 25} <= {_grouped_counts(c)[0] for c in range(len(PLAN))} and {1, 3, 15, 16} == {_grouped_counts(c)[1] for c in range(len(PLAN))}
+
+
+@pytest.mark.parametrize("case", range(len(PLAN)), ids=[f"{r}x{c}-{k}-{cf}" for r, c, k, cf in PLAN])
+def test_front_end_grouped_bit_exact_against_oracle(ctx, made, case):
+    """every shape x element type, both paths, lean = 2: index image, offsets and the planes read out of the grouped records against the oracle bit
+    for bit, the stage counters those of a convert call.  Frame counts and windows move with the case; over the plan the single-pass path meets
+    1, 7, 8, 9, 16, 17, 24 and 25 frames, the latency path 1, 3, 15 and 16."""
+    rows, cols, kind, _ = PLAN[case]
+    b, ref, p = made(rows, cols, kind)
+    n_sp, n_lat = _grouped_counts(case)
+    run_and_compare(ctx, b, ref, p, window(n_sp, 7 * case + 22), D.SINGLE_PASS, G)
+    run_and_compare(ctx, b, ref, p, window(n_lat, 5 * case + 29), D.LATENCY, G)
+
+
+def test_grouped_planes_against_float64(ctx, made):
+    """no oracle in the comparison: the planes read out of the grouped records against float64 sums of the fp32 terms of the device's own points
+    and index image (from a lean = 0 call on the same frames: a grouped call stores no points), within gamma_n * sum |term|, n = r + c + 1"""
+    worst = 0.0
+    for rows, cols, kind in ((129, 513, "float"), (1025, 65, "raw")):
+        b, _, p = made(rows, cols, kind)
+        for path, frames in ((D.SINGLE_PASS, window(16, 0)), (D.LATENCY, window(9, 16))):
+            full = D.run_gpu(ctx, p, b, frames, path, 0)
+            got = D.run_gpu(ctx, p, b, frames, path, G)
+            assert np.array_equal(full["index"], got["index"])
+            for j in range(len(frames)):
+                ratio = D.float64_ratio(got["planes"][j], D.channel_terms(got["index"][j], full["points"][j]))
+                worst = max(worst, ratio)
+                assert ratio <= 1.0, (rows, cols, kind, path, frames[j], ratio)
+    print(f"grouped planes: worst |plane - sum64| / (gamma_n sum|term|) = {worst:.4f}")
+
+
+def test_stale_hand_over_words_across_storage_forms(ctx, made):
+    """The y pass of the grouped strip kernel carries four chains per thread where the plane kernel carries three, so its hand-over words need not
+    sit where the plane kernel's sit; they outlive a call and differ from fresh ones only in their epoch.  In one context: lean 1, 2, 0, 2 in turn
+    on different windows of one shape, on the single-pass and on the latency path, then the same at a shape with other strip and band counts,
+    then the first shape's grouped call once more -- all bit-exact."""
+    a, ra, pa = made(17, 129, "float")         # 3 strips x 3 bands
+    c, rc, pc = made(65, 130, "raw")           # 3 strips x 9 bands
+    for b, ref, p in ((a, ra, pa), (c, rc, pc)):
+        for k, lean in enumerate((1, G, 0, G)):
+            run_and_compare(ctx, b, ref, p, window(16 + k % 2, 6 * k + 1), D.SINGLE_PASS, lean)
+        for k, lean in enumerate((1, G, 0, G)):
+            run_and_compare(ctx, b, ref, p, window((15, 3, 9, 15)[k], 5 * k + 2), D.LATENCY, lean)
+    run_and_compare(ctx, a, ra, pa, window(25, 0), D.SINGLE_PASS, G)
+    run_and_compare(ctx, a, ra, pa, window(15, 7), D.LATENCY, G)
+
+
+@pytest.mark.parametrize("kind", ["float", "raw"])
+def test_grouped_front_end_on_device_frames_at_every_alignment(ctx, made, kind):
+    """9 x 68 in device memory 0, 1, 2 and 4 elements behind a 256-byte boundary, lean = 2: float rows are 16-byte aligned at 0 and 4 elements
+    (k_strip_count) and not at 1 and 2 (k_strip_count_any); raw rows of 68 are never (k_strip_count_any, at byte offsets 0, 2, 4 and 8).  Every
+    placement equals the oracle and so the host frames' result, bit for bit."""
+    b, ref, p = made(9, 68, kind)
+    frames = window(17, 4)
+    outs = [run_and_compare(ctx, b, ref, p, frames, D.SINGLE_PASS, G, off) for off in (None, 0, 1, 2, 4)]
+    for o in outs[1:]:
+        for key in ("index", "rowoff"):
+            assert np.array_equal(outs[0][key], o[key]), key
+        assert D.same_bits(outs[0]["planes"], o["planes"]).all()
+    run_and_compare(ctx, b, ref, p, frames[:3], D.LATENCY, G, 2)
+
+
+def test_front_end_hook_refuses_an_unknown_lean_value(ctx, made):
+    """lean = 3 and -1 are PWN_HIP_ERR_INVALID_ARGUMENT and the output arrays keep what they held"""
+    import ctypes as C
+    b, _, p = made(9, 68, "float")
+    N = b.rows * b.cols
+    src = np.ascontiguousarray(b.frames[:1])
+    from g2o_frontend_amd import api
+    cloud = api.Cloud(ctx, N)
+    integral = np.full(10 * N, -7.0, np.float32); index = np.full(N, -7, np.int32); rowoff = np.full(b.rows * 2, -7, np.int32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    for lean in (3, -1):
+        rc = ctx._L.pwn_hip_debug_front_end(ctx.h, C.addressof(p), (C.c_void_p * 1)(src.ctypes.data), 0.0, 1, b.rows, b.cols, D.SINGLE_PASS, lean,
+                                            (C.c_void_p * 1)(cloud.h.value), vp(integral), vp(index), None, vp(rowoff))
+        assert rc == 1, rc
+        assert (integral == -7.0).all() and (index == -7).all() and (rowoff == -7).all()
 
 
 @pytest.mark.parametrize("path", [D.LATENCY, D.SINGLE_PASS])
