@@ -148,6 +148,7 @@ PROTOTYPES = {
     "pwn_hip_cloud_download_gaussians": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_cloud_add": (_I, [_VP, _VP, _VP, _VP]),
     "pwn_hip_merge": (_I, [_VP, _VP, _VP, _VP, _F, _F, _I, _I, _F, _F, _F, C.POINTER(_I), _VP]),
+    "pwn_hip_merge_clouds": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _F, _F, _I, _I, _VP, _VP, _VP, _VP]),
     "pwn_hip_voxelize": (_I, [_VP, _VP, _F, C.POINTER(_I), _VP]),
     "pwn_hip_cloud_save": (_I, [_VP, _VP, C.c_char_p, _VP, _I, _I]),
     "pwn_hip_cloud_load": (_I, [_VP, _VP, C.c_char_p, _VP]),

@@ -1344,8 +1344,9 @@ def _iso_inverse_d(T):
 
 class Merger2:
     """pwn_tracker2/merger2.{h,cpp}: the depth-image half of the merger -- clear (:36-43), mergeDepthImage (:75-101) and matchWithPartition
-    (:185-203).  The fused image, the weight image (_image_pesi) and the projected planes stay on the device.  Not mirrored: merge (the
-    cloud-level fusion with stats and Gaussians, :106-183), init and scale (:45-73)."""
+    (:185-203) -- and the cloud-level one: clearCloud (:30-34) and merge (:106-183), the fusion of a node list's clouds into _cloud_tot with
+    the weights _pesi_tot.  The fused image, the weight image (_image_pesi), the projected planes, _cloud_tot and _pesi_tot stay on the
+    device.  Not mirrored: init and scale (:45-73), which nothing in the reference calls."""
 
     def __init__(self, ctx: Context, depthImageConverter: DepthImageConverterIntegralImage, matcher: "PwnMatcherBase"):
         self.ctx, self._depthImageConverter, self._matcher = ctx, depthImageConverter, matcher
@@ -1358,6 +1359,9 @@ class Merger2:
         self._currentBigCloud = Cloud(ctx, max(1, self._r * self._c))
         self._result = None
         self.overlaps = []                   # _image_overlapping_points_count after each image of the last call
+        self._cloud_tot = None               # allocated by the first merge; clearCloud() lets it go
+        self._pesi_tot = None                # one float per point of _cloud_tot's capacity
+        self.appended, self.fused = [], []   # pixels that appended / fused, per cloud of the last merge call
 
     def depthImageConverter(self): return self._depthImageConverter
     def matcher(self): return self._matcher
@@ -1408,6 +1412,51 @@ class Merger2:
                                                                C.byref(points), _ptr(planes)))
         self._counted(n, overlap, points)
         return list(self.overlaps)
+
+    # ---- the cloud-level fusion
+    def clearCloud(self):
+        """:30-34"""
+        self._cloud_tot = None
+        self._pesi_tot = None
+
+    def cloudTot(self): return self._cloud_tot
+    def pesiTot(self):
+        """_pesi_tot as a host array, one weight per point of _cloud_tot"""
+        n = self._cloud_tot.size() if self._cloud_tot is not None else 0
+        return self._pesi_tot.numpy()[:n].copy() if n else np.zeros(0, np.float32)
+
+    def _reserve(self, points):
+        """_cloud_tot / _pesi_tot with room for `points` points; what they hold is kept (Cloud::add under the identity is a copy)"""
+        tot = self._cloud_tot
+        if tot is not None and tot.capacity >= points:
+            return
+        grown = Cloud(self.ctx, max(1, points))
+        pesi = np.zeros(grown.capacity, np.float32)
+        if tot is not None and tot.size():
+            grown.add(tot)
+            pesi[:tot.size()] = self._pesi_tot.numpy()[:tot.size()]
+        self._cloud_tot, self._pesi_tot = grown, DeviceBuffer(self.ctx, pesi)
+
+    def merge(self, transform, offset, cloud):
+        """merge(transform, offset, cloud) (:106-183): `cloud` fused into _cloud_tot"""
+        return self.mergeBatch([transform], offset, [cloud])
+
+    def mergeBatch(self, transforms, offset, clouds):
+        """merge for a list of clouds in order, one submission (pwn_hip_merge_clouds): cloud i comes under transforms[i] (float 4x4, its robot
+        frame -> the frame of _cloud_tot), `offset` is the sensor offset.  Returns the pixels that appended a point, per cloud; `fused`
+        holds the pixels that moved one."""
+        pp = self._depthImageConverter.projector()
+        n = len(clouds)
+        held = self._cloud_tot.size() if self._cloud_tot is not None else 0
+        self._reserve(held + sum(c.size() for c in clouds))
+        handles = (C.c_void_p * max(1, n))(*[c.h for c in clouds])
+        tr = np.ascontiguousarray(np.stack([_colmajor(T, 4) for T in transforms]), np.float32) if n else np.zeros((1, 16), np.float32)
+        appended = (C.c_int * max(1, n))(); fused = (C.c_int * max(1, n))()
+        self.ctx.check(self.ctx._L.pwn_hip_merge_clouds(self.ctx.h, _ptr(_colmajor(pp.cameraMatrix(), 3)), _ptr(_colmajor(offset, 4)), n, handles, _ptr(tr),
+                                                        pp.minDistance(), pp.maxDistance(), pp.imageRows(), pp.imageCols(), self._cloud_tot.h,
+                                                        _ptr(self._pesi_tot), appended, fused))
+        self.appended, self.fused = [int(v) for v in appended[:n]], [int(v) for v in fused[:n]]
+        return list(self.appended)
 
     def matchWithPartition(self, currentPartitionImage, offset, partitionMerged):
         """:185-203: both images converted (one pwn_hip_convert_batch of the two device frames), then
@@ -1534,6 +1583,34 @@ class PwnCloserWithMerger:
                 r["informationMatrix"] = self.INFORMATION.copy()
                 relations.append(r)
         return relations
+
+
+class PwnMerger:
+    """pwn_tracker2/pwn_merger.{h,cpp}: mergeNodeList (:28-62), what MapMerger::process (boss_map_building/map_merger.cpp:43-82) calls every
+    listSize + 1 key nodes -- the cached clouds of the list fused, one after the other, into one local-map cloud in the frame of the first
+    ("big") node, which then becomes that node's cloud in the cache."""
+
+    def __init__(self, merger: Merger2, cache: "CloudCache"):
+        self._merger, self._cache = merger, cache
+
+    def merger(self): return self._merger
+
+    @staticmethod
+    def nodeTransform(big: MapNode, node: MapNode):
+        """T = big.transform()^-1 * node.transform() in double (:36, :49), then convertScalar to float (:51)"""
+        return _iso_mul_d(_iso_inverse_d(big.transform()), node.transform()).astype(np.float32)
+
+    def mergeNodeList(self, big: MapNode, nodes):
+        """:28-62 -> the fused cloud, which replaces the big node's cloud in the cache.  The sensor offset is the big node's (:39-41)."""
+        self._merger.clearCloud()
+        clouds = self._cache.getBatch([big.key] + [o.key for o in nodes])[1:]          # :34, :46
+        offset = big.sensorOffset.astype(np.float32)
+        self._merger.mergeBatch([self.nodeTransform(big, o) for o in nodes], offset, clouds)
+        tot = self._merger.cloudTot()
+        fused = Cloud(self._merger.ctx, max(1, tot.size()))                             # :56-61: a cloud of the fused size
+        fused.add(tot)
+        self._cache._insert(big.key, fused)
+        return fused
 
 
 class CloudCache:

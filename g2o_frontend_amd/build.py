@@ -73,6 +73,13 @@ def build_tools(force: bool = False) -> str:
     if force or (not os.path.exists(out7)) or any(os.path.getmtime(d) > os.path.getmtime(out7) for d in deps7):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src7, "-o", out7, "-L", _HERE, "-lpwn_hip",
                                "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
+    # PwnMerger::mergeNodeList of the C++ mirror against the fused cloud the Python mirror wrote to a file (exit status 0 = equal byte for byte)
+    src8 = os.path.join(root, "tools", "pwn_hip_merge_clouds_check.cpp")
+    out8 = os.path.join(root, "tools", "pwn_hip_merge_clouds_check")
+    deps8 = [src8] + deps[1:]
+    if force or (not os.path.exists(out8)) or any(os.path.getmtime(d) > os.path.getmtime(out8) for d in deps8):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src8, "-o", out8, "-L", _HERE, "-lpwn_hip",
+                               "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
     # PwnCloser::processPartition over the GPUs of a node in native code: the mirror + RCCL (broadcast of the flat `current` cloud, all-gather of the
     # match records); the program's own streams and events come from the HIP runtime
     src5 = os.path.join(root, "tools", "pwn_hip_partition_app.cpp")

@@ -189,6 +189,7 @@ struct pwn_hip_ctx {
   DevBuf<DepthCloudDesc> depth_clouds_dev; HostBuf<DepthCloudDesc> depth_clouds_host;
   DevBuf<Mat4> krt_dev; HostBuf<Mat4> krt_host;
   DevBuf<int> merge_counts_dev; HostBuf<int> merge_counts_host;
+  DevBuf<float> cloud_weights_ws;            // pwn_hip_merge_clouds: the staging of host-side `weights` (the total cloud's capacity)
 };
 
 namespace {

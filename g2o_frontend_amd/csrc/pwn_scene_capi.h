@@ -218,6 +218,93 @@ int pwn_hip_merge(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, const float K[9], cons
   return PWN_HIP_OK;
 }
 
+// Merger2::merge (pwn_tracker2/merger2.cpp:106-183) for the clouds of a node list (PwnMerger::mergeNodeList, pwn_tracker2/pwn_merger.cpp:44-54) in one
+// submission: per cloud the two projections, the pixel loop's decisions and in-place fuses, the ordered compaction of the appended pixels and the
+// appends (pwn_scene_kernels.h).  The total's size stays on the device between the clouds (CloudDev::count); the grids are sized by the host's upper
+// bound, size + the sizes of the sources so far, and the host waits once, at the end.  Everything is checked before anything is written.
+int pwn_hip_merge_clouds(pwn_hip_ctx* ctx, const float K[9], const float offset[16], int n, pwn_hip_cloud* const* clouds, const float* transforms,
+                         float min_distance, float max_distance, int rows, int cols, pwn_hip_cloud* total, float* weights, int* appended, int* fused) {
+  if (!ctx || !K || !offset || !total || !weights) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "negative number of clouds");
+  if (n > 0 && (!clouds || !transforms)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (min_distance < 0.f) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "min_distance must be >= 0");
+  if (int rc = check_image(ctx, rows, cols)) return rc;
+  if (total->owner != ctx) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "cloud of another context");
+  const int k0 = total->n_host;
+  size_t bound = (size_t)k0;
+  bool anyGauss = false;
+  for (int i = 0; i < n; ++i) {
+    const pwn_hip_cloud* c = clouds[i];
+    if (!c) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null cloud");
+    if (c->owner != ctx) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "cloud of another context");
+    if (c == total) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "the total cloud is among the clouds merged into it");
+    if (c->d.omSym != total->d.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds with different omega storages");
+    bound += (size_t)c->n_host;
+    anyGauss = anyGauss || (c->sb.G && c->n_gauss > 0);
+  }
+  if (n == 0) return PWN_HIP_OK;
+  if (bound > (size_t)total->d.capacity) return fail(ctx, PWN_HIP_ERR_CAPACITY, "total cloud capacity smaller than its size plus the sizes of the merged clouds");
+  if (bound > (size_t)kMaxCloudPoints) return fail(ctx, PWN_HIP_ERR_CAPACITY, "the total cloud could exceed what the z-buffer index field holds (2^25)");
+  HIPCHK(ctx, hipSetDevice(ctx->device), PWN_HIP_ERR_NO_DEVICE);
+  if (int rc = absorb_copies(ctx)) return rc;      // `weights` may be the destination of a queued pwn_hip_copy_async
+  cloud_changes(ctx, total);
+  const int N = rows * cols;
+  if (int rc = scene_scratch(ctx, (size_t)N, (size_t)N)) return rc;
+  HIPCHK(ctx, ctx->merge_counts_dev.ensure(2 * (size_t)n), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->merge_counts_host.ensure(2 * (size_t)n + 1), PWN_HIP_ERR_ALLOCATION);
+  float* w = weights;
+  if (!is_device_ptr(weights)) { HIPCHK(ctx, ctx->cloud_weights_ws.ensure((size_t)total->d.capacity), PWN_HIP_ERR_ALLOCATION); w = ctx->cloud_weights_ws; }
+  if (int rc = ensure_scene(ctx, total, anyGauss || total->sb.G)) return rc;
+  hipStream_t st = ctx->stream;
+  if (w != weights && k0 > 0) HIPCHK(ctx, hipMemcpyAsync(w, weights, sizeof(float) * (size_t)k0, hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
+  // Gaussians the total has not got for the points it already holds are default Gaussians (as pwn_hip_cloud_add leaves them)
+  if (total->sb.G && k0 > total->n_gauss) HIPCHK(ctx, hipMemsetAsync(total->sb.Gf + total->n_gauss, 0, sizeof(int) * (size_t)(k0 - total->n_gauss), st), PWN_HIP_ERR_COPY);
+  int* d_counts = ctx->merge_counts_dev;             // appended[n], fused[n]
+  HIPCHK(ctx, hipMemsetAsync(d_counts, 0, sizeof(int) * 2 * (size_t)n, st), PWN_HIP_ERR_COPY);
+  unsigned long long* zcur = ctx->scene_k[0]; unsigned long long* ztot = ctx->scene_k[1];
+  int* d_flags = ctx->scene_i[0]; int* d_offs = ctx->scene_i[1]; int* d_sums = ctx->scene_i[2];
+  const Mat3 Km = mat3_from(K);
+  const Mat4 off = mat4_from(offset);
+  Mat4 KRtOff, iKRtOff; Mat3 iK;
+  projector_matrices(Km, off, KRtOff, iKRtOff, iK);                                        // setTransform(offset), :113
+  const int nbp = (N + 255) / 256;
+  size_t upper = (size_t)k0;                         // what the total can hold when cloud i is merged
+  for (int i = 0; i < n; ++i) {
+    const pwn_hip_cloud* c = clouds[i];
+    const Mat4 T = mat4_from(transforms + 16 * (size_t)i);
+    Mat4 KRtTot, iKRtTot;
+    projector_matrices(Km, iso_mul(T, off), KRtTot, iKRtTot, iK);                          // setTransform(transform * offset), :121
+    HIPCHK(ctx, hipMemsetAsync(zcur, 0xFF, sizeof(unsigned long long) * (size_t)N, st), PWN_HIP_ERR_COPY);
+    HIPCHK(ctx, hipMemsetAsync(ztot, 0xFF, sizeof(unsigned long long) * (size_t)N, st), PWN_HIP_ERR_COPY);
+    if (c->n_host > 0)
+      hipLaunchKernelGGL(k_project_single, dim3((c->n_host + 255) / 256), dim3(256), 0, st, c->d, KRtOff, min_distance, max_distance, rows, cols, zcur, kZTag0);
+    if (upper > 0)
+      hipLaunchKernelGGL(k_project_single, dim3((unsigned)((upper + 255) / 256)), dim3(256), 0, st, total->d, KRtTot, min_distance, max_distance, rows, cols, ztot, kZTag0);
+    hipLaunchKernelGGL(k_merge_clouds_classify, dim3(nbp), dim3(256), 0, st, total->d, w, (const unsigned long long*)zcur, (const unsigned long long*)ztot, kZTag0,
+                       rows, cols, iKRtTot, min_distance, max_distance, d_flags, d_counts + n + i);
+    if (int rc = exclusive_scan(ctx, d_flags, d_offs, N, d_sums, ctx->scene_total)) return rc;
+    CloudDev s = c->d;
+    if (!c->has_stats) s.St = nullptr;
+    const int ng = (c->sb.G && c->n_gauss > 0) ? std::min(c->n_gauss, c->n_host) : 0;
+    hipLaunchKernelGGL(k_merge_clouds_append, dim3(nbp), dim3(256), 0, st, total->d, total->sb, w, s, c->sb, ng, forced(transforms + 16 * (size_t)i),
+                       (const unsigned long long*)zcur, kZTag0, N, (const int*)d_flags, (const int*)d_offs);
+    hipLaunchKernelGGL(k_merge_clouds_count, dim3(1), dim3(1), 0, st, total->d.count, (const int*)ctx->scene_total, d_counts + i);
+    HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+    upper += (size_t)c->n_host;
+  }
+  int* h = ctx->merge_counts_host;
+  HIPCHK(ctx, hipMemcpyAsync(h, d_counts, sizeof(int) * 2 * (size_t)n, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipMemcpyAsync(h + 2 * n, total->d.count, sizeof(int), hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
+  const int k1 = h[2 * n];
+  if (w != weights && k1 > 0) HIPCHK(ctx, hipMemcpy(weights, w, sizeof(float) * (size_t)k1, hipMemcpyDeviceToHost), PWN_HIP_ERR_COPY);
+  if (appended) std::copy(h, h + n, appended);
+  if (fused) std::copy(h + n, h + 2 * n, fused);
+  total->n_host = k1; total->idx_valid = false;
+  if (total->sb.G) total->n_gauss = k1;
+  return PWN_HIP_OK;
+}
+
 // VoxelCalculator::compute (voxelcalculator.cpp:15-73) with the intended ordering of the voxel keys (see pwn_scene_kernels.h).
 // kept (optional, host) receives the original indices of the survivors in output order.
 int pwn_hip_voxelize(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, float resolution, int* new_size, int* kept) {

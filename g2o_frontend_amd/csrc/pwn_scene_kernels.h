@@ -118,11 +118,10 @@ __device__ __forceinline__ void omega_transform(const Mat4& m, float* om /* row-
 #pragma unroll
     for (int b = 0; b < 3; ++b) om[3 * a + b] = dot3seq(t1[3 * a], m(b,0), t1[3 * a + 1], m(b,1), t1[3 * a + 2], m(b,2));
 }
-__global__ void __launch_bounds__(256) k_cloud_append(CloudDev dst, SceneBuffers dsb, CloudDev src, SceneBuffers ssb, int k, int n, int ngauss,
-                                                      Mat4 m, int identity) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n || k + i >= dst.capacity) return;
-  const int o = k + i;
+// Point i of src, transformed by m (not at all when `identity`), stored as point o of dst: every per-point array Cloud::add carries.  The one
+// definition of that arithmetic: k_cloud_append (Cloud::add) and k_merge_clouds_append (Merger2::merge's push_backs) both call it.
+__device__ __forceinline__ void cloud_append_point(const CloudDev& dst, const SceneBuffers& dsb, const CloudDev& src, const SceneBuffers& ssb, int i, int o,
+                                                   int ngauss, const Mat4& m, int identity) {
   float4 P, Nm;                    // old-format view: (x, y, z, curvature), (normal, class word)
   cloud_get(src, i, P, Nm);
   float omP[9], omN[9];
@@ -180,6 +179,12 @@ __global__ void __launch_bounds__(256) k_cloud_append(CloudDev dst, SceneBuffers
     if (!identity) gauss_transform(g, flags, m);
     dsb.G[o] = g; dsb.Gf[o] = flags;
   }
+}
+__global__ void __launch_bounds__(256) k_cloud_append(CloudDev dst, SceneBuffers dsb, CloudDev src, SceneBuffers ssb, int k, int n, int ngauss,
+                                                      Mat4 m, int identity) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n || k + i >= dst.capacity) return;
+  cloud_append_point(dst, dsb, src, ssb, i, k + i, ngauss, m, identity);
 }
 // Cloud::transformInPlace on the Gaussians and Stats of an existing cloud (k_cloud_transform handles the other arrays)
 __global__ void __launch_bounds__(256) k_scene_transform(CloudDev cl, SceneBuffers sb, int n, int ngauss, Mat4 m) {
@@ -348,6 +353,76 @@ __global__ void __launch_bounds__(1024) k_scan_add(int* __restrict__ out, int n,
   if (i < n) out[i] += sums[blockIdx.x];
 }
 __global__ void k_set_count(int* count, const int* total) { *count = *total; }
+
+// ------------------------------------------------------------------------------------------------------------------
+// Merger2::merge (pwn_tracker2/merger2.cpp:106-183): one cloud fused into the total cloud (_cloud_tot, weights _pesi_tot).
+// 1. k_project_single twice: the cloud under `offset` (idx_current / scaledImage_current, :113-116) and the total under transform * offset
+//    (:121-127; an empty total projects nothing, so every index stays -1 as :118 leaves it).  The total's size is read on the device.
+// 2. k_merge_clouds_classify: the pixel loop's decisions (:131-179).  A fuse (:153-162) rewrites point and weight of the total in place -- every
+//    index of the total sits in at most one pixel -- an append (:134-149, :164-177) only raises the pixel's flag: indexImage_tot was made before
+//    the loop, so what the loop appends does not change what it decides.
+// 3. exclusive_scan of the flags: the raster-order rank of every appended pixel, the order of the reference's push_backs.
+// 4. k_merge_clouds_append: the push_backs, with Cloud::add's per-point arithmetic (cloud_append_point, never the identity shortcut), at
+//    count + rank; weight 1 / d (:132, :148).  The Stats block is transform * the source point's own block, as Cloud::add stores it: the
+//    reference multiplies a member that every earlier append has left its product in (:139-143) -- docs/parity.md.
+// 5. k_merge_clouds_count: count += appended, for the next cloud of the list to read.
+// The comparisons are made as the reference makes them: a float against a double literal, in double.
+__global__ void __launch_bounds__(256) k_merge_clouds_classify(CloudDev tot, float* __restrict__ weights, const unsigned long long* __restrict__ zcur,
+                                                               const unsigned long long* __restrict__ ztot, unsigned tag, int rows, int cols, Mat4 iKRt,
+                                                               float minD, float maxD, int* __restrict__ flags, int* __restrict__ fused) {
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  bool fuse = false;
+  if (pix < rows * cols) {
+    int flag = 0;
+    const float d = zkey_depth(zcur[pix], tag);                  // FLT_MAX where nothing landed
+    if ((double)d > 0.2 && (double)d < 100) {                    // :131
+      const unsigned long long kt = ztot[pix];
+      const int it = zkey_index(kt, tag);
+      if (it < 0) flag = 1;                                      // :134
+      else {
+        const float delta = d - zkey_depth(kt, tag);
+        if ((double)fabsf(delta) < .15) {                        // :153
+          // PinholePointProjector::unProject(p, j, i, d) (:154): false outside the projector's range, else p = iKRt * (j d, i d, d, 1)
+          if (depth_in_range(d, minD, maxD) && it < tot.capacity) {
+            const int r = pix / cols, c = pix - r * cols;
+            const Vec3 p = unproject_pixel(iKRt, c, r, d);
+            const float peso_current = 1.0f / d;
+            const float peso_tot = weights[it];
+            const float somma_pesi = peso_tot + peso_current;
+            const float4 q = load_xyz(tot.P3, it);
+            store_xyz(tot.P3, it, (q.x * peso_tot + p.x * peso_current) / somma_pesi, (q.y * peso_tot + p.y * peso_current) / somma_pesi,
+                      (q.z * peso_tot + p.z * peso_current) / somma_pesi);
+            weights[it] = somma_pesi;
+            fuse = true;
+          }
+        } else if ((double)delta < -.3) flag = 1;                // :164
+      }
+    }
+    flags[pix] = flag;
+  }
+  const unsigned long long b = __ballot(fuse);
+  if (lane_id() == 0 && b) atomicAdd(fused, __popcll(b));
+}
+__global__ void __launch_bounds__(256) k_merge_clouds_append(CloudDev tot, SceneBuffers tsb, float* __restrict__ weights, CloudDev src, SceneBuffers ssb,
+                                                             int ngauss, Mat4 m, const unsigned long long* __restrict__ zcur, unsigned tag, int N,
+                                                             const int* __restrict__ flags, const int* __restrict__ offs) {
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  if (pix >= N || !flags[pix]) return;
+  const int o = *tot.count + offs[pix];
+  if (o < 0 || o >= tot.capacity) return;
+  const unsigned long long kc = zcur[pix];
+  const int i = zkey_index(kc, tag);
+  if (i < 0 || i >= src.capacity) return;
+  cloud_append_point(tot, tsb, src, ssb, i, o, ngauss, m, 0);
+  if (tsb.G && !(ssb.G && i < ngauss)) {       // a source without Gaussians: the default Gaussian, neither form valid
+    GaussD g;
+    for (int k = 0; k < 3; ++k) g.mean[k] = g.infoVec[k] = 0.f;
+    for (int k = 0; k < 9; ++k) g.cov[k] = g.info[k] = 0.f;
+    tsb.G[o] = g; tsb.Gf[o] = 0;
+  }
+  weights[o] = 1.0f / zkey_depth(kc, tag);
+}
+__global__ void k_merge_clouds_count(int* count, const int* total, int* appended) { *count += *total; *appended = *total; }
 
 // ------------------------------------------------------------------------------------------------------------------
 // VoxelCalculator::compute (voxelcalculator.cpp:15-73), canonical semantics (the intended lexicographic order of the voxel

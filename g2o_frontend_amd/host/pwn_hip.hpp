@@ -793,6 +793,8 @@ class CloudCache {
     insert(key, cloud);
     return cloud;
   }
+  // `cloud` becomes the cloud of `key` (the cache takes ownership and deletes the one it held): PwnMerger::mergeNodeList, pwn_merger.cpp:56-61
+  void put(int key, Cloud* cloud) { insert(key, cloud); }
   size_t resident() const { return _lru.size(); }  size_t capacity() const { return _capacity; }
   int hits = 0, misses = 0;
  private:
@@ -930,9 +932,10 @@ class DeviceImage {
   Context* _ctx; int _rows, _cols; float* _p = nullptr;
 };
 
-// pwn_tracker2/merger2.{h,cpp}: the depth-image half of the merger -- clear (:36-43), mergeDepthImage (:75-101), matchWithPartition (:185-203).
-// The fused image, the weight image (_image_pesi) and the projected planes stay on the device.  Not mirrored: merge (:106-183), init and
-// scale (:45-73).
+// pwn_tracker2/merger2.{h,cpp}: the depth-image half of the merger -- clear (:36-43), mergeDepthImage (:75-101), matchWithPartition (:185-203) --
+// and the cloud-level one: clearCloud (:30-34) and merge (:106-183), the fusion of a node list's clouds into _cloud_tot with the weights
+// _pesi_tot.  The fused image, the weight image (_image_pesi), the projected planes, _cloud_tot and _pesi_tot stay on the device.  Not
+// mirrored: init and scale (:45-73), which nothing in the reference calls.
 class Merger2 {
  public:
   Merger2(Context* ctx, DepthImageConverterIntegralImage* converter, PwnMatcherBase* matcher)
@@ -967,14 +970,52 @@ class Merger2 {
     const Matrix3f K = pp->cameraMatrix();
     _matcher->matchClouds(_result, &_currentBigCloud, &_bigCloud, offset, offset, K, pp->imageRows(), pp->imageCols(), Isometry3f::Identity());
   }
+  // ---- the cloud-level fusion
+  void clearCloud() { _cloud_tot.reset(); _pesi_tot.reset(); }                                               // :30-34
+  Cloud* cloudTot() const { return _cloud_tot.get(); }
+  // _pesi_tot on the host: one weight per point of _cloud_tot
+  std::vector<float> pesiTot() const {
+    std::vector<float> w(_cloud_tot ? _cloud_tot->size() : 0);
+    if (!w.empty()) _ctx->check(pwn_hip_copy(_ctx->handle(), w.data(), _pesi_tot->data(), w.size() * sizeof(float)));
+    return w;
+  }
+  void merge(const Isometry3f& transform, const Isometry3f& offset, Cloud* cloud) { mergeBatch({ transform }, offset, { cloud }); }      // :106-183
+  // merge for a list of clouds in order, one submission (pwn_hip_merge_clouds): cloud i comes under transforms[i] (its robot frame -> the frame
+  // of _cloud_tot), `offset` is the sensor offset; appended / fused receive the pixels that took each action, per cloud
+  void mergeBatch(const std::vector<Isometry3f>& transforms, const Isometry3f& offset, const std::vector<Cloud*>& clouds) {
+    if (clouds.size() != transforms.size()) throw Error(PWN_HIP_ERR_INVALID_ARGUMENT, "mergeBatch: list sizes differ");
+    PinholePointProjector* pp = _depthImageConverter->projector();
+    size_t points = _cloud_tot ? _cloud_tot->size() : 0;
+    for (const Cloud* c : clouds) points += c->size();
+    reserve(points);
+    std::vector<pwn_hip_cloud*> h(clouds.size()); std::vector<float> tr(clouds.size() * 16);
+    for (size_t i = 0; i < h.size(); ++i) { h[i] = clouds[i]->handle(); std::memcpy(&tr[16 * i], transforms[i].data(), 16 * sizeof(float)); }
+    appended.assign(clouds.size(), 0); fused.assign(clouds.size(), 0);
+    _ctx->check(pwn_hip_merge_clouds(_ctx->handle(), pp->cameraMatrix().data(), offset.data(), (int)h.size(), h.data(), tr.data(), pp->minDistance(), pp->maxDistance(),
+                                     pp->imageRows(), pp->imageCols(), _cloud_tot->handle(), _pesi_tot->data(), appended.data(), fused.data()));
+  }
   int _r, _c;
   int _image_points_count = 0, _image_overlapping_points_count = 0;
   std::vector<int> overlaps;
+  std::vector<int> appended, fused;
   PwnMatcherBase::MatcherResult _result;
  private:
+  // _cloud_tot / _pesi_tot with room for `points` points; what they hold is kept (Cloud::add under the identity is a copy)
+  void reserve(size_t points) {
+    if (_cloud_tot && _cloud_capacity >= points) return;
+    const int cap = (int)(points > 0 ? points : 1);
+    std::unique_ptr<Cloud> grown(new Cloud(*_ctx, cap));
+    std::unique_ptr<DeviceImage> pesi(new DeviceImage(*_ctx, 1, cap));
+    if (_cloud_tot && _cloud_tot->size() > 0) {
+      grown->add(*_cloud_tot);
+      _ctx->check(pwn_hip_copy(_ctx->handle(), pesi->data(), _pesi_tot->data(), _cloud_tot->size() * sizeof(float)));
+    }
+    _cloud_tot = std::move(grown); _pesi_tot = std::move(pesi); _cloud_capacity = (size_t)cap;
+  }
   Context* _ctx; DepthImageConverterIntegralImage* _depthImageConverter; PwnMatcherBase* _matcher;
   DeviceImage _image_pesi;
   Cloud _bigCloud, _currentBigCloud;
+  std::unique_ptr<Cloud> _cloud_tot; std::unique_ptr<DeviceImage> _pesi_tot; size_t _cloud_capacity = 0;
 };
 
 // what the merged closer needs of a SyncSensorDataNode: its transform, the sensor offset of its depth camera, the key of its frame in the cache
@@ -1050,6 +1091,33 @@ class PwnCloserWithMerger {
   const MapNode* _current = nullptr;
   std::vector<const MapNode*> _currentPartitionActive, _nodeList;
   std::unique_ptr<DeviceImage> _currentPartitionImage, _otherPartitionImage;
+};
+
+// pwn_tracker2/pwn_merger.{h,cpp}: mergeNodeList (:28-62), what MapMerger::process (boss_map_building/map_merger.cpp:43-82) calls every
+// listSize + 1 key nodes -- the cached clouds of the list fused, one after the other, into one local-map cloud in the frame of the first
+// ("big") node, which then becomes that node's cloud in the cache.
+class PwnMerger {
+ public:
+  PwnMerger(Context* ctx, Merger2* merger, CloudCache* cache) : _ctx(ctx), _merger(merger), _cache(cache) {}
+  // T = big.transform()^-1 * node.transform() in double (:36, :49), then convertScalar to float (:51)
+  static Isometry3f nodeTransform(const MapNode& big, const MapNode& node) { return (big.transform.inverse() * node.transform).toFloat(); }
+  // :28-62 -> the fused cloud (owned by the cache, where it replaces the big node's cloud).  The sensor offset is the big node's (:39-41).
+  Cloud* mergeNodeList(const MapNode* big, const std::vector<const MapNode*>& nodes) {
+    // the cache deletes what it evicts: every cloud of the list has to stay resident until the call has used it
+    if (_cache->capacity() < nodes.size() + 1) throw Error(PWN_HIP_ERR_CAPACITY, "PwnMerger: the cloud cache holds fewer clouds than the node list visits");
+    _merger->clearCloud();
+    _cache->get(big->key);                                                                                // :34
+    std::vector<Cloud*> clouds; std::vector<Isometry3f> trs;
+    for (const MapNode* o : nodes) { clouds.push_back(_cache->get(o->key)); trs.push_back(nodeTransform(*big, *o)); }      // :46-51
+    _merger->mergeBatch(trs, big->sensorOffset.toFloat(), clouds);
+    const Cloud* tot = _merger->cloudTot();
+    Cloud* fused = new Cloud(*_ctx, (int)(tot->size() > 0 ? tot->size() : 1));                            // :56-61: a cloud of the fused size
+    try { fused->add(*tot); } catch (...) { delete fused; throw; }
+    _cache->put(big->key, fused);
+    return fused;
+  }
+ private:
+  Context* _ctx; Merger2* _merger; CloudCache* _cache;
 };
 
 }  // namespace pwn_hip

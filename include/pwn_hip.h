@@ -495,6 +495,24 @@ int pwn_hip_cloud_add(pwn_hip_ctx* ctx, pwn_hip_cloud* dst, const pwn_hip_cloud*
 int pwn_hip_merge(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, const float K[9], const float T[16], float min_distance, float max_distance,
                   int rows, int cols, float distance_threshold, float normal_threshold, float max_point_depth, int* new_size,
                   int* collapsed);
+/* Merger2::merge (pwn_tracker2/merger2.cpp:106-183) for clouds[0..n) in call order, as PwnMerger::mergeNodeList (pwn_tracker2/pwn_merger.cpp:28-62)
+ * calls it for the nodes of a list: one submission on the context's stream, the host waits once at the end.  Cloud i is projected under the sensor
+ * `offset` (:113-116) and `total` (Merger2::_cloud_tot) under transforms[16 i .. 16 i + 16) * offset (:121-127; the product is Isometry3f *
+ * Isometry3f in float, pwn_hip_iso_mul; K, range and image size are the projector's).  A pixel whose depth d lies in (0.2, 100) appends the
+ * cloud's point, transformed by transforms[i] with Cloud::add's per-point arithmetic and never its identity shortcut, with weight 1 / d where
+ * `total` shows nothing (:134-149) or lies more than 0.3 behind (:164-177); where |d - depth of total| < 0.15 and d is inside the projector's range it
+ * moves the total's point to the weighted mean with the pixel's unprojection (:153-162); the appended points follow in raster order of their
+ * pixels.  `weights` (Merger2::_pesi_tot): one float per point of `total`, capacity-of-total floats, host or device memory, in / out.
+ * appended / fused (host, n ints each, may be NULL): the pixels that took each action per cloud.  `total` gets explicit normal information
+ * matrices, Stats (the default Stats() for a source without) and, when it or a source has them, Gaussians (the default Gaussian for a source
+ * without), as pwn_hip_cloud_add gives them.  One deviation: the Stats block of an appended point is transforms[i] * the source point's own
+ * block, what Cloud::add stores; the reference multiplies a member that holds the product of every earlier append (:139-143, :167-171).
+ * Refused with `total`, `weights` and the counters untouched: a null argument, n < 0, a cloud of another context, `total` among the clouds,
+ * clouds of different omega storages, an image larger than the context's, min_distance < 0, and -- PWN_HIP_ERR_CAPACITY, tested on the upper
+ * bound size(total) + sum of size(clouds[i]) before any work -- a bound above the capacity of `total` or above 2^25.  n == 0 is a no-op. */
+int pwn_hip_merge_clouds(pwn_hip_ctx* ctx, const float K[9], const float offset[16], int n, pwn_hip_cloud* const* clouds, const float* transforms,
+                         float min_distance, float max_distance, int rows, int cols, pwn_hip_cloud* total, float* weights, int* appended,
+                         int* fused);
 /* VoxelCalculator::compute (voxelcalculator.cpp:15-73): the first point of every voxel survives, output sorted by voxel indices
  * (the intended lexicographic order; the reference's IndexComparator, voxelcalculator.h:41-48, is not a strict weak ordering).
  * kept (optional, host) receives the original indices of the survivors in output order. */

@@ -1,0 +1,103 @@
+// pwn_hip_merge_clouds_check -- PwnMerger::mergeNodeList of the C++ host mirror against the fused cloud the Python mirror made from the same
+// input (tests/test_gpu_merge_clouds.py writes the file).  Frame 0 is the big node, the list is every frame, frame 0 included.  The point
+// count, the per-cloud counters and every array of the fused cloud and its weights must be equal byte for byte (both mirrors make the same
+// calls on the same device).  Exits 0 when nothing differs, 1 on a difference, 2 on an error.
+//
+//   pwn_hip_merge_clouds_check merge.bin
+//
+// File (little endian): int32 rows, cols, frames; float64 K[4] (fx fy cx cy), min_distance, max_distance; int32 min_image_radius,
+// max_image_radius, min_points; per frame float64 pose[16] (row-major) and float32 depth[rows*cols]; int32 points of the fused cloud; then
+// eleven arrays, each int64 bytes + the bytes: points, normals, curvature, omega_p, omega_n, stats, eigenvalues, npoints, weights, appended,
+// fused.
+//
+//   g++ -O2 -std=c++17 -I. tools/pwn_hip_merge_clouds_check.cpp -o tools/pwn_hip_merge_clouds_check -Lg2o_frontend_amd -lpwn_hip -Wl,-rpath,$ORIGIN/../g2o_frontend_amd
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <iostream>
+
+#include "g2o_frontend_amd/host/pwn_hip.hpp"
+
+using namespace pwn_hip;
+
+template <typename T> static bool get(FILE* f, T* v, size_t n = 1) { return std::fread(v, sizeof(T), n, f) == n; }
+
+int main(int argc, char** argv) {
+  if (argc < 2) { std::cerr << "USAGE: pwn_hip_merge_clouds_check merge.bin" << std::endl; return 2; }
+  FILE* f = std::fopen(argv[1], "rb");
+  if (!f) { std::cerr << "cannot open " << argv[1] << std::endl; return 2; }
+  int head[3]; double Kd[4], range[2]; int conf[3];
+  if (!get(f, head, 3) || !get(f, Kd, 4) || !get(f, range, 2) || !get(f, conf, 3) || head[0] <= 0 || head[1] <= 0 || head[2] < 1) { std::cerr << "bad header" << std::endl; return 2; }
+  const int rows = head[0], cols = head[1], n = head[2];
+  std::vector<MapNode> nodes((size_t)n);
+  std::vector<DepthImage> frames((size_t)n);
+  for (int k = 0; k < n; ++k) {
+    nodes[k].key = k;
+    frames[k].create(rows, cols);
+    if (!get(f, nodes[k].transform.m, 16) || !get(f, frames[k].data.data(), frames[k].data.size())) { std::cerr << "short file" << std::endl; return 2; }
+  }
+  int expectedPoints = 0;
+  if (!get(f, &expectedPoints)) { std::cerr << "short file" << std::endl; return 2; }
+  static const char* names[11] = { "points", "normals", "curvature", "omega_p", "omega_n", "stats", "eigenvalues", "npoints", "weights", "appended", "fused" };
+  std::vector<std::vector<char> > expected(11);
+  for (int a = 0; a < 11; ++a) {
+    long long bytes = 0;
+    if (!get(f, &bytes) || bytes < 0) { std::cerr << "short file" << std::endl; return 2; }
+    expected[a].resize((size_t)bytes);
+    if (bytes && !get(f, expected[a].data(), (size_t)bytes)) { std::cerr << "short file" << std::endl; return 2; }
+  }
+  std::fclose(f);
+
+  try {
+    Context ctx(0, rows, cols, 16);
+    ctx.setOmegaStorage(PWN_HIP_OMEGA_EXACT9);
+    // the converter's projector is the merger's; matcher at scale 1 (the cache makes the clouds)
+    PinholePointProjector projector;
+    Matrix3f K; K(0,0) = (float)Kd[0]; K(1,1) = (float)Kd[1]; K(0,2) = (float)Kd[2]; K(1,2) = (float)Kd[3]; K(2,2) = 1.f;
+    projector.setCameraMatrix(K); projector.setMinDistance((float)range[0]); projector.setMaxDistance((float)range[1]); projector.setImageSize(rows, cols);
+    StatsCalculatorIntegralImage stats;
+    stats.setWorldRadius(0.1f); stats.setMinImageRadius(conf[0]); stats.setMaxImageRadius(conf[1]); stats.setMinPoints(conf[2]); stats.setCurvatureThreshold(0.2f);
+    PointInformationMatrixCalculator pinfo; NormalInformationMatrixCalculator ninfo;
+    pinfo.setCurvatureThreshold(0.02f); ninfo.setCurvatureThreshold(0.02f);
+    DepthImageConverterIntegralImage converter(&ctx, &projector, &stats, &pinfo, &ninfo);
+    Aligner aligner(&ctx);
+    aligner.setProjector(&projector);
+    PwnMatcherBase matcher(&ctx, &aligner, &converter);
+    matcher.setScale(1);
+    CloudCache cache(&matcher, 16);
+    for (int k = 0; k < n; ++k) cache.addFrame(k, frames[k], K, Isometry3f::Identity());
+    Merger2 merger(&ctx, &converter, &matcher);
+    PwnMerger pm(&ctx, &merger, &cache);
+
+    std::vector<const MapNode*> list;
+    for (int k = 0; k < n; ++k) list.push_back(&nodes[k]);
+    const Cloud* fused = pm.mergeNodeList(&nodes[0], list);
+
+    int bad = 0;
+    const size_t m = fused->size();
+    if ((int)m != expectedPoints) { std::cerr << m << " points, expected " << expectedPoints << std::endl; ++bad; }
+    if (cache.get(0) != fused) { std::cerr << "the cache does not hold the fused cloud under the big node's key" << std::endl; ++bad; }
+    std::vector<std::vector<char> > got(11);
+    auto put = [&](int a, const void* p, size_t bytes) { got[a].assign((const char*)p, (const char*)p + bytes); };
+    { const std::vector<float> v = fused->points(); put(0, v.data(), v.size() * 4); }
+    { const std::vector<float> v = fused->normals(); put(1, v.data(), v.size() * 4); }
+    { const std::vector<float> v = fused->curvatures(); put(2, v.data(), v.size() * 4); }
+    { const std::vector<float> v = fused->pointInformationMatrix(); put(3, v.data(), v.size() * 4); }
+    { const std::vector<float> v = fused->normalInformationMatrix(); put(4, v.data(), v.size() * 4); }
+    { std::vector<float> st(m * 16), ev(m * 3); std::vector<int> np(m);
+      ctx.check(pwn_hip_cloud_download_stats(ctx.handle(), fused->handle(), st.data(), ev.data(), np.data()));
+      put(5, st.data(), st.size() * 4); put(6, ev.data(), ev.size() * 4); put(7, np.data(), np.size() * 4); }
+    { const std::vector<float> v = merger.pesiTot(); put(8, v.data(), v.size() * 4); }
+    put(9, merger.appended.data(), merger.appended.size() * sizeof(int));
+    put(10, merger.fused.data(), merger.fused.size() * sizeof(int));
+    for (int a = 0; a < 11; ++a)
+      if (got[a].size() != expected[a].size() || (!got[a].empty() && std::memcmp(got[a].data(), expected[a].data(), got[a].size()) != 0)) {
+        std::cerr << names[a] << ": " << got[a].size() << " bytes against " << expected[a].size() << ", or their content differs" << std::endl; ++bad;
+      }
+    std::cout << n << " frames " << rows << "x" << cols << ": " << m << " points, " << bad << " differences" << std::endl;
+    return bad ? 1 : 0;
+  } catch (const Error& e) {
+    std::cerr << "pwn_hip error: " << e.what() << std::endl;
+    return 2;
+  }
+}
