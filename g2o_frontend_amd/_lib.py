@@ -163,6 +163,7 @@ PROTOTYPES = {
     "pwn_hip_debug_stats_from_integral_lean": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _F, _VP, _I]),
     "pwn_hip_debug_front_end": (_I, [_VP, _VP, _VP, _F, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_debug_trig_eval": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP]),
+    "pwn_hip_debug_cloud_set_gaussians": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_measure_hbm": (_I, [_VP, C.c_size_t, _VP, _VP]),
 }
 

@@ -480,6 +480,14 @@ class Cloud:
                                                                     _ptr(out["info"]), _ptr(out["flags"])))
         return out
 
+    def debugSetGaussians(self, mean, cov, info_vec, info, flags):
+        """test-only (include/pwn_hip_testing.h): the Gaussian vector becomes the records given, in the layout gaussians() returns;
+        their number need not be the cloud's size"""
+        a = [np.ascontiguousarray(x, dtype=np.float32) for x in (mean, cov, info_vec, info)]
+        f = np.ascontiguousarray(flags, dtype=np.int32)
+        assert [x.size for x in a] == [3 * f.size, 9 * f.size, 3 * f.size, 9 * f.size], "one row of mean, cov, info_vec and info per flag word"
+        self.ctx.check(self.ctx._L.pwn_hip_debug_cloud_set_gaussians(self.ctx.h, self.h, len(f), *[_ptr(x) for x in a], _ptr(f)))
+
     def add(self, cloud: "Cloud", T=None):
         """Cloud::add (cloud.cpp:145-171)"""
         self.ctx.check(self.ctx._L.pwn_hip_cloud_add(self.ctx.h, self.h, cloud.h, _ptr(_colmajor(np.eye(4) if T is None else T, 4))))

@@ -23,6 +23,14 @@ int ensure_gauss(pwn_hip_ctx* ctx, pwn_hip_cloud* c) {
   }
   return PWN_HIP_OK;
 }
+// records [from, to) become default Gaussians, all zero and neither form valid (gaussian.h:16-21; what std::vector::resize appends, cloud.cpp:153):
+// whoever lets a record into [0, n_gauss) without writing it calls this -- the buffer holds what hipMalloc or an earlier content left there
+int default_gaussians(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int from, int to) {
+  if (to <= from) return PWN_HIP_OK;
+  HIPCHK(ctx, hipMemsetAsync(c->sb.G + from, 0, sizeof(GaussD) * (size_t)(to - from), ctx->stream), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipMemsetAsync(c->sb.Gf + from, 0, sizeof(int) * (size_t)(to - from), ctx->stream), PWN_HIP_ERR_COPY);
+  return PWN_HIP_OK;
+}
 // a cloud that receives appended clouds keeps explicit normal information matrices and Stats
 int ensure_scene(pwn_hip_ctx* ctx, pwn_hip_cloud* c, bool with_gauss) {
   const size_t cap = (size_t)c->d.capacity;
@@ -142,6 +150,30 @@ int pwn_hip_cloud_download_gaussians(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, f
   }
   return PWN_HIP_OK;
 }
+// Test-only (include/pwn_hip_testing.h): the cloud's Gaussian vector becomes the n records given, in the layout pwn_hip_cloud_download_gaussians
+// returns.  n need not be the cloud's size.  Everything is checked before anything is written.
+int pwn_hip_debug_cloud_set_gaussians(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int n, const float* mean, const float* cov, const float* info_vec,
+                                      const float* info, const int* flags) {
+  if (!ctx || !c) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (c->owner != ctx) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "cloud of another context");
+  if (n < 0 || n > c->d.capacity) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "number of Gaussians outside [0, capacity]");
+  if (n > 0 && (!mean || !cov || !info_vec || !info || !flags)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  for (int i = 0; i < n; ++i)
+    if (flags[i] & ~(kGaussMoments | kGaussInfo)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "Gaussian flags outside 0..3");
+  if (int rc = ensure_gauss(ctx, c)) return rc;
+  if (n > 0) {
+    std::vector<GaussD> g(n);
+    for (int i = 0; i < n; ++i) {
+      std::memcpy(g[i].mean, mean + 3 * (size_t)i, 12); std::memcpy(g[i].cov, cov + 9 * (size_t)i, 36);
+      std::memcpy(g[i].infoVec, info_vec + 3 * (size_t)i, 12); std::memcpy(g[i].info, info + 9 * (size_t)i, 36);
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+    HIPCHK(ctx, hipMemcpy(c->sb.G, g.data(), sizeof(GaussD) * (size_t)n, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
+    HIPCHK(ctx, hipMemcpy(c->sb.Gf, flags, sizeof(int) * (size_t)n, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
+  }
+  c->n_gauss = n;
+  return PWN_HIP_OK;
+}
 
 // Cloud::add (cloud.cpp:145-171): dst gets a copy of src transformed by T appended; src is not modified.
 int pwn_hip_cloud_add(pwn_hip_ctx* ctx, pwn_hip_cloud* dst, const pwn_hip_cloud* src, const float T[16]) {
@@ -161,13 +193,15 @@ int pwn_hip_cloud_add(pwn_hip_ctx* ctx, pwn_hip_cloud* dst, const pwn_hip_cloud*
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   const int total = k + n;
   HIPCHK(ctx, hipMemcpyAsync(dst->d.count, &total, sizeof(int), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
-  // _gaussians.resize(k + cloud.gaussians().size()) (cloud.cpp:153): entries the source does not provide are default Gaussians
+  // _gaussians.resize(k + cloud.gaussians().size()) (cloud.cpp:153): records the vector had stay, the kernel wrote [k, k + ng), every other
+  // record of the new size is a default Gaussian -- the destination's own points up to k, and what a source with more Gaussians than points adds
+  const int newg = dst->sb.G ? std::min(k + (srcGauss ? src->n_gauss : 0), dst->d.capacity) : 0;
   if (dst->sb.G) {
-    const int newg = k + (srcGauss ? src->n_gauss : 0);
-    if (k > dst->n_gauss) HIPCHK(ctx, hipMemset(dst->sb.Gf + dst->n_gauss, 0, sizeof(int) * (size_t)(k - dst->n_gauss)), PWN_HIP_ERR_COPY);
-    dst->n_gauss = std::min(newg, dst->d.capacity);
+    if (int rc = default_gaussians(ctx, dst, dst->n_gauss, std::min(k, newg))) return rc;
+    if (int rc = default_gaussians(ctx, dst, std::max(dst->n_gauss, k + ng), newg)) return rc;
   }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  if (dst->sb.G) dst->n_gauss = newg;
   dst->n_host = total; dst->idx_valid = false;
   return PWN_HIP_OK;
 }
@@ -258,7 +292,7 @@ int pwn_hip_merge_clouds(pwn_hip_ctx* ctx, const float K[9], const float offset[
   hipStream_t st = ctx->stream;
   if (w != weights && k0 > 0) HIPCHK(ctx, hipMemcpyAsync(w, weights, sizeof(float) * (size_t)k0, hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
   // Gaussians the total has not got for the points it already holds are default Gaussians (as pwn_hip_cloud_add leaves them)
-  if (total->sb.G && k0 > total->n_gauss) HIPCHK(ctx, hipMemsetAsync(total->sb.Gf + total->n_gauss, 0, sizeof(int) * (size_t)(k0 - total->n_gauss), st), PWN_HIP_ERR_COPY);
+  if (total->sb.G) { if (int rc = default_gaussians(ctx, total, total->n_gauss, k0)) return rc; }
   int* d_counts = ctx->merge_counts_dev;             // appended[n], fused[n]
   HIPCHK(ctx, hipMemsetAsync(d_counts, 0, sizeof(int) * 2 * (size_t)n, st), PWN_HIP_ERR_COPY);
   unsigned long long* zcur = ctx->scene_k[0]; unsigned long long* ztot = ctx->scene_k[1];

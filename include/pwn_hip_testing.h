@@ -76,6 +76,15 @@ int pwn_hip_debug_front_end(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p,
  * y = sqrt(q) >= 0, x = half_b: the lines of the stats kernel's eigensolver that compute them (one macro, expanded in both places). */
 int pwn_hip_debug_trig_eval(pwn_hip_ctx* ctx, int n, const float* y, const float* x, float* theta, float* cos_theta, float* sin_theta);
 
+/* A cloud's Gaussian vector (Cloud::gaussians()) set from host arrays in the layout pwn_hip_cloud_download_gaussians returns: mean n x 3,
+ * cov n x 9 (column-major 3x3), info_vec n x 3, info n x 9, flags n (1 = moments valid, 2 = information form valid; any of 0..3).  The
+ * records and flags are stored as given -- a field its flag does not declare valid is carried along, never read.  0 <= n <= capacity; n need
+ * not be the cloud's size (Cloud::add's shorter Gaussian vector, Merger::merge's tail, VoxelCalculator's "sizes must match" rule).  Bad
+ * arguments (null pointers with n > 0, n outside the range, flags outside 0..3, a cloud of another context) are refused with
+ * PWN_HIP_ERR_INVALID_ARGUMENT and nothing is written.  A later upload or conversion into the cloud does not keep them in step: set them after. */
+int pwn_hip_debug_cloud_set_gaussians(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, int n, const float* mean, const float* cov, const float* info_vec,
+                                      const float* info, const int* flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,8 @@ def lib():
         L.orc_set_gaussians.argtypes = [C.c_int, C.c_float, C.c_float]
         L.orc_cloud_num_gaussians.argtypes = [C.c_void_p]; L.orc_cloud_num_gaussians.restype = C.c_int
         L.orc_cloud_get_gaussians.argtypes = [C.c_void_p] * 6
+        L.orc_cloud_set_gaussians.restype = C.c_int
+        L.orc_cloud_set_gaussians.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.orc_cloud_transform_in_place.argtypes = [C.c_void_p, C.c_void_p]
         L.orc_cloud_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_merge.restype = C.c_int
@@ -264,6 +266,14 @@ class Cloud:
                    info=np.empty((n, 9), np.float32), flags=np.empty(n, np.int32))
         lib().orc_cloud_get_gaussians(self.h, _p(out["mean"]), _p(out["cov"]), _p(out["info_vec"]), _p(out["info"]), _p(out["flags"]))
         return out
+
+    def set_gaussian_arrays(self, mean, cov, info_vec, info, flags):
+        """the Gaussian vector becomes the records given (the layout gaussians() returns); their number need not be the cloud's size"""
+        a = [_f32(x) for x in (mean, cov, info_vec, info)]
+        f = np.ascontiguousarray(flags, np.int32)
+        assert [x.size for x in a] == [3 * f.size, 9 * f.size, 3 * f.size, 9 * f.size], "one row of mean, cov, info_vec and info per flag word"
+        if lib().orc_cloud_set_gaussians(self.h, len(f), *[_p(x) for x in a], _p(f)):
+            raise ValueError("orc_cloud_set_gaussians refused its arguments")
 
     def transform_in_place(self, T):
         Tc = _f32(np.asarray(T, np.float32).T.reshape(-1))

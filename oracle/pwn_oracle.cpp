@@ -1349,6 +1349,21 @@ void orc_cloud_get_gaussians(const orc_cloud* c, float* mean, float* cov, float*
     if (flags) flags[i] = (g.momentsUpdated ? 1 : 0) | (g.infoUpdated ? 2 : 0);
   }
 }
+/* the Gaussian vector becomes the n records given (same layout): moments, information form and the two flags as they are; n need not be
+ * the cloud's size.  Returns 0, or 1 (nothing written) for n < 0, a null array with n > 0 or flags outside 0..3. */
+int orc_cloud_set_gaussians(orc_cloud* c, int n, const float* mean, const float* cov, const float* info_vec, const float* info, const int* flags) {
+  if (!c || n < 0 || (n > 0 && (!mean || !cov || !info_vec || !info || !flags))) return 1;
+  for (int i = 0; i < n; ++i) if (flags[i] & ~3) return 1;
+  c->gaussians.resize((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    Gauss& g = c->gaussians[(size_t)i];
+    std::memset(&g, 0, sizeof(g));
+    std::memcpy(g.mean, mean + 3 * (size_t)i, 12); std::memcpy(g.cov.m, cov + 9 * (size_t)i, 36);
+    std::memcpy(g.infoVec, info_vec + 3 * (size_t)i, 12); std::memcpy(g.info.m, info + 9 * (size_t)i, 36);
+    g.momentsUpdated = (flags[i] & 1) != 0; g.infoUpdated = (flags[i] & 2) != 0;
+  }
+  return 0;
+}
 void orc_cloud_transform_in_place(orc_cloud* c, const float T[16]) { cloud_transform_in_place(c, T); }
 
 /* Cloud::add (cloud.cpp:145-171): append a transformed copy */
@@ -1362,7 +1377,9 @@ void orc_cloud_add(orc_cloud* dst, const orc_cloud* src, const float T[16]) {
   for (size_t i = 0; i < tmp.points.size(); ++i) {
     dst->points[k + i] = tmp.points[i]; dst->normals[k + i] = tmp.normals[i]; dst->stats[k + i] = tmp.stats[i];
     if (!tmp.omegaP.empty()) { dst->omegaP[k + i] = tmp.omegaP[i]; dst->omegaN[k + i] = tmp.omegaN[i]; }
-    if (!tmp.gaussians.empty()) dst->gaussians[k + i] = tmp.gaussians[i];
+    /* cloud.cpp:165-167 copies gaussians()[i] for every point once the vector is not empty: with 0 < gaussians.size() < points.size() it reads
+     * past the source's vector and writes past the destination's.  Here (and on the device) the entries the source has are copied. */
+    if (i < tmp.gaussians.size()) dst->gaussians[k + i] = tmp.gaussians[i];
   }
 }
 

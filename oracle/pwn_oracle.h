@@ -177,6 +177,8 @@ void orc_set_gaussians(int enabled, float baseline, float alpha);
 int  orc_cloud_num_gaussians(const orc_cloud* c);
 /* per Gaussian: mean[3], cov[9] column-major, info_vec[3], info[9], flags (1 = moments valid, 2 = information form valid) */
 void orc_cloud_get_gaussians(const orc_cloud* c, float* mean, float* cov, float* info_vec, float* info, int* flags);
+/* test input: the Gaussian vector becomes the n records given (n need not be the cloud's size).  0 = done, 1 = refused, nothing written */
+int  orc_cloud_set_gaussians(orc_cloud* c, int n, const float* mean, const float* cov, const float* info_vec, const float* info, const int* flags);
 /* Cloud::transformInPlace (cloud.cpp:173-186) incl. Gaussian3fVector::transformInPlace (gaussian3.h:65-73) */
 void orc_cloud_transform_in_place(orc_cloud* c, const float T[16]);
 /* Cloud::add (cloud.cpp:145-171) */
