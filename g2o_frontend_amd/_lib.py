@@ -149,6 +149,7 @@ PROTOTYPES = {
     "pwn_hip_cloud_add": (_I, [_VP, _VP, _VP, _VP]),
     "pwn_hip_merge": (_I, [_VP, _VP, _VP, _VP, _F, _F, _I, _I, _F, _F, _F, C.POINTER(_I), _VP]),
     "pwn_hip_merge_clouds": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _F, _F, _I, _I, _VP, _VP, _VP, _VP]),
+    "pwn_hip_manifold_image": (_I, [_VP, _I, _VP, _VP, _F, _I, _I, _F, _I, _VP, _VP]),
     "pwn_hip_voxelize": (_I, [_VP, _VP, _F, C.POINTER(_I), _VP]),
     "pwn_hip_cloud_save": (_I, [_VP, _VP, C.c_char_p, _VP, _I, _I]),
     "pwn_hip_cloud_load": (_I, [_VP, _VP, C.c_char_p, _VP]),
@@ -164,6 +165,7 @@ PROTOTYPES = {
     "pwn_hip_debug_front_end": (_I, [_VP, _VP, _VP, _F, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_debug_trig_eval": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_debug_cloud_set_gaussians": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
+    "pwn_hip_debug_set_manifold_chunk": (_I, [_VP, _I]),
     "pwn_hip_measure_hbm": (_I, [_VP, C.c_size_t, _VP, _VP]),
 }
 

@@ -1621,6 +1621,59 @@ class PwnMerger:
         return fused
 
 
+class ManifoldVoronoiData:
+    """pwn_tracker2/manifold_voronoi_extractor.h: the record ManifoldVoronoiExtractor::process puts on its stream -- the image (uint16
+    [xSize, ySize]: 30000 untouched, 65535 obstacle, else 10000 - 1000 z), its resolution and the key node it is centred on"""
+
+    def __init__(self, image=None, resolution=0.2, node=None):
+        self.image, self.resolution, self.node = image, resolution, node
+
+
+class ManifoldVoronoiExtractor:
+    """pwn_tracker2/manifold_voronoi_extractor.{h,cpp}: on every new key node the cached clouds of the last dequeSize key nodes, each moved
+    into the new node's frame, splatted into one traversability image (process, :50-127) -- one pwn_hip_manifold_image call on clouds that
+    stay on the device.  The deque keeps the clouds themselves where the reference keeps cache handles (which pin the clouds).  Not mirrored:
+    ManifoldVoronoi (distance map, Voronoi diagram and graph: pointer-keyed priority queues over a 100 x 100 image, read by the viewer only)
+    and the BOSS serialisation."""
+
+    def __init__(self, cache: "CloudCache"):
+        self._cache = cache
+        self._resolution = 0.2              # :41-45
+        self.xSize = 100
+        self.ySize = 100
+        self.normalThreshold = 0.64
+        self._dequeSize = 30
+        self._deque = []                    # (node, cloud), oldest first
+        self.inside = []                    # points of each cloud of the last call that fell inside the grid
+
+    def setQueueSize(self, v): self._dequeSize = int(v)
+    def dequeSize(self): return self._dequeSize
+    def setResolution(self, v): self._resolution = float(v)
+    def resolution(self): return self._resolution
+    def cache(self): return self._cache
+
+    @staticmethod
+    def nodeTransform(keyNode: MapNode, cn: MapNode):
+        """inT * cn->transform() in double (:66, :81), then convertScalar to float (:83-84)"""
+        return PwnMerger.nodeTransform(keyNode, cn)
+
+    def process(self, keyNode: MapNode) -> ManifoldVoronoiData:
+        """:50-127 for a NewKeyNodeMessage"""
+        self._deque.append((keyNode, self._cache.get(keyNode.key)))                  # :59-60
+        del self._deque[:max(0, len(self._deque) - self._dequeSize)]                 # :61-64
+        clouds = [c for _, c in self._deque]
+        ctx = clouds[0].ctx
+        n = len(clouds)
+        handles = (C.c_void_p * n)(*[c.h for c in clouds])
+        tr = np.ascontiguousarray(np.stack([_colmajor(self.nodeTransform(keyNode, o), 4) for o, _ in self._deque]), np.float32)
+        out = np.empty((self.xSize, self.ySize), np.uint16)
+        inside = (C.c_int * n)()
+        ctx.check(ctx._L.pwn_hip_manifold_image(ctx.h, n, handles, _ptr(tr), self._resolution, self.xSize, self.ySize, self.normalThreshold, 0,
+                                                _ptr(out), inside))
+        self.inside = [int(v) for v in inside]
+        return ManifoldVoronoiData(out, self._resolution, keyNode)                   # :68-69, :123-125
+
+
 class CloudCache:
     """Device-resident LRU of clouds keyed by frame (pwn_tracker/pwn_tracker_cache.cpp:24-51 + boss_map_building cache):
     a miss re-runs the converter on the frame's stored depth image (PwnCache::loadFrame), so loop-closure batches do not

@@ -80,6 +80,13 @@ def build_tools(force: bool = False) -> str:
     if force or (not os.path.exists(out8)) or any(os.path.getmtime(d) > os.path.getmtime(out8) for d in deps8):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src8, "-o", out8, "-L", _HERE, "-lpwn_hip",
                                "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
+    # ManifoldVoronoiExtractor::process of the C++ mirror against the images the Python mirror wrote to a file (exit status 0 = equal byte for byte)
+    src9 = os.path.join(root, "tools", "pwn_hip_manifold_check.cpp")
+    out9 = os.path.join(root, "tools", "pwn_hip_manifold_check")
+    deps9 = [src9] + deps[1:]
+    if force or (not os.path.exists(out9)) or any(os.path.getmtime(d) > os.path.getmtime(out9) for d in deps9):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src9, "-o", out9, "-L", _HERE, "-lpwn_hip",
+                               "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
     # PwnCloser::processPartition over the GPUs of a node in native code: the mirror + RCCL (broadcast of the flat `current` cloud, all-gather of the
     # match records); the program's own streams and events come from the HIP runtime
     src5 = os.path.join(root, "tools", "pwn_hip_partition_app.cpp")

@@ -190,6 +190,11 @@ struct pwn_hip_ctx {
   DevBuf<Mat4> krt_dev; HostBuf<Mat4> krt_host;
   DevBuf<int> merge_counts_dev; HostBuf<int> merge_counts_host;
   DevBuf<float> cloud_weights_ws;            // pwn_hip_merge_clouds: the staging of host-side `weights` (the total cloud's capacity)
+  // pwn_hip_manifold_image: one descriptor per cloud of a call, the staging of a host-side `image`, and the most points a chunk of clouds holds
+  // (pwn_hip_debug_set_manifold_chunk lowers it)
+  DevBuf<ManifoldCloud> manifold_dev; HostBuf<ManifoldCloud> manifold_host;
+  DevBuf<uint16_t> manifold_img_dev; HostBuf<uint16_t> manifold_img_host;
+  int manifold_chunk = kMaxCloudPoints;
 };
 
 namespace {

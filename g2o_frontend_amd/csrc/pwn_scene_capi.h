@@ -339,6 +339,112 @@ int pwn_hip_merge_clouds(pwn_hip_ctx* ctx, const float K[9], const float offset[
   return PWN_HIP_OK;
 }
 
+// ManifoldVoronoiExtractor::process (pwn_tracker2/manifold_voronoi_extractor.cpp:50-127): the traversability image of clouds[0..n), cloud i under
+// transforms[i], in one submission (pwn_scene_kernels.h).  Clouds are taken in chunks of whole clouds with at most ctx->manifold_chunk points; the
+// image carries the state from chunk to chunk, so the bits do not depend on the chunking.  Scratch is sized by the largest chunk's point count, which
+// the host knows; the host waits once, at the end.  Everything is checked before anything is written.
+int pwn_hip_manifold_image(pwn_hip_ctx* ctx, int n, pwn_hip_cloud* const* clouds, const float* transforms, float resolution, int x_size, int y_size,
+                           float normal_threshold, int accumulate, uint16_t* image, int* inside) {
+  if (!ctx || !image) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "negative number of clouds");
+  if (n > 0 && (!clouds || !transforms)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (x_size <= 0 || y_size <= 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "grid has zero size");
+  if ((long long)x_size * y_size > (1ll << 24)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "grid has more than 2^24 cells");
+  if (!std::isfinite(resolution) || !(resolution > 0.f)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "resolution must be finite and positive");
+  // chunks of whole clouds: [first, last), points, largest cloud
+  struct Chunk { int first, last; size_t points; int largest; };
+  std::vector<Chunk> chunks;
+  size_t most = 0;
+  for (int i = 0; i < n; ++i) {
+    const pwn_hip_cloud* c = clouds[i];
+    if (!c) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null cloud");
+    if (c->owner != ctx) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "cloud of another context");
+    if (c->n_host > ctx->manifold_chunk)
+      return fail(ctx, PWN_HIP_ERR_CAPACITY, "a cloud has more points than one chunk holds (" + std::to_string(ctx->manifold_chunk) + ")");
+    if (chunks.empty() || chunks.back().points + (size_t)c->n_host > (size_t)ctx->manifold_chunk || chunks.back().last - chunks.back().first >= 65535)
+      chunks.push_back({ i, i, 0, 0 });
+    Chunk& k = chunks.back();
+    k.last = i + 1; k.points += (size_t)c->n_host; k.largest = std::max(k.largest, c->n_host);
+    most = std::max(most, k.points);
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device), PWN_HIP_ERR_NO_DEVICE);
+  if (int rc = absorb_copies(ctx)) return rc;      // `image` may be the destination of a queued pwn_hip_copy_async
+  const int cells = x_size * y_size;
+  const size_t sortBlocks = (most + kSortChunk - 1) / kSortChunk;
+  if (int rc = scene_scratch(ctx, std::max(std::max(most, (size_t)cells), 256 * sortBlocks + 1024), most)) return rc;
+  HIPCHK(ctx, ctx->manifold_dev.ensure((size_t)std::max(n, 1)), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->manifold_host.ensure((size_t)std::max(n, 1)), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->merge_counts_dev.ensure((size_t)std::max(n, 1)), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->merge_counts_host.ensure((size_t)std::max(n, 1)), PWN_HIP_ERR_ALLOCATION);
+  hipStream_t st = ctx->stream;
+  uint16_t* img = image;
+  if (!is_device_ptr(image)) {
+    HIPCHK(ctx, ctx->manifold_img_dev.ensure((size_t)cells), PWN_HIP_ERR_ALLOCATION);
+    HIPCHK(ctx, ctx->manifold_img_host.ensure((size_t)cells), PWN_HIP_ERR_ALLOCATION);
+    img = ctx->manifold_img_dev;
+    if (accumulate) {
+      std::memcpy(ctx->manifold_img_host.p, image, sizeof(uint16_t) * (size_t)cells);
+      HIPCHK(ctx, hipMemcpyAsync(img, ctx->manifold_img_host.p, sizeof(uint16_t) * (size_t)cells, hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
+    }
+  }
+  if (!accumulate) hipLaunchKernelGGL(k_manifold_fill, dim3((cells + 255) / 256), dim3(256), 0, st, img, cells);      // setTo(30000), :72
+  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  ManifoldGrid g;
+  g.xSize = x_size; g.ySize = y_size;
+  g.cx = (int)(x_size * 0.5); g.cy = (int)(y_size * 0.5);                      // :54-55
+  g.ires = (float)(1. / (double)resolution);                                  // :56
+  g.normalThreshold = normal_threshold;
+  int* d_inside = ctx->merge_counts_dev;
+  if (n > 0) {
+    HIPCHK(ctx, hipMemsetAsync(d_inside, 0, sizeof(int) * (size_t)n, st), PWN_HIP_ERR_COPY);
+    for (const Chunk& k : chunks) {
+      int base = 0;
+      for (int i = k.first; i < k.last; ++i) {
+        ManifoldCloud& m = ctx->manifold_host.p[i];
+        m.P3 = clouds[i]->d.P3; m.Nc = clouds[i]->d.Nc; m.n = clouds[i]->n_host; m.base = base; m.T = mat4_from(transforms + 16 * (size_t)i);
+        base += m.n;
+      }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->manifold_dev.p, ctx->manifold_host.p, sizeof(ManifoldCloud) * (size_t)n, hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
+  }
+  unsigned long long* d_keyA = ctx->scene_k[0]; unsigned long long* d_keyB = ctx->scene_k[1];
+  int* d_valA = ctx->scene_i[0]; int* d_valB = ctx->scene_i[1]; int* d_hist = ctx->scene_i[2]; int* d_sums = ctx->scene_i[3]; int* d_start = ctx->scene_i[4];
+  int cellBits = 0;                                  // bits of the largest cell id, x_size * y_size (the cell of the points that make no event): at most 25,
+                                                     // so at most four passes, all within the key's low word, below the flag (kManifoldBadBit)
+  while ((cells >> cellBits) != 0) ++cellBits;
+  for (const Chunk& k : chunks) {
+    const int m = (int)k.points;
+    if (m == 0) continue;
+    hipLaunchKernelGGL(k_manifold_events, dim3((k.largest + 255) / 256, k.last - k.first), dim3(256), 0, st, (const ManifoldCloud*)(ctx->manifold_dev.p + k.first), g,
+                       d_keyA, d_valA, d_inside + k.first);
+    // stable LSD radix sort by cell: a cell's events stay in cloud order, then index order
+    const int sb_ = (m + kSortChunk - 1) / kSortChunk;
+    for (int pass = 0; 8 * pass < cellBits && m > 1; ++pass) {
+      const int shift = 8 * pass;
+      hipLaunchKernelGGL(k_sort_hist, dim3(sb_), dim3(256), 0, st, (const unsigned long long*)d_keyA, m, shift, d_hist, sb_);
+      if (int rc = exclusive_scan(ctx, d_hist, d_hist, 256 * sb_, d_sums, ctx->scene_total + 2)) return rc;
+      hipLaunchKernelGGL(k_sort_scatter, dim3(sb_), dim3(64), 0, st, (const unsigned long long*)d_keyA, (const int*)d_valA, m, shift, (const int*)d_hist, sb_, d_keyB, d_valB);
+      std::swap(d_keyA, d_keyB); std::swap(d_valA, d_valB);
+    }
+    HIPCHK(ctx, hipMemsetAsync(d_start, 0xFF, sizeof(int) * (size_t)cells, st), PWN_HIP_ERR_COPY);
+    hipLaunchKernelGGL(k_manifold_starts, dim3((m + 255) / 256), dim3(256), 0, st, (const unsigned long long*)d_keyA, m, cells, d_start);
+    hipLaunchKernelGGL(k_manifold_cells, dim3((cells + 3) / 4), dim3(256), 0, st, (const unsigned long long*)d_keyA, (const int*)d_valA, m, cells, (const int*)d_start, img);
+    HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  }
+  if (img != image) HIPCHK(ctx, hipMemcpyAsync(ctx->manifold_img_host.p, img, sizeof(uint16_t) * (size_t)cells, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
+  if (inside && n > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->merge_counts_host.p, d_inside, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
+  if (img != image) std::memcpy(image, ctx->manifold_img_host.p, sizeof(uint16_t) * (size_t)cells);
+  if (inside && n > 0) std::copy(ctx->merge_counts_host.p, ctx->merge_counts_host.p + n, inside);
+  return PWN_HIP_OK;
+}
+// Test-only (include/pwn_hip_testing.h): the most points one chunk of pwn_hip_manifold_image holds; points <= 0 restores 2^25
+int pwn_hip_debug_set_manifold_chunk(pwn_hip_ctx* ctx, int points) {
+  if (!ctx) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  ctx->manifold_chunk = (points <= 0 || points > kMaxCloudPoints) ? kMaxCloudPoints : points;
+  return PWN_HIP_OK;
+}
+
 // VoxelCalculator::compute (voxelcalculator.cpp:15-73) with the intended ordering of the voxel keys (see pwn_scene_kernels.h).
 // kept (optional, host) receives the original indices of the survivors in output order.
 int pwn_hip_voxelize(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, float resolution, int* new_size, int* kept) {

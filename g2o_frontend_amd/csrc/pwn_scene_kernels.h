@@ -524,4 +524,126 @@ __global__ void __launch_bounds__(256) k_voxel_gather(CloudDev src, SceneBuffers
   if (withGauss) { dsb.G[o] = ssb.G[i]; dsb.Gf[o] = ssb.Gf[i]; }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// ManifoldVoronoiExtractor::process (pwn_tracker2/manifold_voronoi_extractor.cpp:50-127): the clouds of the last key nodes, each under its own
+// transform, splatted into an xSize x ySize uint16 grid.  Per cell the reference walks the points in list order, then in index order (:76-121);
+// the state of a cell depends on that order, so the splat is not one per-point kernel:
+// 1. k_manifold_events: one thread per point.  Its order number is the base of its cloud + its index.  An event that can ever change a cell
+//    (inside the grid, :93-98, and squared normal not below 0.1, :109) gets the sort key (bad << 32 | cell) and the value pz; every other point
+//    gets the key of the cell one past the grid.  Dropping on the normal test before the height test is safe: both only skip.
+// 2. k_sort_hist / k_sort_scatter on the bytes of the cell field only (at most four, the key's low word; the flag lies above every sorted byte): the
+//    sort is stable, so a cell's events stay in order.
+// 3. k_manifold_starts: where every cell's run begins.
+// 4. k_manifold_cells: one wave per cell takes its run from the image's current value, 64 events at a time, and stops at the first obstacle.
+// Every dependency is a kernel boundary.
+constexpr int kManifoldBadBit = 32;                   // the key's low word is the cell id, 0 .. x_size * y_size <= 2^24, the last one for the points that
+                                                      // make no event; a radix pass takes a whole byte, so the flag stays out of the low word
+constexpr int kManifoldUntouched = 30000, kManifoldObstacle = 65535;
+struct ManifoldCloud { const float* P3; const float4* Nc; int n; int base; Mat4 T; };
+struct ManifoldGrid { int xSize, ySize, cx, cy; float ires, normalThreshold; };
+// The arithmetic of :91-113 for one point, stated once.  The point and the normal under T as Cloud::transformInPlace computes them; products and
+// sums rounded one by one; the conversions truncate toward zero (a sum in (-1, 0) lands in row / column 0).
+struct ManifoldEvent { int x, y, pz; bool inside, normal, bad; };
+__device__ __forceinline__ ManifoldEvent manifold_event(const ManifoldGrid& g, const Mat4& T, const float4 P, const float4 N) {
+  const float3 p = iso_point(T, P), n = iso_normal(T, N);
+  ManifoldEvent e;
+  e.x = (int)dot2seq((float)g.cx, 1.0f, p.x, g.ires);                                   // :91, indexes rows
+  e.y = (int)dot2seq((float)g.cy, 1.0f, p.y, g.ires);                                   // :92, indexes columns
+  e.inside = !(e.x < 0 || e.x >= g.xSize || e.y < 0 || e.y >= g.ySize);                 // :93-98
+  e.pz = (int)dot2seq(10000.f, 1.0f, -1000.f, p.z);                                     // :100
+  e.normal = !((double)dot4seq(n.x, n.x, n.y, n.y, n.z, n.z, 0.f, 0.f) < 0.1);          // :109, a float against a double literal
+  e.bad = n.z < g.normalThreshold;                                                      // :113
+  return e;
+}
+// :101-120 for one event on the state s of its cell
+__device__ __forceinline__ int manifold_step(int s, int pz, bool bad) {
+  if (s == kManifoldObstacle || s < pz) return s;
+  return bad ? kManifoldObstacle : (int)(uint16_t)pz;
+}
+// grid = (ceil(largest cloud / 256), clouds of the chunk), block = 256.  inside[c] += the points of cloud c that fell inside the grid.
+__global__ void __launch_bounds__(256) k_manifold_events(const ManifoldCloud* __restrict__ clouds, ManifoldGrid g, unsigned long long* __restrict__ keys,
+                                                         int* __restrict__ vals, int* __restrict__ inside) {
+  const ManifoldCloud& c = clouds[blockIdx.y];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  __shared__ int cnt;
+  if (threadIdx.x == 0) cnt = 0;
+  __syncthreads();
+  bool in = false;
+  if (i < c.n) {
+    const float4 nc = c.Nc[i];
+    const ManifoldEvent e = manifold_event(g, c.T, load_xyz(c.P3, i), nc);
+    in = e.inside;
+    const unsigned cell = (in && e.normal) ? (unsigned)(e.x * g.ySize + e.y) : (unsigned)(g.xSize * g.ySize);
+    keys[c.base + i] = (unsigned long long)cell | (e.bad ? 1ull << kManifoldBadBit : 0ull);
+    vals[c.base + i] = e.pz;
+  }
+  const unsigned long long b = __ballot(in);
+  if (lane_id() == 0 && b) atomicAdd(&cnt, __popcll(b));
+  __syncthreads();
+  if (threadIdx.x == 0 && cnt) atomicAdd(inside + blockIdx.y, cnt);
+}
+// start[cell] = the first sorted event of the cell (start holds -1 elsewhere)
+__global__ void __launch_bounds__(256) k_manifold_starts(const unsigned long long* __restrict__ keys, int m, int cells, int* __restrict__ start) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= m) return;
+  const unsigned cell = (unsigned)keys[j];
+  if (cell < (unsigned)cells && (j == 0 || (unsigned)keys[j - 1] != cell)) start[cell] = j;
+}
+// One wave per cell, four cells per workgroup: with a lane per cell the call takes 20 ms for 30 VGA clouds, 17 times this form (DESIGN.md section 5;
+// the fullest cell holds 105 646 events, nearly all good points, so the walk never ends early).  The wave takes the run in trips of 64 events, four trips loaded at once.  For events with 0 <= pz <= 65534
+// the per-event state functions compose as the monoid (T, M) -- s >= T gives obstacle, else min(s, M); good = (inf, pz), bad = (pz, inf);
+// (T1, M1) o (T2, M2) = (M1 >= T2 ? min(T1, T2) : T1, min(M1, M2)) -- which a trip evaluates as: the state before event j is the minimum of the
+// state before the trip and the good heights of the trip's earlier events (an exclusive prefix minimum over the lanes); the cell is an obstacle
+// when any bad event lies at or below its minimum; otherwise the state is the minimum of all.  A trip that holds a wrapped height (pz < 0 stores
+// a larger value, :119) is walked event by event instead (manifold_step), in order, by every lane alike.
+constexpr int kManifoldTrips = 4;
+__device__ __forceinline__ int manifold_trip(int s, bool in, int pz, bool bad, int lane) {
+  const unsigned long long members = __ballot(in);
+  if (__ballot(in && (pz < 0 || pz > 65534))) {
+    const int n = __popcll(members);                  // the members are the first n lanes: the run is contiguous
+    for (int t = 0; t < n && s != kManifoldObstacle; ++t) s = manifold_step(s, __shfl(pz, t), __shfl((int)bad, t) != 0);
+    return s;
+  }
+  int lowest = (in && !bad) ? pz : 0x7fffffff;        // inclusive prefix minimum of the good heights
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(lowest, off); if (lane >= off) lowest = min(lowest, o); }
+  int before = __shfl_up(lowest, 1);
+  before = min(s, lane == 0 ? 0x7fffffff : before);
+  if (__ballot(in && bad && pz <= before)) return kManifoldObstacle;
+  return min(s, __shfl(lowest, 63));
+}
+__global__ void __launch_bounds__(256) k_manifold_cells(const unsigned long long* __restrict__ keys, const int* __restrict__ vals, int m, int cells,
+                                                       const int* __restrict__ start, uint16_t* __restrict__ image) {
+  const int lane = lane_id();
+  const int cell = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (cell >= cells) return;
+  const int first = start[cell];
+  if (first < 0) return;
+  int s = image[cell];
+  for (long long base = first; base < m && s != kManifoldObstacle; base += 64 * kManifoldTrips) {
+    bool in[kManifoldTrips], bad[kManifoldTrips]; int pz[kManifoldTrips];
+#pragma unroll
+    for (int t = 0; t < kManifoldTrips; ++t) {        // all loads first
+      const long long j = base + 64 * t + lane;
+      const unsigned long long k = j < m ? keys[j] : ~0ull;
+      in[t] = (unsigned)k == (unsigned)cell;
+      bad[t] = (k >> kManifoldBadBit) & 1u;
+      pz[t] = j < m ? vals[j] : 0;
+    }
+    bool more = true;
+#pragma unroll
+    for (int t = 0; t < kManifoldTrips; ++t) {
+      if (!more || s == kManifoldObstacle) break;
+      s = manifold_trip(s, in[t], pz[t], bad[t], lane);
+      more = __ballot(in[t]) == ~0ull;                // a trip that is not full ends the run
+    }
+    if (!more) break;
+  }
+  if (lane == 0) image[cell] = (uint16_t)s;
+}
+__global__ void __launch_bounds__(256) k_manifold_fill(uint16_t* __restrict__ image, int cells) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < cells) image[i] = (uint16_t)kManifoldUntouched;
+}
+
 }  // namespace pwnhip

@@ -1120,4 +1120,49 @@ class PwnMerger {
   Context* _ctx; Merger2* _merger; CloudCache* _cache;
 };
 
+// pwn_tracker2/manifold_voronoi_extractor.h: the record ManifoldVoronoiExtractor::process puts on its stream -- the image (xSize rows by ySize
+// columns of uint16: 30000 untouched, 65535 obstacle, else 10000 - 1000 z), its resolution and the key node it is centred on
+struct ManifoldVoronoiData { std::vector<uint16_t> image; int rows = 0, cols = 0; float resolution = 0.2f; const MapNode* node = nullptr; };
+
+// pwn_tracker2/manifold_voronoi_extractor.{h,cpp}: on every new key node the cached clouds of the last dequeSize key nodes, each moved into the new
+// node's frame, splatted into one traversability image (process, :50-127) -- one pwn_hip_manifold_image call on clouds that stay on the device.
+// The reference's deque holds cache handles, which pin the clouds; this cache owns its clouds and deletes what it evicts, so the deque holds the
+// nodes and every call takes their clouds from the cache (which therefore has to hold dequeSize clouds).  Not mirrored: ManifoldVoronoi (distance
+// map, Voronoi diagram and graph: pointer-keyed priority queues over a 100 x 100 image, read by the viewer only) and the BOSS serialisation.
+class ManifoldVoronoiExtractor {
+ public:
+  ManifoldVoronoiExtractor(Context* ctx, CloudCache* cache) : _ctx(ctx), _cache(cache) {}
+  void setQueueSize(size_t v) { _dequeSize = v; }   size_t dequeSize() const { return _dequeSize; }
+  void setResolution(float v) { _resolution = v; }  float resolution() const { return _resolution; }
+  int xSize = 100, ySize = 100;                                                                       // :41-45
+  float normalThreshold = 0.64f;
+  std::vector<int> inside;                           // points of each cloud of the last call that fell inside the grid
+  // inT * cn->transform() in double (:66, :81), then convertScalar to float (:83-84)
+  static Isometry3f nodeTransform(const MapNode& keyNode, const MapNode& cn) { return PwnMerger::nodeTransform(keyNode, cn); }
+  ManifoldVoronoiData process(const MapNode* keyNode) {                                               // :50-127 for a NewKeyNodeMessage
+    _deque.push_back(keyNode);                                                                        // :59-60
+    while (_deque.size() > _dequeSize) _deque.erase(_deque.begin());                                  // :61-64
+    if (_cache->capacity() < _deque.size()) throw Error(PWN_HIP_ERR_CAPACITY, "ManifoldVoronoiExtractor: the cloud cache holds fewer clouds than the deque");
+    std::vector<pwn_hip_cloud*> h; std::vector<float> tr(_deque.size() * 16);
+    for (const MapNode* o : _deque) _cache->get(o->key);                                              // misses are made first: a get may evict
+    for (size_t i = 0; i < _deque.size(); ++i) {
+      h.push_back(_cache->get(_deque[i]->key)->handle());
+      const Isometry3f T = nodeTransform(*keyNode, *_deque[i]);
+      std::memcpy(&tr[16 * i], T.data(), 16 * sizeof(float));
+    }
+    ManifoldVoronoiData out;
+    out.rows = xSize; out.cols = ySize; out.resolution = _resolution; out.node = keyNode;             // :68-69, :124
+    out.image.assign((size_t)(xSize > 0 && ySize > 0 ? xSize * ySize : 0), 0);
+    inside.assign(h.size(), 0);
+    _ctx->check(pwn_hip_manifold_image(_ctx->handle(), (int)h.size(), h.data(), tr.data(), _resolution, xSize, ySize, normalThreshold, 0, out.image.data(),
+                                       inside.data()));
+    return out;
+  }
+ private:
+  Context* _ctx; CloudCache* _cache;
+  float _resolution = 0.2f;
+  size_t _dequeSize = 30;
+  std::vector<const MapNode*> _deque;                // oldest first
+};
+
 }  // namespace pwn_hip

@@ -513,6 +513,26 @@ int pwn_hip_merge(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, const float K[9], cons
 int pwn_hip_merge_clouds(pwn_hip_ctx* ctx, const float K[9], const float offset[16], int n, pwn_hip_cloud* const* clouds, const float* transforms,
                          float min_distance, float max_distance, int rows, int cols, pwn_hip_cloud* total, float* weights, int* appended,
                          int* fused);
+/* ManifoldVoronoiExtractor::process (pwn_tracker2/manifold_voronoi_extractor.cpp:50-127): the traversability image of the last key clouds.
+ * clouds[0..n) in call order (the deque, :76), cloud i under transforms[16 i .. 16 i + 16) (inT * cn->transform() as a float isometry, :81-85; the
+ * per-point arithmetic of Cloud::transformInPlace, never its identity shortcut, which changes no integer computed here), are splatted into `image`,
+ * x_size rows by y_size columns of uint16, host or device memory at any 2-byte alignment.  The image is filled with 30000 first (:72) unless
+ * `accumulate` is not 0; the walk starts from the image's contents either way, so a list may be split over calls.  Per point, in list order and
+ * then in index order (:87-121): cx = (int)(x_size * 0.5), cy likewise, ires = (float)(1. / resolution) (:54-56); x = (int)(cx + p.x * ires) is
+ * the row and y = (int)(cy + p.y * ires) the column (:91-92, :99; product and sum rounded one by one, the conversion truncates toward zero);
+ * outside the grid the point is skipped (:93-98); pz = (int)(10000 - 1000 * p.z) (:100); a cell that holds 65535 or a value below pz keeps it
+ * (:101-108, an int comparison); so does every cell for a normal whose squared norm is below 0.1 (:109, compared in double); otherwise the cell
+ * becomes 65535 where n.z < normal_threshold and (uint16)pz elsewhere (:113-120; the store is modular: a point above 10 m wraps, pz = -1 makes
+ * an obstacle).  A float to int conversion of a NaN or of a magnitude >= 2^31 is undefined in the reference; such a coordinate gives no defined
+ * cell or height here either.  inside (optional, host, n ints): the points of cloud i that fell inside the grid.  One submission on the
+ * context's stream; the host waits once, at the end.  A list above 2^25 points runs as successive chunks of whole clouds that carry the image;
+ * the bits are the same.  Refused with `image` and `inside` untouched: a null argument, n < 0, a cloud of another context, x_size or y_size <= 0,
+ * x_size * y_size > 2^24, a resolution that is not finite or not positive, and -- PWN_HIP_ERR_CAPACITY -- a single cloud above 2^25 points.
+ * n == 0 fills the image (unless `accumulate`) and returns. */
+int pwn_hip_manifold_image(pwn_hip_ctx* ctx, int n, pwn_hip_cloud* const* clouds, const float* transforms /* n x 16 */,
+                           float resolution, int x_size, int y_size, float normal_threshold,
+                           int accumulate, uint16_t* image /* x_size rows x y_size cols, host or device */,
+                           int* inside /* optional, host, n ints: points of cloud i that fell inside the grid */);
 /* VoxelCalculator::compute (voxelcalculator.cpp:15-73): the first point of every voxel survives, output sorted by voxel indices
  * (the intended lexicographic order; the reference's IndexComparator, voxelcalculator.h:41-48, is not a strict weak ordering).
  * kept (optional, host) receives the original indices of the survivors in output order. */

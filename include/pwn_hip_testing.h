@@ -85,6 +85,11 @@ int pwn_hip_debug_trig_eval(pwn_hip_ctx* ctx, int n, const float* y, const float
 int pwn_hip_debug_cloud_set_gaussians(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, int n, const float* mean, const float* cov, const float* info_vec,
                                       const float* info, const int* flags);
 
+/* pwn_hip_manifold_image takes its clouds in chunks of whole clouds with at most 2^25 points and carries the image from chunk to chunk.  This
+ * sets the bound to `points` (<= 0: back to 2^25), so that a small list runs as several chunks; a cloud above the bound is refused as a cloud
+ * above 2^25 is (PWN_HIP_ERR_CAPACITY). */
+int pwn_hip_debug_set_manifold_chunk(pwn_hip_ctx* ctx, int points);
+
 #ifdef __cplusplus
 }
 #endif
