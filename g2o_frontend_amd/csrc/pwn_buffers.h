@@ -1,7 +1,8 @@
 // pwn_buffers.h -- the owner of the library's own device and page-locked host memory: a pointer, a capacity in elements, and a
-// destructor that frees.  Every workspace of pwn_hip_ctx and the index image of a cloud is one of these, so that a buffer is named once (its
-// member) and released without a list to keep in step.  Not owned this way: the per-point arrays of CloudDev (plain pointers the kernels
-// receive and the scene stage swaps; cloud_free) and what pwn_hip_device_alloc / pwn_hip_host_alloc hand to the caller.
+// destructor that frees.  Every workspace of pwn_hip_ctx and every array of a cloud -- its two sets of per-point arrays (CloudArrays), its size
+// word, its index image -- is one of these, so that a buffer is named once (its member) and released without a list to keep in step; CloudDev
+// and SceneBuffers are views of a cloud's owners, made for kernels and descriptors.  Not owned this way: what pwn_hip_device_alloc /
+// pwn_hip_host_alloc hand to the caller.
 #pragma once
 
 #include <hip/hip_runtime.h>

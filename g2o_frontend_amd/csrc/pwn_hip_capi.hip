@@ -85,17 +85,65 @@ struct FinderImages : Slot0Pair {
   void cur_projected() { cur_lazy = false; }      // pwn_hip_align_images has made the projection the alignment skipped
 };
 
+// One side of a cloud's per-point arrays, and their only owner: the core arrays every cloud has, and three optional groups -- explicit normal
+// information matrices (uploaded, imported and scene clouds), Stats (keep_stats conversions, scenes, loaded clouds), the sensor-noise Gaussians
+// with their flags (scene stage).  The elements per point are written here and nowhere else; everything else names groups.
+enum : unsigned { kArrCore = 1, kArrOmN = 2, kArrSt = 4, kArrGauss = 8 };
+struct CloudArrays {
+  DevBuf<float> P3; DevBuf<float4> Nc; DevBuf<float> Om, OmN, St; DevBuf<GaussD> G; DevBuf<int> Gf;
+  // the arrays of the groups `which` for `cap` points; an array that is there stays as it is
+  hipError_t ensure(unsigned which, size_t cap, int sym) {
+    hipError_t e = hipSuccess;
+    auto need = [&](unsigned group, auto& buf, size_t per_point) { if ((which & group) && e == hipSuccess) e = buf.ensure(cap * per_point); };
+    need(kArrCore, P3, 3); need(kArrCore, Nc, 1); need(kArrCore, Om, 3 * (size_t)om_planes(sym));
+    need(kArrOmN, OmN, 9); need(kArrSt, St, 16); need(kArrGauss, G, 1); need(kArrGauss, Gf, 1);
+    return e;
+  }
+  // the groups this side holds anything of
+  unsigned held() const { return ((P3 || Nc || Om) ? kArrCore : 0u) | (OmN ? kArrOmN : 0u) | (St ? kArrSt : 0u) | ((G || Gf) ? kArrGauss : 0u); }
+  size_t core_bytes() const { return P3.cap * sizeof(float) + Nc.cap * sizeof(float4) + Om.cap * sizeof(float); }
+  // The two sides change places after a compaction wrote the other one: the core arrays always, an optional group only where both sides hold it.  A side
+  // without a group stays without: a scene cloud imported from a class-coded one has lost its front OmN and must not get the back's stale planes.
+  void swap(CloudArrays& o) {
+    std::swap(P3, o.P3); std::swap(Nc, o.Nc); std::swap(Om, o.Om);
+    if (OmN && o.OmN) std::swap(OmN, o.OmN);
+    if (St && o.St) std::swap(St, o.St);
+    if (G && o.G) { std::swap(G, o.G); std::swap(Gf, o.Gf); }
+  }
+  void view(CloudDev& d, SceneBuffers& s) const { d.P3 = P3; d.Nc = Nc; d.Om = Om; d.OmN = OmN; d.St = St; s.G = G; s.Gf = Gf; }
+};
+
 }  // namespace
 
 struct pwn_hip_cloud {
-  CloudDev d;
-  int n_host = 0;
-  bool has_stats = false;
-  // scene stage (pwn_scene_capi.h): sensor-noise Gaussians, and a second set of arrays for compactions / reorderings
+  // The owners: the front arrays, the second set the scene stage's compactions / reorderings write before the two change places
+  // (pwn_scene_capi.h), and the size word.  `delete` frees them all.
+  CloudArrays front, back; DevBuf<int> count;
+  // What kernels and descriptors receive by value: the front's pointers beside the cloud's scalar fields, which live here and nowhere else
+  // (capacity, omSym, omN, clsThr).  The pointers are refreshed by the three functions below that change what the front owns, and by nothing else.
+  CloudDev d = {};
   SceneBuffers sb = { nullptr, nullptr };
+  void refresh() { front.view(d, sb); d.count = count; }
+  hipError_t own(unsigned which) {
+    hipError_t e = count.ensure(1);
+    if (e == hipSuccess) e = front.ensure(which, (size_t)d.capacity, d.omSym);
+    refresh();
+    return e;
+  }
+  void drop_omega_n() { front.OmN.release(); refresh(); }      // for a caller that knows no stream still reads the planes
+  void swap_sides() { front.swap(back); refresh(); }
+  // the back set gets the core arrays and whatever optional groups the front holds; bd / bs: its views
+  hipError_t own_back(CloudDev& bd, SceneBuffers& bs) {
+    const hipError_t e = back.ensure(kArrCore | front.held(), (size_t)d.capacity, d.omSym);
+    bd = d; back.view(bd, bs);
+    return e;
+  }
+  // the whole core, the size word and nothing else (but the index image): such a cloud may retire into the context's pool
+  bool plain() const { return front.P3 && front.Nc && front.Om && count && front.held() == kArrCore && back.held() == 0; }
+  size_t core_bytes() const { return front.core_bytes() + idximg.cap * sizeof(int); }      // what the pool's budget counts
+  int n_host = 0;
+  bool has_stats = false;        // St may be allocated while this is false: such call sites pass St = nullptr in the view
   int n_gauss = 0;                       // Cloud::gaussians().size()
-  CloudDev back = {};
-  SceneBuffers sback = { nullptr, nullptr };
   // The index image DepthImageConverter::compute produced for this cloud (written here directly instead of into a workspace), with what
   // it was made from.  Projecting a cloud with the very projector it was unprojected with (same K, size, range, identity pose) returns
   // this image: every point falls back on its own pixel (the round trip moves it by < 0.01 pixel and its depth not at all), so batch
@@ -200,14 +248,6 @@ struct pwn_hip_ctx {
 namespace {
 
 constexpr size_t kCloudPoolBytes = 1ull << 30;
-size_t om_floats(const CloudDev& d) { return (size_t)d.capacity * 3 * (size_t)om_planes(d.omSym); }      // floats of the Om planes (9 or 6 per point)
-size_t cloud_core_bytes(const pwn_hip_cloud* c) { return (size_t)c->d.capacity * (3 * sizeof(float) + sizeof(float4)) + om_floats(c->d) * sizeof(float) + c->idximg.cap * sizeof(int); }
-void cloud_free(pwn_hip_cloud* c) {
-  void* p[] = { c->d.P3, c->d.Nc, c->d.Om, c->d.OmN, c->d.St, c->d.count, c->sb.G, c->sb.Gf,
-                c->back.P3, c->back.Nc, c->back.Om, c->back.OmN, c->back.St, c->sback.G, c->sback.Gf };
-  for (void* q : p) if (q) (void)hipFree(q);
-  delete c;                                   // and with it the index image
-}
 
 // What the aligner's launches for one sub-batch share: the call's parameters and grid (nb workgroups per pair; sym: storage of the current clouds' point
 // information matrices, CloudDev::omSym, the same for every pair), the m consecutive pair descriptors, their stream, and -- when the call runs the
@@ -631,18 +671,29 @@ void fill_frame(pwn_hip_ctx* ctx, int entry, int slot, const float* depth_dev, c
   f.cloud = cl;
   f.count_out = nullptr;
 }
-int ensure_stats(pwn_hip_ctx* ctx, pwn_hip_cloud* c) {
-  if (!c->d.St) HIPCHK(ctx, hipMalloc(&c->d.St, sizeof(float) * 16 * (size_t)c->d.capacity), PWN_HIP_ERR_ALLOCATION);
+// the cloud's front gets the arrays of the groups `which` (kArrSt: keep_stats; kArrOmN: explicit Omega_n planes -- converted clouds keep the two
+// class matrices only; kArrGauss: the scene stage)
+int cloud_own(pwn_hip_ctx* ctx, pwn_hip_cloud* c, unsigned which) {
+  HIPCHK(ctx, c->own(which), PWN_HIP_ERR_ALLOCATION);
   return PWN_HIP_OK;
 }
-// explicit Omega_n planes of a cloud (uploaded, imported and scene clouds; converted clouds keep the two class matrices only).  Dropping
-// them is for a caller that knows no stream still reads them.
-int ensure_omega_n(pwn_hip_ctx* ctx, pwn_hip_cloud* c) {
-  if (!c->d.OmN) HIPCHK(ctx, hipMalloc((void**)&c->d.OmN, (size_t)c->d.capacity * 9 * sizeof(float)), PWN_HIP_ERR_ALLOCATION);
-  return PWN_HIP_OK;
+// The Stats record of a point (CloudDev::St, 16 floats) on the host: the 3x3 block of the matrix column-major at 0..8, the eigenvalues at 9..11, the
+// translation at 12..14, the point count at 15.  To and from Stats as a column-major 4x4 with its eigenvalues and count (stats.h:13-27); the
+// default Stats() is the identity with eigenvalues and count zero.
+void stats_unpack(const float* s, float S[16], float ev[3], int* npts) {
+  for (int q = 0; q < 16; ++q) S[q] = 0.f;
+  for (int r = 0; r < 3; ++r) for (int q = 0; q < 3; ++q) S[r + 4 * q] = s[r + 3 * q];
+  S[12] = s[12]; S[13] = s[13]; S[14] = s[14]; S[15] = 1.0f;
+  ev[0] = s[9]; ev[1] = s[10]; ev[2] = s[11]; *npts = (int)s[15];
 }
-void drop_omega_n(pwn_hip_cloud* c) {
-  if (c->d.OmN) { (void)hipFree(c->d.OmN); c->d.OmN = nullptr; }
+void stats_pack(const float S[16], const float ev[3], int npts, float* s) {
+  for (int r = 0; r < 3; ++r) for (int q = 0; q < 3; ++q) s[r + 3 * q] = S[r + 4 * q];
+  s[12] = S[12]; s[13] = S[13]; s[14] = S[14]; s[9] = ev[0]; s[10] = ev[1]; s[11] = ev[2]; s[15] = (float)npts;
+}
+std::vector<float> default_stats(int n) {
+  std::vector<float> st((size_t)n * 16, 0.f);
+  for (int i = 0; i < n; ++i) { st[(size_t)16 * i] = 1.f; st[(size_t)16 * i + 4] = 1.f; st[(size_t)16 * i + 8] = 1.f; }
+  return st;
 }
 // direct: the kernels of the call have written counts and fault flag into counts_host themselves (FrameDesc::count_out, launch_convert's fault_out)
 // the two halves of sync_and_counts for callers that wait for the stream themselves: queue the copy back of counts + fault flag; digest them
@@ -758,10 +809,10 @@ int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const S
     if (i == 0) cp.omSym = c->d.omSym;
     else if (c->d.omSym != cp.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds of one convert batch must share one omega storage (exact9 / sym6)");
     cloud_changes(ctx, c);
-    if (keep_stats) { if (int rc = ensure_stats(ctx, c)) return rc; }
+    if (keep_stats) { if (int rc = cloud_own(ctx, c, kArrSt)) return rc; }
     c->has_stats = keep_stats != 0;
     c->n_gauss = 0;                              // the cloud's Gaussians (if any) belonged to its previous content
-    if (c->d.OmN) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH); drop_omega_n(c); }
+    if (c->d.OmN) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH); c->drop_omega_n(); }
     make_omega_n_classes(p, c->d);
     job.src[i] = frames[i];
     const float* depth_dev = nullptr;
@@ -905,7 +956,7 @@ int debug_front_end_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, co
   // the kernels; the kernels, their grids and their arguments are the convert call's.
   if (!lean) for (int i = 0; i < n; ++i) {
     HIPCHK(ctx, hipMemsetAsync(clouds[i]->d.Nc, 0, sizeof(float4) * (size_t)clouds[i]->d.capacity, ctx->stream), PWN_HIP_ERR_COPY);
-    HIPCHK(ctx, hipMemsetAsync(clouds[i]->d.Om, 0, sizeof(float) * om_floats(clouds[i]->d), ctx->stream), PWN_HIP_ERR_COPY);
+    HIPCHK(ctx, hipMemsetAsync(clouds[i]->d.Om, 0, sizeof(float) * clouds[i]->front.Om.cap, ctx->stream), PWN_HIP_ERR_COPY);
   }
   if (int rc = launch_front_end(ctx, job.cp, 0, n, ctx->stream, single_pass, direct ? ctx->counts_host + n : nullptr)) return rc;
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
@@ -1188,7 +1239,7 @@ int pwn_hip_ctx_destroy(pwn_hip_ctx* ctx) {
   for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
   if (ctx->t0) (void)hipEventDestroy(ctx->t0);
   if (ctx->t1) (void)hipEventDestroy(ctx->t1);
-  for (pwn_hip_cloud* r : ctx->cloud_pool) cloud_free(r);
+  for (pwn_hip_cloud* r : ctx->cloud_pool) delete r;
   ctx->cloud_pool.clear();
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -1323,11 +1374,11 @@ int pwn_hip_debug_stats_from_integral(pwn_hip_ctx* ctx, const pwn_hip_converter_
   for (int i = 0; i < nframes; ++i) {
     pwn_hip_cloud* c = clouds[i];
     cloud_changes(ctx, c);
-    if (keep_stats) { if (int rc = ensure_stats(ctx, c)) return rc; }
+    if (keep_stats) { if (int rc = cloud_own(ctx, c, kArrSt)) return rc; }
     c->has_stats = keep_stats != 0;
     c->n_gauss = 0;
     c->idx_valid = false;
-    drop_omega_n(c);
+    c->drop_omega_n();
     make_omega_n_classes(p, c->d);
     fill_frame(ctx, i, i, nullptr, c->d);
     const FrameDesc& f = ctx->frames_host[i];
@@ -1373,11 +1424,11 @@ int pwn_hip_debug_stats_from_integral_lean(pwn_hip_ctx* ctx, const pwn_hip_conve
   for (int i = 0; i < nframes; ++i) {
     pwn_hip_cloud* c = clouds[i];
     cloud_changes(ctx, c);
-    if (keep_stats) { if (int rc = ensure_stats(ctx, c)) return rc; }
+    if (keep_stats) { if (int rc = cloud_own(ctx, c, kArrSt)) return rc; }
     c->has_stats = keep_stats != 0;
     c->n_gauss = 0;
     c->idx_valid = false;
-    drop_omega_n(c);
+    c->drop_omega_n();
     make_omega_n_classes(p, c->d);
     fill_frame(ctx, i, i, nullptr, c->d);
     FrameDesc& f = ctx->frames_host[i];
@@ -1525,22 +1576,17 @@ int pwn_hip_cloud_create(pwn_hip_ctx* ctx, int capacity, pwn_hip_cloud** out) {
     pwn_hip_cloud* r = ctx->cloud_pool[k];
     if (r->d.capacity != capacity || r->d.omSym != ctx->omega_sym) continue;
     ctx->cloud_pool.erase(ctx->cloud_pool.begin() + (long)k);
-    ctx->cloud_pool_bytes -= cloud_core_bytes(r);
+    ctx->cloud_pool_bytes -= r->core_bytes();
     HIPCHK(ctx, hipMemsetAsync(r->d.count, 0, sizeof(int), ctx->stream), PWN_HIP_ERR_COPY);      // stream order: after whatever used the retired cloud
     r->owner = ctx;
     *out = r;
     return PWN_HIP_OK;
   }
   pwn_hip_cloud* c = new pwn_hip_cloud();
-  std::memset(&c->d, 0, sizeof(c->d));
   c->d.capacity = capacity;
   c->d.omSym = ctx->omega_sym;
   c->owner = ctx;
-  const size_t cap = (size_t)capacity;
-  hipError_t e = hipMalloc((void**)&c->d.P3, cap * 3 * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&c->d.Nc, cap * sizeof(float4));
-  if (e == hipSuccess) e = hipMalloc((void**)&c->d.Om, om_floats(c->d) * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&c->d.count, sizeof(int));
+  hipError_t e = c->own(kArrCore);
   if (e == hipSuccess) e = hipMemsetAsync(c->d.count, 0, sizeof(int), ctx->stream);
   if (e != hipSuccess) { pwn_hip_cloud_destroy(ctx, c); return fail(ctx, PWN_HIP_ERR_ALLOCATION, std::string("cloud allocation: ") + hipGetErrorString(e)); }
   *out = c;
@@ -1552,16 +1598,14 @@ int pwn_hip_cloud_destroy(pwn_hip_ctx* ctx, pwn_hip_cloud* c) {
   cloud_changes(ctx, c);
   // plain clouds (no scene-stage or uploaded extras) retire into the context's pool: every call that used them has joined its streams
   // back into ctx->stream before returning, and a reuse is enqueued on that stream
-  const bool plain = !c->d.OmN && !c->d.St && !c->sb.G && !c->sb.Gf && !c->back.P3 && !c->back.Nc && !c->back.Om && !c->back.OmN && !c->back.St &&
-                     !c->sback.G && !c->sback.Gf;
-  if (ctx && plain && c->d.P3 && c->d.Nc && c->d.Om && c->d.count && ctx->cloud_pool_bytes + cloud_core_bytes(c) <= kCloudPoolBytes) {
+  if (ctx && c->plain() && ctx->cloud_pool_bytes + c->core_bytes() <= kCloudPoolBytes) {
     c->n_host = 0; c->has_stats = false; c->n_gauss = 0; c->idx_valid = false;
     ctx->cloud_pool.push_back(c);
-    ctx->cloud_pool_bytes += cloud_core_bytes(c);
+    ctx->cloud_pool_bytes += c->core_bytes();
     return PWN_HIP_OK;
   }
   if (ctx) (void)hipStreamSynchronize(ctx->stream);
-  cloud_free(c);
+  delete c;
   return PWN_HIP_OK;
 }
 int pwn_hip_cloud_size(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, int* n) {
@@ -1585,7 +1629,7 @@ int pwn_hip_cloud_upload(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int n, const float*
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_COPY);
   const size_t cap = (size_t)c->d.capacity;
   const int sym = c->d.omSym;
-  std::vector<float> P((size_t)n * 4), Nm((size_t)n * 4), Om(om_floats(c->d), 0.f), OmN(cap * 9, 0.f);
+  std::vector<float> P((size_t)n * 4), Nm((size_t)n * 4), Om(c->front.Om.cap, 0.f), OmN(cap * 9, 0.f);
   for (int i = 0; i < n; ++i) {
     P[4 * i] = hp[4 * i]; P[4 * i + 1] = hp[4 * i + 1]; P[4 * i + 2] = hp[4 * i + 2]; P[4 * i + 3] = hc[i];
     Nm[4 * i] = hn[4 * i]; Nm[4 * i + 1] = hn[4 * i + 1]; Nm[4 * i + 2] = hn[4 * i + 2];
@@ -1595,7 +1639,7 @@ int pwn_hip_cloud_upload(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int n, const float*
       OmN[om_at(cap, i, 3 * r + q)] = hon[(size_t)16 * i + r + 4 * q];
     }
   }
-  if (int rc = ensure_omega_n(ctx, c)) return rc;
+  if (int rc = cloud_own(ctx, c, kArrOmN)) return rc;
   if (int rc = cloud_store_records(ctx, c->d, n, P, Nm)) return rc;
   HIPCHK(ctx, hipMemcpy(c->d.Om, Om.data(), Om.size() * 4, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipMemcpy(c->d.OmN, OmN.data(), OmN.size() * 4, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
@@ -1614,7 +1658,7 @@ int pwn_hip_cloud_download(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, float* poin
   if (normals) { hn.resize((size_t)n * 4); for (int i = 0; i < n; ++i) { hn[4*i] = Nm[4*i]; hn[4*i+1] = Nm[4*i+1]; hn[4*i+2] = Nm[4*i+2]; hn[4*i+3] = 0.0f; } }
   if (curvature) { hc.resize(n); for (int i = 0; i < n; ++i) hc[i] = P[4*i+3]; }
   if (omega_p || omega_n) {
-    std::vector<float> Om(om_floats(c->d)), OmN;
+    std::vector<float> Om(c->front.Om.cap), OmN;
     HIPCHK(ctx, hipMemcpy(Om.data(), c->d.Om, Om.size() * 4, hipMemcpyDeviceToHost), PWN_HIP_ERR_COPY);
     if (c->d.OmN) { OmN.resize(cap * 9); HIPCHK(ctx, hipMemcpy(OmN.data(), c->d.OmN, OmN.size() * 4, hipMemcpyDeviceToHost), PWN_HIP_ERR_COPY); }
     if (omega_p) hop.assign((size_t)n * 16, 0.f);
@@ -1652,14 +1696,11 @@ int pwn_hip_cloud_download_stats(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, float
   if (eigenvalues) he.resize((size_t)n * 3);
   if (npoints) hn.resize(n);
   for (int i = 0; i < n; ++i) {
-    const float* s = &St[(size_t)16 * i];
-    if (stats) {
-      float* o = &hs[(size_t)16 * i];
-      for (int r = 0; r < 3; ++r) for (int q = 0; q < 3; ++q) o[r + 4 * q] = s[r + 3 * q];
-      o[12] = s[12]; o[13] = s[13]; o[14] = s[14]; o[15] = 1.0f;
-    }
-    if (eigenvalues) { he[3 * i] = s[9]; he[3 * i + 1] = s[10]; he[3 * i + 2] = s[11]; }
-    if (npoints) hn[i] = (int)s[15];
+    float S[16], ev[3]; int npts;
+    stats_unpack(&St[(size_t)16 * i], S, ev, &npts);
+    if (stats) std::memcpy(&hs[(size_t)16 * i], S, sizeof(S));
+    if (eigenvalues) std::memcpy(&he[(size_t)3 * i], ev, sizeof(ev));
+    if (npoints) hn[i] = npts;
   }
   if (stats) HIPCHK(ctx, hipMemcpy(stats, hs.data(), hs.size() * 4, hipMemcpyDefault), PWN_HIP_ERR_COPY);
   if (eigenvalues) HIPCHK(ctx, hipMemcpy(eigenvalues, he.data(), he.size() * 4, hipMemcpyDefault), PWN_HIP_ERR_COPY);
@@ -1781,8 +1822,8 @@ int pwn_hip_cloud_import(pwn_hip_ctx* ctx, pwn_hip_cloud* c, const void* src, si
   c->n_host = 0;
   HIPCHK(ctx, hipMemsetAsync(c->d.count, 0, sizeof(int), st), PWN_HIP_ERR_COPY);
   CloudFlatHeader& hp = *(CloudFlatHeader*)ctx->flat_hdr_host.p; hp = h;      // page-locked copy: source of the asynchronous count copy below
-  if (h.hasOmN) { if (int rc = ensure_omega_n(ctx, c)) return rc; }
-  else drop_omega_n(c);                                                         // the stream is idle (synchronised above)
+  if (h.hasOmN) { if (int rc = cloud_own(ctx, c, kArrOmN)) return rc; }
+  else c->drop_omega_n();                                                         // the stream is idle (synchronised above)
   if (idx) HIPCHK(ctx, c->idximg.ensure(npx), PWN_HIP_ERR_ALLOCATION);
   const char* in = (const char*)src;
   if (n > 0) {
@@ -1872,7 +1913,7 @@ int pwn_hip_unproject(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const
   const float* d = nullptr;
   if (int rc = stage_depth(ctx, depth, N, &d)) return rc;
   HIPCHK(ctx, hipMemsetAsync(cloud->d.Nc, 0, sizeof(float4) * (size_t)cloud->d.capacity, ctx->stream), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipMemsetAsync(cloud->d.Om, 0, sizeof(float) * om_floats(cloud->d), ctx->stream), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipMemsetAsync(cloud->d.Om, 0, sizeof(float) * cloud->front.Om.cap, ctx->stream), PWN_HIP_ERR_COPY);
   fill_frame(ctx, 0, 0, d, cloud->d);
   HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev, ctx->frames_host, sizeof(FrameDesc), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
   hipLaunchKernelGGL(k_row_count, dim3(rows, 1), dim3(256), 0, ctx->stream, ctx->frames_dev, cp);

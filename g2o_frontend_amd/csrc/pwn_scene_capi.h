@@ -8,19 +8,11 @@
 
 namespace {
 
-int scene_alloc(pwn_hip_ctx* ctx, void** p, size_t bytes) {
-  if (*p) return PWN_HIP_OK;
-  HIPCHK(ctx, hipMalloc(p, bytes), PWN_HIP_ERR_ALLOCATION);
-  return PWN_HIP_OK;
-}
-// Gaussians of a cloud (24 floats + flags per point)
+// Gaussians of a cloud (24 floats + flags per point); new flags start at zero
 int ensure_gauss(pwn_hip_ctx* ctx, pwn_hip_cloud* c) {
-  const size_t cap = (size_t)c->d.capacity;
-  if (int rc = scene_alloc(ctx, (void**)&c->sb.G, cap * sizeof(GaussD))) return rc;
-  if (!c->sb.Gf) {
-    if (int rc = scene_alloc(ctx, (void**)&c->sb.Gf, cap * sizeof(int))) return rc;
-    HIPCHK(ctx, hipMemsetAsync(c->sb.Gf, 0, cap * sizeof(int), ctx->stream), PWN_HIP_ERR_COPY);
-  }
+  const bool had_flags = c->sb.Gf != nullptr;
+  if (int rc = cloud_own(ctx, c, kArrGauss)) return rc;
+  if (!had_flags) HIPCHK(ctx, hipMemsetAsync(c->sb.Gf, 0, c->front.Gf.cap * sizeof(int), ctx->stream), PWN_HIP_ERR_COPY);
   return PWN_HIP_OK;
 }
 // records [from, to) become default Gaussians, all zero and neither form valid (gaussian.h:16-21; what std::vector::resize appends, cloud.cpp:153):
@@ -33,21 +25,17 @@ int default_gaussians(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int from, int to) {
 }
 // a cloud that receives appended clouds keeps explicit normal information matrices and Stats
 int ensure_scene(pwn_hip_ctx* ctx, pwn_hip_cloud* c, bool with_gauss) {
-  const size_t cap = (size_t)c->d.capacity;
-  if (!c->d.OmN) {
-    float* planes = nullptr;
-    if (int rc = scene_alloc(ctx, (void**)&planes, cap * 9 * sizeof(float))) return rc;
-    if (c->n_host > 0) hipLaunchKernelGGL(k_expand_omega_n, dim3((c->n_host + 255) / 256), dim3(256), 0, ctx->stream, c->d, planes, c->n_host);
-    c->d.OmN = planes;
+  if (!c->d.OmN) {            // the kernel reads normals, curvatures and the two class matrices, not the planes it writes
+    if (int rc = cloud_own(ctx, c, kArrOmN)) return rc;
+    if (c->n_host > 0) hipLaunchKernelGGL(k_expand_omega_n, dim3((c->n_host + 255) / 256), dim3(256), 0, ctx->stream, c->d, c->d.OmN, c->n_host);
   }
   if (!c->d.St) {
-    if (int rc = scene_alloc(ctx, (void**)&c->d.St, cap * 16 * sizeof(float))) return rc;
+    if (int rc = cloud_own(ctx, c, kArrSt)) return rc;
     c->has_stats = false;
   }
   if (!c->has_stats) {        // default Stats() for whatever the cloud already holds
     if (c->n_host > 0) {
-      std::vector<float> st((size_t)c->n_host * 16, 0.f);
-      for (int i = 0; i < c->n_host; ++i) { st[(size_t)16 * i] = 1.f; st[(size_t)16 * i + 4] = 1.f; st[(size_t)16 * i + 8] = 1.f; }
+      const std::vector<float> st = default_stats(c->n_host);
       HIPCHK(ctx, hipMemcpyAsync(c->d.St, st.data(), st.size() * 4, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
       HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_COPY);
     }
@@ -55,28 +43,6 @@ int ensure_scene(pwn_hip_ctx* ctx, pwn_hip_cloud* c, bool with_gauss) {
   }
   if (with_gauss) { if (int rc = ensure_gauss(ctx, c)) return rc; }
   return PWN_HIP_OK;
-}
-// second set of per-point arrays: stable compactions / reorderings write there, then the two sets are swapped
-int ensure_back(pwn_hip_ctx* ctx, pwn_hip_cloud* c) {
-  const size_t cap = (size_t)c->d.capacity;
-  c->back.capacity = c->d.capacity; c->back.count = c->d.count;
-  std::memcpy(c->back.omN, c->d.omN, sizeof(c->d.omN)); c->back.clsThr = c->d.clsThr; c->back.omSym = c->d.omSym;
-  if (int rc = scene_alloc(ctx, (void**)&c->back.P3, cap * 3 * sizeof(float))) return rc;
-  if (int rc = scene_alloc(ctx, (void**)&c->back.Nc, cap * sizeof(float4))) return rc;
-  if (int rc = scene_alloc(ctx, (void**)&c->back.Om, om_floats(c->d) * sizeof(float))) return rc;
-  if (c->d.OmN) { if (int rc = scene_alloc(ctx, (void**)&c->back.OmN, cap * 9 * sizeof(float))) return rc; }
-  if (c->d.St) { if (int rc = scene_alloc(ctx, (void**)&c->back.St, cap * 16 * sizeof(float))) return rc; }
-  if (c->sb.G) {
-    if (int rc = scene_alloc(ctx, (void**)&c->sback.G, cap * sizeof(GaussD))) return rc;
-    if (int rc = scene_alloc(ctx, (void**)&c->sback.Gf, cap * sizeof(int))) return rc;
-  }
-  return PWN_HIP_OK;
-}
-void swap_back(pwn_hip_cloud* c) {
-  std::swap(c->d.P3, c->back.P3); std::swap(c->d.Nc, c->back.Nc); std::swap(c->d.Om, c->back.Om);
-  if (c->d.OmN && c->back.OmN) std::swap(c->d.OmN, c->back.OmN);
-  if (c->d.St && c->back.St) std::swap(c->d.St, c->back.St);
-  if (c->sb.G && c->sback.G) { std::swap(c->sb.G, c->sback.G); std::swap(c->sb.Gf, c->sback.Gf); }
 }
 // context scratch of the scene stage: int arrays of n entries and 64-bit arrays
 int scene_scratch(pwn_hip_ctx* ctx, size_t n_int, size_t n_u64) {
@@ -94,6 +60,23 @@ int exclusive_scan(pwn_hip_ctx* ctx, const int* in, int* out, int n, int* sums, 
   hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, sums, nb, total);
   hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(1024), 0, ctx->stream, out, n, (const int*)sums);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  return PWN_HIP_OK;
+}
+// Stable LSD radix sort of m (key, value) records by the low `bits` bits of the key, 8 bits per pass (k_sort_hist, the scan of the histogram,
+// k_sort_scatter), from (key[0], val[0]) to and fro between the two pairs; *in says which pair holds the result.  hist: 256 ints per block of
+// kSortChunk records, sums: the scan's scratch.
+int radix_sort(pwn_hip_ctx* ctx, unsigned long long* const key[2], int* const val[2], int m, int bits, int* hist, int* sums, int* in) {
+  const int sb_ = (m + kSortChunk - 1) / kSortChunk;
+  int a = 0;
+  for (int pass = 0; 8 * pass < bits && m > 1; ++pass) {
+    const int shift = 8 * pass;
+    hipLaunchKernelGGL(k_sort_hist, dim3(sb_), dim3(256), 0, ctx->stream, (const unsigned long long*)key[a], m, shift, hist, sb_);
+    if (int rc = exclusive_scan(ctx, hist, hist, 256 * sb_, sums, ctx->scene_total + 2)) return rc;
+    hipLaunchKernelGGL(k_sort_scatter, dim3(sb_), dim3(64), 0, ctx->stream, (const unsigned long long*)key[a], (const int*)val[a], m, shift, (const int*)hist, sb_,
+                       key[a ^ 1], val[a ^ 1]);
+    a ^= 1;
+  }
+  *in = a;
   return PWN_HIP_OK;
 }
 
@@ -218,7 +201,8 @@ int pwn_hip_merge(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, const float K[9], cons
   if (n > kMaxCloudPoints) return fail(ctx, PWN_HIP_ERR_CAPACITY, "cloud has more points than the z-buffer index field holds (2^25)");
   if (!cloud->sb.G || cloud->n_gauss < n) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "Merger::merge needs the cloud's Gaussians (pwn_hip_cloud_gaussians)");
   if (n == 0) { if (new_size) *new_size = 0; return PWN_HIP_OK; }
-  if (int rc = ensure_back(ctx, cloud)) return rc;
+  CloudDev back; SceneBuffers sback;      // the second array set: the stable compaction / reordering writes there, then the two sets change places
+  HIPCHK(ctx, cloud->own_back(back, sback), PWN_HIP_ERR_ALLOCATION);
   if (int rc = scene_scratch(ctx, (size_t)n, 0)) return rc;
   int* d_collapsed = ctx->scene_i[0]; int* d_head = ctx->scene_i[1]; int* d_next = ctx->scene_i[2]; int* d_keep = ctx->scene_i[3];
   int* d_offs = ctx->scene_i[4]; int* d_sums = ctx->scene_i[5];
@@ -235,7 +219,7 @@ int pwn_hip_merge(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, const float K[9], cons
   hipLaunchKernelGGL(k_merge_accumulate, dim3(nb), dim3(256), 0, st, cloud->d, cloud->sb, n, (const int*)d_collapsed, (const int*)d_head, (const int*)d_next);
   hipLaunchKernelGGL(k_merge_keep_flags, dim3(nb), dim3(256), 0, st, (const int*)d_collapsed, n, d_keep);
   if (int rc = exclusive_scan(ctx, d_keep, d_offs, n, d_sums, ctx->scene_total)) return rc;
-  hipLaunchKernelGGL(k_merge_compact, dim3(nb), dim3(256), 0, st, cloud->d, cloud->sb, cloud->back, cloud->sback, n, cloud->n_gauss, (const int*)d_keep, (const int*)d_offs);
+  hipLaunchKernelGGL(k_merge_compact, dim3(nb), dim3(256), 0, st, cloud->d, cloud->sb, back, sback, n, cloud->n_gauss, (const int*)d_keep, (const int*)d_offs);
   hipLaunchKernelGGL(k_set_count, dim3(1), dim3(1), 0, st, cloud->d.count, (const int*)ctx->scene_total);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   int k = 0;
@@ -243,9 +227,9 @@ int pwn_hip_merge(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, const float K[9], cons
   if (collapsed) HIPCHK(ctx, hipMemcpyAsync(collapsed, d_collapsed, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
   // the Gaussian vector is compacted but not resized (merger.cpp:108-112): its tail keeps the old entries
-  if (cloud->n_gauss > k) hipLaunchKernelGGL(k_gauss_copy_tail, dim3((cloud->n_gauss - k + 255) / 256), dim3(256), 0, st, cloud->sb, cloud->sback, k, cloud->n_gauss);
+  if (cloud->n_gauss > k) hipLaunchKernelGGL(k_gauss_copy_tail, dim3((cloud->n_gauss - k + 255) / 256), dim3(256), 0, st, cloud->sb, sback, k, cloud->n_gauss);
   HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
-  swap_back(cloud);
+  cloud->swap_sides();
   cloud->n_host = k; cloud->idx_valid = false;
   ctx->img.invalidate();                  // slot 0 of the z-buffer was used
   if (new_size) *new_size = k;
@@ -407,8 +391,8 @@ int pwn_hip_manifold_image(pwn_hip_ctx* ctx, int n, pwn_hip_cloud* const* clouds
     }
     HIPCHK(ctx, hipMemcpyAsync(ctx->manifold_dev.p, ctx->manifold_host.p, sizeof(ManifoldCloud) * (size_t)n, hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
   }
-  unsigned long long* d_keyA = ctx->scene_k[0]; unsigned long long* d_keyB = ctx->scene_k[1];
-  int* d_valA = ctx->scene_i[0]; int* d_valB = ctx->scene_i[1]; int* d_hist = ctx->scene_i[2]; int* d_sums = ctx->scene_i[3]; int* d_start = ctx->scene_i[4];
+  unsigned long long* const d_key[2] = { ctx->scene_k[0], ctx->scene_k[1] };
+  int* const d_val[2] = { ctx->scene_i[0], ctx->scene_i[1] }; int* d_hist = ctx->scene_i[2]; int* d_sums = ctx->scene_i[3]; int* d_start = ctx->scene_i[4];
   int cellBits = 0;                                  // bits of the largest cell id, x_size * y_size (the cell of the points that make no event): at most 25,
                                                      // so at most four passes, all within the key's low word, below the flag (kManifoldBadBit)
   while ((cells >> cellBits) != 0) ++cellBits;
@@ -416,19 +400,13 @@ int pwn_hip_manifold_image(pwn_hip_ctx* ctx, int n, pwn_hip_cloud* const* clouds
     const int m = (int)k.points;
     if (m == 0) continue;
     hipLaunchKernelGGL(k_manifold_events, dim3((k.largest + 255) / 256, k.last - k.first), dim3(256), 0, st, (const ManifoldCloud*)(ctx->manifold_dev.p + k.first), g,
-                       d_keyA, d_valA, d_inside + k.first);
-    // stable LSD radix sort by cell: a cell's events stay in cloud order, then index order
-    const int sb_ = (m + kSortChunk - 1) / kSortChunk;
-    for (int pass = 0; 8 * pass < cellBits && m > 1; ++pass) {
-      const int shift = 8 * pass;
-      hipLaunchKernelGGL(k_sort_hist, dim3(sb_), dim3(256), 0, st, (const unsigned long long*)d_keyA, m, shift, d_hist, sb_);
-      if (int rc = exclusive_scan(ctx, d_hist, d_hist, 256 * sb_, d_sums, ctx->scene_total + 2)) return rc;
-      hipLaunchKernelGGL(k_sort_scatter, dim3(sb_), dim3(64), 0, st, (const unsigned long long*)d_keyA, (const int*)d_valA, m, shift, (const int*)d_hist, sb_, d_keyB, d_valB);
-      std::swap(d_keyA, d_keyB); std::swap(d_valA, d_valB);
-    }
+                       d_key[0], d_val[0], d_inside + k.first);
+    // sorted by cell, stable: a cell's events stay in cloud order, then index order
+    int s = 0;
+    if (int rc = radix_sort(ctx, d_key, d_val, m, cellBits, d_hist, d_sums, &s)) return rc;
     HIPCHK(ctx, hipMemsetAsync(d_start, 0xFF, sizeof(int) * (size_t)cells, st), PWN_HIP_ERR_COPY);
-    hipLaunchKernelGGL(k_manifold_starts, dim3((m + 255) / 256), dim3(256), 0, st, (const unsigned long long*)d_keyA, m, cells, d_start);
-    hipLaunchKernelGGL(k_manifold_cells, dim3((cells + 3) / 4), dim3(256), 0, st, (const unsigned long long*)d_keyA, (const int*)d_valA, m, cells, (const int*)d_start, img);
+    hipLaunchKernelGGL(k_manifold_starts, dim3((m + 255) / 256), dim3(256), 0, st, (const unsigned long long*)d_key[s], m, cells, d_start);
+    hipLaunchKernelGGL(k_manifold_cells, dim3((cells + 3) / 4), dim3(256), 0, st, (const unsigned long long*)d_key[s], (const int*)d_val[s], m, cells, (const int*)d_start, img);
     HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   }
   if (img != image) HIPCHK(ctx, hipMemcpyAsync(ctx->manifold_img_host.p, img, sizeof(uint16_t) * (size_t)cells, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
@@ -452,13 +430,14 @@ int pwn_hip_voxelize(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, float resolution, i
   cloud_changes(ctx, cloud);
   const int n = cloud->n_host;
   if (n == 0) { if (new_size) *new_size = 0; return PWN_HIP_OK; }
-  if (int rc = ensure_back(ctx, cloud)) return rc;
+  CloudDev back; SceneBuffers sback;      // the second array set: the stable compaction / reordering writes there, then the two sets change places
+  HIPCHK(ctx, cloud->own_back(back, sback), PWN_HIP_ERR_ALLOCATION);
   size_t table = 1024; while (table < 2 * (size_t)n) table <<= 1;
   const int nblocksSort = (n + kSortChunk - 1) / kSortChunk;
   if (int rc = scene_scratch(ctx, std::max(table, (size_t)256 * nblocksSort + 1024), std::max(table, (size_t)n))) return rc;
   int* d_first = ctx->scene_i[0]; int* d_slot = ctx->scene_i[1]; int* d_keep = ctx->scene_i[2]; int* d_offs = ctx->scene_i[3]; int* d_sums = ctx->scene_i[4];
-  int* d_idxA = ctx->scene_i[5]; int* d_idxB = ctx->scene_i[6]; int* d_hist = ctx->scene_i[7];
-  unsigned long long* d_table = ctx->scene_k[0]; unsigned long long* d_keyA = ctx->scene_k[1]; unsigned long long* d_keyB = ctx->scene_k[2];
+  int* const d_idx[2] = { ctx->scene_i[5], ctx->scene_i[6] }; int* d_hist = ctx->scene_i[7];
+  unsigned long long* d_table = ctx->scene_k[0]; unsigned long long* const d_key[2] = { ctx->scene_k[1], ctx->scene_k[2] };
   hipStream_t st = ctx->stream;
   const float inverseResolution = 1.0f / resolution;
   const int nb = (n + 255) / 256;
@@ -469,29 +448,24 @@ int pwn_hip_voxelize(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, float resolution, i
   hipLaunchKernelGGL(k_voxel_insert, dim3(nb), dim3(256), 0, st, cloud->d, n, inverseResolution, d_table, d_first, (unsigned)(table - 1), d_slot, d_fault);
   hipLaunchKernelGGL(k_voxel_survivors, dim3(nb), dim3(256), 0, st, n, (const int*)d_slot, (const int*)d_first, d_keep);
   if (int rc = exclusive_scan(ctx, d_keep, d_offs, n, d_sums, ctx->scene_total)) return rc;
-  hipLaunchKernelGGL(k_voxel_records, dim3(nb), dim3(256), 0, st, cloud->d, n, inverseResolution, (const int*)d_keep, (const int*)d_offs, d_keyA, d_idxA);
+  hipLaunchKernelGGL(k_voxel_records, dim3(nb), dim3(256), 0, st, cloud->d, n, inverseResolution, (const int*)d_keep, (const int*)d_offs, d_key[0], d_idx[0]);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   int hostv[2] = { 0, 0 };
   HIPCHK(ctx, hipMemcpyAsync(hostv, ctx->scene_total, 2 * sizeof(int), hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
   if (hostv[1] != 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, hostv[1] == 1 ? "voxel index outside +-2^20 (or NaN point)" : "voxel table full");
   const int m = hostv[0];
-  // LSD radix sort of the survivors by their 63-bit voxel key (8 passes of 8 bits), stable -> lexicographic (ix, iy, iz) order
-  const int sb_ = (m + kSortChunk - 1) / kSortChunk;
-  for (int pass = 0; pass < 8 && m > 1; ++pass) {
-    const int shift = 8 * pass;
-    hipLaunchKernelGGL(k_sort_hist, dim3(sb_), dim3(256), 0, st, (const unsigned long long*)d_keyA, m, shift, d_hist, sb_);
-    if (int rc = exclusive_scan(ctx, d_hist, d_hist, 256 * sb_, d_sums, ctx->scene_total + 2)) return rc;
-    hipLaunchKernelGGL(k_sort_scatter, dim3(sb_), dim3(64), 0, st, (const unsigned long long*)d_keyA, (const int*)d_idxA, m, shift, (const int*)d_hist, sb_, d_keyB, d_idxB);
-    std::swap(d_keyA, d_keyB); std::swap(d_idxA, d_idxB);
-  }
+  // the survivors sorted by their 63-bit voxel key (8 passes of 8 bits), stable -> lexicographic (ix, iy, iz) order
+  int s = 0;
+  if (int rc = radix_sort(ctx, d_key, d_idx, m, 64, d_hist, d_sums, &s)) return rc;
+  const int* d_order = d_idx[s];
   const bool withGauss = cloud->sb.G && cloud->n_gauss == n;          // voxelcalculator.cpp:62-64
-  if (m > 0) hipLaunchKernelGGL(k_voxel_gather, dim3((m + 255) / 256), dim3(256), 0, st, cloud->d, cloud->sb, cloud->back, cloud->sback, m, withGauss ? 1 : 0, (const int*)d_idxA);
+  if (m > 0) hipLaunchKernelGGL(k_voxel_gather, dim3((m + 255) / 256), dim3(256), 0, st, cloud->d, cloud->sb, back, sback, m, withGauss ? 1 : 0, d_order);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   HIPCHK(ctx, hipMemcpyAsync(cloud->d.count, &m, sizeof(int), hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
-  if (kept && m > 0) HIPCHK(ctx, hipMemcpyAsync(kept, d_idxA, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
+  if (kept && m > 0) HIPCHK(ctx, hipMemcpyAsync(kept, d_order, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
-  swap_back(cloud);
+  cloud->swap_sides();
   cloud->n_host = m; cloud->idx_valid = false;
   cloud->n_gauss = withGauss ? m : 0;
   if (new_size) *new_size = m;
@@ -515,15 +489,9 @@ int pwn_hip_cloud_save(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, const char* fil
   float tv[6]; t2v(mat4_from(T), tv);
   os << tv[0] << " " << tv[1] << " " << tv[2] << " " << tv[3] << " " << tv[4] << " " << tv[5] << " " << std::endl;
   for (int i = 0; i < n; i += step) {
-    float S[16];                                     // Stats as a row/column-indexed 4x4 (column-major here)
-    for (int q = 0; q < 16; ++q) S[q] = 0.f;
+    float S[16] = { 0.f };                           // Stats as a row/column-indexed 4x4 (column-major here); all zero for a cloud without Stats
     int npts = 0; float ev[3] = { 0.f, 0.f, 0.f };
-    if (!St.empty()) {
-      const float* s = &St[(size_t)16 * i];
-      for (int r = 0; r < 3; ++r) for (int q = 0; q < 3; ++q) S[r + 4 * q] = s[r + 3 * q];
-      S[12] = s[12]; S[13] = s[13]; S[14] = s[14]; S[15] = 1.0f;
-      ev[0] = s[9]; ev[1] = s[10]; ev[2] = s[11]; npts = (int)s[15];
-    }
+    if (!St.empty()) stats_unpack(&St[(size_t)16 * i], S, ev, &npts);
     const float* p = &P[(size_t)4 * i]; const float* nm = &Nm[(size_t)4 * i];
     if (!binary) {
       os << "POINTWITHSTATS ";
@@ -569,8 +537,7 @@ int pwn_hip_cloud_load(pwn_hip_ctx* ctx, pwn_hip_cloud* c, const char* filename,
   lst >> tv[0] >> tv[1] >> tv[2] >> tv[3] >> tv[4] >> tv[5];
   const Mat4 T = v2t(tv); std::memcpy(T_out, T.m, sizeof(T.m));
   const int n = (int)numPoints;
-  std::vector<float> P((size_t)n * 4, 0.f), Nm((size_t)n * 4, 0.f), St((size_t)n * 16, 0.f);
-  for (int i = 0; i < n; ++i) { St[(size_t)16 * i] = 1.f; St[(size_t)16 * i + 4] = 1.f; St[(size_t)16 * i + 8] = 1.f; }
+  std::vector<float> P((size_t)n * 4, 0.f), Nm((size_t)n * 4, 0.f), St = default_stats(n);
   size_t k = 0;
   while (k < (size_t)n && is.good()) {
     float S[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
@@ -595,21 +562,19 @@ int pwn_hip_cloud_load(pwn_hip_ctx* ctx, pwn_hip_cloud* c, const char* filename,
     if (!haveCurv) curv = (float)((double)ev[0] / ((double)(ev[0] + ev[1] + ev[2]) + 1e-9));     // stats.h:98-103
     p[3] = curv;
     const int cls = 0; std::memcpy(&nm[3], &cls, 4);
-    float* s = &St[16 * k];
-    for (int r = 0; r < 3; ++r) for (int q = 0; q < 3; ++q) s[r + 3 * q] = S[r + 4 * q];
-    s[12] = S[12]; s[13] = S[13]; s[14] = S[14]; s[9] = ev[0]; s[10] = ev[1]; s[11] = ev[2]; s[15] = (float)npts;
+    stats_pack(S, ev, npts, &St[16 * k]);
     ++k;
   }
   const bool ok = is.good();
-  if (int rc = scene_alloc(ctx, (void**)&c->d.St, (size_t)c->d.capacity * 16 * sizeof(float))) return rc;
+  if (int rc = cloud_own(ctx, c, kArrSt)) return rc;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
   // Cloud::load leaves both information-matrix vectors empty (cloud.cpp:25-82): zero matrices for every point.  The class of the normal
   // information matrix is derived from normal and curvature on the device, so a loaded cloud says "zero" with explicit planes.
-  if (int rc = scene_alloc(ctx, (void**)&c->d.OmN, (size_t)c->d.capacity * 9 * sizeof(float))) return rc;
+  if (int rc = cloud_own(ctx, c, kArrOmN)) return rc;
   if (n > 0) {
     if (int rc = cloud_store_records(ctx, c->d, n, P, Nm)) return rc;
     HIPCHK(ctx, hipMemcpy(c->d.St, St.data(), St.size() * 4, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
-    HIPCHK(ctx, hipMemset(c->d.Om, 0, om_floats(c->d) * sizeof(float)), PWN_HIP_ERR_COPY);
+    HIPCHK(ctx, hipMemset(c->d.Om, 0, c->front.Om.cap * sizeof(float)), PWN_HIP_ERR_COPY);
   }
   HIPCHK(ctx, hipMemset(c->d.OmN, 0, (size_t)c->d.capacity * 9 * sizeof(float)), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipMemcpy(c->d.count, &n, sizeof(int), hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);

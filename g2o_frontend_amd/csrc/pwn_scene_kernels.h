@@ -118,6 +118,22 @@ __device__ __forceinline__ void omega_transform(const Mat4& m, float* om /* row-
 #pragma unroll
     for (int b = 0; b < 3; ++b) om[3 * a + b] = dot3seq(t1[3 * a], m(b,0), t1[3 * a + 1], m(b,1), t1[3 * a + 2], m(b,2));
 }
+// StatsVector::transformInPlace on one Stats record (CloudDev::St: the 3x3 block column-major at 0..8, the translation at 12..14): m * S (stats.h:125-131)
+__device__ __forceinline__ void stats_transform(const Mat4& m, float* st) {
+  Mat4 S = mat4_identity();
+  for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) S(a,b) = st[a + 3 * b];
+  S(0,3) = st[12]; S(1,3) = st[13]; S(2,3) = st[14];
+  const Mat4 R = mat4_mul(m, S);
+  for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) st[a + 3 * b] = R(a,b);
+  st[12] = R(0,3); st[13] = R(1,3); st[14] = R(2,3);
+}
+// the default Gaussian, all zero and neither form valid (gaussian.h:16-21), as record o
+__device__ __forceinline__ void gauss_store_default(const SceneBuffers& sb, int o) {
+  GaussD g;
+  for (int k = 0; k < 3; ++k) g.mean[k] = g.infoVec[k] = 0.f;
+  for (int k = 0; k < 9; ++k) g.cov[k] = g.info[k] = 0.f;
+  sb.G[o] = g; sb.Gf[o] = 0;
+}
 // Point i of src, transformed by m (not at all when `identity`), stored as point o of dst: every per-point array Cloud::add carries.  The one
 // definition of that arithmetic: k_cloud_append (Cloud::add) and k_merge_clouds_append (Merger2::merge's push_backs) both call it.
 __device__ __forceinline__ void cloud_append_point(const CloudDev& dst, const SceneBuffers& dsb, const CloudDev& src, const SceneBuffers& ssb, int i, int o,
@@ -163,14 +179,7 @@ __device__ __forceinline__ void cloud_append_point(const CloudDev& dst, const Sc
       for (int q = 0; q < 16; ++q) st[q] = 0.f;
       st[0] = st[4] = st[8] = 1.f;
     }
-    if (!identity) {  // StatsVector::transformInPlace: m * S (stats.h:125-131)
-      Mat4 S = mat4_identity();
-      for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) S(a,b) = st[a + 3 * b];
-      S(0,3) = st[12]; S(1,3) = st[13]; S(2,3) = st[14];
-      const Mat4 R = mat4_mul(m, S);
-      for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) st[a + 3 * b] = R(a,b);
-      st[12] = R(0,3); st[13] = R(1,3); st[14] = R(2,3);
-    }
+    if (!identity) stats_transform(m, st);
 #pragma unroll
     for (int q = 0; q < 16; ++q) dst.St[(size_t)o * 16 + q] = st[q];
   }
@@ -190,15 +199,7 @@ __global__ void __launch_bounds__(256) k_cloud_append(CloudDev dst, SceneBuffers
 __global__ void __launch_bounds__(256) k_scene_transform(CloudDev cl, SceneBuffers sb, int n, int ngauss, Mat4 m) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < ngauss && sb.G) { GaussD g = sb.G[i]; int flags = sb.Gf[i]; gauss_transform(g, flags, m); sb.G[i] = g; sb.Gf[i] = flags; }
-  if (i < n && cl.St) {
-    float* st = cl.St + (size_t)i * 16;
-    Mat4 S = mat4_identity();
-    for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) S(a,b) = st[a + 3 * b];
-    S(0,3) = st[12]; S(1,3) = st[13]; S(2,3) = st[14];
-    const Mat4 R = mat4_mul(m, S);
-    for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) st[a + 3 * b] = R(a,b);
-    st[12] = R(0,3); st[13] = R(1,3); st[14] = R(2,3);
-  }
+  if (i < n && cl.St) stats_transform(m, cl.St + (size_t)i * 16);
 }
 // class-coded normal information -> 9 explicit planes (a cloud that becomes a scene)
 __global__ void __launch_bounds__(256) k_expand_omega_n(CloudDev cl, float* __restrict__ out, int n) {
@@ -282,12 +283,10 @@ __global__ void __launch_bounds__(256) k_merge_keep_flags(const int* __restrict_
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) { const int c = collapsed[i]; keep[i] = (c < 0 || c == i) ? 1 : 0; }
 }
-// stable compaction: point i with keep[i] moves to offs[i] in the destination arrays
-__global__ void __launch_bounds__(256) k_merge_compact(CloudDev src, SceneBuffers ssb, CloudDev dst, SceneBuffers dsb, int n, int ngauss,
-                                                       const int* __restrict__ keep, const int* __restrict__ offs) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n || !keep[i]) return;
-  const int o = offs[i];
+// Record i of one array set becomes record o of another, unchanged: the optional arrays where both sets have them, the Gaussian when `gauss`.
+// What the compaction of a merge and the gather of a voxelization do to a point.
+__device__ __forceinline__ void cloud_move_point(const CloudDev& src, const SceneBuffers& ssb, int i, const CloudDev& dst, const SceneBuffers& dsb, int o,
+                                                 bool gauss) {
   { const float4 p = load_xyz(src.P3, i); store_xyz(dst.P3, o, p.x, p.y, p.z); dst.Nc[o] = src.Nc[i]; }
 #pragma unroll
   for (int q = 0; q < 9; ++q) {
@@ -298,7 +297,14 @@ __global__ void __launch_bounds__(256) k_merge_compact(CloudDev src, SceneBuffer
 #pragma unroll
     for (int q = 0; q < 16; ++q) dst.St[(size_t)o * 16 + q] = src.St[(size_t)i * 16 + q];
   }
-  if (ssb.G && dsb.G && i < ngauss) { dsb.G[o] = ssb.G[i]; dsb.Gf[o] = ssb.Gf[i]; }
+  if (gauss) { dsb.G[o] = ssb.G[i]; dsb.Gf[o] = ssb.Gf[i]; }
+}
+// stable compaction: point i with keep[i] moves to offs[i] in the destination arrays
+__global__ void __launch_bounds__(256) k_merge_compact(CloudDev src, SceneBuffers ssb, CloudDev dst, SceneBuffers dsb, int n, int ngauss,
+                                                       const int* __restrict__ keep, const int* __restrict__ offs) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n || !keep[i]) return;
+  cloud_move_point(src, ssb, i, dst, dsb, offs[i], ssb.G && dsb.G && i < ngauss);
 }
 // the reference does not resize the Gaussian vector after a merge (merger.cpp:108-112): entries [k, ngauss) keep their old values
 __global__ void __launch_bounds__(256) k_gauss_copy_tail(SceneBuffers ssb, SceneBuffers dsb, int from, int to) {
@@ -414,12 +420,7 @@ __global__ void __launch_bounds__(256) k_merge_clouds_append(CloudDev tot, Scene
   const int i = zkey_index(kc, tag);
   if (i < 0 || i >= src.capacity) return;
   cloud_append_point(tot, tsb, src, ssb, i, o, ngauss, m, 0);
-  if (tsb.G && !(ssb.G && i < ngauss)) {       // a source without Gaussians: the default Gaussian, neither form valid
-    GaussD g;
-    for (int k = 0; k < 3; ++k) g.mean[k] = g.infoVec[k] = 0.f;
-    for (int k = 0; k < 9; ++k) g.cov[k] = g.info[k] = 0.f;
-    tsb.G[o] = g; tsb.Gf[o] = 0;
-  }
+  if (tsb.G && !(ssb.G && i < ngauss)) gauss_store_default(tsb, o);       // a source without Gaussians
   weights[o] = 1.0f / zkey_depth(kc, tag);
 }
 __global__ void k_merge_clouds_count(int* count, const int* total, int* appended) { *count += *total; *appended = *total; }
@@ -510,18 +511,7 @@ __global__ void __launch_bounds__(256) k_voxel_gather(CloudDev src, SceneBuffers
                                                       const int* __restrict__ order) {
   const int o = blockIdx.x * 256 + threadIdx.x;
   if (o >= m) return;
-  const int i = order[o];
-  { const float4 p = load_xyz(src.P3, i); store_xyz(dst.P3, o, p.x, p.y, p.z); dst.Nc[o] = src.Nc[i]; }
-#pragma unroll
-  for (int q = 0; q < 9; ++q) {
-    if (!(dst.omSym && om_is_lower(q))) dst.Om[omp_at(dst.capacity, o, q, dst.omSym)] = src.Om[omp_at(src.capacity, i, q, src.omSym)];
-    if (src.OmN && dst.OmN) dst.OmN[om_at(dst.capacity, o, q)] = src.OmN[om_at(src.capacity, i, q)];
-  }
-  if (src.St && dst.St) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) dst.St[(size_t)o * 16 + q] = src.St[(size_t)i * 16 + q];
-  }
-  if (withGauss) { dsb.G[o] = ssb.G[i]; dsb.Gf[o] = ssb.Gf[i]; }
+  cloud_move_point(src, ssb, order[o], dst, dsb, o, withGauss != 0);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -328,12 +328,11 @@ def test_product_sources_carry_no_compile_time_or_environment_switches():
     assert not [x for x in build.FLAGS if x.startswith("-D")]
 
 
-def test_runtime_allocation_calls_live_in_the_buffer_type_and_the_cloud_code_only():
-    """The library's own device and page-locked memory is owned by pwn_buffers.h's buffer type (a member that frees itself: no list in
-    pwn_hip_ctx_destroy to forget it in).  The runtime's four allocation / free calls may appear only there, in the four entry points that
-    hand memory to the caller, and in the functions that own a cloud's CloudDev arrays; a raw call anywhere else fails here."""
-    allowed = {"pwn_hip_device_alloc", "pwn_hip_device_free", "pwn_hip_host_alloc", "pwn_hip_host_free",
-               "pwn_hip_cloud_create", "cloud_free", "ensure_stats", "ensure_omega_n", "drop_omega_n", "scene_alloc"}
+def test_runtime_allocation_calls_live_in_the_buffer_type_and_the_caller_facing_entry_points_only():
+    """The library's own device and page-locked memory -- a cloud's arrays included -- is owned by pwn_buffers.h's buffer type (a member that
+    frees itself: no list in pwn_hip_ctx_destroy or in a cloud's destruction to forget it in).  The runtime's four allocation / free calls may
+    appear only there and in the four entry points that hand memory to the caller; a raw call anywhere else fails here."""
+    allowed = {"pwn_hip_device_alloc", "pwn_hip_device_free", "pwn_hip_host_alloc", "pwn_hip_host_free"}
     call = re.compile(r"\bhip(Malloc|Free|HostMalloc|HostFree)\s*\(")
     d = os.path.join(ROOT, "g2o_frontend_amd", "csrc")
     seen = set()
