@@ -113,6 +113,28 @@ struct CloudArrays {
   void view(CloudDev& d, SceneBuffers& s) const { d.P3 = P3; d.Nc = Nc; d.Om = Om; d.OmN = OmN; d.St = St; s.G = G; s.Gf = Gf; }
 };
 
+// What a cloud's arrays hold at this moment.  The fields are assigned in this struct and nowhere else (tests/test_capi_cpu.py); its functions are
+// called by the three transitions of a cloud's content -- cloud_replace, cloud_commit, cloud_edit -- by a conversion job that ends without a commit,
+// and by the two setters' callers (the Gaussian calls, ensure_scene).  Everything else reads.
+struct CloudContent {
+  int n = 0;                     // points, as the host knows them (pwn_hip_cloud_size); the device keeps a word of its own (pwn_hip_cloud::count)
+  bool stats = false;            // St holds the Stats of these points (St may be allocated while this is false: see pwn_hip_cloud::view)
+  int n_gauss = 0;               // Cloud::gaussians().size(): the records [0, n_gauss) of G / Gf
+  // idximg is what projecting these points with idx_key's projector under the identity pose gives (see pwn_hip_cloud::idximg).  Between the replace
+  // and the commit of a conversion it is a promise: the fused step describes its pairs, shortcut included, before its conversions have run.
+  bool idx_valid = false; IndexKey idx_key;
+  void replace(bool keep_stats, const IndexKey* key, bool promised) { n = 0; stats = keep_stats; n_gauss = 0; idx_valid = promised; if (key) idx_key = *key; }
+  void commit(int points) { n = points; }                                                        // a promised index key stands
+  void commit(int points, const IndexKey& key) { n = points; idx_valid = true; idx_key = key; }  // the index image arrived with the points
+  void withdraw() { n = 0; stats = false; n_gauss = 0; idx_valid = false; }                      // the new content did not arrive: an empty cloud
+  void edit(int points) { n = points; idx_valid = false; }
+  void set_gaussians(int count) { n_gauss = count; }
+  void set_stats() { stats = true; }
+};
+// What a kernel gets of a cloud it only reads: the by-value records with St only where the content has Stats, the size, and the Gaussians a
+// consumer may read -- `gauss` of the vector, point_gauss() of them for the cloud's points
+struct CloudView { CloudDev d; SceneBuffers sb; int n, gauss; int point_gauss() const { return std::min(gauss, n); } };
+
 }  // namespace
 
 struct pwn_hip_cloud {
@@ -141,14 +163,14 @@ struct pwn_hip_cloud {
   // the whole core, the size word and nothing else (but the index image): such a cloud may retire into the context's pool
   bool plain() const { return front.P3 && front.Nc && front.Om && count && front.held() == kArrCore && back.held() == 0; }
   size_t core_bytes() const { return front.core_bytes() + idximg.cap * sizeof(int); }      // what the pool's budget counts
-  int n_host = 0;
-  bool has_stats = false;        // St may be allocated while this is false: such call sites pass St = nullptr in the view
-  int n_gauss = 0;                       // Cloud::gaussians().size()
-  // The index image DepthImageConverter::compute produced for this cloud (written here directly instead of into a workspace), with what
-  // it was made from.  Projecting a cloud with the very projector it was unprojected with (same K, size, range, identity pose) returns
-  // this image: every point falls back on its own pixel (the round trip moves it by < 0.01 pixel and its depth not at all), so batch
+  // What the arrays mean right now; the owners above say nothing about that
+  CloudContent content;
+  CloudView view() const { CloudView v = { d, sb, content.n, sb.G ? content.n_gauss : 0 }; if (!content.stats) v.d.St = nullptr; return v; }
+  // The index image DepthImageConverter::compute produced for this cloud (written here directly instead of into a workspace); what it was
+  // made from is content.idx_key.  Projecting a cloud with the very projector it was unprojected with (same K, size, range, identity pose)
+  // returns this image: every point falls back on its own pixel (the round trip moves it by < 0.01 pixel and its depth not at all), so batch
   // alignments take it as the current index image and skip that projection.  Anything that changes the points invalidates it.
-  DevBuf<int> idximg; bool idx_valid = false; IndexKey idx_key;
+  DevBuf<int> idximg;
   const pwn_hip_ctx* owner = nullptr;    // the context it was created on (pwn_hip_project_merge_batch refuses another context's cloud)
 };
 
@@ -451,21 +473,28 @@ ConvertParams make_convert_params(const pwn_hip_ctx* ctx, const pwn_hip_converte
   cp.omSym = 0;        // set per call from the clouds being written (convert_batch_impl)
   return cp;
 }
-// class matrices of the normal information matrix, after Cloud::transformInPlace (T * Omega * T^t, informationmatrix.h:111-121)
-void make_omega_n_classes(const pwn_hip_converter_params* p, CloudDev& d) {
+// T * Omega * T^t of a row-major 3x3 under the rotation of m, in place (informationmatrix.h:111-121)
+void transform_omega(const Mat4& m, float om[9]) {
+  float t1[9], o2[9];
+  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) t1[3 * i + j] = dot3seq(m(i,0), om[0 + j], m(i,1), om[3 + j], m(i,2), om[6 + j]);
+  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) o2[3 * i + j] = dot3seq(t1[3 * i], m(j,0), t1[3 * i + 1], m(j,1), t1[3 * i + 2], m(j,2));
+  std::memcpy(om, o2, sizeof(o2));
+}
+// The two class matrices that stand for a cloud's normal information matrices where it keeps no explicit planes (CloudDev::omN, clsThr)
+struct OmegaNClasses { float omN[2][9]; float clsThr; };
+// ... of a conversion: the calculator's diagonals after Cloud::transformInPlace(sensorOffset)
+OmegaNClasses make_omega_n_classes(const pwn_hip_converter_params* p) {
+  OmegaNClasses o;
   const Mat4 m = forced(p->sensor_offset);
   const bool ident = is_identity(m);
   for (int c = 0; c < 2; ++c) {
     const float* dg = c == 0 ? p->normal_flat_diag : p->normal_nonflat_diag;
-    float om[9] = { dg[0], 0, 0, 0, dg[1], 0, 0, 0, dg[2] };
-    if (!ident) {
-      float t1[9];
-      for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) t1[3 * i + j] = dot3seq(m(i,0), om[0 + j], m(i,1), om[3 + j], m(i,2), om[6 + j]);
-      for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) om[3 * i + j] = dot3seq(t1[3 * i], m(j,0), t1[3 * i + 1], m(j,1), t1[3 * i + 2], m(j,2));
-    }
-    for (int k = 0; k < 9; ++k) d.omN[c][k] = om[k];
+    const float om[9] = { dg[0], 0, 0, 0, dg[1], 0, 0, 0, dg[2] };
+    std::memcpy(o.omN[c], om, sizeof(om));
+    if (!ident) transform_omega(m, o.omN[c]);
   }
-  d.clsThr = p->normal_info_curvature_threshold;      // what normal_class() needs to tell flat from non-flat
+  o.clsThr = p->normal_info_curvature_threshold;      // what normal_class() needs to tell flat from non-flat
+  return o;
 }
 // Host staging in the records the rest of the host code was written for: P = (x, y, z, curvature), Nm = (nx, ny, nz, class word), n
 // points each; the device keeps 12-byte points and (normal, curvature) records (pwn_kernels.h).
@@ -677,6 +706,30 @@ int cloud_own(pwn_hip_ctx* ctx, pwn_hip_cloud* c, unsigned which) {
   HIPCHK(ctx, c->own(which), PWN_HIP_ERR_ALLOCATION);
   return PWN_HIP_OK;
 }
+// ---- the three transitions of a cloud's content (CloudContent); every entry point that writes a cloud says which one it is ----
+// Replace: the cloud is about to receive new points from outside.  What it held is gone from here on -- it reads as empty, without Gaussians and,
+// unless the caller promises that the points will arrive with the index image of `key`, without an index image -- and the arrays of what is coming
+// are there: St when Stats are kept; for the normal information matrices the explicit planes (`planes`), or no planes and the class matrices
+// `cls` (nullptr: as they are).  Planes are dropped after a wait for the stream, which may still read them; the wait happens only then.
+// (`key` without the promise: what the index image is being made with, kept beside an image that is not valid -- the flat form carries it.)
+int cloud_replace(pwn_hip_ctx* ctx, pwn_hip_cloud* c, bool keep_stats, bool planes, const OmegaNClasses* cls, const IndexKey* key = nullptr, bool promised = false) {
+  cloud_changes(ctx, c);
+  if (const unsigned which = (keep_stats ? kArrSt : 0u) | (planes ? kArrOmN : 0u)) { if (int rc = cloud_own(ctx, c, which)) return rc; }
+  if (!planes && c->d.OmN) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH); c->drop_omega_n(); }
+  if (cls) { std::memcpy(c->d.omN, cls->omN, sizeof(cls->omN)); c->d.clsThr = cls->clsThr; }
+  c->content.replace(keep_stats, key, promised);
+  return PWN_HIP_OK;
+}
+// Commit: the new content has arrived, `n` points of it; with `key` the index image came with them, without it a promised one stands.  (The
+// device's size word is the kernels' or the caller's copy.)
+void cloud_commit(pwn_hip_cloud* c, int n, const IndexKey* key = nullptr) { if (key) c->content.commit(n, *key); else c->content.commit(n); }
+// Edit: the points changed in place, or their number did: no index image, `n` points.  device_word: the host decided the size, and the device's
+// word follows on the stream, as a fill value, so that nothing is read from host memory after the call returned.
+int cloud_edit(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int n, bool device_word) {
+  c->content.edit(n);
+  if (device_word) HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)c->d.count, n, 1, ctx->stream), PWN_HIP_ERR_COPY);
+  return PWN_HIP_OK;
+}
 // The Stats record of a point (CloudDev::St, 16 floats) on the host: the 3x3 block of the matrix column-major at 0..8, the eigenvalues at 9..11, the
 // translation at 12..14, the point count at 15.  To and from Stats as a column-major 4x4 with its eigenvalues and count (stats.h:13-27); the
 // default Stats() is the identity with eigenvalues and count zero.
@@ -703,15 +756,8 @@ int counts_enqueue(pwn_hip_ctx* ctx, int n) {
   HIPCHK(ctx, hipMemcpyAsync(ctx->counts_host, ctx->counts_dev, sizeof(int) * (n + 1), hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
   return PWN_HIP_OK;
 }
-int counts_apply(pwn_hip_ctx* ctx, pwn_hip_cloud* const* clouds, int n);
-int sync_and_counts(pwn_hip_ctx* ctx, pwn_hip_cloud* const* clouds, int n, bool direct = false) {
-  // frames_dev[0..n) must describe clouds[0..n)
-  if (n > 0 && !direct) { if (int rc = counts_enqueue(ctx, n)) return rc; }
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
-  collect_stage_times(ctx);
-  return counts_apply(ctx, clouds, n);
-}
-int counts_apply(pwn_hip_ctx* ctx, pwn_hip_cloud* const* clouds, int n) {
+// the fault flag and the counts against the clouds' capacities; nothing is committed
+int counts_check(pwn_hip_ctx* ctx, pwn_hip_cloud* const* clouds, int n) {
   if (n > 0 && ctx->counts_host[n] != 0) {
     const int code = ctx->counts_host[n];
     (void)hipMemset(ctx->fault_dev, 0, sizeof(int));
@@ -720,11 +766,26 @@ int counts_apply(pwn_hip_ctx* ctx, pwn_hip_cloud* const* clouds, int n) {
     return fail(ctx, PWN_HIP_ERR_LAUNCH, "integral image: strip hand-over timed out (results invalid)");
   }
   ctx->last_convert_fault = 0;
-  for (int i = 0; i < n; ++i) {
+  for (int i = 0; i < n; ++i)
     if (ctx->counts_host[i] > clouds[i]->d.capacity) return fail(ctx, PWN_HIP_ERR_CAPACITY, "cloud capacity smaller than the number of valid depth pixels");
-    clouds[i]->n_host = ctx->counts_host[i];
-  }
   return PWN_HIP_OK;
+}
+// commit: the counts are the clouds' sizes, if the check lets all of them pass
+int counts_apply(pwn_hip_ctx* ctx, pwn_hip_cloud* const* clouds, int n) {
+  if (int rc = counts_check(ctx, clouds, n)) return rc;
+  for (int i = 0; i < n; ++i) cloud_commit(clouds[i], ctx->counts_host[i]);
+  return PWN_HIP_OK;
+}
+// frames_dev[0..n) must describe clouds[0..n): the counts and the fault flag back (direct: the kernels stored them in counts_host themselves), the wait
+int sync_counts(pwn_hip_ctx* ctx, int n, bool direct = false) {
+  if (n > 0 && !direct) { if (int rc = counts_enqueue(ctx, n)) return rc; }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  collect_stage_times(ctx);
+  return PWN_HIP_OK;
+}
+int sync_and_counts(pwn_hip_ctx* ctx, pwn_hip_cloud* const* clouds, int n) {
+  if (int rc = sync_counts(ctx, n)) return rc;
+  return counts_apply(ctx, clouds, n);
 }
 
 // One converter call, cut into the pieces a caller can interleave with other work on the same streams: convert_prepare (descriptors of all
@@ -786,6 +847,10 @@ struct ConvertJob {
   float depth_scale = 0.f;
   std::vector<const void*> src;          // the caller's frame pointers (host frames are staged by convert_enqueue)
   std::vector<int> slot;
+  // The clouds convert_prepare has replaced the content of.  A job that ends any other way than through convert_commit -- an error return, the first
+  // attempt of a repeated call, a front end that stores no points -- leaves them empty and takes the index promise back.
+  std::vector<pwn_hip_cloud*> clouds; bool committed = false;
+  ~ConvertJob() { if (!committed) for (pwn_hip_cloud* c : clouds) c->content.withdraw(); }
 };
 template <typename SRC>
 int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n, int rows, int cols,
@@ -802,18 +867,15 @@ int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const S
   job.n = n; job.rows = rows; job.cols = cols; job.N = N; job.raw = raw; job.depth_scale = depth_scale; job.slot = slot; job.direct = direct;
   job.scale = sc; job.srcN = sc.step ? (size_t)sc.srows * sc.scols : N;
   job.src.assign(n, nullptr);
+  cp.omSym = n > 0 ? clouds[0]->d.omSym : 0;      // one storage for all of them: check_frames_and_clouds
+  const OmegaNClasses cls = make_omega_n_classes(p);
+  // the index image stays with the cloud, promised for the points this conversion will store (a sensor offset moves them off their pixels)
+  const IndexKey key = index_key(p, rows, cols);
   // every frame gets a descriptor; workspace slots are reused round-robin (stream order serialises the reuse)
   for (int i = 0; i < n; ++i) {
     pwn_hip_cloud* c = clouds[i];
-    if (!c || !frames[i]) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null frame or cloud");
-    if (i == 0) cp.omSym = c->d.omSym;
-    else if (c->d.omSym != cp.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds of one convert batch must share one omega storage (exact9 / sym6)");
-    cloud_changes(ctx, c);
-    if (keep_stats) { if (int rc = cloud_own(ctx, c, kArrSt)) return rc; }
-    c->has_stats = keep_stats != 0;
-    c->n_gauss = 0;                              // the cloud's Gaussians (if any) belonged to its previous content
-    if (c->d.OmN) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH); c->drop_omega_n(); }
-    make_omega_n_classes(p, c->d);
+    if (int rc = cloud_replace(ctx, c, keep_stats != 0, false, &cls, &key, cp.hasOffset == 0)) return rc;
+    job.clouds.push_back(c);
     job.src[i] = frames[i];
     const float* depth_dev = nullptr;
     if (sc.step) depth_dev = ctx->scaled_ws + (size_t)slot[i] * ctx->N;      // the front end reads the down-sampled frame of its slot
@@ -823,9 +885,7 @@ int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const S
       HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
       HIPCHK(ctx, c->idximg.ensure(N), PWN_HIP_ERR_ALLOCATION);
     }
-    ctx->frames_host[i].index = c->idximg;                    // the index image stays with the cloud
-    c->idx_valid = cp.hasOffset == 0;
-    c->idx_key = index_key(p, rows, cols);
+    ctx->frames_host[i].index = c->idximg;
     if (sc.step) {                                                            // ... by the box kernel, which reads the caller's frame
       ctx->scale_host[i].src = frames[i];                                     // patched below if it is a host pointer
       ctx->scale_host[i].dst = ctx->scaled_ws + (size_t)slot[i] * ctx->N;
@@ -868,7 +928,7 @@ int convert_stage_frames(pwn_hip_ctx* ctx, const ConvertJob& job, int base, int 
   }
   return PWN_HIP_OK;
 }
-// what convert_prepare would refuse, looked at before it touches a cloud (the *_scaled calls leave the clouds of a refused call as they were)
+// what convert_prepare relies on, looked at by every caller before it touches a cloud (a refused call leaves the clouds as they were)
 template <typename SRC>
 int check_frames_and_clouds(pwn_hip_ctx* ctx, const SRC* const* frames, pwn_hip_cloud* const* clouds, int n) {
   for (int i = 0; i < n; ++i) {
@@ -882,13 +942,23 @@ int convert_enqueue(pwn_hip_ctx* ctx, const ConvertJob& job, int base, int m, hi
   if (job.scale.step) { if (int rc = launch_depth_scale(ctx, job.scale, job.raw, job.depth_scale, base, m, st)) return rc; }
   return launch_convert(ctx, job.cp, base, m, st, fault_out);
 }
-int convert_finish(pwn_hip_ctx* ctx, const ConvertJob& job, pwn_hip_cloud* const* clouds) { return sync_and_counts(ctx, clouds, job.n, job.direct); }
+// commit: the job's clouds hold what its kernels counted (after the wait that brought counts and fault flag back)
+int convert_commit(pwn_hip_ctx* ctx, ConvertJob& job) {
+  if (int rc = counts_apply(ctx, job.clouds.data(), job.n)) return rc;
+  job.committed = true;
+  return PWN_HIP_OK;
+}
+int convert_finish(pwn_hip_ctx* ctx, ConvertJob& job) {
+  if (int rc = sync_counts(ctx, job.n, job.direct)) return rc;
+  return convert_commit(ctx, job);
+}
 
 template <typename SRC>
 int convert_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n,
                        int rows, int cols, pwn_hip_cloud* const* clouds, int keep_stats, bool want_interval = false, const ScaleSpec& sc = ScaleSpec()) {
   if (!ctx || !p || !frames || !clouds || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (int rc = check_image(ctx, rows, cols)) return rc;
+  if (int rc = check_frames_and_clouds(ctx, frames, clouds, n)) return rc;
   if (int rc = absorb_copies(ctx)) return rc;
   // A strip waited for its left neighbour longer than the poll bound (~1 s): the neighbour's workgroup was not dispatched in time -- a device
   // shared with another process's long kernels -- and the planes of this call are invalid.  Nothing is left behind (epoch-tagged words), so
@@ -933,7 +1003,7 @@ int convert_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, cons
       if (ahead) HIPCHK(ctx, hipEventRecord(ctx->sync_events[2 * k + 1], st), PWN_HIP_ERR_LAUNCH);
     }
     if (int rc = plan_join(ctx, plan)) return rc;
-    return convert_finish(ctx, job, clouds);
+    return convert_finish(ctx, job);
   });
 }
 
@@ -942,6 +1012,7 @@ int convert_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, cons
 template <typename SRC>
 int debug_front_end_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n, int rows, int cols,
                          bool single_pass, int lean, pwn_hip_cloud* const* clouds, float* integral_out, int* index_out, int* interval_out, int* rowoff_out) {
+  if (int rc = check_frames_and_clouds(ctx, frames, clouds, n)) return rc;
   ctx->stages.clear();
   std::vector<int> slot((size_t)n);
   for (int i = 0; i < n; ++i) slot[i] = i;
@@ -968,9 +1039,10 @@ int debug_front_end_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, co
     HIPCHK(ctx, copy_any(rowoff_out + (size_t)i * noff, f.rowoff, noff * sizeof(int), ctx->stream), PWN_HIP_ERR_COPY);
     if (!lean) HIPCHK(ctx, copy_any(interval_out + (size_t)i * N, f.interval, N * sizeof(int), ctx->stream), PWN_HIP_ERR_COPY);
   }
-  if (int rc = convert_finish(ctx, job, clouds)) return rc;
-  if (lean) for (int i = 0; i < n; ++i) { clouds[i]->n_host = 0; clouds[i]->idx_valid = false; }      // a lean front end stores no points
-  return PWN_HIP_OK;
+  if (!lean) return convert_finish(ctx, job);
+  // a lean front end stores no points: counts and fault flag are digested and the job ends without a commit, its clouds empty
+  if (int rc = sync_counts(ctx, n, direct)) return rc;
+  return counts_check(ctx, clouds, n);
 }
 
 // DepthImage_scale of n equal-sized frames: chunks of at most max_batch frames, one box launch each; host sources are staged in the slots'
@@ -1046,6 +1118,57 @@ int convert_batch_scaled_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* 
   if (int rc = check_scaled_capacities<SRC>(ctx, p, frames, depth_scale, n, sc, clouds)) return rc;
   if (int rc = ensure_scale(ctx, n)) return rc;
   return convert_batch_impl<SRC>(ctx, p, frames, depth_scale, n, sc.orows, sc.ocols, clouds, 0, false, sc);
+}
+
+// pwn_hip_debug_stats_from_integral and its lean form (`frames` given): the stats pass, launched as launch_convert launches it, on windows the
+// caller supplies.  The clouds are replaced as a conversion replaces them; they end with the points they held (the index image must stay
+// inside them), or lean, where k_stats writes the points, with max(index image) + 1 points inside their capacity.
+int debug_stats_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, int rows, int cols, int nframes, const float* integral, const int* index_image,
+                     const int* interval_image, const void* const* frames, float depth_scale, pwn_hip_cloud* const* clouds, int keep_stats) {
+  const bool lean = frames != nullptr, raw = depth_scale > 0.f;
+  if (nframes < 1 || nframes > ctx->max_batch) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "nframes must be 1..max_batch");
+  if (int rc = check_image(ctx, rows, cols)) return rc;
+  if (int rc = absorb_copies(ctx)) return rc;
+  if (int rc = ensure_desc(ctx, nframes)) return rc;
+  const size_t N = (size_t)rows * cols;
+  ConvertParams cp = make_convert_params(ctx, p, nullptr, rows, cols, keep_stats);
+  cp.lean = lean ? kLeanGrouped : 0;
+  std::vector<int> npoints((size_t)nframes, 0);
+  for (int i = 0; i < nframes; ++i) {
+    const pwn_hip_cloud* c = clouds[i];
+    if (!c || (lean && !frames[i])) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, lean ? "null frame or cloud" : "null cloud");
+    if (c->d.omSym != clouds[0]->d.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds of one call must share one omega storage (exact9 / sym6)");
+    const int* idx = index_image + (size_t)i * N;
+    const int limit = lean ? c->d.capacity : c->content.n;
+    if (!lean) npoints[i] = c->content.n;
+    for (size_t k = 0; k < N; ++k) {
+      if (idx[k] >= limit)
+        return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, lean ? "index image refers to a point beyond the cloud's capacity" : "index image refers to a point the cloud does not hold");
+      if (lean && idx[k] >= npoints[i]) npoints[i] = idx[k] + 1;
+    }
+  }
+  cp.omSym = clouds[0]->d.omSym;
+  const OmegaNClasses cls = make_omega_n_classes(p);
+  for (int i = 0; i < nframes; ++i) {
+    pwn_hip_cloud* c = clouds[i];
+    if (int rc = cloud_replace(ctx, c, keep_stats != 0, false, &cls)) return rc;
+    fill_frame(ctx, i, i, nullptr, c->d);
+    FrameDesc& f = ctx->frames_host[i];
+    if (lean) {      // k_stats recomputes point and interval of every pixel from the staged frame, raw or float
+      if (raw) { f.raw = ctx->raw_ws + (size_t)i * ctx->N; f.raw_scale = depth_scale; } else f.depth = ctx->depth_ws + (size_t)i * ctx->N;
+      HIPCHK(ctx, hipMemcpyAsync(raw ? (void*)f.raw : (void*)f.depth, frames[i], N * (raw ? sizeof(uint16_t) : sizeof(float)), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(f.index, index_image + (size_t)i * N, N * sizeof(int), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+    if (!lean) HIPCHK(ctx, hipMemcpyAsync(f.interval, interval_image + (size_t)i * N, N * sizeof(int), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+    HIPCHK(ctx, hipMemcpyAsync(f.integral, integral + (size_t)i * N * kIntegralChannels, N * kIntegralChannels * sizeof(float), hipMemcpyHostToDevice,
+                               ctx->stream), PWN_HIP_ERR_COPY);
+  }
+  HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev, ctx->frames_host, sizeof(FrameDesc) * nframes, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+  launch_stats(cp, ctx->frames_dev, nframes, ctx->stream);      // launch_convert's grid
+  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  for (int i = 0; i < nframes; ++i) cloud_commit(clouds[i], npoints[i]);
+  return PWN_HIP_OK;
 }
 
 }  // namespace
@@ -1354,44 +1477,7 @@ int pwn_hip_debug_projection_fallbacks(pwn_hip_ctx* ctx, int* calls) {
 int pwn_hip_debug_stats_from_integral(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, int rows, int cols, int nframes, const float* integral,
                                       const int* index_image, const int* interval_image, pwn_hip_cloud* const* clouds, int keep_stats) {
   if (!ctx || !p || !integral || !index_image || !interval_image || !clouds) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  if (nframes < 1 || nframes > ctx->max_batch) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "nframes must be 1..max_batch");
-  if (int rc = check_image(ctx, rows, cols)) return rc;
-  if (int rc = absorb_copies(ctx)) return rc;
-  if (int rc = ensure_desc(ctx, nframes)) return rc;
-  const size_t N = (size_t)rows * cols;
-  ConvertParams cp = make_convert_params(ctx, p, nullptr, rows, cols, keep_stats);
-  cp.lean = 0;
-  for (int i = 0; i < nframes; ++i) {
-    pwn_hip_cloud* c = clouds[i];
-    if (!c) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null cloud");
-    if (i == 0) cp.omSym = c->d.omSym;
-    else if (c->d.omSym != cp.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds of one call must share one omega storage (exact9 / sym6)");
-    const int* idx = index_image + (size_t)i * N;
-    for (size_t k = 0; k < N; ++k)
-      if (idx[k] >= c->n_host) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "index image refers to a point the cloud does not hold");
-  }
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
-  for (int i = 0; i < nframes; ++i) {
-    pwn_hip_cloud* c = clouds[i];
-    cloud_changes(ctx, c);
-    if (keep_stats) { if (int rc = cloud_own(ctx, c, kArrSt)) return rc; }
-    c->has_stats = keep_stats != 0;
-    c->n_gauss = 0;
-    c->idx_valid = false;
-    c->drop_omega_n();
-    make_omega_n_classes(p, c->d);
-    fill_frame(ctx, i, i, nullptr, c->d);
-    const FrameDesc& f = ctx->frames_host[i];
-    HIPCHK(ctx, hipMemcpyAsync(f.index, index_image + (size_t)i * N, N * sizeof(int), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
-    HIPCHK(ctx, hipMemcpyAsync(f.interval, interval_image + (size_t)i * N, N * sizeof(int), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
-    HIPCHK(ctx, hipMemcpyAsync(f.integral, integral + (size_t)i * N * kIntegralChannels, N * kIntegralChannels * sizeof(float), hipMemcpyHostToDevice,
-                               ctx->stream), PWN_HIP_ERR_COPY);
-  }
-  HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev, ctx->frames_host, sizeof(FrameDesc) * nframes, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
-  launch_stats(cp, ctx->frames_dev, nframes, ctx->stream);      // launch_convert's grid
-  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
-  return PWN_HIP_OK;
+  return debug_stats_impl(ctx, p, rows, cols, nframes, integral, index_image, interval_image, nullptr, 0.f, clouds, keep_stats);
 }
 // Test hook: the stats pass of a lean convert call (cp.lean = kLeanGrouped) on caller-supplied windows: the integral image arrives in the grouped
 // form (ig_at: three arrays of records per slot), and k_stats recomputes point and interval of every pixel from the staged depth frame, float or
@@ -1399,58 +1485,8 @@ int pwn_hip_debug_stats_from_integral(pwn_hip_ctx* ctx, const pwn_hip_converter_
 int pwn_hip_debug_stats_from_integral_lean(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, int rows, int cols, int nframes, const float* integral,
                                            const int* index_image, const void* const* frames, float depth_scale, pwn_hip_cloud* const* clouds, int keep_stats) {
   if (!ctx || !p || !integral || !index_image || !frames || !clouds) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  if (nframes < 1 || nframes > ctx->max_batch) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "nframes must be 1..max_batch");
   if (depth_scale < 0.f) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "negative depth scale");
-  if (int rc = check_image(ctx, rows, cols)) return rc;
-  if (int rc = absorb_copies(ctx)) return rc;
-  if (int rc = ensure_desc(ctx, nframes)) return rc;
-  const size_t N = (size_t)rows * cols;
-  const bool raw = depth_scale > 0.f;
-  ConvertParams cp = make_convert_params(ctx, p, nullptr, rows, cols, keep_stats);
-  cp.lean = kLeanGrouped;
-  std::vector<int> npoints((size_t)nframes, 0);
-  for (int i = 0; i < nframes; ++i) {
-    pwn_hip_cloud* c = clouds[i];
-    if (!c || !frames[i]) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null frame or cloud");
-    if (i == 0) cp.omSym = c->d.omSym;
-    else if (c->d.omSym != cp.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds of one call must share one omega storage (exact9 / sym6)");
-    const int* idx = index_image + (size_t)i * N;
-    for (size_t k = 0; k < N; ++k) {
-      if (idx[k] >= c->d.capacity) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "index image refers to a point beyond the cloud's capacity");
-      if (idx[k] >= npoints[i]) npoints[i] = idx[k] + 1;
-    }
-  }
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
-  for (int i = 0; i < nframes; ++i) {
-    pwn_hip_cloud* c = clouds[i];
-    cloud_changes(ctx, c);
-    if (keep_stats) { if (int rc = cloud_own(ctx, c, kArrSt)) return rc; }
-    c->has_stats = keep_stats != 0;
-    c->n_gauss = 0;
-    c->idx_valid = false;
-    c->drop_omega_n();
-    make_omega_n_classes(p, c->d);
-    fill_frame(ctx, i, i, nullptr, c->d);
-    FrameDesc& f = ctx->frames_host[i];
-    if (raw) {
-      uint16_t* staged = ctx->raw_ws + (size_t)i * ctx->N;
-      HIPCHK(ctx, hipMemcpyAsync(staged, frames[i], N * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
-      f.raw = staged; f.raw_scale = depth_scale;
-    } else {
-      float* staged = ctx->depth_ws + (size_t)i * ctx->N;
-      HIPCHK(ctx, hipMemcpyAsync(staged, frames[i], N * sizeof(float), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
-      f.depth = staged;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(f.index, index_image + (size_t)i * N, N * sizeof(int), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
-    HIPCHK(ctx, hipMemcpyAsync(f.integral, integral + (size_t)i * N * kIntegralChannels, N * kIntegralChannels * sizeof(float), hipMemcpyHostToDevice,
-                               ctx->stream), PWN_HIP_ERR_COPY);
-  }
-  HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev, ctx->frames_host, sizeof(FrameDesc) * nframes, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
-  launch_stats(cp, ctx->frames_dev, nframes, ctx->stream);      // launch_convert's grid
-  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
-  for (int i = 0; i < nframes; ++i) clouds[i]->n_host = npoints[i];
-  return PWN_HIP_OK;
+  return debug_stats_impl(ctx, p, rows, cols, nframes, integral, index_image, nullptr, frames, depth_scale, clouds, keep_stats);
 }
 // Test hook: the front end of a convert call (launch_front_end, the function launch_convert itself calls) on the caller's frames, the path chosen
 // by the caller instead of by the frame count, and everything it wrote handed back: planes, index images, offsets, and with lean = 0 the
@@ -1599,7 +1635,7 @@ int pwn_hip_cloud_destroy(pwn_hip_ctx* ctx, pwn_hip_cloud* c) {
   // plain clouds (no scene-stage or uploaded extras) retire into the context's pool: every call that used them has joined its streams
   // back into ctx->stream before returning, and a reuse is enqueued on that stream
   if (ctx && c->plain() && ctx->cloud_pool_bytes + c->core_bytes() <= kCloudPoolBytes) {
-    c->n_host = 0; c->has_stats = false; c->n_gauss = 0; c->idx_valid = false;
+    (void)cloud_replace(ctx, c, false, false, nullptr);      // a plain cloud: nothing to allocate, no planes to wait for
     ctx->cloud_pool.push_back(c);
     ctx->cloud_pool_bytes += c->core_bytes();
     return PWN_HIP_OK;
@@ -1610,15 +1646,14 @@ int pwn_hip_cloud_destroy(pwn_hip_ctx* ctx, pwn_hip_cloud* c) {
 }
 int pwn_hip_cloud_size(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, int* n) {
   if (!c || !n) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  *n = c->n_host;
+  *n = c->content.n;
   return PWN_HIP_OK;
 }
 int pwn_hip_cloud_upload(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int n, const float* points, const float* normals, const float* curvature,
                          const float* omega_p, const float* omega_n) {
   if (!ctx || !c || n < 0 || !points || !normals || !curvature || !omega_p || !omega_n) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (n > c->d.capacity) return fail(ctx, PWN_HIP_ERR_CAPACITY, "cloud capacity too small");
-  cloud_changes(ctx, c);
-  if (int rc = absorb_copies(ctx)) return rc;      // caller pointers may be the destination of a queued pwn_hip_copy_async
+  if (int rc = absorb_copies(ctx)) return rc;     // caller pointers may be the destination of a queued pwn_hip_copy_async
   // repack on the host into the device layout (upload is not on the hot path)
   std::vector<float> hp((size_t)n * 4), hn((size_t)n * 4), hc(n), hop((size_t)n * 16), hon((size_t)n * 16);
   HIPCHK(ctx, copy_any(hp.data(), points, hp.size() * 4, ctx->stream), PWN_HIP_ERR_COPY);
@@ -1639,17 +1674,17 @@ int pwn_hip_cloud_upload(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int n, const float*
       OmN[om_at(cap, i, 3 * r + q)] = hon[(size_t)16 * i + r + 4 * q];
     }
   }
-  if (int rc = cloud_own(ctx, c, kArrOmN)) return rc;
+  if (int rc = cloud_replace(ctx, c, false, true, nullptr)) return rc;      // replace: points with explicit Omega_n planes, no Stats
   if (int rc = cloud_store_records(ctx, c->d, n, P, Nm)) return rc;
   HIPCHK(ctx, hipMemcpy(c->d.Om, Om.data(), Om.size() * 4, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipMemcpy(c->d.OmN, OmN.data(), OmN.size() * 4, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipMemcpy(c->d.count, &n, sizeof(int), hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
-  c->n_host = n; c->has_stats = false; c->idx_valid = false;
+  cloud_commit(c, n);
   return PWN_HIP_OK;
 }
 int pwn_hip_cloud_download(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, float* points, float* normals, float* curvature, float* omega_p, float* omega_n) {
   if (!ctx || !c) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  const int n = c->n_host; const size_t cap = (size_t)c->d.capacity;
+  const int n = c->content.n; const size_t cap = (size_t)c->d.capacity;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
   std::vector<float> P, Nm;
   if (int rc = cloud_fetch_records(ctx, c->d, n, P, Nm)) return rc;
@@ -1686,8 +1721,8 @@ int pwn_hip_cloud_download(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, float* poin
 }
 int pwn_hip_cloud_download_stats(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, float* stats, float* eigenvalues, int* npoints) {
   if (!ctx || !c) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  if (!c->has_stats || !c->d.St) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "cloud was not converted with keep_stats");
-  const int n = c->n_host;
+  if (!c->content.stats || !c->d.St) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "cloud was not converted with keep_stats");
+  const int n = c->content.n;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
   std::vector<float> St((size_t)n * 16);
   HIPCHK(ctx, hipMemcpy(St.data(), c->d.St, St.size() * 4, hipMemcpyDeviceToHost), PWN_HIP_ERR_COPY);
@@ -1712,20 +1747,13 @@ int pwn_hip_cloud_transform_in_place(pwn_hip_ctx* ctx, pwn_hip_cloud* c, const f
   const Mat4 m = forced(T);
   if (is_identity(m)) return PWN_HIP_OK;                       // cloud.cpp:176
   cloud_changes(ctx, c);
-  if (!c->d.OmN) {                                             // class matrices transform with the cloud
-    for (int k = 0; k < 2; ++k) {
-      float* om = c->d.omN[k]; float t1[9], o2[9];
-      for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) t1[3 * i + j] = dot3seq(m(i,0), om[0 + j], m(i,1), om[3 + j], m(i,2), om[6 + j]);
-      for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) o2[3 * i + j] = dot3seq(t1[3 * i], m(j,0), t1[3 * i + 1], m(j,1), t1[3 * i + 2], m(j,2));
-      std::memcpy(om, o2, sizeof(o2));
-    }
-  }
-  c->idx_valid = false;
+  if (!c->d.OmN) for (int k = 0; k < 2; ++k) transform_omega(m, c->d.omN[k]);      // class matrices transform with the cloud
+  if (int rc = cloud_edit(ctx, c, c->content.n, false)) return rc;                 // edit: the same points, moved
   hipLaunchKernelGGL(k_cloud_transform, dim3((c->d.capacity + 255) / 256), dim3(256), 0, ctx->stream, c->d, m);
   {   // StatsVector / Gaussian3fVector::transformInPlace (stats.h:125-131, gaussian3.h:65-73)
-    CloudDev d = c->d; if (!c->has_stats) d.St = nullptr;
-    const int ng = c->sb.G ? c->n_gauss : 0, cnt = std::max(c->n_host, ng);
-    if (cnt > 0 && (d.St || ng > 0)) hipLaunchKernelGGL(k_scene_transform, dim3((cnt + 255) / 256), dim3(256), 0, ctx->stream, d, c->sb, c->n_host, ng, m);
+    const CloudView v = c->view();
+    const int cnt = std::max(v.n, v.gauss);
+    if (cnt > 0 && (v.d.St || v.gauss > 0)) hipLaunchKernelGGL(k_scene_transform, dim3((cnt + 255) / 256), dim3(256), 0, ctx->stream, v.d, v.sb, v.n, v.gauss, m);
   }
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
@@ -1767,14 +1795,14 @@ size_t pwn_hip_cloud_export_bound(int capacity, int omega_storage, int index_pix
 int pwn_hip_cloud_export(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, void* dst, size_t dst_bytes, size_t* written) {
   if (!ctx || !c || (!dst && !written)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   HIPCHK(ctx, hipSetDevice(ctx->device), PWN_HIP_ERR_NO_DEVICE);
-  const size_t n = (size_t)std::min(c->n_host, c->d.capacity), cap = (size_t)c->d.capacity;
+  const size_t n = (size_t)std::min(c->content.n, c->d.capacity), cap = (size_t)c->d.capacity;
   // the header is staged in page-locked memory of the context: the copy below is asynchronous, and an error return further down must not
   // leave it reading a dead stack frame
   CloudFlatHeader& h = *(CloudFlatHeader*)ctx->flat_hdr_host.p; std::memset(&h, 0, sizeof(h));
   h.magic = kFlatMagic; h.version = 1; h.n = (int32_t)n; h.omSym = c->d.omSym; h.hasOmN = c->d.OmN ? 1 : 0;
   h.clsThr = c->d.clsThr; std::memcpy(h.omN, c->d.omN, sizeof(h.omN));
-  const IndexKey& key = c->idx_key;
-  const bool idx = c->idx_valid && c->idximg && (size_t)key.rows * key.cols <= c->idximg.cap;
+  const IndexKey& key = c->content.idx_key;
+  const bool idx = c->content.idx_valid && c->idximg && (size_t)key.rows * key.cols <= c->idximg.cap;
   h.idxValid = idx ? 1 : 0; h.idxRows = idx ? key.rows : 0; h.idxCols = idx ? key.cols : 0;
   h.idxMinD = key.minD; h.idxMaxD = key.maxD; std::memcpy(h.idxK, key.K, sizeof(h.idxK));
   const size_t npx = idx ? (size_t)key.rows * key.cols : 0;
@@ -1815,15 +1843,12 @@ int pwn_hip_cloud_import(pwn_hip_ctx* ctx, pwn_hip_cloud* c, const void* src, si
   if (src_bytes < h.total) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "flat cloud buffer shorter than its header says");
   if (n > cap) return fail(ctx, PWN_HIP_ERR_CAPACITY, "cloud capacity smaller than the flat cloud");
   if ((h.omSym ? 1 : 0) != c->d.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "flat cloud and destination cloud differ in omega storage (exact9 / sym6)");
-  cloud_changes(ctx, c);
-  c->has_stats = false; c->n_gauss = 0; c->idx_valid = false;
-  // from here on the destination's previous content is being overwritten: it reads as EMPTY (host size and device count) until every section
-  // has arrived, so that a copy that fails half way leaves an empty cloud behind, not a mixture with the old sizes
-  c->n_host = 0;
+  // replace: from here on the destination's previous content is being overwritten and it reads as EMPTY (host size and device count) until every
+  // section has arrived, so that a copy that fails half way leaves an empty cloud behind, not a mixture with the old sizes
+  OmegaNClasses cls; std::memcpy(cls.omN, h.omN, sizeof(h.omN)); cls.clsThr = h.clsThr;
+  if (int rc = cloud_replace(ctx, c, false, h.hasOmN != 0, &cls)) return rc;
   HIPCHK(ctx, hipMemsetAsync(c->d.count, 0, sizeof(int), st), PWN_HIP_ERR_COPY);
   CloudFlatHeader& hp = *(CloudFlatHeader*)ctx->flat_hdr_host.p; hp = h;      // page-locked copy: source of the asynchronous count copy below
-  if (h.hasOmN) { if (int rc = cloud_own(ctx, c, kArrOmN)) return rc; }
-  else c->drop_omega_n();                                                         // the stream is idle (synchronised above)
   if (idx) HIPCHK(ctx, c->idximg.ensure(npx), PWN_HIP_ERR_ALLOCATION);
   const char* in = (const char*)src;
   if (n > 0) {
@@ -1837,9 +1862,8 @@ int pwn_hip_cloud_import(pwn_hip_ctx* ctx, pwn_hip_cloud* c, const void* src, si
   if (idx) HIPCHK(ctx, copy_section(c->idximg, in + h.offIdx, npx * 4, st), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, copy_any(c->d.count, &hp.n, sizeof(int), st), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_COPY);
-  c->d.clsThr = h.clsThr; std::memcpy(c->d.omN, h.omN, sizeof(h.omN));
-  c->n_host = h.n;
-  if (idx) { c->idx_valid = true; c->idx_key = IndexKey(h.idxRows, h.idxCols, h.idxK, h.idxMinD, h.idxMaxD); }
+  const IndexKey key(h.idxRows, h.idxCols, h.idxK, h.idxMinD, h.idxMaxD);
+  cloud_commit(c, h.n, idx ? &key : nullptr);
   return PWN_HIP_OK;
 }
 
@@ -1907,8 +1931,10 @@ int pwn_hip_unproject(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const
   if (!ctx || !p || !depth || !cloud) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (int rc = check_image(ctx, rows, cols)) return rc;
   const size_t N = (size_t)rows * cols;
-  cloud->idx_valid = false;                      // the cloud gets new points
-  cloud_changes(ctx, cloud);
+  // replace: points only.  Normals and point information are zeroed below; the normal information is the two class matrices, which give zero for a
+  // zero normal, so nothing of the previous content's (Stats, Gaussians, explicit planes) is read beside the new points
+  const OmegaNClasses cls = make_omega_n_classes(p);
+  if (int rc = cloud_replace(ctx, cloud, false, false, &cls)) return rc;
   const ConvertParams cp = make_convert_params(ctx, p, T, rows, cols, 0);
   const float* d = nullptr;
   if (int rc = stage_depth(ctx, depth, N, &d)) return rc;
@@ -1921,9 +1947,8 @@ int pwn_hip_unproject(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const
   hipLaunchKernelGGL(k_unproject, dim3(rows, 1), dim3(256), 0, ctx->stream, ctx->frames_dev, cp);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   if (index_image) HIPCHK(ctx, copy_any(index_image, ctx->frames_host[0].index, N * 4, ctx->stream), PWN_HIP_ERR_COPY);
-  cloud->has_stats = false;
   pwn_hip_cloud* arr[1] = { cloud };
-  return sync_and_counts(ctx, arr, 1);
+  return sync_and_counts(ctx, arr, 1);      // commit
 }
 int pwn_hip_project_intervals(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const float* depth, int rows, int cols, int* interval_image) {
   if (!ctx || !p || !depth || !interval_image) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
@@ -2334,7 +2359,7 @@ static int check_align_params(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p)
 }
 // the aligner's 32-bit z-buffer word indexes 2^21 points (every frame up to 1448 x 1448 pixels); larger clouds are scenes (merge, voxelize)
 static int check_pair_points(pwn_hip_ctx* ctx, const pwn_hip_cloud* ref, const pwn_hip_cloud* cur) {
-  if (std::min(ref->n_host, ref->d.capacity) > kMaxAlignerPoints || std::min(cur->n_host, cur->d.capacity) > kMaxAlignerPoints)
+  if (std::min(ref->content.n, ref->d.capacity) > kMaxAlignerPoints || std::min(cur->content.n, cur->d.capacity) > kMaxAlignerPoints)
     return fail(ctx, PWN_HIP_ERR_CAPACITY, "Aligner::align: a cloud holds more than 2^21 points (index field of the aligner's z-buffer word)");
   return PWN_HIP_OK;
 }
@@ -2412,8 +2437,8 @@ static int align_describe_pairs(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& 
     std::memset(&st, 0, offsetof(PairState, chi2));
     Mat4 T = mat4_from(c.guesses ? c.guesses + 16 * (size_t)i : p->initial_guess);
     set_last_row(T);
-    if (!(shortcut && cu->idx_valid && cu->idx_key == key)) run.sub_own[i / sub] = 0;
-    if (!(shortcut_ref && is_identity(T) && r->idx_valid && r->idx_key == key)) run.sub_ownref[i / sub] = 0;
+    if (!(shortcut && cu->content.idx_valid && cu->content.idx_key == key)) run.sub_own[i / sub] = 0;
+    if (!(shortcut_ref && is_identity(T) && r->content.idx_valid && r->content.idx_key == key)) run.sub_ownref[i / sub] = 0;
     set_pose(st, T, run.ap, KRtCur0);
   }
   for (int i = 0; i < n; ++i) {
@@ -2538,7 +2563,7 @@ static void fill_result(pwn_hip_align_result& r, const PairState& st, const pwn_
     r.chi2[k] = st.chi2[k]; r.iter_inliers[k] = st.inliers[k]; r.iter_correspondences[k] = st.ncorr[k]; r.iter_candidates[k] = st.ncand[k];
   }
   if (st.it > 0) { r.error = st.chi2[st.it - 1]; r.inliers = st.inliers[st.it - 1]; }
-  r.n_reference = ref->n_host; r.n_current = cur->n_host;
+  r.n_reference = ref->content.n; r.n_current = cur->content.n;
   r.total_time_ms = ms;
 }
 // Aligner::_computeStatistics from the re-linearization at the final transform T (so: its sums; nullptr when the call ran no iteration)
@@ -2774,17 +2799,26 @@ static int convert_align_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_pa
       return PWN_HIP_OK;
     };
     hooks.before_sync = [&]() -> int { return counts_enqueue(ctx, 2 * n); };
-    hooks.after_sync = [&]() -> int { return counts_apply(ctx, clouds.data(), 2 * n); };
+    hooks.after_sync = [&]() -> int { return convert_commit(ctx, job); };
     AlignCall call = align_call(ap, n, refs, curs, guesses, results);
     call.hooks = &hooks; call.records = records; call.pair_ids = pair_ids; call.first_pair_id = first_pair_id;
     return align_batch_impl(ctx, call);
   });
+}
+// what the step's conversions rely on (check_frames_and_clouds, for the 2 n frames and clouds), before a cloud is touched
+static int check_step_clouds(pwn_hip_ctx* ctx, const uint16_t* const* ref_frames, const uint16_t* const* cur_frames, pwn_hip_cloud* const* refs,
+                             pwn_hip_cloud* const* curs, int n) {
+  if (int rc = check_frames_and_clouds(ctx, ref_frames, refs, n)) return rc;
+  if (int rc = check_frames_and_clouds(ctx, cur_frames, curs, n)) return rc;
+  if (n > 0 && refs[0]->d.omSym != curs[0]->d.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds of one convert batch must share one omega storage (exact9 / sym6)");
+  return PWN_HIP_OK;
 }
 int pwn_hip_convert_align_batch_u16(pwn_hip_ctx* ctx, const pwn_hip_converter_params* cp, const pwn_hip_aligner_params* ap, int n,
                                     const uint16_t* const* ref_frames, const uint16_t* const* cur_frames, float depth_scale, int rows, int cols,
                                     pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs, const float* guesses, const int* pair_ids, int first_pair_id,
                                     pwn_hip_align_result* results, float* records) {
   if (!ctx || !cp || !ap || !ref_frames || !cur_frames || !refs || !curs || (!results && !records) || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (int rc = check_step_clouds(ctx, ref_frames, cur_frames, refs, curs, n)) return rc;
   return convert_align_batch_impl(ctx, cp, ap, n, ref_frames, cur_frames, depth_scale, rows, cols, refs, curs, guesses, pair_ids, first_pair_id, results, records,
                                   ScaleSpec());
 }
@@ -2795,10 +2829,7 @@ int pwn_hip_convert_align_batch_u16_scaled(pwn_hip_ctx* ctx, const pwn_hip_conve
   if (!ctx || !cp || !ap || !ref_frames || !cur_frames || !refs || !curs || (!results && !records) || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   ScaleSpec sc;
   if (int rc = make_scale_spec(ctx, rows, cols, step, max_depth_cov, sc)) return rc;
-  // what the conversions would refuse, before a cloud is touched
-  if (int rc = check_frames_and_clouds(ctx, ref_frames, refs, n)) return rc;
-  if (int rc = check_frames_and_clouds(ctx, cur_frames, curs, n)) return rc;
-  if (n > 0 && refs[0]->d.omSym != curs[0]->d.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds of one convert batch must share one omega storage (exact9 / sym6)");
+  if (int rc = check_step_clouds(ctx, ref_frames, cur_frames, refs, curs, n)) return rc;
   if (int rc = check_scaled_capacities<uint16_t>(ctx, cp, ref_frames, depth_scale, n, sc, refs)) return rc;
   if (int rc = check_scaled_capacities<uint16_t>(ctx, cp, cur_frames, depth_scale, n, sc, curs)) return rc;
   if (int rc = ensure_scale(ctx, 2 * n)) return rc;

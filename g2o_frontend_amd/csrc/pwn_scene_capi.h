@@ -27,19 +27,16 @@ int default_gaussians(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int from, int to) {
 int ensure_scene(pwn_hip_ctx* ctx, pwn_hip_cloud* c, bool with_gauss) {
   if (!c->d.OmN) {            // the kernel reads normals, curvatures and the two class matrices, not the planes it writes
     if (int rc = cloud_own(ctx, c, kArrOmN)) return rc;
-    if (c->n_host > 0) hipLaunchKernelGGL(k_expand_omega_n, dim3((c->n_host + 255) / 256), dim3(256), 0, ctx->stream, c->d, c->d.OmN, c->n_host);
+    if (c->content.n > 0) hipLaunchKernelGGL(k_expand_omega_n, dim3((c->content.n + 255) / 256), dim3(256), 0, ctx->stream, c->d, c->d.OmN, c->content.n);
   }
-  if (!c->d.St) {
-    if (int rc = cloud_own(ctx, c, kArrSt)) return rc;
-    c->has_stats = false;
-  }
-  if (!c->has_stats) {        // default Stats() for whatever the cloud already holds
-    if (c->n_host > 0) {
-      const std::vector<float> st = default_stats(c->n_host);
+  if (int rc = cloud_own(ctx, c, kArrSt)) return rc;
+  if (!c->content.stats) {    // default Stats() for whatever the cloud already holds
+    if (c->content.n > 0) {
+      const std::vector<float> st = default_stats(c->content.n);
       HIPCHK(ctx, hipMemcpyAsync(c->d.St, st.data(), st.size() * 4, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
       HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_COPY);
     }
-    c->has_stats = true;
+    c->content.set_stats();
   }
   if (with_gauss) { if (int rc = ensure_gauss(ctx, c)) return rc; }
   return PWN_HIP_OK;
@@ -107,18 +104,18 @@ int pwn_hip_cloud_gaussians(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p,
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   pwn_hip_cloud* cl[1] = { cloud };
   if (int rc = sync_and_counts(ctx, cl, 1)) return rc;
-  cloud->n_gauss = cloud->n_host;
+  cloud->content.set_gaussians(cloud->content.n);
   return PWN_HIP_OK;
 }
 int pwn_hip_cloud_num_gaussians(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, int* n) {
   if (!c || !n) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  *n = c->sb.G ? c->n_gauss : 0;
+  *n = c->view().gauss;
   return PWN_HIP_OK;
 }
 // mean n*3, cov n*9 (column-major 3x3), info_vec n*3, info n*9, flags n (1 = moments valid, 2 = information form valid); host pointers
 int pwn_hip_cloud_download_gaussians(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, float* mean, float* cov, float* info_vec, float* info, int* flags) {
   if (!ctx || !c) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  const int n = c->sb.G ? c->n_gauss : 0;
+  const int n = c->view().gauss;
   if (n == 0) return PWN_HIP_OK;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
   std::vector<GaussD> g(n); std::vector<int> f(n);
@@ -154,7 +151,7 @@ int pwn_hip_debug_cloud_set_gaussians(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int n,
     HIPCHK(ctx, hipMemcpy(c->sb.G, g.data(), sizeof(GaussD) * (size_t)n, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
     HIPCHK(ctx, hipMemcpy(c->sb.Gf, flags, sizeof(int) * (size_t)n, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
   }
-  c->n_gauss = n;
+  c->content.set_gaussians(n);
   return PWN_HIP_OK;
 }
 
@@ -163,29 +160,25 @@ int pwn_hip_cloud_add(pwn_hip_ctx* ctx, pwn_hip_cloud* dst, const pwn_hip_cloud*
   if (!ctx || !dst || !src || !T) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (dst == src) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "cannot add a cloud to itself");
   cloud_changes(ctx, dst);
-  const int k = dst->n_host, n = src->n_host;
+  const CloudView s = src->view();
+  const int k = dst->content.n, n = s.n;
   if ((size_t)k + (size_t)n > (size_t)dst->d.capacity) return fail(ctx, PWN_HIP_ERR_CAPACITY, "destination cloud capacity too small for Cloud::add");
-  const bool srcGauss = src->sb.G && src->n_gauss > 0;
-  if (int rc = ensure_scene(ctx, dst, srcGauss || dst->sb.G)) return rc;
+  if (int rc = ensure_scene(ctx, dst, s.gauss > 0 || dst->sb.G)) return rc;
   const Mat4 m = forced(T);
   const int ident = is_identity(m) ? 1 : 0;                                  // cloud.cpp:176
-  CloudDev s = src->d;
-  if (!src->has_stats) s.St = nullptr;
-  const int ng = srcGauss ? std::min(src->n_gauss, n) : 0;
-  if (n > 0) hipLaunchKernelGGL(k_cloud_append, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dst->d, dst->sb, s, src->sb, k, n, ng, m, ident);
+  const int ng = s.point_gauss();
+  if (n > 0) hipLaunchKernelGGL(k_cloud_append, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dst->d, dst->sb, s.d, s.sb, k, n, ng, m, ident);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
-  const int total = k + n;
-  HIPCHK(ctx, hipMemcpyAsync(dst->d.count, &total, sizeof(int), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
   // _gaussians.resize(k + cloud.gaussians().size()) (cloud.cpp:153): records the vector had stay, the kernel wrote [k, k + ng), every other
   // record of the new size is a default Gaussian -- the destination's own points up to k, and what a source with more Gaussians than points adds
-  const int newg = dst->sb.G ? std::min(k + (srcGauss ? src->n_gauss : 0), dst->d.capacity) : 0;
+  const int newg = dst->sb.G ? std::min(k + s.gauss, dst->d.capacity) : 0;
   if (dst->sb.G) {
-    if (int rc = default_gaussians(ctx, dst, dst->n_gauss, std::min(k, newg))) return rc;
-    if (int rc = default_gaussians(ctx, dst, std::max(dst->n_gauss, k + ng), newg)) return rc;
+    if (int rc = default_gaussians(ctx, dst, dst->content.n_gauss, std::min(k, newg))) return rc;
+    if (int rc = default_gaussians(ctx, dst, std::max(dst->content.n_gauss, k + ng), newg)) return rc;
+    dst->content.set_gaussians(newg);
   }
+  if (int rc = cloud_edit(ctx, dst, k + n, true)) return rc;      // edit: the host decides the new size
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
-  if (dst->sb.G) dst->n_gauss = newg;
-  dst->n_host = total; dst->idx_valid = false;
   return PWN_HIP_OK;
 }
 
@@ -197,9 +190,9 @@ int pwn_hip_merge(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, const float K[9], cons
   if (int rc = check_image(ctx, rows, cols)) return rc;
   if (min_distance < 0.f) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "min_distance must be >= 0");
   cloud_changes(ctx, cloud);
-  const int n = cloud->n_host;
+  const int n = cloud->content.n, ngauss = cloud->content.n_gauss;
   if (n > kMaxCloudPoints) return fail(ctx, PWN_HIP_ERR_CAPACITY, "cloud has more points than the z-buffer index field holds (2^25)");
-  if (!cloud->sb.G || cloud->n_gauss < n) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "Merger::merge needs the cloud's Gaussians (pwn_hip_cloud_gaussians)");
+  if (!cloud->sb.G || ngauss < n) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "Merger::merge needs the cloud's Gaussians (pwn_hip_cloud_gaussians)");
   if (n == 0) { if (new_size) *new_size = 0; return PWN_HIP_OK; }
   CloudDev back; SceneBuffers sback;      // the second array set: the stable compaction / reordering writes there, then the two sets change places
   HIPCHK(ctx, cloud->own_back(back, sback), PWN_HIP_ERR_ALLOCATION);
@@ -219,7 +212,7 @@ int pwn_hip_merge(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, const float K[9], cons
   hipLaunchKernelGGL(k_merge_accumulate, dim3(nb), dim3(256), 0, st, cloud->d, cloud->sb, n, (const int*)d_collapsed, (const int*)d_head, (const int*)d_next);
   hipLaunchKernelGGL(k_merge_keep_flags, dim3(nb), dim3(256), 0, st, (const int*)d_collapsed, n, d_keep);
   if (int rc = exclusive_scan(ctx, d_keep, d_offs, n, d_sums, ctx->scene_total)) return rc;
-  hipLaunchKernelGGL(k_merge_compact, dim3(nb), dim3(256), 0, st, cloud->d, cloud->sb, back, sback, n, cloud->n_gauss, (const int*)d_keep, (const int*)d_offs);
+  hipLaunchKernelGGL(k_merge_compact, dim3(nb), dim3(256), 0, st, cloud->d, cloud->sb, back, sback, n, ngauss, (const int*)d_keep, (const int*)d_offs);
   hipLaunchKernelGGL(k_set_count, dim3(1), dim3(1), 0, st, cloud->d.count, (const int*)ctx->scene_total);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   int k = 0;
@@ -227,10 +220,10 @@ int pwn_hip_merge(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, const float K[9], cons
   if (collapsed) HIPCHK(ctx, hipMemcpyAsync(collapsed, d_collapsed, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
   // the Gaussian vector is compacted but not resized (merger.cpp:108-112): its tail keeps the old entries
-  if (cloud->n_gauss > k) hipLaunchKernelGGL(k_gauss_copy_tail, dim3((cloud->n_gauss - k + 255) / 256), dim3(256), 0, st, cloud->sb, sback, k, cloud->n_gauss);
+  if (ngauss > k) hipLaunchKernelGGL(k_gauss_copy_tail, dim3((ngauss - k + 255) / 256), dim3(256), 0, st, cloud->sb, sback, k, ngauss);
   HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
   cloud->swap_sides();
-  cloud->n_host = k; cloud->idx_valid = false;
+  if (int rc = cloud_edit(ctx, cloud, k, false)) return rc;      // edit: k_set_count has set the device's word
   ctx->img.invalidate();                  // slot 0 of the z-buffer was used
   if (new_size) *new_size = k;
   return PWN_HIP_OK;
@@ -248,7 +241,7 @@ int pwn_hip_merge_clouds(pwn_hip_ctx* ctx, const float K[9], const float offset[
   if (min_distance < 0.f) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "min_distance must be >= 0");
   if (int rc = check_image(ctx, rows, cols)) return rc;
   if (total->owner != ctx) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "cloud of another context");
-  const int k0 = total->n_host;
+  const int k0 = total->content.n;
   size_t bound = (size_t)k0;
   bool anyGauss = false;
   for (int i = 0; i < n; ++i) {
@@ -257,8 +250,8 @@ int pwn_hip_merge_clouds(pwn_hip_ctx* ctx, const float K[9], const float offset[
     if (c->owner != ctx) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "cloud of another context");
     if (c == total) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "the total cloud is among the clouds merged into it");
     if (c->d.omSym != total->d.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds with different omega storages");
-    bound += (size_t)c->n_host;
-    anyGauss = anyGauss || (c->sb.G && c->n_gauss > 0);
+    bound += (size_t)c->content.n;
+    anyGauss = anyGauss || c->view().gauss > 0;
   }
   if (n == 0) return PWN_HIP_OK;
   if (bound > (size_t)total->d.capacity) return fail(ctx, PWN_HIP_ERR_CAPACITY, "total cloud capacity smaller than its size plus the sizes of the merged clouds");
@@ -276,7 +269,7 @@ int pwn_hip_merge_clouds(pwn_hip_ctx* ctx, const float K[9], const float offset[
   hipStream_t st = ctx->stream;
   if (w != weights && k0 > 0) HIPCHK(ctx, hipMemcpyAsync(w, weights, sizeof(float) * (size_t)k0, hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
   // Gaussians the total has not got for the points it already holds are default Gaussians (as pwn_hip_cloud_add leaves them)
-  if (total->sb.G) { if (int rc = default_gaussians(ctx, total, total->n_gauss, k0)) return rc; }
+  if (total->sb.G) { if (int rc = default_gaussians(ctx, total, total->content.n_gauss, k0)) return rc; }
   int* d_counts = ctx->merge_counts_dev;             // appended[n], fused[n]
   HIPCHK(ctx, hipMemsetAsync(d_counts, 0, sizeof(int) * 2 * (size_t)n, st), PWN_HIP_ERR_COPY);
   unsigned long long* zcur = ctx->scene_k[0]; unsigned long long* ztot = ctx->scene_k[1];
@@ -294,21 +287,19 @@ int pwn_hip_merge_clouds(pwn_hip_ctx* ctx, const float K[9], const float offset[
     projector_matrices(Km, iso_mul(T, off), KRtTot, iKRtTot, iK);                          // setTransform(transform * offset), :121
     HIPCHK(ctx, hipMemsetAsync(zcur, 0xFF, sizeof(unsigned long long) * (size_t)N, st), PWN_HIP_ERR_COPY);
     HIPCHK(ctx, hipMemsetAsync(ztot, 0xFF, sizeof(unsigned long long) * (size_t)N, st), PWN_HIP_ERR_COPY);
-    if (c->n_host > 0)
-      hipLaunchKernelGGL(k_project_single, dim3((c->n_host + 255) / 256), dim3(256), 0, st, c->d, KRtOff, min_distance, max_distance, rows, cols, zcur, kZTag0);
+    if (c->content.n > 0)
+      hipLaunchKernelGGL(k_project_single, dim3((c->content.n + 255) / 256), dim3(256), 0, st, c->d, KRtOff, min_distance, max_distance, rows, cols, zcur, kZTag0);
     if (upper > 0)
       hipLaunchKernelGGL(k_project_single, dim3((unsigned)((upper + 255) / 256)), dim3(256), 0, st, total->d, KRtTot, min_distance, max_distance, rows, cols, ztot, kZTag0);
     hipLaunchKernelGGL(k_merge_clouds_classify, dim3(nbp), dim3(256), 0, st, total->d, w, (const unsigned long long*)zcur, (const unsigned long long*)ztot, kZTag0,
                        rows, cols, iKRtTot, min_distance, max_distance, d_flags, d_counts + n + i);
     if (int rc = exclusive_scan(ctx, d_flags, d_offs, N, d_sums, ctx->scene_total)) return rc;
-    CloudDev s = c->d;
-    if (!c->has_stats) s.St = nullptr;
-    const int ng = (c->sb.G && c->n_gauss > 0) ? std::min(c->n_gauss, c->n_host) : 0;
-    hipLaunchKernelGGL(k_merge_clouds_append, dim3(nbp), dim3(256), 0, st, total->d, total->sb, w, s, c->sb, ng, forced(transforms + 16 * (size_t)i),
+    const CloudView s = c->view();
+    hipLaunchKernelGGL(k_merge_clouds_append, dim3(nbp), dim3(256), 0, st, total->d, total->sb, w, s.d, s.sb, s.point_gauss(), forced(transforms + 16 * (size_t)i),
                        (const unsigned long long*)zcur, kZTag0, N, (const int*)d_flags, (const int*)d_offs);
     hipLaunchKernelGGL(k_merge_clouds_count, dim3(1), dim3(1), 0, st, total->d.count, (const int*)ctx->scene_total, d_counts + i);
     HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
-    upper += (size_t)c->n_host;
+    upper += (size_t)c->content.n;
   }
   int* h = ctx->merge_counts_host;
   HIPCHK(ctx, hipMemcpyAsync(h, d_counts, sizeof(int) * 2 * (size_t)n, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
@@ -318,9 +309,8 @@ int pwn_hip_merge_clouds(pwn_hip_ctx* ctx, const float K[9], const float offset[
   if (w != weights && k1 > 0) HIPCHK(ctx, hipMemcpy(weights, w, sizeof(float) * (size_t)k1, hipMemcpyDeviceToHost), PWN_HIP_ERR_COPY);
   if (appended) std::copy(h, h + n, appended);
   if (fused) std::copy(h + n, h + 2 * n, fused);
-  total->n_host = k1; total->idx_valid = false;
-  if (total->sb.G) total->n_gauss = k1;
-  return PWN_HIP_OK;
+  if (total->sb.G) total->content.set_gaussians(k1);
+  return cloud_edit(ctx, total, k1, false);      // edit: k_merge_clouds_count kept the device's word
 }
 
 // ManifoldVoronoiExtractor::process (pwn_tracker2/manifold_voronoi_extractor.cpp:50-127): the traversability image of clouds[0..n), cloud i under
@@ -343,12 +333,12 @@ int pwn_hip_manifold_image(pwn_hip_ctx* ctx, int n, pwn_hip_cloud* const* clouds
     const pwn_hip_cloud* c = clouds[i];
     if (!c) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null cloud");
     if (c->owner != ctx) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "cloud of another context");
-    if (c->n_host > ctx->manifold_chunk)
+    if (c->content.n > ctx->manifold_chunk)
       return fail(ctx, PWN_HIP_ERR_CAPACITY, "a cloud has more points than one chunk holds (" + std::to_string(ctx->manifold_chunk) + ")");
-    if (chunks.empty() || chunks.back().points + (size_t)c->n_host > (size_t)ctx->manifold_chunk || chunks.back().last - chunks.back().first >= 65535)
+    if (chunks.empty() || chunks.back().points + (size_t)c->content.n > (size_t)ctx->manifold_chunk || chunks.back().last - chunks.back().first >= 65535)
       chunks.push_back({ i, i, 0, 0 });
     Chunk& k = chunks.back();
-    k.last = i + 1; k.points += (size_t)c->n_host; k.largest = std::max(k.largest, c->n_host);
+    k.last = i + 1; k.points += (size_t)c->content.n; k.largest = std::max(k.largest, c->content.n);
     most = std::max(most, k.points);
   }
   HIPCHK(ctx, hipSetDevice(ctx->device), PWN_HIP_ERR_NO_DEVICE);
@@ -385,7 +375,7 @@ int pwn_hip_manifold_image(pwn_hip_ctx* ctx, int n, pwn_hip_cloud* const* clouds
       int base = 0;
       for (int i = k.first; i < k.last; ++i) {
         ManifoldCloud& m = ctx->manifold_host.p[i];
-        m.P3 = clouds[i]->d.P3; m.Nc = clouds[i]->d.Nc; m.n = clouds[i]->n_host; m.base = base; m.T = mat4_from(transforms + 16 * (size_t)i);
+        m.P3 = clouds[i]->d.P3; m.Nc = clouds[i]->d.Nc; m.n = clouds[i]->content.n; m.base = base; m.T = mat4_from(transforms + 16 * (size_t)i);
         base += m.n;
       }
     }
@@ -428,7 +418,7 @@ int pwn_hip_debug_set_manifold_chunk(pwn_hip_ctx* ctx, int points) {
 int pwn_hip_voxelize(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, float resolution, int* new_size, int* kept) {
   if (!ctx || !cloud || !(resolution > 0.f)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "bad argument");
   cloud_changes(ctx, cloud);
-  const int n = cloud->n_host;
+  const int n = cloud->content.n;
   if (n == 0) { if (new_size) *new_size = 0; return PWN_HIP_OK; }
   CloudDev back; SceneBuffers sback;      // the second array set: the stable compaction / reordering writes there, then the two sets change places
   HIPCHK(ctx, cloud->own_back(back, sback), PWN_HIP_ERR_ALLOCATION);
@@ -459,15 +449,14 @@ int pwn_hip_voxelize(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, float resolution, i
   int s = 0;
   if (int rc = radix_sort(ctx, d_key, d_idx, m, 64, d_hist, d_sums, &s)) return rc;
   const int* d_order = d_idx[s];
-  const bool withGauss = cloud->sb.G && cloud->n_gauss == n;          // voxelcalculator.cpp:62-64
+  const bool withGauss = cloud->sb.G && cloud->content.n_gauss == n;          // voxelcalculator.cpp:62-64
   if (m > 0) hipLaunchKernelGGL(k_voxel_gather, dim3((m + 255) / 256), dim3(256), 0, st, cloud->d, cloud->sb, back, sback, m, withGauss ? 1 : 0, d_order);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
-  HIPCHK(ctx, hipMemcpyAsync(cloud->d.count, &m, sizeof(int), hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
+  if (int rc = cloud_edit(ctx, cloud, m, true)) return rc;      // edit: the host decides the new size
+  cloud->content.set_gaussians(withGauss ? m : 0);
   if (kept && m > 0) HIPCHK(ctx, hipMemcpyAsync(kept, d_order, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
   cloud->swap_sides();
-  cloud->n_host = m; cloud->idx_valid = false;
-  cloud->n_gauss = withGauss ? m : 0;
   if (new_size) *new_size = m;
   return PWN_HIP_OK;
 }
@@ -476,12 +465,12 @@ int pwn_hip_voxelize(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, float resolution, i
 // reference's object layout on x86-64 (Point 32 B, Normal 32 B, Stats 112 B: vptr, padding, data) with the non-data bytes zeroed.
 int pwn_hip_cloud_save(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, const char* filename, const float T[16], int step, int binary) {
   if (!ctx || !c || !filename || !T || step <= 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "bad argument");
-  const int n = c->n_host;
+  const int n = c->content.n;
   std::vector<float> P, Nm, St;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
   if (int rc = cloud_fetch_records(ctx, c->d, n, P, Nm)) return rc;
   if (n > 0) {
-    if (c->has_stats && c->d.St) { St.resize((size_t)n * 16); HIPCHK(ctx, hipMemcpy(St.data(), c->d.St, St.size() * 4, hipMemcpyDeviceToHost), PWN_HIP_ERR_COPY); }
+    if (c->content.stats && c->d.St) { St.resize((size_t)n * 16); HIPCHK(ctx, hipMemcpy(St.data(), c->d.St, St.size() * 4, hipMemcpyDeviceToHost), PWN_HIP_ERR_COPY); }
   }
   std::ofstream os(filename);
   if (!os) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, std::string("cannot open ") + filename);
@@ -530,7 +519,6 @@ int pwn_hip_cloud_load(pwn_hip_ctx* ctx, pwn_hip_cloud* c, const char* filename,
   if (tag != "PWNCLOUD") return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "not a PWNCLOUD file");
   ls >> numPoints >> binary;
   if (numPoints > (size_t)c->d.capacity) return fail(ctx, PWN_HIP_ERR_CAPACITY, "cloud capacity smaller than the file's point count");
-  cloud_changes(ctx, c);
   is.getline(buf, 1024);
   std::istringstream lst(buf);
   float tv[6] = { 0, 0, 0, 0, 0, 0 };
@@ -566,11 +554,10 @@ int pwn_hip_cloud_load(pwn_hip_ctx* ctx, pwn_hip_cloud* c, const char* filename,
     ++k;
   }
   const bool ok = is.good();
-  if (int rc = cloud_own(ctx, c, kArrSt)) return rc;
+  // replace: points with Stats.  Cloud::load leaves both information-matrix vectors empty (cloud.cpp:25-82): zero matrices for every point.  The
+  // class of the normal information matrix is derived from normal and curvature on the device, so a loaded cloud says "zero" with explicit planes.
+  if (int rc = cloud_replace(ctx, c, true, true, nullptr)) return rc;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
-  // Cloud::load leaves both information-matrix vectors empty (cloud.cpp:25-82): zero matrices for every point.  The class of the normal
-  // information matrix is derived from normal and curvature on the device, so a loaded cloud says "zero" with explicit planes.
-  if (int rc = cloud_own(ctx, c, kArrOmN)) return rc;
   if (n > 0) {
     if (int rc = cloud_store_records(ctx, c->d, n, P, Nm)) return rc;
     HIPCHK(ctx, hipMemcpy(c->d.St, St.data(), St.size() * 4, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
@@ -578,7 +565,7 @@ int pwn_hip_cloud_load(pwn_hip_ctx* ctx, pwn_hip_cloud* c, const char* filename,
   }
   HIPCHK(ctx, hipMemset(c->d.OmN, 0, (size_t)c->d.capacity * 9 * sizeof(float)), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipMemcpy(c->d.count, &n, sizeof(int), hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
-  c->n_host = n; c->has_stats = true; c->n_gauss = 0; c->idx_valid = false;
+  cloud_commit(c, n);
   if (!ok) return fail(ctx, PWN_HIP_ERR_COPY, "read error / truncated PWNCLOUD file");
   return PWN_HIP_OK;
 }

@@ -234,7 +234,8 @@ int pwn_hip_cloud_destroy(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud);
 int pwn_hip_cloud_size(pwn_hip_ctx* ctx, const pwn_hip_cloud* cloud, int* n);    /* Cloud::points().size() */
 /* Upload a host/device pwn::Cloud: points/normals n*4 floats (Point/Normal, homogeneousvector4f.h:78-93),
  * curvature n floats (Stats::curvature(), stats.h:98-103), omega_p/omega_n n*16 floats
- * (InformationMatrix 4x4, informationmatrix.h:13).  cf. pwn_cuda initComputation (cudaaligner.h:63-75). */
+ * (InformationMatrix 4x4, informationmatrix.h:13).  cf. pwn_cuda initComputation (cudaaligner.h:63-75).  The cloud's previous content is
+ * replaced whole: no Stats, no Gaussians, no index image afterwards. */
 int pwn_hip_cloud_upload(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, int n, const float* points, const float* normals,
                          const float* curvature, const float* omega_p, const float* omega_n);
 /* Any output may be NULL.  Same layouts as upload. */
@@ -282,7 +283,8 @@ int pwn_hip_depth_scale_batch_u16(pwn_hip_ctx* ctx, const uint16_t* const* src, 
 /* ------------------------------------------------------------------ converter stages --------- */
 /* PinholePointProjector::unProject(points, gaussians, indexImage, depthImage) (pinholepointprojector.cpp:93-133)
  * with the projector transform T (identity inside the converter).  Fills cloud points (normals etc. are
- * reset to "invalid").  The per-point sensor Gaussians are not produced (only Merger consumes them). */
+ * reset to "invalid").  The per-point sensor Gaussians are not produced (only Merger consumes them); the cloud's previous content is replaced
+ * whole: no Stats, no Gaussians, zero normal information for the zero normals. */
 int pwn_hip_unproject(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const float T[16], const float* depth,
                       int rows, int cols, pwn_hip_cloud* cloud, int* index_image);
 /* PinholePointProjector::projectIntervals (pinholepointprojector.cpp:135-147) */
@@ -293,7 +295,9 @@ int pwn_hip_project_intervals(pwn_hip_ctx* ctx, const pwn_hip_converter_params* 
 int pwn_hip_integral_image(pwn_hip_ctx* ctx, const int* index_image, const pwn_hip_cloud* cloud, int rows, int cols, float* out);
 /* DepthImageConverterIntegralImage::compute(cloud, depthImage, sensorOffset)
  * (depthimageconverterintegralimage.cpp:15-55).  index_image / interval_image: optional outputs
- * (DepthImageConverter::indexImage(), depthimageconverter.h:111). keep_stats: also keep per-point Stats. */
+ * (DepthImageConverter::indexImage(), depthimageconverter.h:111). keep_stats: also keep per-point Stats.
+ * Every conversion call (this one, the batch and scaled forms, the one-submission steps) that returns an error after it has begun to write
+ * leaves its clouds empty: size 0, no Stats, no Gaussians, no index image. */
 int pwn_hip_convert(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const float* depth, int rows, int cols,
                     pwn_hip_cloud* cloud, int* index_image, int* interval_image, int keep_stats);
 /* PwnMatcherBase::makeCloud's data path in one call (pwn_tracker/pwn_matcher_base.cpp:71-79): DepthImage_scale(depth, step,
@@ -324,7 +328,8 @@ int pwn_hip_convert_export_begin(pwn_hip_ctx* ctx, const pwn_hip_converter_param
                                  pwn_hip_cloud* cloud, void* flat_dst, size_t flat_bytes);
 int pwn_hip_convert_export_end(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, size_t* written, float* job_ms);
 /* n independent frames of equal size in one call.  depth[i] -> clouds[i].
- * depth_frames: n pointers (host array) to rows*cols floats each (each host or device). */
+ * depth_frames: n pointers (host array) to rows*cols floats each (each host or device).  A call refused for a null frame or cloud, or for
+ * clouds of mixed omega storages, leaves every cloud as it was. */
 int pwn_hip_convert_batch(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const float* const* depth_frames,
                           int n, int rows, int cols, pwn_hip_cloud* const* clouds);
 /* Same, from raw uint16 millimetre frames: fuses DepthImage_convert_16UC1_to_32FC1 (scale) in front. */
@@ -446,7 +451,8 @@ int pwn_hip_match_batch_records(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* 
  * cur_frames[i] -> currents[i] (PwnMatcherBase::makeCloud, pwn_matcher_base.cpp:77-85), then Aligner::align of the pair
  * (pwn_matcher_base.cpp:120-128).  The conversion of a sub-batch's frames is queued in front of its alignment on the same stream, so one
  * sub-batch converts while the other aligns and nothing waits for the host between the two halves.  Results are bit for bit those of
- * pwn_hip_convert_batch_u16 followed by pwn_hip_align_batch.  The 2 n clouds must be distinct; frames: uint16 millimetres, host or device. */
+ * pwn_hip_convert_batch_u16 followed by pwn_hip_align_batch.  The 2 n clouds must be distinct; frames: uint16 millimetres, host or device.
+ * A call refused for a null frame or cloud, or for clouds of mixed omega storages, leaves every cloud as it was. */
 int pwn_hip_convert_align_batch_u16(pwn_hip_ctx* ctx, const pwn_hip_converter_params* converter, const pwn_hip_aligner_params* aligner, int n,
                                     const uint16_t* const* ref_frames, const uint16_t* const* cur_frames, float depth_scale, int rows, int cols,
                                     pwn_hip_cloud* const* references, pwn_hip_cloud* const* currents, const float* initial_guesses,

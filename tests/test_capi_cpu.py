@@ -352,6 +352,28 @@ def test_runtime_allocation_calls_live_in_the_buffer_type_and_the_caller_facing_
     assert seen == allowed, sorted(allowed - seen)
 
 
+def test_a_clouds_content_record_is_written_by_its_own_functions_only():
+    """What a cloud's arrays mean -- size, Stats, Gaussians, index image and its key -- is the CloudContent member of pwn_hip_cloud.  Its fields are
+    assigned inside that struct and nowhere else in csrc/: the transitions (replace, commit, edit) and the named setters call its functions, nothing
+    takes a writable reference to it, and the loose fields it replaced are gone."""
+    d = os.path.join(ROOT, "g2o_frontend_amd", "csrc")
+    text = {f: re.sub(r"//[^\n]*", "", open(os.path.join(d, f)).read()) for f in sorted(os.listdir(d))}
+    capi = text["pwn_hip_capi.hip"]
+    m = re.search(r"\nstruct CloudContent \{\n.*?\n\};\n", capi, flags=re.S)
+    assert m and capi.count("struct CloudContent") == 1
+    names = ["n", "stats", "n_gauss", "idx_valid", "idx_key"]
+    decls = re.findall(r"^  (?:int|bool) (\w+) = \w+;| IndexKey (\w+);", m.group(0), flags=re.M)
+    assert sorted(a or b for a, b in decls) == sorted(names), decls
+    text["pwn_hip_capi.hip"] = capi.replace(m.group(0), "\n")
+    write = re.compile(r"\bcontent\s*(?:\.\s*(?:%s)\s*)?(?:=(?!=)|[-+*/|&^]=|\+\+|--)|(?:\+\+|--)\s*[\w>.-]*\bcontent\b" % "|".join(names))
+    for f, t in text.items():
+        for n, line in enumerate(t.splitlines(), 1):
+            assert not write.search(line), (f, n, line.strip())
+            assert not re.search(r"(?<!const )CloudContent\s*[&*]", line), (f, n, line.strip())
+            assert not re.search(r"\b(n_host|has_stats)\b|->\s*(n_gauss|idx_valid|idx_key)\b", line), (f, n, line.strip())
+    assert len(re.findall(r"\bCloudContent\b", text["pwn_hip_capi.hip"])) == 1, "one member of that type, in pwn_hip_cloud"
+
+
 def test_single_point_projector_forms_against_the_numpy_model():
     """PinholePointProjector::project(x, y, f, p) / unProject(p, x, y, d) / projectInterval (pinholepointprojector.h:174,187,200) are host code of the
     library (no GPU): against the numpy statement of the reference's lines (tests/numpy_reference_model.py), point by point, bit for bit."""

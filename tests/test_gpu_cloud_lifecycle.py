@@ -1,7 +1,8 @@
 """A cloud's device arrays over its lifetime: a cloud with a history -- a scene with Stats, explicit normal information, Gaussians and the second
 array set of the compactions; a cloud out of the context's pool -- against a freshly created cloud given the same final content, every
 downloadable array bit for bit (points, normals, curvature, both information matrices, Stats where present, the Gaussians and their flags, the
-size).  24 x 32 frames of the synthetic scene, clouds of 4 x 768 points."""
+size).  24 x 32 frames of the synthetic scene, clouds of 4 x 768 points.  The calls that replace a cloud's content -- conversions, upload, unProject,
+import, load, the pool -- leave nothing of the history behind, a conversion that fails leaves an empty cloud, a refused one an untouched cloud."""
 import os
 import sys
 
@@ -109,6 +110,140 @@ def scene(context, frames):
     assert 0 < k < n and sc.numGaussians() == n
     assert 0 < api.VoxelCalculator().compute(sc, RES) <= k
     return sc
+
+
+def uploaded(context, capacity=CAP, n=None):
+    """an uploaded cloud -- explicit normal information -- with a Gaussian for every point"""
+    from g2o_frontend_amd import api
+    src = S.add_source()
+    n = src["n"] if n is None else n
+    c = api.Cloud(context, capacity)
+    c.upload(*[src["arrays"][k][:n] for k in S.CLOUD_KEYS])
+    c.debugSetGaussians(*[S.head_gauss(src["gauss"], n)[k] for k in S.GAUSS_KEYS])
+    assert c.size() == c.numGaussians() == n and c.arrays()["omega_n"].any()
+    return c
+
+
+def make_aligner(context):
+    """the converter's projector, so that the aligner's index key is the converted clouds' and the projection shortcuts are taken"""
+    from g2o_frontend_amd import api
+    finder = api.CorrespondenceFinder(); finder.setImageSize(ROWS, COLS)
+    a = api.Aligner(context)
+    a.setProjector(projector(api)); a.setLinearizer(api.Linearizer()); a.setCorrespondenceFinder(finder)
+    a.setOuterIterations(3); a.setInnerIterations(1)
+    return a
+
+
+def aligned(aligner, ref, cur):
+    aligner.setReferenceCloud(ref); aligner.setCurrentCloud(cur)
+    r = aligner.align()
+    assert r["iterations"] == 3 and r["inliers"] > 0
+    return [r[k].tobytes() for k in ("T", "chi2", "iter_inliers", "C", "K")] + [r["n_reference"], r["n_current"]]
+
+
+@pytest.mark.parametrize("how", ["plain", "keep_stats", "gaussians"])
+def test_compute_over_a_used_cloud(ctx, frames, how):
+    """a conversion replaces whatever the cloud held, and the index image it promises while it is queued is the new content's: the cloud equals a
+    fresh one, and aligns like it on either side of a pair"""
+    from g2o_frontend_amd import api
+    other = converted(ctx, frames[1])
+    aligner = make_aligner(ctx)
+    got = []
+    for c in (scene(ctx, frames), api.Cloud(ctx, CAP)):
+        make_converter(api).compute(c, frames[0], keep_stats=how == "keep_stats", gaussians=how == "gaussians")
+        got.append((snapshot(c), aligned(aligner, other, c), aligned(aligner, c, other)))
+    assert_same(got[0][0], got[1][0], how)
+    assert ("stats" in got[0][0]) == (how == "keep_stats") and len(got[0][0]["gauss"]["flags"]) == (got[0][0]["size"] if how == "gaussians" else 0)
+    assert got[0][1:] == got[1][1:], how
+
+
+@pytest.fixture(scope="module")
+def ctx2():
+    from g2o_frontend_amd import api
+    c = api.Context(device=0, max_rows=S.ROWS, max_cols=S.COLS, max_batch=2)
+    yield c
+    c.close()
+
+
+@pytest.mark.parametrize("form", ["batch", "scaled"])
+def test_batch_forms_over_used_clouds(ctx2, frames, form):
+    """computeBatch of two frames, and the 2 x scaled batch form from 48 x 64 sources, over a scene and over an uploaded cloud with Gaussians"""
+    import ctypes as C
+    from g2o_frontend_amd import api, synth
+    conv = make_converter(api)
+    if form == "scaled":
+        src = [synth.make_pair(seed, 2 * ROWS, 2 * COLS, synth.scaled_K(synth.K_VGA, 10))[0].astype(F) * F(0.001) for seed in (3, 4)]
+        ptrs, p = (C.c_void_p * 2)(*[f.ctypes.data for f in src]), conv.params()
+    snaps = []
+    for clouds in ((scene(ctx2, frames), uploaded(ctx2)), (api.Cloud(ctx2, CAP), api.Cloud(ctx2, CAP))):
+        if form == "batch":
+            conv.computeBatch(list(clouds), frames[2:4])
+        else:
+            handles = (C.c_void_p * 2)(*[c.h for c in clouds])
+            ctx2.check(ctx2._L.pwn_hip_convert_batch_scaled(ctx2.h, C.byref(p), ptrs, 2, 2 * ROWS, 2 * COLS, 2, 0.01, handles))
+        snaps.append([snapshot(c) for c in clouds])
+    for i, (a, b) in enumerate(zip(*snaps)):
+        assert a["size"] > ROWS * COLS // 2 and a["normals"].any()
+        assert_same(a, b, (form, i))
+
+
+def test_upload_over_a_cloud_with_gaussians(ctx):
+    """the Gaussians belonged to the points that are gone"""
+    from g2o_frontend_amd import api
+    src = S.add_source(seed=22)
+    snaps = []
+    for c in (uploaded(ctx), api.Cloud(ctx, CAP)):
+        c.upload(*[src["arrays"][k] for k in S.CLOUD_KEYS])
+        assert c.numGaussians() == 0
+        snaps.append(snapshot(c))
+    assert_same(snaps[0], snaps[1], "upload")
+
+
+def test_unproject_over_an_uploaded_cloud_with_gaussians(ctx, frames):
+    """points only: zero normals, and zero normal information for them, not the rows the uploaded points left behind"""
+    from g2o_frontend_amd import api
+    snaps = []
+    for c in (uploaded(ctx), api.Cloud(ctx, CAP)):
+        projector(api).unProject(c, frames[0])
+        snaps.append(snapshot(c))
+    assert snaps[0]["size"] > ROWS * COLS // 2 and not snaps[1]["omega_n"].any() and not snaps[1]["normals"].any()
+    assert len(snaps[1]["gauss"]["flags"]) == 0
+    assert_same(snaps[0], snaps[1], "unProject")
+
+
+def test_a_refused_batch_leaves_its_first_cloud_as_it_was(ctx2, frames):
+    import ctypes as C
+    from g2o_frontend_amd import api
+    from g2o_frontend_amd._lib import PwnHipError
+    first, second = uploaded(ctx2), api.Cloud(ctx2, CAP)
+    before = snapshot(first)
+    p = make_converter(api).params()
+    ptrs, handles = (C.c_void_p * 2)(frames[2].ctypes.data, None), (C.c_void_p * 2)(first.h, second.h)
+    with pytest.raises(PwnHipError, match="null frame or cloud"):
+        ctx2.check(ctx2._L.pwn_hip_convert_batch(ctx2.h, C.byref(p), ptrs, 2, ROWS, COLS, handles))
+    assert_same(snapshot(first), before, "refused batch")
+    assert before["size"] > 0 and len(before["gauss"]["flags"]) == before["size"]
+
+
+def test_a_conversion_that_fails_leaves_an_empty_cloud(ctx):
+    """PWN_HIP_ERR_CAPACITY: 768 valid pixels into a cloud of 16 points (the kernels' stores are guarded by the capacity; the call returns the
+    status when it has seen the count).  The cloud must not go on reporting the 16 uploaded points and their Gaussians over arrays the failed
+    conversion wrote into."""
+    from g2o_frontend_amd import api
+    from g2o_frontend_amd._lib import PwnHipError, STATUS
+    c = uploaded(ctx, capacity=16, n=16)
+    with pytest.raises(PwnHipError) as e:
+        make_converter(api).compute(c, np.full((ROWS, COLS), 2.0, F), keep_stats=True)
+    assert STATUS[e.value.code] == "CAPACITY"
+    assert c.size() == 0 and c.numGaussians() == 0
+    with pytest.raises(PwnHipError, match="not converted with keep_stats"):
+        c.arrays(stats=True)
+    small = (np.arange(16, dtype=F).reshape(4, 4) * F(0.01) + F(2.0))
+    fresh = api.Cloud(ctx, 16)
+    for x in (c, fresh):
+        make_converter(api).compute(x, small)
+    assert fresh.size() == 16
+    assert_same(snapshot(c), snapshot(fresh), "after a failed conversion")
 
 
 def test_back_set_survives_an_import_of_a_class_coded_cloud(ctx, frames):
