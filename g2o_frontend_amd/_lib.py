@@ -59,6 +59,10 @@ class AlignStatistics(C.Structure):
                 ("rotational_eigen_ratio", C.c_float), ("H", C.c_float * 36), ("b", C.c_float * 6), ("error", C.c_float), ("inliers", C.c_int)]
 
 
+class ConvertExtras(C.Structure):
+    _fields_ = [("keep_stats", C.c_int), ("gaussians", C.c_int), ("baseline", C.c_float), ("alpha", C.c_float)]
+
+
 class Prior(C.Structure):
     _fields_ = [("kind", C.c_int), ("mean", C.c_float * 16), ("reference_transform", C.c_float * 16), ("information", C.c_float * 36)]
 
@@ -116,6 +120,8 @@ PROTOTYPES = {
     "pwn_hip_convert_batch_u16": (_I, [_VP, _VP, _VP, _F, _I, _I, _I, _VP]),
     "pwn_hip_convert_batch_scaled": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _F, _VP]),
     "pwn_hip_convert_batch_u16_scaled": (_I, [_VP, _VP, _VP, _F, _I, _I, _I, _I, _F, _VP]),
+    "pwn_hip_default_convert_extras": (None, [_VP]),
+    "pwn_hip_convert_batch_ex": (_I, [_VP, _VP, _VP, _I, _F, _I, _I, _I, _I, _F, _VP, _VP]),
     "pwn_hip_project": (_I, [_VP, _VP, _VP, _F, _F, _I, _I, _VP, _VP, _VP]),
     "pwn_hip_merge_depth_images": (_I, [_VP, _I, _VP, _I, _I, _VP, _VP, _VP, _VP]),
     "pwn_hip_project_merge_batch": (_I, [_VP, _VP, _I, _VP, _VP, _F, _F, _I, _I, _VP, _VP, _VP, _VP, _VP]),
@@ -165,7 +171,9 @@ PROTOTYPES = {
     "pwn_hip_debug_front_end": (_I, [_VP, _VP, _VP, _F, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_debug_trig_eval": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_debug_cloud_set_gaussians": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
+    "pwn_hip_debug_cloud_expose_gaussians": (_I, [_VP, _VP, _I]),
     "pwn_hip_debug_set_manifold_chunk": (_I, [_VP, _I]),
+    "pwn_hip_debug_set_gaussian_stores": (_I, [_VP, _I]),
     "pwn_hip_measure_hbm": (_I, [_VP, C.c_size_t, _VP, _VP]),
 }
 

@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AlignerParams, AlignResult, AlignStatistics, ConverterParams, MatchResult, Prior, PwnHipError
+from ._lib import AlignerParams, AlignResult, AlignStatistics, ConvertExtras, ConverterParams, MatchResult, Prior, PwnHipError
 
 
 def _ptr(x):
@@ -488,6 +488,10 @@ class Cloud:
         assert [x.size for x in a] == [3 * f.size, 9 * f.size, 3 * f.size, 9 * f.size], "one row of mean, cov, info_vec and info per flag word"
         self.ctx.check(self.ctx._L.pwn_hip_debug_cloud_set_gaussians(self.ctx.h, self.h, len(f), *[_ptr(x) for x in a], _ptr(f)))
 
+    def debugExposeGaussians(self, n: int):
+        """test-only (include/pwn_hip_testing.h): the Gaussian vector becomes the first n records of the cloud's arrays as they are"""
+        self.ctx.check(self.ctx._L.pwn_hip_debug_cloud_expose_gaussians(self.ctx.h, self.h, int(n)))
+
     def add(self, cloud: "Cloud", T=None):
         """Cloud::add (cloud.cpp:145-171)"""
         self.ctx.check(self.ctx._L.pwn_hip_cloud_add(self.ctx.h, self.h, cloud.h, _ptr(_colmajor(np.eye(4) if T is None else T, 4))))
@@ -729,16 +733,28 @@ class DepthImageConverterIntegralImage:
         n = len(clouds)
         return (C.c_void_p * n)(*[c.h for c in clouds]), (C.c_void_p * n)(*[_ptr(d) for d in depthImages]), n, tuple(depthImages[0].shape)
 
-    def computeBatch(self, clouds, depthImages, sensorOffset=None, raw_scale=None, prepared=None):
+    def extras(self, keep_stats: bool, gaussians: bool):
+        """pwn_hip_convert_extras of a scene-ready batch conversion (the projector's baseline and alpha), or None for a lean one"""
+        if not (keep_stats or gaussians):
+            return None
+        return ConvertExtras(1 if keep_stats else 0, 1 if gaussians else 0, self._projector._baseline, self._projector._alpha)
+
+    def computeBatch(self, clouds, depthImages, sensorOffset=None, raw_scale=None, prepared=None, keep_stats: bool = False, gaussians: bool = False):
         """n independent frames in one call.  depthImages: list of float32 [rows, cols] arrays / CUDA tensors,
-        or uint16 millimetre frames when raw_scale is given (fuses DepthImage_convert_16UC1_to_32FC1)."""
+        or uint16 millimetre frames when raw_scale is given (fuses DepthImage_convert_16UC1_to_32FC1).  keep_stats / gaussians: the clouds
+        leave scene-ready, with the Stats and the sensor-noise Gaussians compute(keep_stats=True, gaussians=True) gives frame by frame
+        (pwn_hip_convert_batch_ex), inside the same submission."""
         ctx = clouds[0].ctx
         p = self.params(sensorOffset)
         if prepared is not None:
             handles, ptrs, n, (rows, cols) = prepared
         else:
             handles, ptrs, n, (rows, cols) = self.batchHandles(clouds, depthImages)
-        if raw_scale is None:
+        ex = self.extras(keep_stats, gaussians)
+        if ex is not None:
+            ctx.check(ctx._L.pwn_hip_convert_batch_ex(ctx.h, C.byref(p), ptrs, 0 if raw_scale is None else 1, raw_scale or 0.0, n, rows, cols, 0, 0.0,
+                                                      C.byref(ex), handles))
+        elif raw_scale is None:
             ctx.check(ctx._L.pwn_hip_convert_batch(ctx.h, C.byref(p), ptrs, n, rows, cols, handles))
         else:
             ctx.check(ctx._L.pwn_hip_convert_batch_u16(ctx.h, C.byref(p), ptrs, raw_scale, n, rows, cols, handles))
@@ -1130,8 +1146,12 @@ class PwnMatcherBase:
     def setAligner(self, a): self._aligner = a                                                   # pwn_matcher_base.h:30,33
     def setConverter(self, c): self._converter = c
 
-    def makeCloud(self, cameraMatrix, sensorOffset, depthImage, ctx: Context = None):
-        """pwn_matcher_base.cpp:57-86 -> (cloud, r, c, scaledCameraMatrix)"""
+    def makeCloud(self, cameraMatrix, sensorOffset, depthImage, ctx: Context = None, keep_stats: bool = False, gaussians: bool = False):
+        """pwn_matcher_base.cpp:57-86 -> (cloud, r, c, scaledCameraMatrix).  keep_stats / gaussians: a scene-ready cloud (makeCloudBatch of
+        the one frame)."""
+        if keep_stats or gaussians:
+            clouds, r, c, K = self.makeCloudBatch(cameraMatrix, sensorOffset, [depthImage], ctx=ctx, keep_stats=keep_stats, gaussians=gaussians)
+            return clouds[0], r, c, K
         ctx = ctx or self._aligner.ctx
         projector = self._converter.projector()
         invScale = np.float32(1.0) / np.float32(self._scale)
@@ -1150,11 +1170,13 @@ class PwnMatcherBase:
         self.numCalls += 1
         return cloud, projector.imageRows(), projector.imageCols(), projector.cameraMatrix().copy()
 
-    def makeCloudBatch(self, cameraMatrix, sensorOffset, depthImages, raw_scale=None, clouds=None, ctx: Context = None):
+    def makeCloudBatch(self, cameraMatrix, sensorOffset, depthImages, raw_scale=None, clouds=None, ctx: Context = None, keep_stats: bool = False,
+                       gaussians: bool = False):
         """makeCloud (pwn_matcher_base.cpp:57-86) of n frames of one size, camera matrix and sensor offset in one call
         (pwn_hip_convert_batch[_u16]_scaled) -> (clouds, r, c, scaledCameraMatrix).  depthImages: float32 arrays / CUDA tensors, or uint16
         frames when raw_scale is given; clouds: optional clouds to fill instead of new ones.  The projector ends as n makeCloud calls leave
-        it; numCalls advances by n."""
+        it; numCalls advances by n.  keep_stats / gaussians: the clouds carry the Stats and the sensor-noise Gaussians the reference's converter
+        always leaves (pwn_hip_convert_batch_ex), which Merger.merge, Cloud.save and PwnMerger need."""
         ctx = ctx or self._aligner.ctx
         projector = self._converter.projector()
         invScale = np.float32(1.0) / np.float32(self._scale)
@@ -1176,7 +1198,11 @@ class PwnMatcherBase:
         projector.setTransform(np.eye(4, dtype=np.float32))
         p = self._converter.params(sensorOffset)
         handles = (C.c_void_p * n)(*[cl.h for cl in clouds]); ptrs = (C.c_void_p * n)(*[_ptr(d) for d in frames])
-        if raw_scale is None:
+        ex = self._converter.extras(keep_stats, gaussians)
+        if ex is not None:
+            ctx.check(ctx._L.pwn_hip_convert_batch_ex(ctx.h, C.byref(p), ptrs, 0 if raw_scale is None else 1, raw_scale or 0.0, n, rows, cols, self._scale, 0.01,
+                                                      C.byref(ex), handles))
+        elif raw_scale is None:
             ctx.check(ctx._L.pwn_hip_convert_batch_scaled(ctx.h, C.byref(p), ptrs, n, rows, cols, self._scale, 0.01, handles))
         else:
             ctx.check(ctx._L.pwn_hip_convert_batch_u16_scaled(ctx.h, C.byref(p), ptrs, raw_scale, n, rows, cols, self._scale, 0.01, handles))
@@ -1596,7 +1622,9 @@ class PwnCloserWithMerger:
 class PwnMerger:
     """pwn_tracker2/pwn_merger.{h,cpp}: mergeNodeList (:28-62), what MapMerger::process (boss_map_building/map_merger.cpp:43-82) calls every
     listSize + 1 key nodes -- the cached clouds of the list fused, one after the other, into one local-map cloud in the frame of the first
-    ("big") node, which then becomes that node's cloud in the cache."""
+    ("big") node, which then becomes that node's cloud in the cache.  The cache must be a CloudCache(..., sceneReady=True): the reference's
+    cached clouds carry Stats and Gaussians, the fused cloud copies both (:56-61), and only then can it be handed to Merger.merge or saved
+    with real Stats.  With a lean cache the fused cloud has default Stats and no Gaussians."""
 
     def __init__(self, merger: Merger2, cache: "CloudCache"):
         self._merger, self._cache = merger, cache
@@ -1677,10 +1705,11 @@ class ManifoldVoronoiExtractor:
 class CloudCache:
     """Device-resident LRU of clouds keyed by frame (pwn_tracker/pwn_tracker_cache.cpp:24-51 + boss_map_building cache):
     a miss re-runs the converter on the frame's stored depth image (PwnCache::loadFrame), so loop-closure batches do not
-    re-convert frames that are still resident in HBM."""
+    re-convert frames that are still resident in HBM.  sceneReady: the misses of get and getBatch are converted with Stats and sensor-noise
+    Gaussians, as the reference's converter always does (what PwnMerger needs of its cache); clouds handed to addFrame stay as they are."""
 
-    def __init__(self, matcher: "PwnMatcherBase", capacity: int = 64):
-        self._matcher, self._capacity = matcher, capacity
+    def __init__(self, matcher: "PwnMatcherBase", capacity: int = 64, sceneReady: bool = False):
+        self._matcher, self._capacity, self._sceneReady = matcher, capacity, bool(sceneReady)
         self._clouds = {}        # key -> Cloud, insertion order = recency
         self._frames = {}        # key -> (depthImage, cameraMatrix, sensorOffset)
         self.hits = self.misses = 0
@@ -1705,7 +1734,7 @@ class CloudCache:
             return c
         self.misses += 1
         depth, K, off = self._frames[key]
-        c, _, _, _ = self._matcher.makeCloud(K, off, depth)    # pwn_tracker_cache.cpp:38-44
+        c, _, _, _ = self._matcher.makeCloud(K, off, depth, keep_stats=self._sceneReady, gaussians=self._sceneReady)    # pwn_tracker_cache.cpp:38-44
         self._insert(key, c)
         return c
 
@@ -1728,7 +1757,7 @@ class CloudCache:
         made = {}
         for members in groups.values():
             _, K, off = self._frames[members[0]]
-            clouds = self._matcher.makeCloudBatch(K, off, [self._frames[k][0] for k in members])[0]
+            clouds = self._matcher.makeCloudBatch(K, off, [self._frames[k][0] for k in members], keep_stats=self._sceneReady, gaussians=self._sceneReady)[0]
             made.update(zip(members, clouds))
         out = []
         for key in keys:

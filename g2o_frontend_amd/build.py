@@ -87,6 +87,13 @@ def build_tools(force: bool = False) -> str:
     if force or (not os.path.exists(out9)) or any(os.path.getmtime(d) > os.path.getmtime(out9) for d in deps9):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src9, "-o", out9, "-L", _HERE, "-lpwn_hip",
                                "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
+    # CloudCache(sceneReady) -> PwnMerger::mergeNodeList of the C++ mirror against the Python mirror's fused cloud, Stats and Gaussians included
+    src10 = os.path.join(root, "tools", "pwn_hip_scene_ready_check.cpp")
+    out10 = os.path.join(root, "tools", "pwn_hip_scene_ready_check")
+    deps10 = [src10] + deps[1:]
+    if force or (not os.path.exists(out10)) or any(os.path.getmtime(d) > os.path.getmtime(out10) for d in deps10):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src10, "-o", out10, "-L", _HERE, "-lpwn_hip",
+                               "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
     # PwnCloser::processPartition over the GPUs of a node in native code: the mirror + RCCL (broadcast of the flat `current` cloud, all-gather of the
     # match records); the program's own streams and events come from the HIP runtime
     src5 = os.path.join(root, "tools", "pwn_hip_partition_app.cpp")

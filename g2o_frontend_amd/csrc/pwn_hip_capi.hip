@@ -115,6 +115,7 @@ struct CloudArrays {
 
 // What a cloud's arrays hold at this moment.  The fields are assigned in this struct and nowhere else (tests/test_capi_cpu.py); its functions are
 // called by the three transitions of a cloud's content -- cloud_replace, cloud_commit, cloud_edit -- by a conversion job that ends without a commit,
+// or whose kernels wrote the Gaussians of the points they counted (commit_with_gaussians),
 // and by the two setters' callers (the Gaussian calls, ensure_scene).  Everything else reads.
 struct CloudContent {
   int n = 0;                     // points, as the host knows them (pwn_hip_cloud_size); the device keeps a word of its own (pwn_hip_cloud::count)
@@ -126,6 +127,7 @@ struct CloudContent {
   void replace(bool keep_stats, const IndexKey* key, bool promised) { n = 0; stats = keep_stats; n_gauss = 0; idx_valid = promised; if (key) idx_key = *key; }
   void commit(int points) { n = points; }                                                        // a promised index key stands
   void commit(int points, const IndexKey& key) { n = points; idx_valid = true; idx_key = key; }  // the index image arrived with the points
+  void commit_with_gaussians(int points) { n = points; n_gauss = points; }                       // ... and a sensor-noise Gaussian with every point
   void withdraw() { n = 0; stats = false; n_gauss = 0; idx_valid = false; }                      // the new content did not arrive: an empty cloud
   void edit(int points) { n = points; idx_valid = false; }
   void set_gaussians(int count) { n_gauss = count; }
@@ -198,6 +200,9 @@ struct pwn_hip_ctx {
   // the *_scaled batch calls (allocated by the first of them): the down-sampled frame of every slot, which its front end reads, and the box
   // kernel's descriptors (one per frame of a call)
   DevBuf<float> scaled_ws; DevBuf<ScaleDesc> scale_dev; HostBuf<ScaleDesc> scale_host;
+  // pwn_hip_convert_batch_ex with Gaussians (allocated by the first such call): the Gaussian arrays of every frame's cloud, beside frames_dev
+  DevBuf<SceneBuffers> gauss_dev; HostBuf<SceneBuffers> gauss_host;
+  int gauss_staged = kGaussStagedDefault;                    // pwn_hip_debug_set_gaussian_stores (test hook): how k_gaussians_batch stores its records
   DevBuf<unsigned long long> carry_ws; size_t carry_slot = 0; size_t rowoff_slot = 0;   // single-pass integral image: hand-over words, strip offsets
   unsigned convert_epoch = 0; DevBuf<int> fault_dev;
   int last_convert_fault = 0;              // fault word of the last converter launch of the CURRENT call (1 = a bounded poll timed out); reset when a call starts
@@ -710,11 +715,12 @@ int cloud_own(pwn_hip_ctx* ctx, pwn_hip_cloud* c, unsigned which) {
 // Replace: the cloud is about to receive new points from outside.  What it held is gone from here on -- it reads as empty, without Gaussians and,
 // unless the caller promises that the points will arrive with the index image of `key`, without an index image -- and the arrays of what is coming
 // are there: St when Stats are kept; for the normal information matrices the explicit planes (`planes`), or no planes and the class matrices
-// `cls` (nullptr: as they are).  Planes are dropped after a wait for the stream, which may still read them; the wait happens only then.
+// `cls` (nullptr: as they are); the Gaussian arrays when the conversion will write Gaussians (`gauss`; the count stays 0 until its commit).  Planes are dropped after a wait for the stream, which may still read them; the wait happens only then.
 // (`key` without the promise: what the index image is being made with, kept beside an image that is not valid -- the flat form carries it.)
-int cloud_replace(pwn_hip_ctx* ctx, pwn_hip_cloud* c, bool keep_stats, bool planes, const OmegaNClasses* cls, const IndexKey* key = nullptr, bool promised = false) {
+int cloud_replace(pwn_hip_ctx* ctx, pwn_hip_cloud* c, bool keep_stats, bool planes, const OmegaNClasses* cls, const IndexKey* key = nullptr, bool promised = false,
+                  bool gauss = false) {
   cloud_changes(ctx, c);
-  if (const unsigned which = (keep_stats ? kArrSt : 0u) | (planes ? kArrOmN : 0u)) { if (int rc = cloud_own(ctx, c, which)) return rc; }
+  if (const unsigned which = (keep_stats ? kArrSt : 0u) | (planes ? kArrOmN : 0u) | (gauss ? kArrGauss : 0u)) { if (int rc = cloud_own(ctx, c, which)) return rc; }
   if (!planes && c->d.OmN) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH); c->drop_omega_n(); }
   if (cls) { std::memcpy(c->d.omN, cls->omN, sizeof(cls->omN)); c->d.clsThr = cls->clsThr; }
   c->content.replace(keep_stats, key, promised);
@@ -723,6 +729,7 @@ int cloud_replace(pwn_hip_ctx* ctx, pwn_hip_cloud* c, bool keep_stats, bool plan
 // Commit: the new content has arrived, `n` points of it; with `key` the index image came with them, without it a promised one stands.  (The
 // device's size word is the kernels' or the caller's copy.)
 void cloud_commit(pwn_hip_cloud* c, int n, const IndexKey* key = nullptr) { if (key) c->content.commit(n, *key); else c->content.commit(n); }
+void cloud_commit_with_gaussians(pwn_hip_cloud* c, int n) { c->content.commit_with_gaussians(n); }      // a promised index key stands here too
 // Edit: the points changed in place, or their number did: no index image, `n` points.  device_word: the host decided the size, and the device's
 // word follows on the stream, as a fill value, so that nothing is read from host memory after the call returned.
 int cloud_edit(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int n, bool device_word) {
@@ -771,9 +778,9 @@ int counts_check(pwn_hip_ctx* ctx, pwn_hip_cloud* const* clouds, int n) {
   return PWN_HIP_OK;
 }
 // commit: the counts are the clouds' sizes, if the check lets all of them pass
-int counts_apply(pwn_hip_ctx* ctx, pwn_hip_cloud* const* clouds, int n) {
+int counts_apply(pwn_hip_ctx* ctx, pwn_hip_cloud* const* clouds, int n, bool gauss = false) {
   if (int rc = counts_check(ctx, clouds, n)) return rc;
-  for (int i = 0; i < n; ++i) cloud_commit(clouds[i], ctx->counts_host[i]);
+  for (int i = 0; i < n; ++i) { if (gauss) cloud_commit_with_gaussians(clouds[i], ctx->counts_host[i]); else cloud_commit(clouds[i], ctx->counts_host[i]); }
   return PWN_HIP_OK;
 }
 // frames_dev[0..n) must describe clouds[0..n): the counts and the fault flag back (direct: the kernels stored them in counts_host themselves), the wait
@@ -837,8 +844,22 @@ int launch_depth_scale(pwn_hip_ctx* ctx, const ScaleSpec& sc, bool raw, float ra
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
 }
+// The sensor-noise Gaussians a conversion writes beside its points (pwn_hip_convert_batch_ex): the arguments k_gaussians takes
+struct GaussSpec {
+  bool on = false;
+  Mat3 iK; float fB = 0.f, alpha = 0.f;
+};
+// the per-frame Gaussian arrays of a call of n frames (grown after a wait for the stream, as ensure_desc grows its arrays)
+int ensure_gauss_desc(pwn_hip_ctx* ctx, int n) {
+  if ((size_t)n > ctx->gauss_dev.cap) HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  const size_t B = (size_t)std::max(n, 16);
+  HIPCHK(ctx, ctx->gauss_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->gauss_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  return PWN_HIP_OK;
+}
 struct ConvertJob {
   ConvertParams cp;
+  GaussSpec gauss;
   int n = 0, rows = 0, cols = 0;
   size_t N = 0;
   size_t srcN = 0;                       // pixels of a frame as the caller hands it over (= N unless the job down-samples)
@@ -855,7 +876,7 @@ struct ConvertJob {
 template <typename SRC>
 int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n, int rows, int cols,
                     pwn_hip_cloud* const* clouds, int keep_stats, bool want_interval, const std::vector<int>& slot, bool direct, ConvertJob& job,
-                    const ScaleSpec& sc = ScaleSpec()) {
+                    const ScaleSpec& sc = ScaleSpec(), const GaussSpec& gs = GaussSpec()) {
   const size_t N = (size_t)rows * cols;
   ctx->last_convert_fault = 0;            // the fault word belongs to this call from here on (a stale 1 would make an unrelated failure look like a time-out)
   ConvertParams cp = make_convert_params(ctx, p, nullptr, rows, cols, keep_stats);
@@ -863,7 +884,9 @@ int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const S
   // integral image: grouped storage (ig_at)
   cp.lean = want_interval ? 0 : kLeanGrouped;
   if (int rc = ensure_desc(ctx, n)) return rc;
+  if (gs.on) { if (int rc = ensure_gauss_desc(ctx, n)) return rc; }
   const bool raw = std::is_same<SRC, uint16_t>::value;
+  job.gauss = gs;
   job.n = n; job.rows = rows; job.cols = cols; job.N = N; job.raw = raw; job.depth_scale = depth_scale; job.slot = slot; job.direct = direct;
   job.scale = sc; job.srcN = sc.step ? (size_t)sc.srows * sc.scols : N;
   job.src.assign(n, nullptr);
@@ -874,8 +897,9 @@ int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const S
   // every frame gets a descriptor; workspace slots are reused round-robin (stream order serialises the reuse)
   for (int i = 0; i < n; ++i) {
     pwn_hip_cloud* c = clouds[i];
-    if (int rc = cloud_replace(ctx, c, keep_stats != 0, false, &cls, &key, cp.hasOffset == 0)) return rc;
+    if (int rc = cloud_replace(ctx, c, keep_stats != 0, false, &cls, &key, cp.hasOffset == 0, gs.on)) return rc;
     job.clouds.push_back(c);
+    if (gs.on) ctx->gauss_host[i] = c->sb;
     job.src[i] = frames[i];
     const float* depth_dev = nullptr;
     if (sc.step) depth_dev = ctx->scaled_ws + (size_t)slot[i] * ctx->N;      // the front end reads the down-sampled frame of its slot
@@ -905,6 +929,7 @@ int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const S
     }
   }
   if (sc.step) HIPCHK(ctx, hipMemcpyAsync(ctx->scale_dev, ctx->scale_host, sizeof(ScaleDesc) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+  if (gs.on && n > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->gauss_dev, ctx->gauss_host, sizeof(SceneBuffers) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
   // a call of a few frames (latency path, one launch): counts and fault flag land in page-locked host words straight from the kernels
   if (direct) for (int i = 0; i < n; ++i) ctx->frames_host[i].count_out = ctx->counts_host + i;
   HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev, ctx->frames_host, sizeof(FrameDesc) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
@@ -937,14 +962,29 @@ int check_frames_and_clouds(pwn_hip_ctx* ctx, const SRC* const* frames, pwn_hip_
   }
   return PWN_HIP_OK;
 }
-// the kernels of frames [base, base + m) of the job on st: the box mean into the frames' slots first when the job down-samples
+// the Gaussians of frames [base, base + m) on st, behind the front end that wrote their index images (and on its stream: the kernel reads the depth
+// the front end read, which for a down-sampling job is the slot's frame, and stream order keeps the slot's next user behind it)
+int launch_gaussians(pwn_hip_ctx* ctx, const ConvertJob& job, int base, int m, hipStream_t st) {
+  if (m <= 0) return PWN_HIP_OK;
+  StageTimer t(ctx, "gaussians", st);
+  const dim3 grid((unsigned)((job.N + 255) / 256), (unsigned)m);
+  const FrameDesc* fr = ctx->frames_dev + base; const SceneBuffers* sbs = ctx->gauss_dev + base;
+  if (ctx->gauss_staged) hipLaunchKernelGGL(k_gaussians_batch<true>, grid, dim3(256), 0, st, fr, sbs, job.cp, job.gauss.iK, job.gauss.fB, job.gauss.alpha);
+  else hipLaunchKernelGGL(k_gaussians_batch<false>, grid, dim3(256), 0, st, fr, sbs, job.cp, job.gauss.iK, job.gauss.fB, job.gauss.alpha);
+  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  return PWN_HIP_OK;
+}
+// the kernels of frames [base, base + m) of the job on st: the box mean into the frames' slots first when the job down-samples, the Gaussians last
+// when it makes them
 int convert_enqueue(pwn_hip_ctx* ctx, const ConvertJob& job, int base, int m, hipStream_t st, int* fault_out = nullptr) {
   if (job.scale.step) { if (int rc = launch_depth_scale(ctx, job.scale, job.raw, job.depth_scale, base, m, st)) return rc; }
-  return launch_convert(ctx, job.cp, base, m, st, fault_out);
+  if (int rc = launch_convert(ctx, job.cp, base, m, st, fault_out)) return rc;
+  if (job.gauss.on) return launch_gaussians(ctx, job, base, m, st);
+  return PWN_HIP_OK;
 }
 // commit: the job's clouds hold what its kernels counted (after the wait that brought counts and fault flag back)
 int convert_commit(pwn_hip_ctx* ctx, ConvertJob& job) {
-  if (int rc = counts_apply(ctx, job.clouds.data(), job.n)) return rc;
+  if (int rc = counts_apply(ctx, job.clouds.data(), job.n, job.gauss.on)) return rc;
   job.committed = true;
   return PWN_HIP_OK;
 }
@@ -955,7 +995,8 @@ int convert_finish(pwn_hip_ctx* ctx, ConvertJob& job) {
 
 template <typename SRC>
 int convert_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n,
-                       int rows, int cols, pwn_hip_cloud* const* clouds, int keep_stats, bool want_interval = false, const ScaleSpec& sc = ScaleSpec()) {
+                       int rows, int cols, pwn_hip_cloud* const* clouds, int keep_stats, bool want_interval = false, const ScaleSpec& sc = ScaleSpec(),
+                       const GaussSpec& gs = GaussSpec()) {
   if (!ctx || !p || !frames || !clouds || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (int rc = check_image(ctx, rows, cols)) return rc;
   if (int rc = check_frames_and_clouds(ctx, frames, clouds, n)) return rc;
@@ -971,7 +1012,7 @@ int convert_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, cons
     for (int i = 0; i < n; ++i) slot[i] = plan.slot0(i / sub) + i % sub;
     const bool direct = n > 0 && n < kSinglePassMinFrames && n <= sub;
     ConvertJob job;
-    if (int rc = convert_prepare<SRC>(ctx, p, frames, depth_scale, n, rows, cols, clouds, keep_stats, want_interval, slot, direct, job, sc)) return rc;
+    if (int rc = convert_prepare<SRC>(ctx, p, frames, depth_scale, n, rows, cols, clouds, keep_stats, want_interval, slot, direct, job, sc, gs)) return rc;
     if (int rc = plan_fork(ctx, plan)) return rc;
     // Host frames travel on the copy stream, ahead of the kernels: the frames of sub-batch k are copied while sub-batches k-1, k-2 ... are
     // being converted (with the copies on the sub-batch's own stream the two streams copy at the same time and then compute at the same
@@ -1110,14 +1151,14 @@ int check_scaled_capacities(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p,
 // call is looked at before a cloud is touched.
 template <typename SRC>
 int convert_batch_scaled_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n, int rows, int cols,
-                                     int step, float max_depth_cov, pwn_hip_cloud* const* clouds) {
+                                     int step, float max_depth_cov, pwn_hip_cloud* const* clouds, int keep_stats = 0, const GaussSpec& gs = GaussSpec()) {
   if (!ctx || !p || !frames || !clouds || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   ScaleSpec sc;
   if (int rc = make_scale_spec(ctx, rows, cols, step, max_depth_cov, sc)) return rc;
   if (int rc = check_frames_and_clouds(ctx, frames, clouds, n)) return rc;
   if (int rc = check_scaled_capacities<SRC>(ctx, p, frames, depth_scale, n, sc, clouds)) return rc;
   if (int rc = ensure_scale(ctx, n)) return rc;
-  return convert_batch_impl<SRC>(ctx, p, frames, depth_scale, n, sc.orows, sc.ocols, clouds, 0, false, sc);
+  return convert_batch_impl<SRC>(ctx, p, frames, depth_scale, n, sc.orows, sc.ocols, clouds, keep_stats, false, sc, gs);
 }
 
 // pwn_hip_debug_stats_from_integral and its lean form (`frames` given): the stats pass, launched as launch_convert launches it, on windows the
@@ -2125,6 +2166,38 @@ int pwn_hip_convert_batch_u16_scaled(pwn_hip_ctx* ctx, const pwn_hip_converter_p
 int pwn_hip_convert_batch_u16(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const uint16_t* const* raw_frames, float depth_scale, int n,
                               int rows, int cols, pwn_hip_cloud* const* clouds) {
   return convert_batch_impl<uint16_t>(ctx, p, raw_frames, depth_scale, n, rows, cols, clouds, 0);
+}
+void pwn_hip_default_convert_extras(pwn_hip_convert_extras* e) {
+  if (!e) return;
+  e->keep_stats = 0; e->gaussians = 0; e->baseline = 0.075f; e->alpha = 0.1f;      // pinholepointprojector.cpp:10-11
+}
+// The four batch forms with the extras.  What the extras can be refused for is looked at here; everything else by the form's own implementation,
+// before it touches a cloud.
+int pwn_hip_convert_batch_ex(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const void* const* frames, int raw_u16, float depth_scale, int n, int rows,
+                             int cols, int step, float max_depth_cov, const pwn_hip_convert_extras* extras, pwn_hip_cloud* const* clouds) {
+  if (!ctx || !p || !frames || !clouds || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (step < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "DepthImage_scale: step < 0");
+  int keep_stats = 0;
+  GaussSpec gs;
+  if (extras) {
+    if ((extras->keep_stats != 0 && extras->keep_stats != 1) || (extras->gaussians != 0 && extras->gaussians != 1))
+      return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "convert extras: keep_stats and gaussians must be 0 or 1");
+    if (!std::isfinite(extras->baseline) || !std::isfinite(extras->alpha)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "convert extras: baseline or alpha is not finite");
+    keep_stats = extras->keep_stats;
+    if (extras->gaussians) {
+      Mat4 KRt, iKRt;
+      projector_matrices(mat3_from(p->K), mat4_identity(), KRt, iKRt, gs.iK);
+      gs.on = true; gs.fB = extras->baseline * p->K[0]; gs.alpha = extras->alpha;
+    }
+  }
+  const uint16_t* const* raw = reinterpret_cast<const uint16_t* const*>(frames);
+  const float* const* flt = reinterpret_cast<const float* const*>(frames);
+  if (step == 0) {
+    if (raw_u16) return convert_batch_impl<uint16_t>(ctx, p, raw, depth_scale, n, rows, cols, clouds, keep_stats, false, ScaleSpec(), gs);
+    return convert_batch_impl<float>(ctx, p, flt, 0.f, n, rows, cols, clouds, keep_stats, false, ScaleSpec(), gs);
+  }
+  if (raw_u16) return convert_batch_scaled_impl<uint16_t>(ctx, p, raw, depth_scale, n, rows, cols, step, max_depth_cov, clouds, keep_stats, gs);
+  return convert_batch_scaled_impl<float>(ctx, p, flt, 0.f, n, rows, cols, step, max_depth_cov, clouds, keep_stats, gs);
 }
 
 // ------------------------------------------------------------------------------------------------ aligner stages

@@ -107,6 +107,12 @@ int pwn_hip_cloud_gaussians(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p,
   cloud->content.set_gaussians(cloud->content.n);
   return PWN_HIP_OK;
 }
+// Test-only (include/pwn_hip_testing.h): the store form of k_gaussians_batch
+int pwn_hip_debug_set_gaussian_stores(pwn_hip_ctx* ctx, int staged) {
+  if (!ctx) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  ctx->gauss_staged = (staged == 0 || staged == 1) ? staged : kGaussStagedDefault;
+  return PWN_HIP_OK;
+}
 int pwn_hip_cloud_num_gaussians(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, int* n) {
   if (!c || !n) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   *n = c->view().gauss;
@@ -151,6 +157,14 @@ int pwn_hip_debug_cloud_set_gaussians(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int n,
     HIPCHK(ctx, hipMemcpy(c->sb.G, g.data(), sizeof(GaussD) * (size_t)n, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
     HIPCHK(ctx, hipMemcpy(c->sb.Gf, flags, sizeof(int) * (size_t)n, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
   }
+  c->content.set_gaussians(n);
+  return PWN_HIP_OK;
+}
+// Test-only (include/pwn_hip_testing.h): the vector's length alone
+int pwn_hip_debug_cloud_expose_gaussians(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int n) {
+  if (!ctx || !c) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (c->owner != ctx) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "cloud of another context");
+  if (n < 0 || n > c->d.capacity || !c->sb.G || !c->sb.Gf) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "number of Gaussians outside [0, capacity], or no Gaussian arrays");
   c->content.set_gaussians(n);
   return PWN_HIP_OK;
 }

@@ -57,6 +57,28 @@ __device__ __forceinline__ void gauss_transform(GaussD& g, int& flags, const Mat
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// The sensor-noise Gaussian of one valid pixel (c, r) of depth d (pinholepointprojector.cpp:104-123), moved by the sensor offset as
+// Cloud::transformInPlace moves it (cloud.cpp:180).  The one definition of that arithmetic: k_gaussians and k_gaussians_batch both call it.
+__device__ __forceinline__ void gauss_of_pixel(const ConvertParams& cp, const Mat3& iK, float fB, float alpha, int c, int r, float d, GaussD& g, int& flags) {
+  const Vec3 mean = unproject_pixel(cp.iKRt, c, r, d);
+  g.mean[0] = mean.x; g.mean[1] = mean.y; g.mean[2] = mean.z;
+  const float z = d;
+  const float zVariation = (alpha * z * z) / (fB + z * alpha);
+  Mat3 J;
+  J(0,0) = z;   J(0,1) = 0.f; J(0,2) = (float)c;
+  J(1,0) = 0.f; J(1,1) = z;   J(1,2) = (float)r;
+  J(2,0) = 0.f; J(2,1) = 0.f; J(2,2) = 1.f;
+  J = mat3_mul(iK, J);
+  const float dg[3] = { 3.0f, 3.0f, zVariation };
+  Mat3 JD;
+  for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) JD(i,k) = J(i,k) * dg[k];
+  const Mat3 C = mat3_mul(JD, mat3_transpose(J));
+  for (int k = 0; k < 9; ++k) { g.cov[k] = C.m[k]; g.info[k] = 0.f; }
+  g.infoVec[0] = g.infoVec[1] = g.infoVec[2] = 0.f;
+  flags = kGaussMoments;
+  if (cp.hasOffset) gauss_transform(g, flags, cp.offset);
+}
+
 // The Gaussian half of PinholePointProjector::unProject(points, gaussians, index, depth) (pinholepointprojector.cpp:104-123)
 // followed by Cloud::transformInPlace(sensorOffset) on the Gaussians (cloud.cpp:180).  Same ordered compaction as k_unproject
 // (the point index is the row-major rank of the valid pixel); f.rowoff holds the exclusive row offsets (k_row_count + k_row_offsets).
@@ -78,23 +100,8 @@ __global__ void __launch_bounds__(256) k_gaussians(const FrameDesc* __restrict__
     if (valid) {
       if (idx < f.cloud.capacity) {
         GaussD g;
-        const Vec3 mean = unproject_pixel(cp.iKRt, c, r, d);
-        g.mean[0] = mean.x; g.mean[1] = mean.y; g.mean[2] = mean.z;
-        const float z = d;
-        const float zVariation = (alpha * z * z) / (fB + z * alpha);
-        Mat3 J;
-        J(0,0) = z;   J(0,1) = 0.f; J(0,2) = (float)c;
-        J(1,0) = 0.f; J(1,1) = z;   J(1,2) = (float)r;
-        J(2,0) = 0.f; J(2,1) = 0.f; J(2,2) = 1.f;
-        J = mat3_mul(iK, J);
-        const float dg[3] = { 3.0f, 3.0f, zVariation };
-        Mat3 JD;
-        for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) JD(i,k) = J(i,k) * dg[k];
-        const Mat3 C = mat3_mul(JD, mat3_transpose(J));
-        for (int k = 0; k < 9; ++k) { g.cov[k] = C.m[k]; g.info[k] = 0.f; }
-        g.infoVec[0] = g.infoVec[1] = g.infoVec[2] = 0.f;
-        int flags = kGaussMoments;
-        if (cp.hasOffset) gauss_transform(g, flags, cp.offset);
+        int flags;
+        gauss_of_pixel(cp, iK, fB, alpha, c, r, d, g, flags);
         sb.G[idx] = g;
         sb.Gf[idx] = flags;
       }
@@ -102,6 +109,56 @@ __global__ void __launch_bounds__(256) k_gaussians(const FrameDesc* __restrict__
     base += tot;
     __syncthreads();
   }
+}
+
+// The same records for the frames of a converter sub-batch, queued behind their front end on its stream: the front end has written the cloud's index
+// image (FrameDesc::index: the point of a valid pixel, -1 elsewhere), so the point index is read, not recounted; the depth is the one the front end
+// read (frame_depth: a float frame, a raw frame with its scale, the slot's down-sampled frame).  sbs[frame]: the Gaussian arrays of the frame's
+// cloud; records at or beyond the cloud's capacity are not written.  One thread per pixel; grid = (ceil(rows * cols / 256), frames), block = 256.
+//
+// STAGED = false: every lane stores its own 96-byte record and its flag word (six 16-byte stores at a 96-byte stride across the wave).
+// STAGED = true: the valid pixels of a block are consecutive points (the index is the row-major rank), so the block's records are one contiguous
+// run of 24 * count floats: they are staged in LDS (25 floats apart: an odd stride keeps the lanes' writes on different banks) and leave as
+// consecutive dwords, lane after lane.  Same records, same bits.
+constexpr int kGaussStage = kGaussFloats + 1;
+constexpr int kGaussStagedDefault = 1;      // the form the library uses (DESIGN.md section 5 has both forms' times)
+template <bool STAGED>
+__global__ void __launch_bounds__(256) k_gaussians_batch(const FrameDesc* __restrict__ frames, const SceneBuffers* __restrict__ sbs, ConvertParams cp,
+                                                         Mat3 iK, float fB, float alpha) {
+  const FrameDesc& f = frames[blockIdx.y];
+  const SceneBuffers sb = sbs[blockIdx.y];
+  const unsigned N = (unsigned)cp.rows * (unsigned)cp.cols;
+  const unsigned pix = blockIdx.x * 256u + threadIdx.x;
+  const int cap = f.cloud.capacity;
+  int idx = -1;
+  if (pix < N) idx = f.index[pix];
+  const bool valid = idx >= 0 && idx < cap;
+  GaussD g;
+  int flags = 0;
+  if (valid) {
+    const int r = (int)(pix / (unsigned)cp.cols), c = (int)(pix - (unsigned)r * (unsigned)cp.cols);
+    gauss_of_pixel(cp, iK, fB, alpha, c, r, frame_depth(f, pix), g, flags);
+  }
+  if (!STAGED) {
+    if (valid) { sb.G[idx] = g; sb.Gf[idx] = flags; }
+    return;
+  }
+  __shared__ float stage[256 * kGaussStage];
+  __shared__ int first, count;
+  if (threadIdx.x == 0) { first = 0x7fffffff; count = 0; }
+  __syncthreads();
+  if (valid) { atomicMin(&first, idx); atomicAdd(&count, 1); }
+  __syncthreads();
+  const int i0 = first, cnt = count;
+  if (valid) {
+    float* s = stage + (idx - i0) * kGaussStage;      // idx - i0 < cnt <= 256: the block's valid pixels are consecutive points
+    for (int k = 0; k < 3; ++k) { s[k] = g.mean[k]; s[12 + k] = g.infoVec[k]; }
+    for (int k = 0; k < 9; ++k) { s[3 + k] = g.cov[k]; s[15 + k] = g.info[k]; }
+    sb.Gf[idx] = flags;                               // one dword per lane, consecutive already
+  }
+  __syncthreads();
+  float* out = (float*)(sb.G + i0);
+  for (int j = threadIdx.x; j < cnt * kGaussFloats; j += 256) out[j] = stage[(j / kGaussFloats) * kGaussStage + j % kGaussFloats];
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -266,6 +266,16 @@ class DepthImageConverter {
   // The reference fills Cloud::gaussians() inside every compute() (depthimageconverterintegralimage.cpp:39); only Merger::merge reads
   // them, so here they are produced when asked for (clouds that will enter a scene).
   bool computeGaussians() const { return _computeGaussians; }  void setComputeGaussians(bool v) { _computeGaussians = v; }
+  // The batch calls make lean clouds; with either flag they make scene-ready ones inside the same submission (pwn_hip_convert_batch_ex): the Stats
+  // Cloud::save writes and PwnMerger copies (compute() keeps them whenever it computes Gaussians), and the Gaussians
+  bool keepStats() const { return _keepStats; }  void setKeepStats(bool v) { _keepStats = v; }
+  // the extras of a batch conversion with the two options given; false when both are off (the lean call)
+  bool extras(pwn_hip_convert_extras& e, bool keepStats, bool gaussians) const {
+    pwn_hip_default_convert_extras(&e);
+    e.keep_stats = keepStats ? 1 : 0; e.gaussians = gaussians ? 1 : 0;
+    e.baseline = _projector->baseline(); e.alpha = _projector->alpha();
+    return keepStats || gaussians;
+  }
   virtual void compute(Cloud& cloud, const DepthImage& depthImage, const Isometry3f& sensorOffset = Isometry3f::Identity()) = 0;
   pwn_hip_converter_params params(const Isometry3f& sensorOffset) const {
     if (!_projector || !_statsCalculator || !_pointInformationMatrixCalculator || !_normalInformationMatrixCalculator)
@@ -289,7 +299,7 @@ class DepthImageConverter {
   Context* _ctx; PinholePointProjector* _projector; StatsCalculatorIntegralImage* _statsCalculator;
   PointInformationMatrixCalculator* _pointInformationMatrixCalculator; NormalInformationMatrixCalculator* _normalInformationMatrixCalculator;
   IntImage _indexImage;
-  bool _computeGaussians = false;
+  bool _computeGaussians = false, _keepStats = false;
 };
 class DepthImageConverterIntegralImage : public DepthImageConverter {
  public:
@@ -304,7 +314,10 @@ class DepthImageConverterIntegralImage : public DepthImageConverter {
     _projector->setImageSize(rows, cols); _projector->setTransform(Isometry3f::Identity());
     std::vector<pwn_hip_cloud*> h(clouds.size());
     for (size_t i = 0; i < h.size(); ++i) h[i] = clouds[i]->handle();
-    _ctx->check(pwn_hip_convert_batch(_ctx->handle(), &p, depthFrames.data(), (int)h.size(), rows, cols, h.data()));
+    pwn_hip_convert_extras e;
+    if (extras(e, _keepStats, _computeGaussians))
+      _ctx->check(pwn_hip_convert_batch_ex(_ctx->handle(), &p, reinterpret_cast<const void* const*>(depthFrames.data()), 0, 0.f, (int)h.size(), rows, cols, 0, 0.f, &e, h.data()));
+    else _ctx->check(pwn_hip_convert_batch(_ctx->handle(), &p, depthFrames.data(), (int)h.size(), rows, cols, h.data()));
   }
   void computeBatchRaw(const std::vector<Cloud*>& clouds, const std::vector<const uint16_t*>& rawFrames, float depthScale, int rows, int cols,
                        const Isometry3f& sensorOffset = Isometry3f::Identity()) {
@@ -313,7 +326,11 @@ class DepthImageConverterIntegralImage : public DepthImageConverter {
     _projector->setImageSize(rows, cols); _projector->setTransform(Isometry3f::Identity());
     std::vector<pwn_hip_cloud*> h(clouds.size());
     for (size_t i = 0; i < h.size(); ++i) h[i] = clouds[i]->handle();
-    _ctx->check(pwn_hip_convert_batch_u16(_ctx->handle(), &p, rawFrames.data(), depthScale, (int)h.size(), rows, cols, h.data()));
+    pwn_hip_convert_extras e;
+    if (extras(e, _keepStats, _computeGaussians))
+      _ctx->check(pwn_hip_convert_batch_ex(_ctx->handle(), &p, reinterpret_cast<const void* const*>(rawFrames.data()), 1, depthScale, (int)h.size(), rows, cols, 0, 0.f, &e,
+                                           h.data()));
+    else _ctx->check(pwn_hip_convert_batch_u16(_ctx->handle(), &p, rawFrames.data(), depthScale, (int)h.size(), rows, cols, h.data()));
   }
   // the look-ahead of a sharded PwnCloser::processPartition (pwn_hip_convert_export_begin / _end): returns at once; the helper thread converts the raw
   // frame into `cloud` and then writes the cloud's flat form into flatDst (may be nullptr); computeExportEnd waits and returns the bytes written
@@ -614,7 +631,10 @@ struct PwnMatcherBase {
 
   // .cpp:57-86: returns a new Cloud owned by the caller; r, c, cameraMatrix receive the scaled values.  DepthImage_scale (:72) and
   // converter->compute (:79) run as one device-side call (no scaled image on the host); same side effects on the converter's projector.
-  Cloud* makeCloud(int& r, int& c, Matrix3f& cameraMatrix, const Isometry3f& sensorOffset, const DepthImage& depthImage) {
+  // keepStats / gaussians: a scene-ready cloud (makeCloudBatch of the one image).
+  Cloud* makeCloud(int& r, int& c, Matrix3f& cameraMatrix, const Isometry3f& sensorOffset, const DepthImage& depthImage, bool keepStats = false,
+                   bool gaussians = false) {
+    if (keepStats || gaussians) return makeCloudBatch(r, c, cameraMatrix, sensorOffset, { &depthImage }, keepStats, gaussians)[0];
     PinholePointProjector* projector = _converter->projector();
     const float invScale = 1.0f / _scale;
     Matrix3f scaled = cameraMatrix;
@@ -632,8 +652,10 @@ struct PwnMatcherBase {
     return cloud;
   }
   // makeCloud of n depth images of one size, camera matrix and sensor offset in one call (pwn_hip_convert_batch_scaled; not in the reference):
-  // the clouds are new and owned by the caller, the same bits as n makeCloud calls; r, c, cameraMatrix and the projector as those leave them
-  std::vector<Cloud*> makeCloudBatch(int& r, int& c, Matrix3f& cameraMatrix, const Isometry3f& sensorOffset, const std::vector<const DepthImage*>& depthImages) {
+  // the clouds are new and owned by the caller, the same bits as n makeCloud calls; r, c, cameraMatrix and the projector as those leave them.
+  // keepStats / gaussians: the clouds carry the Stats and the sensor-noise Gaussians the reference's converter always leaves (pwn_hip_convert_batch_ex).
+  std::vector<Cloud*> makeCloudBatch(int& r, int& c, Matrix3f& cameraMatrix, const Isometry3f& sensorOffset, const std::vector<const DepthImage*>& depthImages,
+                                     bool keepStats = false, bool gaussians = false) {
     std::vector<Cloud*> clouds;
     if (depthImages.empty()) return clouds;
     const int rows = depthImages[0]->rows, cols = depthImages[0]->cols;
@@ -654,7 +676,10 @@ struct PwnMatcherBase {
     std::vector<pwn_hip_cloud*> h(frames.size());
     for (size_t i = 0; i < frames.size(); ++i) { clouds.push_back(new Cloud(*_ctx, r * c > 0 ? r * c : 1)); h[i] = clouds.back()->handle(); }
     const pwn_hip_converter_params p = _converter->params(sensorOffset);
-    const int rc = pwn_hip_convert_batch_scaled(_ctx->handle(), &p, frames.data(), (int)frames.size(), rows, cols, _scale, 0.01f, h.data());
+    pwn_hip_convert_extras e;
+    const int rc = _converter->extras(e, keepStats, gaussians)
+        ? pwn_hip_convert_batch_ex(_ctx->handle(), &p, reinterpret_cast<const void* const*>(frames.data()), 0, 0.f, (int)frames.size(), rows, cols, _scale, 0.01f, &e, h.data())
+        : pwn_hip_convert_batch_scaled(_ctx->handle(), &p, frames.data(), (int)frames.size(), rows, cols, _scale, 0.01f, h.data());
     if (rc) { for (Cloud* cl : clouds) delete cl; _ctx->check(rc); }
     numCalls += (int)frames.size();
     return clouds;
@@ -773,9 +798,11 @@ struct PwnCloserAcceptance {
 
 // pwn_tracker/pwn_tracker_cache.cpp:24-51 (+ boss_map_building cache.hpp): device-resident LRU of clouds keyed by frame; a miss re-runs the
 // converter on the frame's stored depth image (PwnCache::loadFrame), so closure batches do not re-convert frames still resident in HBM.
+// sceneReady: a miss makes its cloud with Stats and sensor-noise Gaussians, as the reference's converter always does -- what PwnMerger needs of
+// its cache (the fused cloud copies both, pwn_merger.cpp:56-61); clouds handed to addFrame stay as they are.
 class CloudCache {
  public:
-  CloudCache(PwnMatcherBase* matcher, size_t capacity = 64) : _matcher(matcher), _capacity(capacity) {}
+  CloudCache(PwnMatcherBase* matcher, size_t capacity = 64, bool sceneReady = false) : _matcher(matcher), _capacity(capacity), _sceneReady(sceneReady) {}
   ~CloudCache() { for (auto& e : _lru) delete e.second; }
   // the cache takes ownership of `cloud` (may be nullptr: the cloud is then made on the first get)
   void addFrame(int key, const DepthImage& depthImage, const Matrix3f& cameraMatrix, const Isometry3f& sensorOffset, Cloud* cloud = nullptr) {
@@ -789,7 +816,7 @@ class CloudCache {
     auto f = _frames.find(key);
     if (f == _frames.end()) throw Error(PWN_HIP_ERR_INVALID_ARGUMENT, "CloudCache: unknown frame");
     int r, c; Matrix3f K = f->second.cameraMatrix;
-    Cloud* cloud = _matcher->makeCloud(r, c, K, f->second.sensorOffset, f->second.depth);      // pwn_tracker_cache.cpp:38-44
+    Cloud* cloud = _matcher->makeCloud(r, c, K, f->second.sensorOffset, f->second.depth, _sceneReady, _sceneReady);      // pwn_tracker_cache.cpp:38-44
     insert(key, cloud);
     return cloud;
   }
@@ -804,7 +831,7 @@ class CloudCache {
     _lru.emplace_back(key, cloud);
     while (_lru.size() > _capacity) { delete _lru.front().second; _lru.pop_front(); }          // least recently used
   }
-  PwnMatcherBase* _matcher; size_t _capacity;
+  PwnMatcherBase* _matcher; size_t _capacity; bool _sceneReady;
   std::list<std::pair<int, Cloud*> > _lru;       // front = least recently used
   std::map<int, Frame> _frames;
 };
@@ -1095,7 +1122,8 @@ class PwnCloserWithMerger {
 
 // pwn_tracker2/pwn_merger.{h,cpp}: mergeNodeList (:28-62), what MapMerger::process (boss_map_building/map_merger.cpp:43-82) calls every
 // listSize + 1 key nodes -- the cached clouds of the list fused, one after the other, into one local-map cloud in the frame of the first
-// ("big") node, which then becomes that node's cloud in the cache.
+// ("big") node, which then becomes that node's cloud in the cache.  The cache must be a CloudCache(matcher, capacity, true): only from scene-ready
+// clouds does the fused cloud get real Stats and its Gaussians, and only then can it be handed to Merger::merge.
 class PwnMerger {
  public:
   PwnMerger(Context* ctx, Merger2* merger, CloudCache* cache) : _ctx(ctx), _merger(merger), _cache(cache) {}

@@ -347,6 +347,26 @@ int pwn_hip_convert_batch_scaled(pwn_hip_ctx* ctx, const pwn_hip_converter_param
 int pwn_hip_convert_batch_u16_scaled(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const uint16_t* const* raw_frames,
                                      float depth_scale, int n, int rows, int cols, int step, float max_depth_cov,
                                      pwn_hip_cloud* const* clouds);
+/* What a cloud that leaves DepthImageConverter::compute carries besides points, normals and matrices (depthimageconverterintegralimage.cpp:39,
+ * pinholepointprojector.cpp:104-123), and the scene stage needs: Merger::merge reads the Gaussians, Cloud::save writes the Stats, PwnMerger::
+ * mergeNodeList copies both.  The batch calls above make lean clouds; pwn_hip_convert_batch_ex makes scene-ready ones on request. */
+typedef struct pwn_hip_convert_extras {
+  int keep_stats;                 /* 1: cloud i holds the Stats pwn_hip_convert(..., keep_stats = 1) gives for the image the front end read */
+  int gaussians;                  /* 1: cloud i holds, for every point, the record pwn_hip_cloud_gaussians writes (sensor offset included) */
+  float baseline, alpha;          /* PinholePointProjector::_baseline, _alpha (pinholepointprojector.cpp:10-11) */
+} pwn_hip_convert_extras;
+void pwn_hip_default_convert_extras(pwn_hip_convert_extras* e);   /* 0, 0, 0.075, 0.1 */
+/* The four batch calls above behind one entry point, with the extras.  raw_u16 != 0: frames are uint16 with depth_scale (the _u16 forms), else
+ * floats (depth_scale is ignored).  step == 0: the unscaled call on rows x cols frames; step >= 1: the _scaled form (rows, cols: the SOURCE
+ * size, p->K already scaled, max_depth_cov as there).  extras == NULL or all flags zero: the launches and the clouds of the matching call
+ * above, bit for bit.  With extras->gaussians the image the Gaussians are made from is the one the front end read (depth_scale * raw, the
+ * box-averaged image, or both) and pwn_hip_cloud_num_gaussians equals the cloud's size afterwards; without, the clouds have none.  Everything is
+ * queued inside the batch plan, one kernel per sub-batch behind its conversion, and the host waits once.  Refused, every cloud as it was: what
+ * the matching call above refuses; a non-finite baseline or alpha; keep_stats or gaussians outside {0, 1} (PWN_HIP_ERR_INVALID_ARGUMENT).  A call
+ * that fails later leaves its clouds empty, without Stats and Gaussians. */
+int pwn_hip_convert_batch_ex(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const void* const* frames, int raw_u16, float depth_scale,
+                             int n, int rows, int cols, int step, float max_depth_cov, const pwn_hip_convert_extras* extras,
+                             pwn_hip_cloud* const* clouds);
 
 /* ------------------------------------------------------------------ aligner stages ----------- */
 /* PinholePointProjector::project(indexImage, depthImage, points) (pinholepointprojector.cpp:33-66) with

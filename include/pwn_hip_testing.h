@@ -85,10 +85,19 @@ int pwn_hip_debug_trig_eval(pwn_hip_ctx* ctx, int n, const float* y, const float
 int pwn_hip_debug_cloud_set_gaussians(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, int n, const float* mean, const float* cov, const float* info_vec,
                                       const float* info, const int* flags);
 
+/* The Gaussian vector becomes the first n records of the cloud's Gaussian arrays as they are, nothing written (0 <= n <= capacity; the arrays
+ * must exist: a cloud that has had Gaussians).  Lets a test read records beyond the vector's end, to see that a call left them alone. */
+int pwn_hip_debug_cloud_expose_gaussians(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, int n);
+
 /* pwn_hip_manifold_image takes its clouds in chunks of whole clouds with at most 2^25 points and carries the image from chunk to chunk.  This
  * sets the bound to `points` (<= 0: back to 2^25), so that a small list runs as several chunks; a cloud above the bound is refused as a cloud
  * above 2^25 is (PWN_HIP_ERR_CAPACITY). */
 int pwn_hip_debug_set_manifold_chunk(pwn_hip_ctx* ctx, int points);
+
+/* How k_gaussians_batch (pwn_hip_convert_batch_ex with Gaussians) stores its records: 0 = every lane its own 96-byte record, 1 = staged in LDS
+ * and written as consecutive dwords, anything else = back to the library's choice.  Same bits either way; for the timing tool and the test that
+ * says so. */
+int pwn_hip_debug_set_gaussian_stores(pwn_hip_ctx* ctx, int staged);
 
 #ifdef __cplusplus
 }
