@@ -1926,10 +1926,17 @@ __global__ void __launch_bounds__(kAlignBlock) k_linearize_list(CloudDev ref, Cl
 // mask && diff < threshold, sum of diff.  Every surviving diff is a multiple of 1/64 (or < 2^-120), so the sum is kept
 // exactly in 1/64 fixed point with integer atomics -> bitwise reproducible.  out[pair] = {nonZeros, inliers, sum64, tiny}.
 struct MatchAcc { unsigned long long nonZeros, inliers; long long sum64; unsigned long long tiny; };
-// sum of the masked differences / nonZeros (pwn_matcher_base.cpp:179; 0/0 = NaN like the reference): the sum is exact in 1/64 units; values
-// below 2^-120 only matter when nothing else was added.  One expression for the host (pwn_hip_match_result) and the device (result records).
+// sum of the masked differences / nonZeros (pwn_matcher_base.cpp:179; 0/0 = NaN like the reference): the float nearest to the exact sum.  That
+// sum is exact in 1/64 units; a `tiny` pixel (a difference of 1 mm: bits(1.0f) & bits(255.0f) = 0x03000000) adds 2^-121, which shows when
+// nothing else was added, and where the rest lies exactly half-way between two floats (it then rounds up instead of to even).  One expression
+// for the host (pwn_hip_match_result) and the device (result records).
 __host__ __device__ __forceinline__ float match_reprojection_distance(const MatchAcc& a) {
-  const double sum = a.sum64 ? (double)a.sum64 / 64.0 : (double)a.tiny * 1e-37;
+  long long s64 = a.sum64;
+  if (a.tiny && s64 >= (1ll << 24)) {
+    const int sh = 40 - __builtin_clzll((unsigned long long)s64);      // bits of s64 below the float's 24
+    if ((s64 & ((1ll << sh) - 1)) == (1ll << (sh - 1))) s64 += 1;
+  }
+  const double sum = s64 ? (double)s64 / 64.0 : (double)a.tiny * 0x1p-121;
   return (float)sum / (float)(int)a.nonZeros;
 }
 __device__ __forceinline__ unsigned short depth_to_u16(float d, float scale) { return (d < FLT_MAX) ? (unsigned short)(scale * d) : (unsigned short)0; }
