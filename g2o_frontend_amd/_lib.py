@@ -63,6 +63,15 @@ class ConvertExtras(C.Structure):
     _fields_ = [("keep_stats", C.c_int), ("gaussians", C.c_int), ("baseline", C.c_float), ("alpha", C.c_float)]
 
 
+class Convergence(C.Structure):
+    _fields_ = [("enabled", C.c_int), ("translation_epsilon", C.c_float), ("rotation_epsilon", C.c_float), ("min_iterations", C.c_int)]
+
+
+class AlignSteps(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("step_translation", C.c_float * MAX_ITERATIONS),
+                ("step_rotation", C.c_float * MAX_ITERATIONS)]
+
+
 class Prior(C.Structure):
     _fields_ = [("kind", C.c_int), ("mean", C.c_float * 16), ("reference_transform", C.c_float * 16), ("information", C.c_float * 36)]
 
@@ -81,6 +90,9 @@ PROTOTYPES = {
     "pwn_hip_ctx_set_concurrency": (_I, [_VP, _I]),
     "pwn_hip_ctx_set_omega_storage": (_I, [_VP, _I]),
     "pwn_hip_cloud_omega_storage": (_I, [_VP, _VP, C.POINTER(_I)]),
+    "pwn_hip_ctx_set_convergence": (_I, [_VP, _VP]),
+    "pwn_hip_ctx_get_convergence": (_I, [_VP, _VP]),
+    "pwn_hip_last_align_steps": (_I, [_VP, _I, _I, _VP]),
     "pwn_hip_last_error_string": (C.c_char_p, [_VP]),
     "pwn_hip_device_count": (_I, []),
     "pwn_hip_host_alloc": (_I, [C.POINTER(C.c_void_p), C.c_size_t]),

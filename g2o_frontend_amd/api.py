@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AlignerParams, AlignResult, AlignStatistics, ConvertExtras, ConverterParams, MatchResult, Prior, PwnHipError
+from ._lib import AlignerParams, AlignResult, AlignSteps, AlignStatistics, Convergence, ConvertExtras, ConverterParams, MatchResult, Prior, PwnHipError
 
 
 def _ptr(x):
@@ -254,6 +254,31 @@ class Context:
             raise ValueError(f"omega_storage must be one of {sorted(OMEGA_STORAGE)}")
         self.check(self._L.pwn_hip_ctx_set_omega_storage(self.h, OMEGA_STORAGE[mode]))
         self.omega_storage = mode
+
+    def set_convergence(self, translation: float, rotation: float, min_iterations: int = 0):
+        """"stop when converged" for every alignment call of the context (pwn_hip_ctx_set_convergence; opt-in, a deviation from the reference's
+        fixed outerIterations): a pair's loop ends on the device after the first outer iteration i with i + 1 >= min_iterations whose last step
+        has a translation norm <= translation and a rotation norm <= rotation; its results are those of outer_iterations = i + 1, bit for bit"""
+        s = Convergence(1, float(translation), float(rotation), int(min_iterations))
+        self.check(self._L.pwn_hip_ctx_set_convergence(self.h, C.byref(s)))
+
+    def clear_convergence(self):
+        self.check(self._L.pwn_hip_ctx_set_convergence(self.h, None))
+
+    def convergence(self):
+        """None while the setting is off, else dict(translation, rotation, min_iterations)"""
+        s = Convergence()
+        self.check(self._L.pwn_hip_ctx_get_convergence(self.h, C.byref(s)))
+        return dict(translation=s.translation_epsilon, rotation=s.rotation_epsilon, min_iterations=s.min_iterations) if s.enabled else None
+
+    def last_align_steps(self, first: int = 0, n: int = 1):
+        """the step norms of pairs [first, first + n) of the last alignment call (pwn_hip_last_align_steps): a list of
+        dict(iterations, converged, step_translation, step_rotation), the traces cut to the executed outer iterations"""
+        out = (AlignSteps * n)()
+        self.check(self._L.pwn_hip_last_align_steps(self.h, int(first), int(n), out))
+        return [dict(iterations=s.iterations, converged=bool(s.converged),
+                     step_translation=np.frombuffer(s.step_translation, np.float32, s.iterations).copy(),
+                     step_rotation=np.frombuffer(s.step_rotation, np.float32, s.iterations).copy()) for s in out]
 
     def upload(self, array):
         """DeviceBuffer holding a copy of a host array (pwn_hip_device_alloc + pwn_hip_copy): a frame resident in HBM without torch"""
@@ -964,6 +989,10 @@ class Aligner:
                     chi2=np.frombuffer(r.chi2, np.float32, n).copy(), iter_inliers=np.frombuffer(r.iter_inliers, np.int32, n).copy(),
                     C=np.frombuffer(r.iter_correspondences, np.int32, n).copy(), K=np.frombuffer(r.iter_candidates, np.int32, n).copy(),
                     n_reference=r.n_reference, n_current=r.n_current)
+
+    def lastSteps(self, first: int = 0, n: int = 1):
+        """the step norms of the pairs [first, first + n) of the context's last alignment call (Context.last_align_steps)"""
+        return self.ctx.last_align_steps(first, n)
 
     def addRelativePrior(self, mean, informationMatrix):
         """aligner.cpp:34-36"""

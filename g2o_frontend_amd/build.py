@@ -94,6 +94,13 @@ def build_tools(force: bool = False) -> str:
     if force or (not os.path.exists(out10)) or any(os.path.getmtime(d) > os.path.getmtime(out10) for d in deps10):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src10, "-o", out10, "-L", _HERE, "-lpwn_hip",
                                "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
+    # "stop when converged" through the C++ mirror against the results and step traces the Python mirror wrote to a file (exit status 0 = equal bit for bit)
+    src11 = os.path.join(root, "tools", "pwn_hip_early_stop_check.cpp")
+    out11 = os.path.join(root, "tools", "pwn_hip_early_stop_check")
+    deps11 = [src11] + deps[1:]
+    if force or (not os.path.exists(out11)) or any(os.path.getmtime(d) > os.path.getmtime(out11) for d in deps11):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src11, "-o", out11, "-L", _HERE, "-lpwn_hip",
+                               "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
     # PwnCloser::processPartition over the GPUs of a node in native code: the mirror + RCCL (broadcast of the flat `current` cloud, all-gather of the
     # match records); the program's own streams and events come from the HIP runtime
     src5 = os.path.join(root, "tools", "pwn_hip_partition_app.cpp")

@@ -225,6 +225,10 @@ struct pwn_hip_ctx {
   DevBuf<float> io_ws;      // N*16 floats staging for cloud up/download
   FinderImages img;                         // images of the last alignment
   int index_shortcut = 1;                   // pwn_hip_debug_set_index_shortcut (test hook): 0 = always project
+  StopRule stop = { 0, 0.f, 0.f, 0 };       // pwn_hip_ctx_set_convergence: when a pair's loop ends on the device before outer_iterations (off by default)
+  // pwn_hip_last_align_steps: the pairs of the last alignment call, and whether their final states are in state_host already (a call that
+  // returned records only leaves them in state_ws until somebody asks)
+  int last_pairs = 0; bool last_states_on_host = false;
   // z-buffer epoch tags are handed out in descending order ACROSS batch calls (a smaller tag wins, so whatever earlier calls left in
   // the buffers reads as empty): the buffers are cleared only when the 12-bit tag space is used up, not once per alignment
   unsigned ztag_next = 0;                   // 64-bit buffer (scene stage)
@@ -532,6 +536,7 @@ int cloud_store_records(pwn_hip_ctx* ctx, const CloudDev& d, int n, const std::v
 AlignParams make_align_params(const pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p) {
   AlignParams ap;
   ap.settleGuard = ctx ? ctx->settle_guard : kSettleGuard;
+  ap.mayFreeze = ctx ? ctx->stop.enabled : 0;
   ap.rows = p->rows; ap.cols = p->cols;
   ap.K = mat3_from(p->K);
   ap.refOffset = mat4_from(p->reference_sensor_offset);
@@ -2467,6 +2472,7 @@ static int align_check_and_plan(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& 
   if (!ctx || !c.p || !c.refs || !c.curs || (!c.results && !c.records) || c.n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (int rc = check_image(ctx, c.p->rows, c.p->cols)) return rc;
   ctx->img.invalidate();                  // whatever happens below (set again on success)
+  ctx->last_pairs = 0;
   if (int rc = check_align_params(ctx, c.p)) return rc;
   if (int rc = start_align_attempt(ctx, run.robust)) return rc;
   run.want_scores = c.scores != nullptr || (c.records && c.match_records);
@@ -2488,7 +2494,10 @@ static int align_describe_pairs(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& 
   // z-buffer the statistics pass re-reads) project as usual.
   const IndexKey key = index_key(p);
   const bool shortcut = n >= 1 && ctx->index_shortcut && is_identity(forced(p->current_sensor_offset));
-  const bool shortcut_ref = shortcut && p->outer_iterations > 1 && is_identity(forced(p->reference_sensor_offset));
+  // the first outer iteration may be a pair's last under the convergence setting: then its z-buffer is read afterwards too, so the shortcut is decided
+  // as for a call of the fewest outer iterations a pair can run
+  const int min_outer = ctx->stop.enabled ? std::min(p->outer_iterations, std::max(1, ctx->stop.minIterations)) : p->outer_iterations;
+  const bool shortcut_ref = shortcut && min_outer > 1 && is_identity(forced(p->reference_sensor_offset));
   // a few pairs (latency path): k_solve_update writes the pose and the traces into the page-locked host copy itself, no copy back at the end;
   // batches copy the states back in one transfer (64 workgroups storing across PCIe in every solve launch cost more than that: 16 against 11 us per launch)
   run.direct_state = n <= 4;
@@ -2574,7 +2583,8 @@ static int align_enqueue_sub(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& run
         if (j == 0) launch_corr_linearize<true, false>(ctx, L, tag, 0, ownRef);
         else launch_corr_linearize<false, false>(ctx, L, tag, 0, ownRef); }
       { StageTimer t(ctx, "solve", st);
-        hipLaunchKernelGGL(k_solve_update, dim3(m), dim3(256), 0, st, L.pr, run.ap, run.nb, lastInner ? 1 : 0, (lastInner && i == p->outer_iterations - 1) ? 1 : 0); }
+        hipLaunchKernelGGL(k_solve_update, dim3(m), dim3(256), 0, st, L.pr, run.ap, run.nb, lastInner ? 1 : 0, (lastInner && i == p->outer_iterations - 1) ? 1 : 0,
+                           tag, ctx->stop); }
     }
   }
   if (c.statistics && p->outer_iterations > 0) {
@@ -2659,6 +2669,7 @@ static int align_finish(pwn_hip_ctx* ctx, const AlignCall& c, const AlignRun& ru
   }
   // batches: no current z-buffer after a skipped projection; a single alignment makes it on demand
   ctx->img.set(run.ap, run.slot0, n > 0 && (!run.any_own || n == 1), n == 1 && run.any_own);
+  ctx->last_pairs = n; ctx->last_states_on_host = run.direct_state || c.results != nullptr;
   collect_stage_times(ctx);
   return PWN_HIP_OK;
 }
@@ -2790,6 +2801,7 @@ static int align_with_priors_once(pwn_hip_ctx* ctx, const AlignCall& call, int n
   fill_result(*call.results, hs, ref, cur, ms);
   if (call.statistics) fill_statistics(*call.statistics, p->outer_iterations > 0 ? ctx->stats_host : nullptr, T);
   ctx->img.set(ap, slot0, true, false);
+  ctx->last_pairs = 1; ctx->last_states_on_host = true;      // the host drove the loop: no step traces (outer = 0)
   return PWN_HIP_OK;
 }
 int pwn_hip_align_with_priors_ex(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, const pwn_hip_cloud* ref, const pwn_hip_cloud* cur, int n_priors,
@@ -2799,6 +2811,7 @@ int pwn_hip_align_with_priors_ex(pwn_hip_ctx* ctx, const pwn_hip_aligner_params*
   AlignCall call = align_call(p, 1, r, c, nullptr, result);
   call.statistics = statistics;
   if (n_priors <= 0) return align_batch_impl(ctx, call);
+  if (ctx && ctx->stop.enabled) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "the loop with priors runs a fixed iteration count: switch the convergence setting off");
   return repeat_once(ctx, kSettleFault, [&](bool robust) { return align_with_priors_once(ctx, call, n_priors, priors, robust); });
 }
 int pwn_hip_align_batch_ex(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs,
@@ -2908,6 +2921,37 @@ int pwn_hip_convert_align_batch_u16_scaled(pwn_hip_ctx* ctx, const pwn_hip_conve
   if (int rc = ensure_scale(ctx, 2 * n)) return rc;
   return convert_align_batch_impl(ctx, cp, ap, n, ref_frames, cur_frames, depth_scale, sc.orows, sc.ocols, refs, curs, guesses, pair_ids, first_pair_id, results,
                                   records, sc);
+}
+int pwn_hip_ctx_set_convergence(pwn_hip_ctx* ctx, const pwn_hip_convergence* s) {
+  if (!ctx) return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, "null ctx");
+  if (!s || !s->enabled) { ctx->stop = StopRule{ 0, 0.f, 0.f, 0 }; return PWN_HIP_OK; }
+  if (!std::isfinite(s->translation_epsilon) || !std::isfinite(s->rotation_epsilon) || s->translation_epsilon < 0.f || s->rotation_epsilon < 0.f)
+    return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "convergence epsilons must be finite and >= 0");
+  if (s->min_iterations < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "min_iterations must be >= 0");
+  ctx->stop = StopRule{ 1, s->translation_epsilon, s->rotation_epsilon, s->min_iterations };
+  return PWN_HIP_OK;
+}
+int pwn_hip_ctx_get_convergence(const pwn_hip_ctx* ctx, pwn_hip_convergence* s) {
+  if (!ctx || !s) return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  s->enabled = ctx->stop.enabled; s->translation_epsilon = ctx->stop.epsT; s->rotation_epsilon = ctx->stop.epsR; s->min_iterations = ctx->stop.minIterations;
+  return PWN_HIP_OK;
+}
+int pwn_hip_last_align_steps(pwn_hip_ctx* ctx, int first, int n, pwn_hip_align_steps* out) {
+  if (!ctx || (!out && n > 0)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (first < 0 || n < 0 || (long long)first + n > ctx->last_pairs) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "pairs outside the last alignment call");
+  if (n > 0 && !ctx->last_states_on_host) {      // the call returned records only: its final states are still in state_ws
+    HIPCHK(ctx, hipMemcpyAsync(ctx->state_host, ctx->state_ws, sizeof(PairState) * ctx->last_pairs, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+    ctx->last_states_on_host = true;
+  }
+  for (int i = 0; i < n; ++i) {
+    const PairState& st = ctx->state_host[first + i];
+    pwn_hip_align_steps& o = out[i];
+    std::memset(&o, 0, sizeof(o));
+    o.iterations = st.outer; o.converged = st.frozen;
+    for (int k = 0; k < st.outer && k < PWN_HIP_MAX_ITERATIONS; ++k) { o.step_translation[k] = st.stepT[k]; o.step_rotation[k] = st.stepR[k]; }
+  }
+  return PWN_HIP_OK;
 }
 void pwn_hip_compute_statistics(const float H[36], const float T[16], float mean[6], float omega[36], float* tr, float* rr) {
   compute_statistics(H, mat4_from(T), mean, omega, tr, rr);

@@ -150,12 +150,21 @@ struct PairState {
   Mat4 KRtLast;    // projector matrix of the reference projection executed last (its depth image is recomputed with it)
   Mat4 KRtCur;     // projector matrix of the current-cloud projection
   int   it;
-  int   pad[3];
+  int   frozen;    // 1 = the pair met the context's convergence rule (StopRule) at the end of outer iteration `outer` - 1: every later launch of the
+                   // call's loop returns for its workgroups, so this state and the pair's z-buffer words stay those of that iteration
+  unsigned refTag; // z-buffer epoch of the reference projection executed last (what the readers after the loop take for a frozen pair)
+  int   outer;     // outer iterations executed = entries of the two step traces
   float chi2[kMaxIter];
   int   inliers[kMaxIter];
   int   ncorr[kMaxIter];
   int   ncand[kMaxIter];
+  float stepT[kMaxIter];   // per outer iteration: norm of the translation part of the last inner step dx, and of its rotation part as v2t reads it
+  float stepR[kMaxIter];   // (pwn_hip.h: pwn_hip_align_steps)
 };
+// "Stop when converged" (pwn_hip_ctx_set_convergence): after outer iteration i (0-based) a pair freezes iff
+// i + 1 >= minIterations && stepT[i] <= epsT && stepR[i] <= epsR (a NaN never passes).  enabled == 0: nobody freezes.
+struct StopRule { int enabled; float epsT, epsR; int minIterations; };
+
 
 struct PairDesc {
   CloudDev ref, cur;
@@ -180,6 +189,8 @@ struct AlignParams {
   float maxChi2;
   int robust;
   int settleGuard;         // rounds of z32_settle's compare-and-swap loop before a thread gives up (kSettleGuard)
+  int mayFreeze;           // the call runs under an enabled StopRule: the loop's kernels look at the pairs' convergence flags.  0 (the default setting): nobody
+                           // can freeze and no kernel of the loop loads a flag -- the launches are the ones of a library without the feature
 };
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -212,6 +223,10 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 // says so, which gives global_* instructions with a scalar base + 32-bit lane offset.
 template <typename T> using gptr = T __attribute__((address_space(1)))*;
 template <typename T> __device__ __forceinline__ gptr<T> as_global(T* p) { return (gptr<T>)(uintptr_t)p; }
+// a pair's convergence flag (workgroup-uniform: every thread reads the same word)
+__device__ __forceinline__ int pair_frozen(const PairState* st) { return *as_global(&st->frozen); }
+// The epoch of a pair's last reference projection for the readers after the loop: the launch's, or a frozen pair's own older one
+__device__ __forceinline__ unsigned pair_ref_tag(const PairState* st, unsigned launchTag) { return pair_frozen(st) ? *as_global(&st->refTag) : launchTag; }
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 load4(gptr<const v4f> p) { const v4f v = *p; return make_float4(v.x, v.y, v.z, v.w); }
@@ -1329,6 +1344,7 @@ template <int PPT>
 __global__ void __launch_bounds__(256) k_project(const PairDesc* __restrict__ pairs, AlignParams ap, int which, unsigned tag) {
   constexpr int kProjectPointsPerThread = PPT;
   const PairDesc& pd = pairs[blockIdx.y];
+  if (!which && ap.mayFreeze && pair_frozen(pd.state)) return;      // a converged pair keeps the z-buffer words of its last iteration: nothing is inserted (workgroup-uniform)
   const CloudDev& cl = which ? pd.cur : pd.ref;
   const int n = min(*cl.count, cl.capacity);
   const int i0 = blockIdx.x * 256 * kProjectPointsPerThread + threadIdx.x;
@@ -1356,6 +1372,7 @@ __global__ void __launch_bounds__(256) k_project(const PairDesc* __restrict__ pa
 // the nearest point, ties to the lowest index -- the reference's sequential strict '>' (pinholepointprojector.cpp:61), the word k_project leaves.
 __global__ void __launch_bounds__(256) k_project_robust(const PairDesc* __restrict__ pairs, AlignParams ap, int which, unsigned tag, int pass) {
   const PairDesc& pd = pairs[blockIdx.y];
+  if (!which && ap.mayFreeze && pair_frozen(pd.state)) return;      // as in k_project: neither the pair's depth image nor its z-buffer words are touched
   const CloudDev& cl = which ? pd.cur : pd.ref;
   const int n = min(*cl.count, cl.capacity);
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -1382,6 +1399,7 @@ __global__ void k_pair_images(const PairDesc* __restrict__ pairs, int which, uns
   const unsigned* z = which ? pd.zcur : pd.zref;
   const Mat4 KRt = which ? pd.state->KRtCur : pd.state->KRtLast;
   const int np = min(*cl.count, cl.capacity);
+  if (!which) tag = pair_ref_tag(pd.state, tag);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const int k = z32_index(z[i], tag);
     if (index) index[i] = k;
@@ -1742,6 +1760,8 @@ __global__ void __launch_bounds__(kAlignBlock, 1) k_corr_linearize(const PairDes
   const PairDesc& pd = pairs[blockIdx.y];
   const int N = ap.rows * ap.cols;
   const PairState* stp = pd.state;
+  // a converged pair: the loop's passes return (workgroup-uniform, in front of the first barrier); the statistics pass reads its own last epoch
+  if (ap.mayFreeze && pair_frozen(stp)) { if (!usePrevTc) return; tag = *as_global(&stp->refTag); }
   const Mat4 Tc = uniform_iso_global(as_global((const float*)(usePrevTc ? stp->invTcorrPrev.m : stp->invTcorr.m)));
   const Mat4 Tl = uniform_iso_global(as_global((const float*)stp->invT.m));
   constexpr int kSlots = LdsAcc<FULL_H>::kSlots;
@@ -1799,6 +1819,8 @@ __global__ void __launch_bounds__(kLatBlock) k_corr_linearize_lat(const PairDesc
   const PairDesc& pd = pairs[blockIdx.y];
   const int N = ap.rows * ap.cols;
   const PairState* stp = pd.state;
+  // a converged pair: the loop's passes return (workgroup-uniform, in front of the first barrier); the statistics pass reads its own last epoch
+  if (ap.mayFreeze && pair_frozen(stp)) { if (!usePrevTc) return; tag = *as_global(&stp->refTag); }
   const Mat4 Tc = uniform_iso_global(as_global((const float*)(usePrevTc ? stp->invTcorrPrev.m : stp->invTcorr.m)));
   const Mat4 Tl = uniform_iso_global(as_global((const float*)stp->invT.m));
   constexpr int kSlots = LdsAcc<FULL_H>::kSlots;
@@ -1946,6 +1968,7 @@ __device__ __forceinline__ unsigned short depth_to_u16(float d, float scale) { r
 __global__ void __launch_bounds__(256) k_match_score(const PairDesc* __restrict__ pairs, int n, unsigned refTag, unsigned curTag, float scale,
                                                      float threshold, MatchAcc* __restrict__ out, int curOwn) {
   const PairDesc& pd = pairs[blockIdx.y];
+  refTag = pair_ref_tag(pd.state, refTag);
   int nz = 0, inl = 0; long long sum = 0; int tiny = 0;
   const int ncur = min(*pd.cur.count, pd.cur.capacity), nref = min(*pd.ref.count, pd.ref.capacity);
   const Mat4 KRtRef = uniform_iso(pd.state->KRtLast), KRtCur = uniform_iso(pd.state->KRtCur);
@@ -2041,8 +2064,13 @@ __device__ __forceinline__ void assemble_Hb(const double* s, float* H, float* b)
 // LDS-promoted array, and a 64-pair launch 18 us instead of 10.5 -- found in the v14 kernel trace and undone.)
 // last: this is the alignment's final step -- with pd.state_out set (a few pairs: latency path), the pose goes to the page-locked host copy of
 // the state as well (the traces go there step by step), and the host needs no copy back of the state.
-__global__ void __launch_bounds__(256) k_solve_update(const PairDesc* __restrict__ pairs, AlignParams ap, int nblocks, int outerEnd, int last) {
+// tag: the epoch of this outer iteration's reference projection.  At the end of an outer iteration the norms of the step just solved are recorded
+// (stepT / stepR, entry `outer`), and under an enabled StopRule the pair may freeze: its update is applied as usual, and with pd.state_out set the
+// pose goes to the host copy now, because the launch with `last` set will return for this pair like every other one.
+__global__ void __launch_bounds__(256) k_solve_update(const PairDesc* __restrict__ pairs, AlignParams ap, int nblocks, int outerEnd, int last, unsigned tag,
+                                                      StopRule stop) {
   const PairDesc& pd = pairs[blockIdx.x];
+  if (stop.enabled && pair_frozen(pd.state)) return;      // workgroup-uniform, in front of reduce_partials' barriers
   __shared__ double sums[kAccN];
   reduce_partials(pd.partials, nblocks, sums);
   if (threadIdx.x != 0) return;
@@ -2077,7 +2105,19 @@ __global__ void __launch_bounds__(256) k_solve_update(const PairDesc* __restrict
     T = v2t(v);
     set_last_row(T);
     st.T = T;
-    if (so && last) { so->T = T; so->it = it + 1; }
+    // fp32, every product and sum rounded on its own, left to right
+    const float sT = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx[0], dx[0]), __fmul_rn(dx[1], dx[1])), __fmul_rn(dx[2], dx[2])));
+    const float sR = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx[3], dx[3]), __fmul_rn(dx[4], dx[4])), __fmul_rn(dx[5], dx[5])));
+    const int oi = st.outer;
+    if (oi < kMaxIter) {
+      st.stepT[oi] = sT; st.stepR[oi] = sR;
+      if (so) { so->stepT[oi] = sT; so->stepR[oi] = sR; }
+    }
+    st.outer = oi + 1;
+    st.refTag = tag;
+    const bool freeze = stop.enabled && oi + 1 >= stop.minIterations && sT <= stop.epsT && sR <= stop.epsR;      // false for a NaN
+    if (freeze) st.frozen = 1;
+    if (so && (last || freeze)) { so->T = T; so->it = it + 1; so->outer = oi + 1; so->frozen = freeze ? 1 : 0; }
     const Mat4 Tinv = iso_inverse(T);
     st.invTcorrPrev = st.invTcorr;
     st.invTcorr = Tinv;

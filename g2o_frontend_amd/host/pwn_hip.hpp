@@ -100,6 +100,21 @@ class Context {
   void setConcurrency(int streams) { check(pwn_hip_ctx_set_concurrency(_ctx, streams)); }
   // PWN_HIP_OMEGA_SYM6 (default) / PWN_HIP_OMEGA_EXACT9 (every entry of Omega_p bit-identical to pwn_core's): storage of the point information matrices of clouds created from now on
   void setOmegaStorage(int mode) { check(pwn_hip_ctx_set_omega_storage(_ctx, mode)); }
+  // "stop when converged" for every alignment call of the context (include/pwn_hip.h: pwn_hip_ctx_set_convergence; opt-in, a deviation from the
+  // reference's fixed outerIterations): a pair's loop ends on the device after the first outer iteration i with i + 1 >= minIterations whose last
+  // step is no longer than the two epsilons; its results are those of outerIterations = i + 1, bit for bit
+  void setConvergence(float translation, float rotation, int minIterations = 0) {
+    const pwn_hip_convergence s = { 1, translation, rotation, minIterations };
+    check(pwn_hip_ctx_set_convergence(_ctx, &s));
+  }
+  void clearConvergence() { check(pwn_hip_ctx_set_convergence(_ctx, nullptr)); }
+  pwn_hip_convergence convergence() const { pwn_hip_convergence s; check(pwn_hip_ctx_get_convergence(_ctx, &s)); return s; }      // enabled == 0: off
+  // the step norms of the pairs [first, first + n) of the last alignment call
+  std::vector<pwn_hip_align_steps> lastAlignSteps(int first = 0, int n = 1) {
+    std::vector<pwn_hip_align_steps> out((size_t)(n > 0 ? n : 0));
+    check(pwn_hip_last_align_steps(_ctx, first, n, out.data()));
+    return out;
+  }
   void synchronize() { check(pwn_hip_ctx_synchronize(_ctx)); }
   void waitStream(void* hipStream) { check(pwn_hip_ctx_wait_stream(_ctx, hipStream)); }      // what the context queues from now on runs after that stream's work
   void signalStream(void* hipStream) { check(pwn_hip_ctx_signal_stream(_ctx, hipStream)); }  // what that stream gets from now on runs after everything the context has queued
@@ -482,6 +497,8 @@ class Aligner {
   void setCurrentSensorOffset(Isometry3f o) { o.forceLastRow(); _currentSensorOffset = o; }
   float error() const { return _error; }  int inliers() const { return _inliers; }  double totalTime() const { return _totalTime; }
   const pwn_hip_align_result& result() const { return _result; }
+  // the step norms of the pairs [first, first + n) of the context's last alignment call (Context::lastAlignSteps)
+  std::vector<pwn_hip_align_steps> lastSteps(int first = 0, int n = 1) { return _ctx->lastAlignSteps(first, n); }
   pwn_hip_aligner_params params() const {
     if (!_projector || !_linearizer || !_correspondenceFinder) throw Error(PWN_HIP_ERR_INVALID_ARGUMENT, "Aligner: missing collaborator");   // aligner.cpp:50-52
     pwn_hip_aligner_params p; pwn_hip_default_aligner_params(&p);

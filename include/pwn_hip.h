@@ -190,6 +190,43 @@ int pwn_hip_ctx_set_concurrency(pwn_hip_ctx* ctx, int streams);
 #define PWN_HIP_OMEGA_SYM6 1
 int pwn_hip_ctx_set_omega_storage(pwn_hip_ctx* ctx, int mode);
 int pwn_hip_cloud_omega_storage(pwn_hip_ctx* ctx, const pwn_hip_cloud* cloud, int* mode);
+/* "Stop when converged": a deviation from the reference, whose Aligner::align always runs outerIterations (aligner.cpp:70); opt-in and off by
+ * default, and a context with the default setting computes bit for bit what it computed without it.
+ *   Let dx be the Gauss-Newton step solved in the LAST inner iteration of outer iteration i (0-based): dx[0:3] the translation, dx[3:6] the
+ *   rotation part as v2t reads it, and
+ *     s_t = sqrt((dx0*dx0 + dx1*dx1) + dx2*dx2)      s_r = sqrt((dx3*dx3 + dx4*dx4) + dx5*dx5)
+ *   in fp32, every product rounded on its own, the sums left to right, the square root correctly rounded.  Both are recorded per pair at index i,
+ *   whether or not the setting is enabled (pwn_hip_last_align_steps).
+ *   Enabled, a pair is converged after outer iteration i iff  i + 1 >= min_iterations && s_t <= translation_epsilon && s_r <= rotation_epsilon
+ *   (a NaN never converges).  The update of iteration i is applied as usual; from then on the pair is frozen: the remaining launches of the call
+ *   return for it on the device (no host round trip; the launches themselves still happen, so this saves time in batches whose pairs converge
+ *   at different iterations, not in the latency of a single pair).
+ *   Contract: everything the call returns for a pair frozen after iteration i -- its pwn_hip_align_result (T, error, inliers, iterations, the
+ *   traces), its record words, its matchClouds score, its statistics, and for the pair of slot 0 pwn_hip_align_images / pwn_hip_match_score -- equals
+ *   bit for bit what the same call returns with outer_iterations = i + 1.  total_time_ms is exempt.
+ * Every alignment entry point honours the setting.  The one exception is the host-driven loop with priors: pwn_hip_align_with_priors* with
+ * n_priors > 0 returns PWN_HIP_ERR_INVALID_ARGUMENT while the setting is enabled, and touches nothing.
+ * set: NULL or enabled == 0 switches it off; enabling is refused (INVALID_ARGUMENT, setting unchanged) unless both epsilons are finite and >= 0
+ * and min_iterations >= 0. */
+typedef struct pwn_hip_convergence {
+  int   enabled;
+  float translation_epsilon;      /* metres */
+  float rotation_epsilon;         /* norm of the rotation part of the step (about half the angle in radians) */
+  int   min_iterations;           /* outer iterations every pair runs at least */
+} pwn_hip_convergence;
+int pwn_hip_ctx_set_convergence(pwn_hip_ctx* ctx, const pwn_hip_convergence* setting);
+int pwn_hip_ctx_get_convergence(const pwn_hip_ctx* ctx, pwn_hip_convergence* setting);
+/* The step norms of the pairs [first, first + n) of the context's last alignment call: `iterations` OUTER iterations were executed (the entries
+ * [0, iterations) of both traces, zeros behind them), `converged` = 1 when the pair froze under the setting above.  Reads what the call left
+ * behind (a call that returned records only fetches the states from the device on the first such request); INVALID_ARGUMENT when the range
+ * is not inside the last call's pairs.  After pwn_hip_align_with_priors* with n_priors > 0 the traces are empty. */
+typedef struct pwn_hip_align_steps {
+  int   iterations;
+  int   converged;
+  float step_translation[PWN_HIP_MAX_ITERATIONS];
+  float step_rotation[PWN_HIP_MAX_ITERATIONS];
+} pwn_hip_align_steps;
+int pwn_hip_last_align_steps(pwn_hip_ctx* ctx, int first, int n, pwn_hip_align_steps* out);
 /* ctx may be NULL (errors of ctx_create). Never returns NULL. cf. AlignerStatus::toString (cudaaligner.h:54) */
 const char* pwn_hip_last_error_string(const pwn_hip_ctx* ctx);
 /* number of HIP devices visible; does not initialise a device */
