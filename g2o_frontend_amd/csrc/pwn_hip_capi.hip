@@ -259,6 +259,10 @@ struct pwn_hip_ctx {
   int settle_guard = kSettleGuard;                       // pwn_hip_debug_set_settle_guard (test hook)
   int last_align_fault = 0;                              // the last alignment call ended with the fault word raised
   int projection_fallbacks = 0;                          // calls repeated with the two-pass projection so far (pwn_hip_debug_projection_fallbacks)
+  // the frames of a step's current clouds, per pair (CurDepthSrc::raw), and how many sub-batches of the last batch alignment ran the fused pass
+  // on them (pwn_hip_debug_cur_depth_sub_batches)
+  DevBuf<const uint16_t*> cur_raw_dev; HostBuf<const uint16_t*> cur_raw_host;
+  int cur_depth_subs = 0;
   // The merged closure (pwn_hip_merge_depth_images, pwn_hip_project_merge_batch), allocated by the first such call: the staging images of
   // host-side `merged` / `weights` ([0, N) and [N, 2N)) and behind them merge_planes = min(max_batch, kMergePlanesMax) depth planes of N words;
   // a call with more images runs in chunks of that many.  Per image of a call: its plane's address, its cloud, its projector matrix; the
@@ -283,14 +287,18 @@ constexpr size_t kCloudPoolBytes = 1ull << 30;
 // What the aligner's launches for one sub-batch share: the call's parameters and grid (nb workgroups per pair; sym: storage of the current clouds' point
 // information matrices, CloudDev::omSym, the same for every pair), the m consecutive pair descriptors, their stream, and -- when the call runs the
 // two-pass projection, else nullptr -- the depth images of their workspace slots (contiguous, ctx->N words each)
-struct PairLaunch { const AlignParams* ap; int nb, sym; int m; hipStream_t st; const PairDesc* pr; unsigned* zd; };
+// cd: the depth source of the pairs' current side (CurDepthSrc, raw already that of the launch's first pair), nullptr = the stored points
+struct PairLaunch { const AlignParams* ap; int nb, sym; int m; hipStream_t st; const PairDesc* pr; unsigned* zd; const CurDepthSrc* cd; };
 // the fused correspondence + linearize pass: the throughput shape, or the latency shape (same sums bit for bit, see k_corr_linearize_lat)
 // when all workgroups of the launch find a CU of their own -- its 1024-thread workgroups fit one per CU, a second round costs more than
 // the shape saves: one VGA pair is 150 workgroups, two pairs or one 1280x960 pair are not worth it on 256 CUs
+bool latency_shape(const pwn_hip_ctx* ctx, int nb, int m) { return (long long)nb * m <= ctx->num_cus; }
+// The depth source is a trade of bytes, so it belongs to the throughput shape: the latency shape keeps the stored points.
 template <bool SAME_T, bool FULL_H, bool SYM>
 void launch_corr_linearize_s(const pwn_hip_ctx* ctx, const PairLaunch& L, unsigned tag, int usePrevTc, int ownRef) {
-  if ((long long)L.nb * L.m <= ctx->num_cus) hipLaunchKernelGGL((k_corr_linearize_lat<SAME_T, FULL_H, SYM>), dim3(L.nb, L.m), dim3(kLatBlock), 0, L.st, L.pr, *L.ap, tag, usePrevTc, ownRef);
-  else hipLaunchKernelGGL((k_corr_linearize<SAME_T, FULL_H, SYM>), dim3(L.nb, L.m), dim3(kAlignBlock), 0, L.st, L.pr, *L.ap, tag, usePrevTc, ownRef);
+  if (latency_shape(ctx, L.nb, L.m)) hipLaunchKernelGGL((k_corr_linearize_lat<SAME_T, FULL_H, SYM>), dim3(L.nb, L.m), dim3(kLatBlock), 0, L.st, L.pr, *L.ap, tag, usePrevTc, ownRef);
+  else if (L.cd) hipLaunchKernelGGL((k_corr_linearize<SAME_T, FULL_H, SYM, kPixPerThread, true>), dim3(L.nb, L.m), dim3(kAlignBlock), 0, L.st, L.pr, *L.ap, tag, usePrevTc, ownRef, *L.cd);
+  else hipLaunchKernelGGL((k_corr_linearize<SAME_T, FULL_H, SYM>), dim3(L.nb, L.m), dim3(kAlignBlock), 0, L.st, L.pr, *L.ap, tag, usePrevTc, ownRef, NoCurDepthSrc());
 }
 template <bool SAME_T, bool FULL_H>
 void launch_corr_linearize(const pwn_hip_ctx* ctx, const PairLaunch& L, unsigned tag, int usePrevTc, int ownRef) {
@@ -631,6 +639,8 @@ int ensure_desc(pwn_hip_ctx* ctx, int n) {
   HIPCHK(ctx, ctx->raw_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
   HIPCHK(ctx, ctx->state_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
   HIPCHK(ctx, ctx->counts_host.ensure(B + 1), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->cur_raw_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->cur_raw_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
   HIPCHK(ctx, ctx->match_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
   HIPCHK(ctx, ctx->match_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
   HIPCHK(ctx, ctx->stats_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
@@ -1518,6 +1528,12 @@ int pwn_hip_debug_projection_fallbacks(pwn_hip_ctx* ctx, int* calls) {
   *calls = ctx->projection_fallbacks;
   return PWN_HIP_OK;
 }
+// Test hook: sub-batches of the last batch alignment whose fused pass took the current points from the depth frames (CurDepthSrc)
+int pwn_hip_debug_cur_depth_sub_batches(pwn_hip_ctx* ctx, int* sub_batches) {
+  if (!ctx || !sub_batches) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  *sub_batches = ctx->cur_depth_subs;
+  return PWN_HIP_OK;
+}
 // Test hook: the converter's stats pass (k_stats, launched as launch_convert launches it) on caller-supplied integral planes, index and
 // interval images -- windows that no depth frame produces.  The clouds hold the points the index images refer to (pwn_hip_cloud_upload).
 int pwn_hip_debug_stats_from_integral(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, int rows, int cols, int nframes, const float* integral,
@@ -2399,6 +2415,9 @@ struct AlignHooks {
   std::function<int()> before_sync;                                        // on ctx->stream, after the streams have joined
   std::function<int()> after_sync;                                         // after the final wait, before the results are filled in
 };
+// The resident full-resolution uint16 frames the current clouds of a call are converted from in front of their alignment, with that conversion's
+// parameters: a sub-batch whose pairs all take the current cloud's own index image runs the fused pass on them (CurDepthSrc)
+struct CurDepthFrames { const uint16_t* const* frames; float scale; const ConvertParams* cp; };
 // What a caller asks of a batch alignment; every member defaults to "not asked for", an entry point names the ones it uses.
 struct AlignCall {
   const pwn_hip_aligner_params* p = nullptr;
@@ -2412,6 +2431,7 @@ struct AlignCall {
   float* records = nullptr;                                    // n records, device or host, written by k_pack_records: PWN_HIP_RECORD_FLOATS floats each,
   bool match_records = false;                                  // or the long form with the score words
   const int* pair_ids = nullptr; int first_pair_id = 0;        // record word 19: pair_ids[i] (host), else first_pair_id + i
+  const CurDepthFrames* cur_depth = nullptr;                   // the one-call step: the frames curs[i] are being converted from
 };
 // What the phases of one attempt at a call share (on align_batch_once's stack)
 struct AlignRun {
@@ -2472,7 +2492,7 @@ static int align_check_and_plan(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& 
   if (!ctx || !c.p || !c.refs || !c.curs || (!c.results && !c.records) || c.n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (int rc = check_image(ctx, c.p->rows, c.p->cols)) return rc;
   ctx->img.invalidate();                  // whatever happens below (set again on success)
-  ctx->last_pairs = 0;
+  ctx->last_pairs = 0; ctx->cur_depth_subs = 0;
   if (int rc = check_align_params(ctx, c.p)) return rc;
   if (int rc = start_align_attempt(ctx, run.robust)) return rc;
   run.want_scores = c.scores != nullptr || (c.records && c.match_records);
@@ -2530,6 +2550,10 @@ static int align_describe_pairs(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& 
   if (n > 0) {
     HIPCHK(ctx, hipMemcpyAsync(ctx->pairs_dev, ctx->pairs_host, sizeof(PairDesc) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
     HIPCHK(ctx, hipMemcpyAsync(ctx->state_ws, ctx->state_host, sizeof(PairState) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+    if (c.cur_depth && run.any_own) {
+      for (int i = 0; i < n; ++i) ctx->cur_raw_host[i] = c.cur_depth->frames[i];
+      HIPCHK(ctx, hipMemcpyAsync(ctx->cur_raw_dev, ctx->cur_raw_host, sizeof(const uint16_t*) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+    }
     if (run.want_scores) HIPCHK(ctx, hipMemsetAsync(ctx->match_dev, 0, sizeof(MatchAcc) * n, ctx->stream), PWN_HIP_ERR_COPY);
   }
   return PWN_HIP_OK;
@@ -2555,7 +2579,15 @@ static int align_enqueue_sub(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& run
   const int m = std::min(run.plan.sub, c.n - base), N = run.N;
   hipStream_t st = run.plan.stream(k);
   const size_t s0 = (size_t)run.plan.slot0(k);
-  const PairLaunch L = { &run.ap, run.nb, run.omSym, m, st, ctx->pairs_dev + base, run.robust ? ctx->zdepth_ws + s0 * ctx->N : nullptr };
+  // the current points from the frames: every pair of the sub-batch reads the index image its frame's conversion wrote, in the throughput shape
+  CurDepthSrc cd;
+  const bool cur_depth = c.cur_depth && run.sub_own[k] && !latency_shape(ctx, run.nb, m);
+  if (cur_depth) {
+    const ConvertParams& cp = *c.cur_depth->cp;
+    cd.raw = ctx->cur_raw_dev + base; cd.scale = c.cur_depth->scale; cd.iKRt = cp.iKRt; cd.hasOffset = cp.hasOffset; cd.offset = cp.offset;
+    ++ctx->cur_depth_subs;
+  }
+  const PairLaunch L = { &run.ap, run.nb, run.omSym, m, st, ctx->pairs_dev + base, run.robust ? ctx->zdepth_ws + s0 * ctx->N : nullptr, cur_depth ? &cd : nullptr };
   int maxcap_ref = 0, maxcap_cur = 0;
   for (int i = 0; i < m; ++i) { maxcap_ref = std::max(maxcap_ref, c.refs[base + i]->d.capacity); maxcap_cur = std::max(maxcap_cur, c.curs[base + i]->d.capacity); }
   const unsigned tag0 = run.rolling ? run.tagBase - (unsigned)k * run.tagsPerSub : kZ32Tag0, lastRefTag = tag0 - (run.tagsPerSub - 1);
@@ -2888,6 +2920,10 @@ static int convert_align_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_pa
     hooks.after_sync = [&]() -> int { return convert_commit(ctx, job); };
     AlignCall call = align_call(ap, n, refs, curs, guesses, results);
     call.hooks = &hooks; call.records = records; call.pair_ids = pair_ids; call.first_pair_id = first_pair_id;
+    // the current frames as a depth source: the caller's own resident frames only -- a staged host frame or a down-sampled one lives in a workspace
+    // slot that the next launch of conversions reuses
+    const CurDepthFrames cur_depth = { cur_frames, depth_scale, &job.cp };
+    if (job.raw && !job.host_input && !sc.step) call.cur_depth = &cur_depth;
     return align_batch_impl(ctx, call);
   });
 }
@@ -3036,6 +3072,22 @@ int pwn_hip_unproject_pixel(const float K[9], const float T[16], float min_dista
   const Vec3 q = unproject_pixel(iKRt, x, y, d);
   p[0] = q.x; p[1] = q.y; p[2] = q.z;
   return 1;
+}
+// Test hook, host code: converter_point -- the expression the stats pass stores and the fused pass's depth source recomputes -- of every pixel
+// of a uint16 frame whose index is >= 0, written to points[3 * index]
+int pwn_hip_debug_converter_points(const pwn_hip_converter_params* p, int rows, int cols, const uint16_t* raw, float depth_scale, const int* index_image,
+                                   int capacity, float* points) {
+  if (!p || !raw || !index_image || !points || rows <= 0 || cols <= 0) return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  const ConvertParams cp = make_convert_params(nullptr, p, nullptr, rows, cols, 0);
+  for (int r = 0; r < rows; ++r)
+    for (int c = 0; c < cols; ++c) {
+      const size_t pix = (size_t)r * cols + c;
+      const int idx = index_image[pix];
+      if (idx < 0 || idx >= capacity) continue;
+      const Vec3 q = converter_point(cp.iKRt, cp.hasOffset, cp.offset, c, r, raw_to_metres(raw[pix], depth_scale));
+      points[3 * (size_t)idx] = q.x; points[3 * (size_t)idx + 1] = q.y; points[3 * (size_t)idx + 2] = q.z;
+    }
+  return PWN_HIP_OK;
 }
 int pwn_hip_project_interval(const float K[9], float min_distance, float max_distance, float d, float world_radius) {
   if (!K) return -1;

@@ -193,6 +193,20 @@ struct AlignParams {
                            // can freeze and no kernel of the loop loads a flag -- the launches are the ones of a library without the feature
 };
 
+// A depth source for the current side of a sub-batch's pairs (k_corr_linearize<..., CUR_DEPTH = true>): the one-call step aligns clouds it has
+// just converted from frames that are still resident, and where a pair takes the current cloud's own index image (PairDesc::curidx = the
+// converter's), candidate pixel pix with ci = curidx[pix] is the pixel point ci was unprojected from.  The fused pass then reads the pixel's
+// 2-byte raw depth, coalesced, instead of gathering the 12-byte point, and evaluates the converter's own expression (converter_point: the bits
+// k_stats stored).  raw[y] belongs to pair y of the launch, like pairs[y]; the other members are those of the step's conversions.  It sits next to
+// the descriptors, not in them: PairDesc and AlignParams keep their layout, and every other kernel its code.
+struct CurDepthSrc {
+  const uint16_t* const* raw;   // per pair of the launch: the uint16 frame the current cloud was converted from (rows x cols, the aligner's size)
+  float scale;                  // metres per raw unit
+  Mat4 iKRt;                    // ConvertParams::iKRt
+  int hasOffset; Mat4 offset;   // ConvertParams::hasOffset / offset
+};
+struct NoCurDepthSrc {};        // what the other instantiations take in its place
+
 // ------------------------------------------------------------------------------------------------------------------
 // small device helpers
 __device__ __forceinline__ float wave_sum(float v) {
@@ -1188,10 +1202,10 @@ __device__ __forceinline__ void stats_pixel(const FrameDesc& f, const ConvertPar
   if (cp.hasOffset) {
     // Cloud::transformInPlace: p = m*p, n = m*n, Omega = T*Omega*T^t with T = m without last row/col
     const Mat4& m = cp.offset;
-    const float px = dot4seq(m(0,0), P.x, m(0,1), P.y, m(0,2), P.z, m(0,3), 1.0f);
-    const float py = dot4seq(m(1,0), P.x, m(1,1), P.y, m(1,2), P.z, m(1,3), 1.0f);
-    const float pz = dot4seq(m(2,0), P.x, m(2,1), P.y, m(2,2), P.z, m(2,3), 1.0f);
-    P.x = px; P.y = py; P.z = pz;
+    // the point: the second half of converter_point (pwn_math.h); the first is the lean path's unproject_pixel above -- the normal's
+    // orientation test in between wants the point in the sensor's frame
+    const Vec3 po = offset_point(m, P.x, P.y, P.z);
+    P.x = po.x; P.y = po.y; P.z = po.z;
     const float tx = dot4seq(m(0,0), nx, m(0,1), ny, m(0,2), nz, m(0,3), 0.0f);
     const float ty = dot4seq(m(1,0), nx, m(1,1), ny, m(1,2), nz, m(1,3), 0.0f);
     const float tz = dot4seq(m(2,0), nx, m(2,1), ny, m(2,2), nz, m(2,3), 0.0f);
@@ -1681,6 +1695,7 @@ struct Candidate {
   float4 rP, rN, cP, cN;
   int ci;
   bool valid;
+  unsigned craw;      // CUR_DEPTH: the pixel's raw depth stands for cP.xyz (CurDepthSrc), one register instead of three
 };
 // The descriptor's pointers are generic to the compiler: flat_* loads, which count on BOTH the vector-memory and the LDS counter, so
 // every wait for an LDS accumulator update would also wait for the gathers of the next pixel that are meant to stay in flight.
@@ -1709,6 +1724,16 @@ __device__ __forceinline__ void candidate_load(const PairPtrs& q, int ri, int ci
   if (c.valid) {
     // 12 + 16 bytes per side; the rest of the pass keeps the (point, curvature) / (normal, -) records it was written for
     c.rP = load_xyz(q.refP, (unsigned)ri); c.cP = load_xyz(q.curP, (unsigned)ci); c.cN = load4(q.curN + (unsigned)ci);
+    c.rN = load4(q.refN + (unsigned)ri);
+    c.rP.w = c.rN.w; c.cP.w = c.cN.w;
+  }
+}
+// the same without the load of the current point: craw, the raw depth of the candidate's pixel (it arrived with the indices), is kept in its place
+__device__ __forceinline__ void candidate_load_depth(const PairPtrs& q, int ri, int ci, unsigned craw, int nref, int ncur, Candidate& c) {
+  c.valid = !(ri < 0 || ci < 0 || ri >= nref || ci >= ncur);
+  c.ci = ci; c.craw = craw;
+  if (c.valid) {
+    c.rP = load_xyz(q.refP, (unsigned)ri); c.cN = load4(q.curN + (unsigned)ci);
     c.rN = load4(q.refN + (unsigned)ri);
     c.rP.w = c.rN.w; c.cP.w = c.cN.w;
   }
@@ -1755,8 +1780,11 @@ __device__ __forceinline__ void candidate_consume(const PairDesc& pd, const Pair
 }
 // usePrevTc: the acceptance tests run with the previous outer iteration's transform (Aligner::_computeStatistics re-linearizes
 // the finder's existing correspondences at the final transform, aligner.cpp:165-170).
-template <bool SAME_T, bool FULL_H, bool SYM = false, int PPT = kPixPerThread>
-__global__ void __launch_bounds__(kAlignBlock, 1) k_corr_linearize(const PairDesc* __restrict__ pairs, AlignParams ap, unsigned tag, int usePrevTc, int ownRefIndex) {
+// CUR_DEPTH: the pairs' current clouds own their index images (curidx) and their frames are at hand (cd, CurDepthSrc): the current point is
+// recomputed from the pixel's depth instead of loaded -- 2 coalesced bytes per pixel in place of a 12-byte gather per candidate, the same bits.
+template <bool SAME_T, bool FULL_H, bool SYM = false, int PPT = kPixPerThread, bool CUR_DEPTH = false>
+__global__ void __launch_bounds__(kAlignBlock, 1) k_corr_linearize(const PairDesc* __restrict__ pairs, AlignParams ap, unsigned tag, int usePrevTc, int ownRefIndex,
+                                                                   std::conditional_t<CUR_DEPTH, CurDepthSrc, NoCurDepthSrc> cd) {
   const PairDesc& pd = pairs[blockIdx.y];
   const int N = ap.rows * ap.cols;
   const PairState* stp = pd.state;
@@ -1776,25 +1804,42 @@ __global__ void __launch_bounds__(kAlignBlock, 1) k_corr_linearize(const PairDes
   const int nref = min(*as_global((const int*)pd.ref.count), pd.ref.capacity), ncur = min(*as_global((const int*)pd.cur.count), pd.cur.capacity);
   const int pix0 = blockIdx.x * PPT * kAlignBlock + threadIdx.x;
   const PairPtrs q = pair_ptrs(pd);
-  auto load_indices = [&](int j, int& ri, int& ci) {
+  gptr<const uint16_t> craw = nullptr;                    // CUR_DEPTH: the pair's current frame
+  int row = 0, col = 0;                                   // CUR_DEPTH: row and column of pixel j
+  if constexpr (CUR_DEPTH) { craw = as_global(as_global(cd.raw)[blockIdx.y]); row = pix0 / ap.cols; col = pix0 - row * ap.cols; }
+  auto load_indices = [&](int j, int& ri, int& ci, unsigned& cr) {
     const int pix = pix0 + j * kAlignBlock;
     ri = -1; ci = -1;
     if (j < PPT && pix < N) {
       ri = ownRefIndex ? q.refidx0[(unsigned)pix] : z32_index(q.zref[(unsigned)pix], tag);      // wave-uniform choice
       ci = q.curidx[(unsigned)pix];
+      if constexpr (CUR_DEPTH) cr = craw[(unsigned)pix];    // 2 bytes per pixel, coalesced: what the 12-byte gather of the current point is traded for
     }
   };
   int ri1, ci1, ri2, ci2;
-  load_indices(0, ri1, ci1);
-  load_indices(1, ri2, ci2);
+  unsigned cr1 = 0u, cr2 = 0u;
+  load_indices(0, ri1, ci1, cr1);
+  load_indices(1, ri2, ci2, cr2);
   Candidate nxt;
-  candidate_load(q, ri1, ci1, nref, ncur, nxt);
+  if constexpr (CUR_DEPTH) candidate_load_depth(q, ri1, ci1, cr1, nref, ncur, nxt);
+  else candidate_load(q, ri1, ci1, nref, ncur, nxt);
 #pragma unroll 1
   for (int j = 0; j < PPT; ++j) {
-    const Candidate cur = nxt;
-    candidate_load(q, ri2, ci2, nref, ncur, nxt);        // gathers of pixel j+1: in flight during the arithmetic below
-    load_indices(j + 2, ri2, ci2);                        // indices of pixel j+2
+    Candidate cur = nxt;
+    if constexpr (CUR_DEPTH) candidate_load_depth(q, ri2, ci2, cr2, nref, ncur, nxt);
+    else candidate_load(q, ri2, ci2, nref, ncur, nxt);    // gathers of pixel j+1: in flight during the arithmetic below
+    load_indices(j + 2, ri2, ci2, cr2);                   // indices of pixel j+2
+    if constexpr (CUR_DEPTH) {                            // the current point of pixel j = (row, col), as the converter stored it
+      if (cur.valid) {
+        const Vec3 p = converter_point(cd.iKRt, cd.hasOffset, cd.offset, col, row, raw_to_metres(cur.craw, cd.scale));
+        cur.cP.x = p.x; cur.cP.y = p.y; cur.cP.z = p.z;
+      }
+    }
     candidate_consume<SAME_T, SYM>(pd, q, ap, Tc, Tl, cur, sums, cnt, omNtab);
+    if constexpr (CUR_DEPTH) {                            // pixel j + 1 lies 256 pixels on: no division; cols may be below 256, so the wrap is a loop
+      col += kAlignBlock;
+      while (col >= ap.cols) { col -= ap.cols; ++row; }
+    }
   }
   float acc[kAccN];
 #pragma unroll

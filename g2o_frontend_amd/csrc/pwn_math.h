@@ -137,6 +137,18 @@ PWN_HD Vec3 unproject_pixel(const Mat4& iKRt, int c, int r, float d) {
   const Vec3 p = { affine_row(iKRt, 0, a, b, d), affine_row(iKRt, 1, a, b, d), affine_row(iKRt, 2, a, b, d) };
   return p;
 }
+// Cloud::transformInPlace's point rows: the converter's sensor offset m applied to a point (last row of m forced)
+PWN_HD Vec3 offset_point(const Mat4& m, float x, float y, float z) {
+  const Vec3 p = { affine_row(m, 0, x, y, z), affine_row(m, 1, x, y, z), affine_row(m, 2, x, y, z) };
+  return p;
+}
+// The point of pixel (column c, row r) at depth d as the converter stores it in the cloud: _unProject, then the sensor-offset rows when the
+// converter has an offset.  The stats pass stores exactly this, so a reader that knows a point's pixel and depth can have the point's bits
+// without loading it (the aligner's fused pass, CurDepthSrc).
+PWN_HD Vec3 converter_point(const Mat4& iKRt, int hasOffset, const Mat4& offset, int c, int r, float d) {
+  const Vec3 p = unproject_pixel(iKRt, c, r, d);
+  return hasOffset ? offset_point(offset, p.x, p.y, p.z) : p;
+}
 // _projectInterval (pinholepointprojector.h:264-274): K * (R, R, 0), the image extent of the world radius R at unit depth ...
 PWN_HD void interval_scale(const Mat3& K, float R, float& ivx, float& ivy) {
   ivx = dot3seq(K(0,0), R, K(0,1), R, K(0,2), 0.f);

@@ -34,6 +34,19 @@ int pwn_hip_debug_set_index_shortcut(pwn_hip_ctx* ctx, int enabled);
 int pwn_hip_debug_set_settle_guard(pwn_hip_ctx* ctx, int rounds);
 int pwn_hip_debug_projection_fallbacks(pwn_hip_ctx* ctx, int* calls);
 
+/* The one-call step (pwn_hip_convert_align_batch_u16) aligns clouds it has just converted from frames that are still on the device.  Where every
+ * pair of a sub-batch takes the current cloud's own index image (see pwn_hip_debug_set_index_shortcut), the frames are the caller's resident
+ * uint16 frames, and the sub-batch is large enough for the throughput shape of the fused correspondence + linearize pass (more workgroups than
+ * compute units), that pass does not load the current points: it recomputes each from its pixel's raw depth, the converter's expression, the same
+ * bits.  Number of sub-batches of the context's last batch alignment that ran this way (0 after every other alignment call, after the _scaled
+ * step, and after a step on host frames): */
+int pwn_hip_debug_cur_depth_sub_batches(pwn_hip_ctx* ctx, int* sub_batches);
+/* The expression that pass evaluates, on the host (no GPU, no context): for every pixel (r, c) of a rows x cols uint16 frame with
+ * 0 <= index_image[r][c] < capacity, points[3 * index] = the point the converter stores for that pixel -- PinholePointProjector::unProject of
+ * (c, r, depth_scale * raw), then p's sensor offset if it is not the identity.  Other entries of points are left alone. */
+int pwn_hip_debug_converter_points(const pwn_hip_converter_params* p, int rows, int cols, const uint16_t* raw, float depth_scale, const int* index_image,
+                                   int capacity, float* points);
+
 /* The converter's stats pass (the kernel DepthImageConverter::compute runs after its integral image) on windows the caller supplies:
  * integral = nframes x [10][rows][cols] planes (x, y, z, n, xx, xy, xz, yy, yz, zz), index_image / interval_image = nframes x [rows][cols];
  * clouds[i] holds the points (pwn_hip_cloud_upload) index image i refers to.  Normals, curvature, information matrices (and stats with
