@@ -810,10 +810,12 @@ int sync_and_counts(pwn_hip_ctx* ctx, pwn_hip_cloud* const* clouds, int n) {
   return counts_apply(ctx, clouds, n);
 }
 
-// One converter call, cut into the pieces a caller can interleave with other work on the same streams: convert_prepare (descriptors of all
-// frames, uploaded on ctx->stream), convert_enqueue (the kernels of frames [base, base + m) on one stream) and convert_finish (counts and
-// fault flag back, clouds' host-side sizes).  slot[i] = workspace slot of frame i: frames that are in flight at the same time on different
-// streams must not share one; a stream reuses its slots from launch to launch (stream order serialises the reuse).
+// One converter call.  What the caller asks for is one record (ConvertCall, below); the work is cut into the pieces a caller can interleave with
+// other work on the same streams: convert_prepare (descriptors of all frames, uploaded on ctx->stream), convert_stage_frames (host frames
+// [base, base + m) into their slots), convert_enqueue (the kernels of those frames on one stream) and convert_finish (counts and fault flag back,
+// clouds' host-side sizes).  A batch call runs them phase by phase (convert_batch_once); the one-call step weaves them into an alignment.
+// slot[i] = workspace slot of frame i: frames that are in flight at the same time on different streams must not share one; a stream reuses its
+// slots from launch to launch (stream order serialises the reuse).
 // DepthImage_scale in front of a conversion (PwnMatcherBase::makeCloud, pwn_matcher_base.cpp:57-86): the source size, the step and what it leaves
 struct ScaleSpec {
   int step = 0;                          // 0: the frames are converted as they are
@@ -872,6 +874,25 @@ int ensure_gauss_desc(pwn_hip_ctx* ctx, int n) {
   HIPCHK(ctx, ctx->gauss_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
   return PWN_HIP_OK;
 }
+// What a caller asks of a conversion; every member defaults to "not asked for", an entry point names the ones it uses (on its stack; handed down by reference).
+struct ConvertCall {
+  const pwn_hip_converter_params* p = nullptr;
+  int n = 0;                                                   // frames: frames[i] into clouds[i]
+  const void* const* frames = nullptr;                         // device or host, all of one kind; all float (metres), or
+  bool raw = false; float depth_scale = 0.f;                   // all uint16 with their scale
+  int rows = 0, cols = 0;                                      // the size that is converted (scale.step != 0: of the down-sampled image)
+  pwn_hip_cloud* const* clouds = nullptr;
+  int keep_stats = 0; bool want_interval = false;              // the interval image stays readable (pwn_hip_convert(..., interval_image))
+  ScaleSpec scale; GaussSpec gauss;                            // DepthImage_scale in front of every conversion; the sensor-noise Gaussians beside the points
+};
+// The members every entry point fills, and where the typed ones hand their frame arrays over: behind it the frame type is ConvertCall::raw
+template <typename T>
+ConvertCall convert_call(const pwn_hip_converter_params* p, const T* const* frames, float depth_scale, int n, int rows, int cols, pwn_hip_cloud* const* clouds) {
+  static_assert(std::is_same<T, float>::value || std::is_same<T, uint16_t>::value, "depth frames are float or uint16");
+  ConvertCall c; c.p = p; c.n = n; c.rows = rows; c.cols = cols; c.clouds = clouds;
+  c.frames = reinterpret_cast<const void* const*>(frames); c.raw = std::is_same<T, uint16_t>::value; c.depth_scale = c.raw ? depth_scale : 0.f;
+  return c;
+}
 struct ConvertJob {
   ConvertParams cp;
   GaussSpec gauss;
@@ -888,60 +909,43 @@ struct ConvertJob {
   std::vector<pwn_hip_cloud*> clouds; bool committed = false;
   ~ConvertJob() { if (!committed) for (pwn_hip_cloud* c : clouds) c->content.withdraw(); }
 };
-template <typename SRC>
-int convert_prepare(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n, int rows, int cols,
-                    pwn_hip_cloud* const* clouds, int keep_stats, bool want_interval, const std::vector<int>& slot, bool direct, ConvertJob& job,
-                    const ScaleSpec& sc = ScaleSpec(), const GaussSpec& gs = GaussSpec()) {
-  const size_t N = (size_t)rows * cols;
+int convert_prepare(pwn_hip_ctx* ctx, const ConvertCall& c, const std::vector<int>& slot, bool direct, ConvertJob& job) {
+  const int n = c.n; const bool raw = c.raw; const ScaleSpec& sc = c.scale; const GaussSpec& gs = c.gauss;
+  const size_t N = (size_t)c.rows * c.cols;
   ctx->last_convert_fault = 0;            // the fault word belongs to this call from here on (a stale 1 would make an unrelated failure look like a time-out)
-  ConvertParams cp = make_convert_params(ctx, p, nullptr, rows, cols, keep_stats);
+  ConvertParams cp = make_convert_params(ctx, c.p, nullptr, c.rows, c.cols, c.keep_stats);
   // the interval image leaves the converter only through pwn_hip_convert(..., interval_image); nothing outside the library sees a lean call's
   // integral image: grouped storage (ig_at)
-  cp.lean = want_interval ? 0 : kLeanGrouped;
+  cp.lean = c.want_interval ? 0 : kLeanGrouped;
   if (int rc = ensure_desc(ctx, n)) return rc;
   if (gs.on) { if (int rc = ensure_gauss_desc(ctx, n)) return rc; }
-  const bool raw = std::is_same<SRC, uint16_t>::value;
   job.gauss = gs;
-  job.n = n; job.rows = rows; job.cols = cols; job.N = N; job.raw = raw; job.depth_scale = depth_scale; job.slot = slot; job.direct = direct;
+  job.n = n; job.rows = c.rows; job.cols = c.cols; job.N = N; job.raw = raw; job.depth_scale = c.depth_scale; job.slot = slot; job.direct = direct;
   job.scale = sc; job.srcN = sc.step ? (size_t)sc.srows * sc.scols : N;
   job.src.assign(n, nullptr);
-  cp.omSym = n > 0 ? clouds[0]->d.omSym : 0;      // one storage for all of them: check_frames_and_clouds
-  const OmegaNClasses cls = make_omega_n_classes(p);
+  cp.omSym = n > 0 ? c.clouds[0]->d.omSym : 0;      // one storage for all of them: check_frames_and_clouds
+  const OmegaNClasses cls = make_omega_n_classes(c.p);
   // the index image stays with the cloud, promised for the points this conversion will store (a sensor offset moves them off their pixels)
-  const IndexKey key = index_key(p, rows, cols);
+  const IndexKey key = index_key(c.p, c.rows, c.cols);
+  job.host_input = n > 0 && !is_device_ptr(c.frames[0]);      // host frames are staged per launch, in their slots; device frames are read in place
   // every frame gets a descriptor; workspace slots are reused round-robin (stream order serialises the reuse)
   for (int i = 0; i < n; ++i) {
-    pwn_hip_cloud* c = clouds[i];
-    if (int rc = cloud_replace(ctx, c, keep_stats != 0, false, &cls, &key, cp.hasOffset == 0, gs.on)) return rc;
-    job.clouds.push_back(c);
-    if (gs.on) ctx->gauss_host[i] = c->sb;
-    job.src[i] = frames[i];
-    const float* depth_dev = nullptr;
-    if (sc.step) depth_dev = ctx->scaled_ws + (size_t)slot[i] * ctx->N;      // the front end reads the down-sampled frame of its slot
-    else if (!raw) depth_dev = reinterpret_cast<const float*>(frames[i]);    // patched below if it is a host pointer
-    fill_frame(ctx, i, slot[i], depth_dev, c->d);
-    if (c->idximg.cap < N) {
+    pwn_hip_cloud* cl = c.clouds[i];
+    if (int rc = cloud_replace(ctx, cl, c.keep_stats != 0, false, &cls, &key, cp.hasOffset == 0, gs.on)) return rc;
+    job.clouds.push_back(cl);
+    if (gs.on) ctx->gauss_host[i] = cl->sb;
+    job.src[i] = c.frames[i];
+    const void* src = c.frames[i];      // where the kernels find the frame
+    if (job.host_input) src = raw ? (const void*)(ctx->raw_ws + (size_t)slot[i] * ctx->N) : (const void*)(ctx->depth_ws + (size_t)slot[i] * ctx->N);
+    float* scaled = sc.step ? ctx->scaled_ws + (size_t)slot[i] * ctx->N : nullptr;      // a down-sampling job: the box kernel writes, the front end reads the slot's frame
+    fill_frame(ctx, i, slot[i], sc.step ? scaled : raw ? nullptr : static_cast<const float*>(src), cl->d);
+    if (cl->idximg.cap < N) {
       HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
-      HIPCHK(ctx, c->idximg.ensure(N), PWN_HIP_ERR_ALLOCATION);
+      HIPCHK(ctx, cl->idximg.ensure(N), PWN_HIP_ERR_ALLOCATION);
     }
-    ctx->frames_host[i].index = c->idximg;
-    if (sc.step) {                                                            // ... by the box kernel, which reads the caller's frame
-      ctx->scale_host[i].src = frames[i];                                     // patched below if it is a host pointer
-      ctx->scale_host[i].dst = ctx->scaled_ws + (size_t)slot[i] * ctx->N;
-    } else if (raw) {                                                         // uint16 frames are converted on the fly by the kernels
-      ctx->frames_host[i].raw = reinterpret_cast<const uint16_t*>(frames[i]); // patched below if it is a host pointer
-      ctx->frames_host[i].raw_scale = depth_scale;
-    }
-  }
-  // host inputs are staged per launch; device inputs are used in place
-  job.host_input = n > 0 && !is_device_ptr(frames[0]);
-  if (job.host_input) {
-    for (int i = 0; i < n; ++i) {
-      const void* staged = raw ? (const void*)(ctx->raw_ws + (size_t)slot[i] * ctx->N) : (const void*)(ctx->depth_ws + (size_t)slot[i] * ctx->N);
-      if (sc.step) ctx->scale_host[i].src = staged;
-      else if (raw) ctx->frames_host[i].raw = (const uint16_t*)staged;
-      else ctx->frames_host[i].depth = (const float*)staged;
-    }
+    ctx->frames_host[i].index = cl->idximg;
+    if (sc.step) { ctx->scale_host[i].src = src; ctx->scale_host[i].dst = scaled; }
+    else if (raw) { ctx->frames_host[i].raw = static_cast<const uint16_t*>(src); ctx->frames_host[i].raw_scale = c.depth_scale; }      // converted on the fly by the kernels
   }
   if (sc.step) HIPCHK(ctx, hipMemcpyAsync(ctx->scale_dev, ctx->scale_host, sizeof(ScaleDesc) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
   if (gs.on && n > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->gauss_dev, ctx->gauss_host, sizeof(SceneBuffers) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
@@ -969,8 +973,7 @@ int convert_stage_frames(pwn_hip_ctx* ctx, const ConvertJob& job, int base, int 
   return PWN_HIP_OK;
 }
 // what convert_prepare relies on, looked at by every caller before it touches a cloud (a refused call leaves the clouds as they were)
-template <typename SRC>
-int check_frames_and_clouds(pwn_hip_ctx* ctx, const SRC* const* frames, pwn_hip_cloud* const* clouds, int n) {
+int check_frames_and_clouds(pwn_hip_ctx* ctx, const void* const* frames, pwn_hip_cloud* const* clouds, int n) {
   for (int i = 0; i < n; ++i) {
     if (!clouds[i] || !frames[i]) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null frame or cloud");
     if (clouds[i]->d.omSym != clouds[0]->d.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds of one convert batch must share one omega storage (exact9 / sym6)");
@@ -1008,73 +1011,98 @@ int convert_finish(pwn_hip_ctx* ctx, ConvertJob& job) {
   return convert_commit(ctx, job);
 }
 
-template <typename SRC>
-int convert_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n,
-                       int rows, int cols, pwn_hip_cloud* const* clouds, int keep_stats, bool want_interval = false, const ScaleSpec& sc = ScaleSpec(),
-                       const GaussSpec& gs = GaussSpec()) {
-  if (!ctx || !p || !frames || !clouds || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  if (int rc = check_image(ctx, rows, cols)) return rc;
-  if (int rc = check_frames_and_clouds(ctx, frames, clouds, n)) return rc;
-  if (int rc = absorb_copies(ctx)) return rc;
-  // A strip waited for its left neighbour longer than the poll bound (~1 s): the neighbour's workgroup was not dispatched in time -- a device
-  // shared with another process's long kernels -- and the planes of this call are invalid.  Nothing is left behind (epoch-tagged words), so
-  // the call is simply made again, once; a second time-out is reported.
-  return repeat_once(ctx, kHandoverTimeout, [&](bool) -> int {
-    ctx->stages.clear();
-    const StreamPlan plan = make_plan(ctx, ctx->sub_frames, n);
-    const int sub = plan.sub;
-    std::vector<int> slot((size_t)std::max(n, 0));
-    for (int i = 0; i < n; ++i) slot[i] = plan.slot0(i / sub) + i % sub;
-    const bool direct = n > 0 && n < kSinglePassMinFrames && n <= sub;
-    ConvertJob job;
-    if (int rc = convert_prepare<SRC>(ctx, p, frames, depth_scale, n, rows, cols, clouds, keep_stats, want_interval, slot, direct, job, sc, gs)) return rc;
-    if (int rc = plan_fork(ctx, plan)) return rc;
-    // Host frames travel on the copy stream, ahead of the kernels: the frames of sub-batch k are copied while sub-batches k-1, k-2 ... are
-    // being converted (with the copies on the sub-batch's own stream the two streams copy at the same time and then compute at the same
-    // time: 7.5 ms per 256 VGA frames against 5).  copied[k] orders convert k after its copies; converted[k] orders the copies into a
-    // staging block after the kernels that read its previous content.
-    const int nsub = (n + sub - 1) / sub;
-    const bool ahead = job.host_input && ctx->copy_stream && plan.dual();
-    if (ahead) {
-      while ((int)ctx->sync_events.size() < 2 * nsub) {
-        hipEvent_t e = nullptr;
-        HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming), PWN_HIP_ERR_ALLOCATION);
-        ctx->sync_events.push_back(e);
-      }
-      HIPCHK(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->fork_ev, 0), PWN_HIP_ERR_LAUNCH);      // after everything queued before this call
+// What the phases of one attempt at a conversion share (on convert_batch_once's stack)
+struct ConvertRun {
+  StreamPlan plan;
+  std::vector<int> slot;                 // workspace slot of every frame
+  bool direct = false;                   // a few frames in one launch (latency path): counts and fault flag arrive in host words, no copy back
+  bool ahead = false;                    // host frames travel on the copy stream, ahead of the kernels
+  ConvertJob job;
+};
+// ---- one attempt at a batch conversion, phase by phase (convert_batch_once calls them in this order) ----
+// Check: what can refuse the call before a cloud is touched.  Once per call, in front of the attempts; on the streams: nothing (queued copies absorbed).
+int convert_check(pwn_hip_ctx* ctx, const ConvertCall& c) {
+  if (!ctx || !c.p || !c.frames || !c.clouds || c.n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (int rc = check_image(ctx, c.rows, c.cols)) return rc;
+  if (int rc = check_frames_and_clouds(ctx, c.frames, c.clouds, c.n)) return rc;
+  return absorb_copies(ctx);
+}
+// Plan and slots.  On the streams: nothing.  Sub-batch k takes the slots of its stream's block, frame by frame.
+void convert_plan_slots(pwn_hip_ctx* ctx, const ConvertCall& c, ConvertRun& run) {
+  ctx->stages.clear();
+  run.plan = make_plan(ctx, ctx->sub_frames, c.n);
+  const int sub = run.plan.sub;
+  run.slot.resize((size_t)std::max(c.n, 0));
+  for (int i = 0; i < c.n; ++i) run.slot[i] = run.plan.slot0(i / sub) + i % sub;
+  run.direct = c.n > 0 && c.n < kSinglePassMinFrames && c.n <= sub;
+}
+// Set the copy-ahead up (prepare has found out whether the frames are host memory).  On the copy stream: the wait for everything queued before this call.
+// Host frames travel on the copy stream, ahead of the kernels: the frames of sub-batch k are copied while sub-batches k-1, k-2 ... are
+// being converted (with the copies on the sub-batch's own stream the two streams copy at the same time and then compute at the same
+// time: 7.5 ms per 256 VGA frames against 5).  copied[k] (sync_events[2 k]) orders convert k after its copies; converted[k]
+// (sync_events[2 k + 1]) orders the copies into a staging block after the kernels that read its previous content.
+int convert_copy_ahead(pwn_hip_ctx* ctx, const ConvertCall& c, ConvertRun& run) {
+  run.ahead = run.job.host_input && ctx->copy_stream && run.plan.dual();
+  if (!run.ahead) return PWN_HIP_OK;
+  const int nsub = (c.n + run.plan.sub - 1) / run.plan.sub;
+  while ((int)ctx->sync_events.size() < 2 * nsub) {
+    hipEvent_t e = nullptr;
+    HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming), PWN_HIP_ERR_ALLOCATION);
+    ctx->sync_events.push_back(e);
+  }
+  HIPCHK(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->fork_ev, 0), PWN_HIP_ERR_LAUNCH);
+  return PWN_HIP_OK;
+}
+// Enqueue sub-batch k, the frames [base, base + m).  On its stream: its kernels, behind its host frames' copies (on the copy stream when they travel ahead).
+int convert_enqueue_sub(pwn_hip_ctx* ctx, const ConvertCall& c, ConvertRun& run, int base, int k) {
+  const ConvertJob& job = run.job;
+  const int m = std::min(run.plan.sub, c.n - base), ns = run.plan.ns;
+  hipStream_t st = run.plan.stream(k);
+  if (job.host_input) {
+    hipStream_t cs = run.ahead ? ctx->copy_stream : st;
+    if (run.ahead && k >= ns) HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->sync_events[2 * (k - ns) + 1], 0), PWN_HIP_ERR_LAUNCH);
+    if (int rc = convert_stage_frames(ctx, job, base, m, cs)) return rc;
+    if (run.ahead) {
+      HIPCHK(ctx, hipEventRecord(ctx->sync_events[2 * k], cs), PWN_HIP_ERR_LAUNCH);
+      HIPCHK(ctx, hipStreamWaitEvent(st, ctx->sync_events[2 * k], 0), PWN_HIP_ERR_LAUNCH);
     }
-    for (int base = 0, k = 0; base < n; base += sub, ++k) {
-      const int m = std::min(sub, n - base);
-      hipStream_t st = plan.stream(k);
-      if (job.host_input) {
-        hipStream_t cs = ahead ? ctx->copy_stream : st;
-        if (ahead && k >= plan.ns) HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->sync_events[2 * (k - plan.ns) + 1], 0), PWN_HIP_ERR_LAUNCH);
-        if (int rc = convert_stage_frames(ctx, job, base, m, cs)) return rc;
-        if (ahead) {
-          HIPCHK(ctx, hipEventRecord(ctx->sync_events[2 * k], cs), PWN_HIP_ERR_LAUNCH);
-          HIPCHK(ctx, hipStreamWaitEvent(st, ctx->sync_events[2 * k], 0), PWN_HIP_ERR_LAUNCH);
-        }
-      }
-      if (int rc = convert_enqueue(ctx, job, base, m, st, direct ? ctx->counts_host + n : nullptr)) return rc;
-      if (ahead) HIPCHK(ctx, hipEventRecord(ctx->sync_events[2 * k + 1], st), PWN_HIP_ERR_LAUNCH);
-    }
-    if (int rc = plan_join(ctx, plan)) return rc;
-    return convert_finish(ctx, job);
-  });
+  }
+  if (int rc = convert_enqueue(ctx, job, base, m, st, run.direct ? ctx->counts_host + c.n : nullptr)) return rc;
+  if (run.ahead) HIPCHK(ctx, hipEventRecord(ctx->sync_events[2 * k + 1], st), PWN_HIP_ERR_LAUNCH);
+  return PWN_HIP_OK;
+}
+// One attempt at the call.  Prepare leaves the descriptor uploads on ctx->stream and the clouds replaced (the job withdraws them unless it
+// commits); after the join everything is on ctx->stream again, and finish waits for it and commits.
+int convert_batch_once(pwn_hip_ctx* ctx, const ConvertCall& call) {
+  ConvertRun run;
+  convert_plan_slots(ctx, call, run);
+  if (int rc = convert_prepare(ctx, call, run.slot, run.direct, run.job)) return rc;
+  if (int rc = plan_fork(ctx, run.plan)) return rc;
+  if (int rc = convert_copy_ahead(ctx, call, run)) return rc;
+  for (int base = 0, k = 0; base < call.n; base += run.plan.sub, ++k) { if (int rc = convert_enqueue_sub(ctx, call, run, base, k)) return rc; }
+  if (int rc = plan_join(ctx, run.plan)) return rc;
+  return convert_finish(ctx, run.job);
+}
+// The call; and once more after a hand-over time-out.  A strip waited for its left neighbour longer than the poll bound (~1 s): the neighbour's
+// workgroup was not dispatched in time -- a device shared with another process's long kernels -- and the planes of this call are invalid.
+// Nothing is left behind (epoch-tagged words), so the call is simply made again, once; a second time-out is reported.
+int convert_batch_impl(pwn_hip_ctx* ctx, const ConvertCall& call) {
+  if (int rc = convert_check(ctx, call)) return rc;
+  return repeat_once(ctx, kHandoverTimeout, [&](bool) { return convert_batch_once(ctx, call); });
 }
 
 // pwn_hip_debug_front_end: one launch of launch_front_end over n frames prepared as a convert call prepares them (frame i in workspace slot i),
 // and what it wrote copied back per frame.  No stats pass, no repeat after a time-out.
-template <typename SRC>
-int debug_front_end_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n, int rows, int cols,
-                         bool single_pass, int lean, pwn_hip_cloud* const* clouds, float* integral_out, int* index_out, int* interval_out, int* rowoff_out) {
-  if (int rc = check_frames_and_clouds(ctx, frames, clouds, n)) return rc;
+int debug_front_end_impl(pwn_hip_ctx* ctx, const ConvertCall& call, bool single_pass, int lean, float* integral_out, int* index_out, int* interval_out,
+                         int* rowoff_out) {
+  const int n = call.n, rows = call.rows, cols = call.cols; pwn_hip_cloud* const* clouds = call.clouds;
+  if (int rc = check_frames_and_clouds(ctx, call.frames, clouds, n)) return rc;
   ctx->stages.clear();
   std::vector<int> slot((size_t)n);
   for (int i = 0; i < n; ++i) slot[i] = i;
-  const bool direct = !single_pass && n < kSinglePassMinFrames;      // as convert_batch_impl decides for a call of n frames in one launch
+  const bool direct = !single_pass && n < kSinglePassMinFrames;      // as convert_plan_slots decides for a call of n frames in one launch
   ConvertJob job;
-  if (int rc = convert_prepare<SRC>(ctx, p, frames, depth_scale, n, rows, cols, clouds, 0, lean == 0, slot, direct, job)) return rc;
+  if (int rc = convert_prepare(ctx, call, slot, direct, job)) return rc;
   if (job.host_input) { if (int rc = convert_stage_frames(ctx, job, 0, n, ctx->stream)) return rc; }
   if (lean == PWN_HIP_FRONT_END_LEAN_PLANES) job.cp.lean = 1;      // ten planes; PWN_HIP_FRONT_END_LEAN_GROUPED keeps convert_prepare's kLeanGrouped and
                                                                    // integral_out receives the slot as stored (three arrays of records, ig_at)
@@ -1101,21 +1129,18 @@ int debug_front_end_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, co
   return counts_check(ctx, clouds, n);
 }
 
-// DepthImage_scale of n equal-sized frames: chunks of at most max_batch frames, one box launch each; host sources are staged in the slots'
-// source-size workspaces, host destinations leave through the slots' scaled frames.  dst == nullptr (check_scaled_capacities): the images stay
-// in the slots and only valid[i], the pixels of image i inside [min_d, max_d], comes back.
-template <typename SRC>
-int depth_scale_batch_impl(pwn_hip_ctx* ctx, const SRC* const* src, float depth_scale, int n, int rows, int cols, int step, float max_depth_cov,
-                           float* const* dst, float min_d = 0.f, float max_d = 0.f, int* valid = nullptr) {
-  if (!ctx || !src || (!dst && !valid) || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  ScaleSpec sc;
-  if (int rc = make_scale_spec(ctx, rows, cols, step, max_depth_cov, sc)) return rc;
+// DepthImage_scale of the call's n equal-sized frames (frames, raw, depth_scale, n and scale of `c`; its rows, cols and clouds are not looked at):
+// chunks of at most max_batch frames, one box launch each; host sources are staged in the slots' source-size workspaces, host destinations leave
+// through the slots' scaled frames.  dst == nullptr (check_scaled_capacities): the images stay in the slots and only valid[i], the pixels of
+// image i inside the converter's [min_distance, max_distance], comes back.
+int depth_scale_batch_impl(pwn_hip_ctx* ctx, const ConvertCall& c, float* const* dst, int* valid = nullptr) {
+  const void* const* src = c.frames; const int n = c.n; const bool raw = c.raw; const ScaleSpec& sc = c.scale;
   for (int i = 0; i < n; ++i) if (!src[i] || (dst && !dst[i])) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null frame");
   if (int rc = absorb_copies(ctx)) return rc;
   if (int rc = ensure_scale(ctx, std::min(n, ctx->max_batch))) return rc;
   ctx->stages.clear();
-  const bool raw = std::is_same<SRC, uint16_t>::value;
-  const size_t sbytes = (size_t)rows * cols * sizeof(SRC), obytes = (size_t)sc.orows * sc.ocols * sizeof(float);
+  const float min_d = valid ? c.p->min_distance : 0.f, max_d = valid ? c.p->max_distance : 0.f;
+  const size_t sbytes = (size_t)sc.srows * sc.scols * (raw ? sizeof(uint16_t) : sizeof(float)), obytes = (size_t)sc.orows * sc.ocols * sizeof(float);
   for (int base = 0; base < n; base += ctx->max_batch) {
     const int m = std::min(ctx->max_batch, n - base);
     for (int j = 0; j < m; ++j) {
@@ -1129,7 +1154,7 @@ int depth_scale_batch_impl(pwn_hip_ctx* ctx, const SRC* const* src, float depth_
       if (!is_device_ptr(d.dst)) d.dst = ctx->scaled_ws + (size_t)j * ctx->N;
     }
     HIPCHK(ctx, hipMemcpyAsync(ctx->scale_dev, ctx->scale_host, sizeof(ScaleDesc) * m, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
-    if (int rc = launch_depth_scale(ctx, sc, raw, depth_scale, 0, m, ctx->stream)) return rc;
+    if (int rc = launch_depth_scale(ctx, sc, raw, c.depth_scale, 0, m, ctx->stream)) return rc;
     for (int j = 0; j < m && dst; ++j)
       if (ctx->scale_host[j].dst != dst[base + j]) HIPCHK(ctx, hipMemcpyAsync(dst[base + j], ctx->scale_host[j].dst, obytes, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
     if (valid) {
@@ -1149,31 +1174,29 @@ int depth_scale_batch_impl(pwn_hip_ctx* ctx, const SRC* const* src, float depth_
 // A cloud too small for its frame's valid pixels is otherwise found when the kernels have written into it.  The *_scaled calls refuse before they
 // touch a cloud: where a cloud holds fewer points than the scaled image has pixels, the frames are down-sampled and counted first (a pass of its
 // own, only then).
-template <typename SRC>
-int check_scaled_capacities(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n, const ScaleSpec& sc,
-                            pwn_hip_cloud* const* clouds) {
+int check_scaled_capacities(pwn_hip_ctx* ctx, const ConvertCall& c) {
+  const ScaleSpec& sc = c.scale;
   bool tight = false;
-  for (int i = 0; i < n; ++i) tight = tight || (size_t)clouds[i]->d.capacity < (size_t)sc.orows * sc.ocols;
+  for (int i = 0; i < c.n; ++i) tight = tight || (size_t)c.clouds[i]->d.capacity < (size_t)sc.orows * sc.ocols;
   if (!tight) return PWN_HIP_OK;
-  std::vector<int> valid((size_t)n);
-  if (int rc = depth_scale_batch_impl<SRC>(ctx, frames, depth_scale, n, sc.srows, sc.scols, sc.step, sc.maxCov, nullptr, p->min_distance, p->max_distance, valid.data()))
-    return rc;
-  for (int i = 0; i < n; ++i)
-    if (valid[i] > clouds[i]->d.capacity) return fail(ctx, PWN_HIP_ERR_CAPACITY, "cloud capacity smaller than the number of valid depth pixels");
+  std::vector<int> valid((size_t)c.n);
+  if (int rc = depth_scale_batch_impl(ctx, c, nullptr, valid.data())) return rc;
+  for (int i = 0; i < c.n; ++i)
+    if (valid[i] > c.clouds[i]->d.capacity) return fail(ctx, PWN_HIP_ERR_CAPACITY, "cloud capacity smaller than the number of valid depth pixels");
   return PWN_HIP_OK;
 }
-// n x makeCloud's data path (DepthImage_scale, then the conversion of the small image) inside the batch plan.  Everything that can refuse the
-// call is looked at before a cloud is touched.
-template <typename SRC>
-int convert_batch_scaled_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const SRC* const* frames, float depth_scale, int n, int rows, int cols,
-                                     int step, float max_depth_cov, pwn_hip_cloud* const* clouds, int keep_stats = 0, const GaussSpec& gs = GaussSpec()) {
-  if (!ctx || !p || !frames || !clouds || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  ScaleSpec sc;
-  if (int rc = make_scale_spec(ctx, rows, cols, step, max_depth_cov, sc)) return rc;
-  if (int rc = check_frames_and_clouds(ctx, frames, clouds, n)) return rc;
-  if (int rc = check_scaled_capacities<SRC>(ctx, p, frames, depth_scale, n, sc, clouds)) return rc;
-  if (int rc = ensure_scale(ctx, n)) return rc;
-  return convert_batch_impl<SRC>(ctx, p, frames, depth_scale, n, sc.orows, sc.ocols, clouds, keep_stats, false, sc, gs);
+// n x makeCloud's data path (DepthImage_scale, then the conversion of the small image) inside the batch plan: the extra checks in front of
+// convert_batch_impl.  `src` carries the size of the frames as the caller holds them; everything that can refuse the call is looked at before a
+// cloud is touched.
+int convert_batch_scaled_impl(pwn_hip_ctx* ctx, const ConvertCall& src, int step, float max_depth_cov) {
+  if (!ctx || !src.p || !src.frames || !src.clouds || src.n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  ConvertCall call = src;
+  if (int rc = make_scale_spec(ctx, src.rows, src.cols, step, max_depth_cov, call.scale)) return rc;
+  call.rows = call.scale.orows; call.cols = call.scale.ocols;
+  if (int rc = check_frames_and_clouds(ctx, call.frames, call.clouds, call.n)) return rc;
+  if (int rc = check_scaled_capacities(ctx, call)) return rc;
+  if (int rc = ensure_scale(ctx, call.n)) return rc;
+  return convert_batch_impl(ctx, call);
 }
 
 // pwn_hip_debug_stats_from_integral and its lean form (`frames` given): the stats pass, launched as launch_convert launches it, on windows the
@@ -1565,12 +1588,9 @@ int pwn_hip_debug_front_end(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p,
   if (depth_scale < 0.f) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "negative depth scale");
   if (int rc = check_image(ctx, rows, cols)) return rc;
   if (int rc = absorb_copies(ctx)) return rc;
-  const bool single = path == PWN_HIP_FRONT_END_SINGLE_PASS;
-  if (depth_scale > 0.f)
-    return debug_front_end_impl<uint16_t>(ctx, p, reinterpret_cast<const uint16_t* const*>(frames), depth_scale, nframes, rows, cols, single, lean, clouds,
-                                          integral_out, index_out, interval_out, rowoff_out);
-  return debug_front_end_impl<float>(ctx, p, reinterpret_cast<const float* const*>(frames), 0.f, nframes, rows, cols, single, lean, clouds,
-                                     integral_out, index_out, interval_out, rowoff_out);
+  ConvertCall call; call.p = p; call.n = nframes; call.rows = rows; call.cols = cols; call.clouds = clouds;
+  call.frames = frames; call.raw = depth_scale > 0.f; call.depth_scale = depth_scale; call.want_interval = lean == 0;
+  return debug_front_end_impl(ctx, call, path == PWN_HIP_FRONT_END_SINGLE_PASS, lean, integral_out, index_out, interval_out, rowoff_out);
 }
 __global__ void __launch_bounds__(256) k_debug_trig(int n, const float* __restrict__ y, const float* __restrict__ x, float* __restrict__ theta,
                                                     float* __restrict__ c, float* __restrict__ s) {
@@ -1972,12 +1992,18 @@ int pwn_hip_depth_scale(pwn_hip_ctx* ctx, const float* src, int rows, int cols, 
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
 }
+// the two typed forms' argument checks, then the frames of `c` down-sampled into dst
+static int depth_scale_batch_checked(pwn_hip_ctx* ctx, ConvertCall c, int step, float max_depth_cov, float* const* dst) {
+  if (!ctx || !c.frames || !dst || c.n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (int rc = make_scale_spec(ctx, c.rows, c.cols, step, max_depth_cov, c.scale)) return rc;
+  return depth_scale_batch_impl(ctx, c, dst);
+}
 int pwn_hip_depth_scale_batch(pwn_hip_ctx* ctx, const float* const* src, int n, int rows, int cols, int step, float max_depth_cov, float* const* dst) {
-  return depth_scale_batch_impl<float>(ctx, src, 0.f, n, rows, cols, step, max_depth_cov, dst);
+  return depth_scale_batch_checked(ctx, convert_call(nullptr, src, 0.f, n, rows, cols, nullptr), step, max_depth_cov, dst);
 }
 int pwn_hip_depth_scale_batch_u16(pwn_hip_ctx* ctx, const uint16_t* const* src, float depth_scale, int n, int rows, int cols, int step, float max_depth_cov,
                                   float* const* dst) {
-  return depth_scale_batch_impl<uint16_t>(ctx, src, depth_scale, n, rows, cols, step, max_depth_cov, dst);
+  return depth_scale_batch_checked(ctx, convert_call(nullptr, src, depth_scale, n, rows, cols, nullptr), step, max_depth_cov, dst);
 }
 
 // ---------------------------------------------------------------------------------------------- converter stages
@@ -2049,7 +2075,9 @@ int pwn_hip_convert(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const f
                     int* index_image, int* interval_image, int keep_stats) {
   const float* frames[1] = { depth };
   pwn_hip_cloud* clouds[1] = { cloud };
-  if (int rc = convert_batch_impl<float>(ctx, p, frames, 0.f, 1, rows, cols, clouds, keep_stats, interval_image != nullptr)) return rc;
+  ConvertCall call = convert_call(p, frames, 0.f, 1, rows, cols, clouds);
+  call.keep_stats = keep_stats; call.want_interval = interval_image != nullptr;
+  if (int rc = convert_batch_impl(ctx, call)) return rc;
   const size_t N = (size_t)rows * cols;
   if (index_image) HIPCHK(ctx, hipMemcpy(index_image, ctx->frames_host[0].index, N * 4, hipMemcpyDefault), PWN_HIP_ERR_COPY);
   if (interval_image) HIPCHK(ctx, hipMemcpy(interval_image, ctx->frames_host[0].interval, N * 4, hipMemcpyDefault), PWN_HIP_ERR_COPY);
@@ -2061,16 +2089,15 @@ int pwn_hip_convert_scaled(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, 
   if (int rc = check_image(ctx, rows, cols)) return rc;
   const int orows = rows / step, ocols = cols / step;
   if (orows <= 0 || ocols <= 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "scaled image has zero size");
-  if (int rc = absorb_copies(ctx)) return rc;
-  const size_t n = (size_t)rows * cols, on = (size_t)orows * ocols;
-  const float* src = depth;
-  if (!is_device_ptr(depth)) { HIPCHK(ctx, hipMemcpyAsync(ctx->depth_ws, depth, n * 4, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY); src = ctx->depth_ws; }
+  const size_t on = (size_t)orows * ocols;
+  const float* src = nullptr;
+  if (int rc = stage_depth(ctx, depth, (size_t)rows * cols, &src)) return rc;
   float* scaled = ctx->io_ws;                                        // device scratch (N*16 floats)
   hipLaunchKernelGGL(k_depth_scale, dim3((unsigned)((on + 255) / 256)), dim3(256), 0, ctx->stream, src, rows, cols, step, max_depth_cov, scaled);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   const float* frames[1] = { scaled };
   pwn_hip_cloud* clouds[1] = { cloud };
-  return convert_batch_impl<float>(ctx, p, frames, 0.f, 1, orows, ocols, clouds, 0);
+  return convert_batch_impl(ctx, convert_call(p, frames, 0.f, 1, orows, ocols, clouds));
 }
 static void async_convert_loop(AsyncConvert* a, int device) {
   (void)hipSetDevice(device);
@@ -2083,7 +2110,7 @@ static void async_convert_loop(AsyncConvert* a, int device) {
     int rc;
     if (a->raw) {
       const uint16_t* frames[1] = { a->raw }; pwn_hip_cloud* clouds[1] = { a->cloud };
-      rc = convert_batch_impl<uint16_t>(a->job_ctx, &a->p, frames, a->raw_scale, 1, a->rows, a->cols, clouds, 0);
+      rc = convert_batch_impl(a->job_ctx, convert_call(&a->p, frames, a->raw_scale, 1, a->rows, a->cols, clouds));
     } else {
       rc = pwn_hip_convert_scaled(a->job_ctx, &a->p, a->depth, a->rows, a->cols, a->step, a->max_depth_cov, a->cloud);
     }
@@ -2174,19 +2201,19 @@ int pwn_hip_convert_end(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud) {
 }
 int pwn_hip_convert_batch(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const float* const* depth_frames, int n, int rows, int cols,
                           pwn_hip_cloud* const* clouds) {
-  return convert_batch_impl<float>(ctx, p, depth_frames, 0.f, n, rows, cols, clouds, 0);
+  return convert_batch_impl(ctx, convert_call(p, depth_frames, 0.f, n, rows, cols, clouds));
 }
 int pwn_hip_convert_batch_scaled(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const float* const* depth_frames, int n, int rows, int cols, int step,
                                  float max_depth_cov, pwn_hip_cloud* const* clouds) {
-  return convert_batch_scaled_impl<float>(ctx, p, depth_frames, 0.f, n, rows, cols, step, max_depth_cov, clouds);
+  return convert_batch_scaled_impl(ctx, convert_call(p, depth_frames, 0.f, n, rows, cols, clouds), step, max_depth_cov);
 }
 int pwn_hip_convert_batch_u16_scaled(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const uint16_t* const* raw_frames, float depth_scale, int n,
                                      int rows, int cols, int step, float max_depth_cov, pwn_hip_cloud* const* clouds) {
-  return convert_batch_scaled_impl<uint16_t>(ctx, p, raw_frames, depth_scale, n, rows, cols, step, max_depth_cov, clouds);
+  return convert_batch_scaled_impl(ctx, convert_call(p, raw_frames, depth_scale, n, rows, cols, clouds), step, max_depth_cov);
 }
 int pwn_hip_convert_batch_u16(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const uint16_t* const* raw_frames, float depth_scale, int n,
                               int rows, int cols, pwn_hip_cloud* const* clouds) {
-  return convert_batch_impl<uint16_t>(ctx, p, raw_frames, depth_scale, n, rows, cols, clouds, 0);
+  return convert_batch_impl(ctx, convert_call(p, raw_frames, depth_scale, n, rows, cols, clouds));
 }
 void pwn_hip_default_convert_extras(pwn_hip_convert_extras* e) {
   if (!e) return;
@@ -2198,27 +2225,21 @@ int pwn_hip_convert_batch_ex(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p
                              int cols, int step, float max_depth_cov, const pwn_hip_convert_extras* extras, pwn_hip_cloud* const* clouds) {
   if (!ctx || !p || !frames || !clouds || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (step < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "DepthImage_scale: step < 0");
-  int keep_stats = 0;
-  GaussSpec gs;
+  ConvertCall call; call.p = p; call.n = n; call.rows = rows; call.cols = cols; call.clouds = clouds;
+  call.frames = frames; call.raw = raw_u16 != 0; call.depth_scale = call.raw ? depth_scale : 0.f;
   if (extras) {
+    GaussSpec& gs = call.gauss;
     if ((extras->keep_stats != 0 && extras->keep_stats != 1) || (extras->gaussians != 0 && extras->gaussians != 1))
       return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "convert extras: keep_stats and gaussians must be 0 or 1");
     if (!std::isfinite(extras->baseline) || !std::isfinite(extras->alpha)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "convert extras: baseline or alpha is not finite");
-    keep_stats = extras->keep_stats;
+    call.keep_stats = extras->keep_stats;
     if (extras->gaussians) {
       Mat4 KRt, iKRt;
       projector_matrices(mat3_from(p->K), mat4_identity(), KRt, iKRt, gs.iK);
       gs.on = true; gs.fB = extras->baseline * p->K[0]; gs.alpha = extras->alpha;
     }
   }
-  const uint16_t* const* raw = reinterpret_cast<const uint16_t* const*>(frames);
-  const float* const* flt = reinterpret_cast<const float* const*>(frames);
-  if (step == 0) {
-    if (raw_u16) return convert_batch_impl<uint16_t>(ctx, p, raw, depth_scale, n, rows, cols, clouds, keep_stats, false, ScaleSpec(), gs);
-    return convert_batch_impl<float>(ctx, p, flt, 0.f, n, rows, cols, clouds, keep_stats, false, ScaleSpec(), gs);
-  }
-  if (raw_u16) return convert_batch_scaled_impl<uint16_t>(ctx, p, raw, depth_scale, n, rows, cols, step, max_depth_cov, clouds, keep_stats, gs);
-  return convert_batch_scaled_impl<float>(ctx, p, flt, 0.f, n, rows, cols, step, max_depth_cov, clouds, keep_stats, gs);
+  return step == 0 ? convert_batch_impl(ctx, call) : convert_batch_scaled_impl(ctx, call, step, max_depth_cov);
 }
 
 // ------------------------------------------------------------------------------------------------ aligner stages
@@ -2417,7 +2438,7 @@ struct AlignHooks {
 };
 // The resident full-resolution uint16 frames the current clouds of a call are converted from in front of their alignment, with that conversion's
 // parameters: a sub-batch whose pairs all take the current cloud's own index image runs the fused pass on them (CurDepthSrc)
-struct CurDepthFrames { const uint16_t* const* frames; float scale; const ConvertParams* cp; };
+struct CurDepthFrames { const void* const* frames; float scale; const ConvertParams* cp; };
 // What a caller asks of a batch alignment; every member defaults to "not asked for", an entry point names the ones it uses.
 struct AlignCall {
   const pwn_hip_aligner_params* p = nullptr;
@@ -2551,7 +2572,7 @@ static int align_describe_pairs(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& 
     HIPCHK(ctx, hipMemcpyAsync(ctx->pairs_dev, ctx->pairs_host, sizeof(PairDesc) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
     HIPCHK(ctx, hipMemcpyAsync(ctx->state_ws, ctx->state_host, sizeof(PairState) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
     if (c.cur_depth && run.any_own) {
-      for (int i = 0; i < n; ++i) ctx->cur_raw_host[i] = c.cur_depth->frames[i];
+      for (int i = 0; i < n; ++i) ctx->cur_raw_host[i] = static_cast<const uint16_t*>(c.cur_depth->frames[i]);
       HIPCHK(ctx, hipMemcpyAsync(ctx->cur_raw_dev, ctx->cur_raw_host, sizeof(const uint16_t*) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
     }
     if (run.want_scores) HIPCHK(ctx, hipMemsetAsync(ctx->match_dev, 0, sizeof(MatchAcc) * n, ctx->stream), PWN_HIP_ERR_COPY);
@@ -2868,19 +2889,19 @@ int pwn_hip_match_batch_records(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* 
   call.scores = scores; call.match_threshold = threshold; call.records = records; call.match_records = true; call.pair_ids = pair_ids; call.first_pair_id = first_pair_id;
   return align_batch_impl(ctx, call);
 }
-// the one-submission step; sc.step != 0: every frame is down-sampled in front of its conversion (rows, cols: the size that is converted and aligned)
-static int convert_align_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* cp, const pwn_hip_aligner_params* ap, int n,
-                                    const uint16_t* const* ref_frames, const uint16_t* const* cur_frames, float depth_scale, int rows, int cols,
-                                    pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs, const float* guesses, const int* pair_ids, int first_pair_id,
-                                    pwn_hip_align_result* results, float* records, const ScaleSpec& sc) {
+// The one-submission step: the reference frames (`ref`) and the current frames (`cur`, the same request but for frames and clouds) converted in
+// front of the alignment `align` asks for, whose pairs are their clouds.  scale.step != 0: every frame is down-sampled in front of its
+// conversion (rows, cols: the size that is converted and aligned)
+static int convert_align_batch_impl(pwn_hip_ctx* ctx, const ConvertCall& ref, const ConvertCall& cur, const AlignCall& align) {
+  const int n = align.n, rows = ref.rows, cols = ref.cols;
   if (int rc = check_image(ctx, rows, cols)) return rc;
-  if (ap->rows != rows || ap->cols != cols) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "aligner image size differs from the frames'");
+  if (align.p->rows != rows || align.p->cols != cols) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "aligner image size differs from the frames'");
   // the clouds' host-side sizes are those of their PREVIOUS content while the step is being queued: bound what the conversion can produce instead
   if ((size_t)rows * cols > (size_t)kMaxAlignerPoints)
     return fail(ctx, PWN_HIP_ERR_CAPACITY, "Aligner::align: frames of more than 2^21 pixels (index field of the aligner's z-buffer word)");
   {   // sub-batches run on different streams: a cloud that appears twice would be written by two of them at once
     std::vector<const pwn_hip_cloud*> all; all.reserve((size_t)2 * std::max(n, 0));
-    for (int i = 0; i < n; ++i) { all.push_back(refs[i]); all.push_back(curs[i]); }
+    for (int i = 0; i < n; ++i) { all.push_back(align.refs[i]); all.push_back(align.curs[i]); }
     std::sort(all.begin(), all.end());
     if (std::adjacent_find(all.begin(), all.end()) != all.end()) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "the 2 n clouds of a step must be distinct");
   }
@@ -2894,19 +2915,21 @@ static int convert_align_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_pa
     const StreamPlan plan = make_plan(ctx, ctx->sub_pairs, n);
     const int sub = plan.sub;
     const int fslots = std::max(1, std::min(ctx->sub_frames, ctx->max_batch / plan.ns));
-    std::vector<const uint16_t*> frames((size_t)2 * std::max(n, 0));
+    std::vector<const void*> frames((size_t)2 * std::max(n, 0));
     std::vector<pwn_hip_cloud*> clouds((size_t)2 * std::max(n, 0));
     std::vector<int> slot((size_t)2 * std::max(n, 0));
     for (int base = 0, k = 0; base < n; base += sub, ++k) {
       const int m = std::min(sub, n - base);
       for (int j = 0; j < m; ++j) {
-        frames[2 * base + j] = ref_frames[base + j]; clouds[2 * base + j] = refs[base + j];
-        frames[2 * base + m + j] = cur_frames[base + j]; clouds[2 * base + m + j] = curs[base + j];
+        frames[2 * base + j] = ref.frames[base + j]; clouds[2 * base + j] = ref.clouds[base + j];
+        frames[2 * base + m + j] = cur.frames[base + j]; clouds[2 * base + m + j] = cur.clouds[base + j];
       }
       for (int f = 0; f < 2 * m; ++f) slot[2 * base + f] = (k % plan.ns) * fslots + f % fslots;
     }
+    ConvertCall both = ref;                // one job for the 2 n frames, in the order they are converted
+    both.n = 2 * n; both.frames = frames.data(); both.clouds = clouds.data();
     ConvertJob job;
-    if (int rc = convert_prepare<uint16_t>(ctx, cp, frames.data(), depth_scale, 2 * n, rows, cols, clouds.data(), 0, false, slot, false, job, sc)) return rc;
+    if (int rc = convert_prepare(ctx, both, slot, false, job)) return rc;
     AlignHooks hooks;
     hooks.pre_sub = [&](int base, int m, int, hipStream_t st) -> int {
       for (int f = 0; f < 2 * m; f += fslots) {
@@ -2918,21 +2941,21 @@ static int convert_align_batch_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_pa
     };
     hooks.before_sync = [&]() -> int { return counts_enqueue(ctx, 2 * n); };
     hooks.after_sync = [&]() -> int { return convert_commit(ctx, job); };
-    AlignCall call = align_call(ap, n, refs, curs, guesses, results);
-    call.hooks = &hooks; call.records = records; call.pair_ids = pair_ids; call.first_pair_id = first_pair_id;
+    AlignCall call = align;
+    call.hooks = &hooks;
     // the current frames as a depth source: the caller's own resident frames only -- a staged host frame or a down-sampled one lives in a workspace
     // slot that the next launch of conversions reuses
-    const CurDepthFrames cur_depth = { cur_frames, depth_scale, &job.cp };
-    if (job.raw && !job.host_input && !sc.step) call.cur_depth = &cur_depth;
+    const CurDepthFrames cur_depth = { cur.frames, cur.depth_scale, &job.cp };
+    if (job.raw && !job.host_input && !both.scale.step) call.cur_depth = &cur_depth;
     return align_batch_impl(ctx, call);
   });
 }
 // what the step's conversions rely on (check_frames_and_clouds, for the 2 n frames and clouds), before a cloud is touched
-static int check_step_clouds(pwn_hip_ctx* ctx, const uint16_t* const* ref_frames, const uint16_t* const* cur_frames, pwn_hip_cloud* const* refs,
-                             pwn_hip_cloud* const* curs, int n) {
-  if (int rc = check_frames_and_clouds(ctx, ref_frames, refs, n)) return rc;
-  if (int rc = check_frames_and_clouds(ctx, cur_frames, curs, n)) return rc;
-  if (n > 0 && refs[0]->d.omSym != curs[0]->d.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds of one convert batch must share one omega storage (exact9 / sym6)");
+static int check_step_clouds(pwn_hip_ctx* ctx, const ConvertCall& ref, const ConvertCall& cur) {
+  if (int rc = check_frames_and_clouds(ctx, ref.frames, ref.clouds, ref.n)) return rc;
+  if (int rc = check_frames_and_clouds(ctx, cur.frames, cur.clouds, cur.n)) return rc;
+  if (ref.n > 0 && ref.clouds[0]->d.omSym != cur.clouds[0]->d.omSym)
+    return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds of one convert batch must share one omega storage (exact9 / sym6)");
   return PWN_HIP_OK;
 }
 int pwn_hip_convert_align_batch_u16(pwn_hip_ctx* ctx, const pwn_hip_converter_params* cp, const pwn_hip_aligner_params* ap, int n,
@@ -2940,9 +2963,11 @@ int pwn_hip_convert_align_batch_u16(pwn_hip_ctx* ctx, const pwn_hip_converter_pa
                                     pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs, const float* guesses, const int* pair_ids, int first_pair_id,
                                     pwn_hip_align_result* results, float* records) {
   if (!ctx || !cp || !ap || !ref_frames || !cur_frames || !refs || !curs || (!results && !records) || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  if (int rc = check_step_clouds(ctx, ref_frames, cur_frames, refs, curs, n)) return rc;
-  return convert_align_batch_impl(ctx, cp, ap, n, ref_frames, cur_frames, depth_scale, rows, cols, refs, curs, guesses, pair_ids, first_pair_id, results, records,
-                                  ScaleSpec());
+  const ConvertCall ref = convert_call(cp, ref_frames, depth_scale, n, rows, cols, refs), cur = convert_call(cp, cur_frames, depth_scale, n, rows, cols, curs);
+  if (int rc = check_step_clouds(ctx, ref, cur)) return rc;
+  AlignCall call = align_call(ap, n, refs, curs, guesses, results);
+  call.records = records; call.pair_ids = pair_ids; call.first_pair_id = first_pair_id;
+  return convert_align_batch_impl(ctx, ref, cur, call);
 }
 int pwn_hip_convert_align_batch_u16_scaled(pwn_hip_ctx* ctx, const pwn_hip_converter_params* cp, const pwn_hip_aligner_params* ap, int n,
                                            const uint16_t* const* ref_frames, const uint16_t* const* cur_frames, float depth_scale, int rows, int cols,
@@ -2951,12 +2976,15 @@ int pwn_hip_convert_align_batch_u16_scaled(pwn_hip_ctx* ctx, const pwn_hip_conve
   if (!ctx || !cp || !ap || !ref_frames || !cur_frames || !refs || !curs || (!results && !records) || n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   ScaleSpec sc;
   if (int rc = make_scale_spec(ctx, rows, cols, step, max_depth_cov, sc)) return rc;
-  if (int rc = check_step_clouds(ctx, ref_frames, cur_frames, refs, curs, n)) return rc;
-  if (int rc = check_scaled_capacities<uint16_t>(ctx, cp, ref_frames, depth_scale, n, sc, refs)) return rc;
-  if (int rc = check_scaled_capacities<uint16_t>(ctx, cp, cur_frames, depth_scale, n, sc, curs)) return rc;
+  ConvertCall ref = convert_call(cp, ref_frames, depth_scale, n, sc.orows, sc.ocols, refs), cur = convert_call(cp, cur_frames, depth_scale, n, sc.orows, sc.ocols, curs);
+  ref.scale = cur.scale = sc;
+  if (int rc = check_step_clouds(ctx, ref, cur)) return rc;
+  if (int rc = check_scaled_capacities(ctx, ref)) return rc;
+  if (int rc = check_scaled_capacities(ctx, cur)) return rc;
   if (int rc = ensure_scale(ctx, 2 * n)) return rc;
-  return convert_align_batch_impl(ctx, cp, ap, n, ref_frames, cur_frames, depth_scale, sc.orows, sc.ocols, refs, curs, guesses, pair_ids, first_pair_id, results,
-                                  records, sc);
+  AlignCall call = align_call(ap, n, refs, curs, guesses, results);
+  call.records = records; call.pair_ids = pair_ids; call.first_pair_id = first_pair_id;
+  return convert_align_batch_impl(ctx, ref, cur, call);
 }
 int pwn_hip_ctx_set_convergence(pwn_hip_ctx* ctx, const pwn_hip_convergence* s) {
   if (!ctx) return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, "null ctx");
