@@ -152,6 +152,7 @@ PROTOTYPES = {
     "pwn_hip_match_score": (_I, [_VP, _F, _VP]),
     "pwn_hip_match_batch": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _F, _VP, _VP]),
     "pwn_hip_match_batch_records": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _F, _VP, _I, _VP, _VP, _VP]),
+    "pwn_hip_closure_batch_records": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _F, _VP, _I, _VP, _VP, _VP, _VP]),
     "pwn_hip_projector_matrices": (None, [_VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_project_point": (_I, [_VP, _VP, _F, _F, _VP, C.POINTER(_I), C.POINTER(_I), C.POINTER(_F)]),
     "pwn_hip_unproject_pixel": (_I, [_VP, _VP, _F, _F, _I, _I, _F, _VP]),
@@ -184,6 +185,7 @@ PROTOTYPES = {
     "pwn_hip_debug_stats_from_integral_lean": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _F, _VP, _I]),
     "pwn_hip_debug_front_end": (_I, [_VP, _VP, _VP, _F, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_debug_trig_eval": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP]),
+    "pwn_hip_debug_statistics_eval": (_I, [_VP, _I, _VP, _VP, _VP]),
     "pwn_hip_debug_cloud_set_gaussians": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_debug_cloud_expose_gaussians": (_I, [_VP, _VP, _I]),
     "pwn_hip_debug_set_manifold_chunk": (_I, [_VP, _I]),

@@ -198,6 +198,7 @@ assert ALIGN_RESULT_DTYPE.itemsize == C.sizeof(AlignResult)
 OMEGA_STORAGE = {"exact9": 0, "sym6": 1}      # PWN_HIP_OMEGA_EXACT9 / PWN_HIP_OMEGA_SYM6
 RECORD_FLOATS = 64                            # PWN_HIP_RECORD_FLOATS
 MATCH_RECORD_FLOATS = 72                      # PWN_HIP_MATCH_RECORD_FLOATS
+CLOSURE_RECORD_FLOATS = 128                   # PWN_HIP_CLOSURE_RECORD_FLOATS
 
 
 def device_count() -> int:
@@ -1340,6 +1341,36 @@ class PwnMatcherBase:
         a.ctx.check(a.ctx._L.pwn_hip_match_batch_records(a.ctx.h, C.byref(p), n, refs, curs, _ptr(g), self._frameInlierDepthThreshold, _ptr(ids),
                                                          int(first_pair_id), res, sc, _ptr(records)))
         return (np.frombuffer(res, dtype=ALIGN_RESULT_DTYPE, count=n), sc) if want_results else None
+
+    def matchCloudsBatchClosureRecords(self, fromClouds, toClouds, fromOffset, toOffset, toCameraMatrix, toRows, toCols, records, initialGuesses=None,
+                                       pair_ids=None, first_pair_id=0, want_results=True, want_statistics=False, prepared=None):
+        """matchCloudsBatchRecords whose records also carry Aligner::omega() -- MatcherResult::informationMatrix as pwn_tracker2 sets it
+        (pwn_matcher_base.cpp:158-163) -- computed on the device (pwn_hip_closure_batch_records).  records: float32 [n, CLOSURE_RECORD_FLOATS]
+        CUDA tensor or numpy array.  Returns (align results as a structured array, scores, statistics or None) or None."""
+        a = self._aligner
+        self._configure(fromOffset, toOffset, toCameraMatrix, toRows, toCols, None)
+        p = a.params()
+        refs, curs, g, n = prepared if prepared is not None else self.matchHandles(fromClouds, toClouds, initialGuesses)
+        _check_records(records, n, CLOSURE_RECORD_FLOATS, a.ctx)
+        ids = None if pair_ids is None else np.ascontiguousarray(pair_ids, np.int32)
+        if ids is not None and ids.size < n:
+            raise ValueError("pair_ids shorter than the batch")
+        res = (AlignResult * n)() if want_results else None
+        sc = (MatchResult * n)() if want_results else None
+        st = (AlignStatistics * n)() if want_statistics else None
+        a.ctx.check(a.ctx._L.pwn_hip_closure_batch_records(a.ctx.h, C.byref(p), n, refs, curs, _ptr(g), self._frameInlierDepthThreshold, _ptr(ids),
+                                                           int(first_pair_id), res, sc, st, _ptr(records)))
+        return (np.frombuffer(res, dtype=ALIGN_RESULT_DTYPE, count=n), sc, st) if want_results else None
+
+    @staticmethod
+    def closureResult(record):
+        """MatcherResult of one closure record as a dict: informationMatrix is the record's omega cast to double (convertScalar, as
+        pwn_tracker2/pwn_matcher_base.cpp:158-163 does it); _result's 100 * I is pwn_tracker v1's."""
+        q = np.asarray(record, np.float32).reshape(-1)
+        return dict(transform=q[:16].reshape(4, 4).T.astype(np.float64), informationMatrix=q[72:108].reshape(6, 6).T.astype(np.float64),
+                    cloud_inliers=int(q[17]), image_nonZeros=int(q[64]), image_outliers=int(q[65]), image_inliers=int(q[66]),
+                    image_reprojectionDistance=float(q[67]), translationalEigenRatio=float(q[114]), rotationalEigenRatio=float(q[115]),
+                    statisticsComputed=bool(q[118] != 0))
 
 
 class PwnCloserAcceptance:

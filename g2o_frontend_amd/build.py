@@ -101,6 +101,13 @@ def build_tools(force: bool = False) -> str:
     if force or (not os.path.exists(out11)) or any(os.path.getmtime(d) > os.path.getmtime(out11) for d in deps11):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src11, "-o", out11, "-L", _HERE, "-lpwn_hip",
                                "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
+    # the closure records (Aligner::omega() computed on the device) through the C++ mirror against the bytes the Python mirror wrote to a file (exit status 0 = equal)
+    src12 = os.path.join(root, "tools", "pwn_hip_closure_records_check.cpp")
+    out12 = os.path.join(root, "tools", "pwn_hip_closure_records_check")
+    deps12 = [src12] + deps[1:]
+    if force or (not os.path.exists(out12)) or any(os.path.getmtime(d) > os.path.getmtime(out12) for d in deps12):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src12, "-o", out12, "-L", _HERE, "-lpwn_hip",
+                               "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
     # PwnCloser::processPartition over the GPUs of a node in native code: the mirror + RCCL (broadcast of the flat `current` cloud, all-gather of the
     # match records); the program's own streams and events come from the HIP runtime
     src5 = os.path.join(root, "tools", "pwn_hip_partition_app.cpp")

@@ -220,6 +220,7 @@ struct pwn_hip_ctx {
   HostBuf<FrameDesc> frames_host; HostBuf<PairDesc> pairs_host; HostBuf<RawDesc> raw_host; HostBuf<PairState> state_host; HostBuf<int> counts_host;
   DevBuf<MatchAcc> match_dev; HostBuf<MatchAcc> match_host;
   DevBuf<SolveOut> stats_dev; HostBuf<SolveOut> stats_host;
+  DevBuf<PairStats> pairstats_dev; HostBuf<PairStats> pairstats_host;      // k_pair_statistics: Aligner::_computeStatistics' result per pair
   // misc scratch
   DevBuf<SolveOut> solve_dev; DevBuf<int> counters_dev; DevBuf<int2> corr_ws; DevBuf<int> scratch_count;
   DevBuf<float> io_ws;      // N*16 floats staging for cloud up/download
@@ -645,6 +646,8 @@ int ensure_desc(pwn_hip_ctx* ctx, int n) {
   HIPCHK(ctx, ctx->match_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
   HIPCHK(ctx, ctx->stats_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
   HIPCHK(ctx, ctx->stats_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->pairstats_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->pairstats_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
   ctx->desc_cap = (int)B;
   return PWN_HIP_OK;
 }
@@ -1619,6 +1622,33 @@ int pwn_hip_debug_trig_eval(pwn_hip_ctx* ctx, int n, const float* y, const float
   if (e != hipSuccess) return fail(ctx, PWN_HIP_ERR_LAUNCH, std::string("trig eval: ") + hipGetErrorString(e));
   return PWN_HIP_OK;
 }
+// Test hook: the shipped k_pair_statistics on n injected systems (H: n x 36 column-major, T: n x 16 column-major) through the context's own pair
+// arrays; out: n x 44 = omega[36], mean[6], the translational and the rotational eigen ratio
+int pwn_hip_debug_statistics_eval(pwn_hip_ctx* ctx, int n, const float* H, const float* T, float* out) {
+  if (!ctx || n < 0 || (n > 0 && (!H || !T || !out))) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (n == 0) return PWN_HIP_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device), PWN_HIP_ERR_NO_DEVICE);
+  if (int rc = ensure_desc(ctx, n)) return rc;
+  ctx->img.invalidate(); ctx->last_pairs = 0;      // the pair arrays of the last alignment are overwritten
+  for (int i = 0; i < n; ++i) {
+    std::memset(&ctx->pairs_host[i], 0, sizeof(PairDesc));
+    ctx->pairs_host[i].state = ctx->state_ws + i;
+    std::memset(&ctx->state_host[i], 0, sizeof(PairState));
+    std::memcpy(ctx->state_host[i].T.m, T + 16 * (size_t)i, sizeof(float) * 16);
+    std::memset(&ctx->stats_host[i], 0, sizeof(SolveOut));
+    std::memcpy(ctx->stats_host[i].H, H + 36 * (size_t)i, sizeof(float) * 36);
+  }
+  hipStream_t st = ctx->stream;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->pairs_dev, ctx->pairs_host, sizeof(PairDesc) * n, hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->state_ws, ctx->state_host, sizeof(PairState) * n, hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->stats_dev, ctx->stats_host, sizeof(SolveOut) * n, hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
+  hipLaunchKernelGGL(k_pair_statistics, dim3(n), dim3(64), 0, st, ctx->pairs_dev, (const SolveOut*)ctx->stats_dev, ctx->pairstats_dev);
+  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->pairstats_host, ctx->pairstats_dev, sizeof(PairStats) * n, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
+  for (int i = 0; i < n; ++i) std::memcpy(out + 44 * (size_t)i, &ctx->pairstats_host[i], sizeof(float) * 44);
+  return PWN_HIP_OK;
+}
 int pwn_hip_set_profiling(pwn_hip_ctx* ctx, int enabled) {
   if (!ctx) return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, "null ctx");
   ctx->profiling = enabled != 0;
@@ -2451,6 +2481,7 @@ struct AlignCall {
   const AlignHooks* hooks = nullptr;
   float* records = nullptr;                                    // n records, device or host, written by k_pack_records: PWN_HIP_RECORD_FLOATS floats each,
   bool match_records = false;                                  // or the long form with the score words
+  bool closure_records = false;                                // or the closure form: the score words and Aligner::_computeStatistics, computed on the device
   const int* pair_ids = nullptr; int first_pair_id = 0;        // record word 19: pair_ids[i] (host), else first_pair_id + i
   const CurDepthFrames* cur_depth = nullptr;                   // the one-call step: the frames curs[i] are being converted from
 };
@@ -2516,7 +2547,7 @@ static int align_check_and_plan(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& 
   ctx->last_pairs = 0; ctx->cur_depth_subs = 0;
   if (int rc = check_align_params(ctx, c.p)) return rc;
   if (int rc = start_align_attempt(ctx, run.robust)) return rc;
-  run.want_scores = c.scores != nullptr || (c.records && c.match_records);
+  run.want_scores = c.scores != nullptr || (c.records && (c.match_records || c.closure_records));
   run.ap = make_align_params(ctx, c.p); run.N = c.p->rows * c.p->cols; run.nb = align_nblocks(run.N);
   ctx->stages.clear();
   run.plan = make_plan(ctx, ctx->sub_pairs, c.n);
@@ -2640,9 +2671,13 @@ static int align_enqueue_sub(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& run
                            tag, ctx->stop); }
     }
   }
-  if (c.statistics && p->outer_iterations > 0) {
+  if ((c.statistics || c.closure_records) && p->outer_iterations > 0) {
     StageTimer t(ctx, "statistics", st);
     launch_statistics(ctx, L, lastRefTag, ctx->stats_dev + base);
+  }
+  if (c.closure_records && p->outer_iterations > 0) {
+    StageTimer t(ctx, "pair_statistics", st);
+    hipLaunchKernelGGL(k_pair_statistics, dim3(m), dim3(64), 0, st, L.pr, (const SolveOut*)(ctx->stats_dev + base), ctx->pairstats_dev + base);
   }
   if (run.want_scores && p->outer_iterations > 0) {
     StageTimer t(ctx, "match_score", st);     // the z-buffers of this sub-batch still hold the finder's last depth images
@@ -2660,15 +2695,19 @@ static int align_enqueue_records(pwn_hip_ctx* ctx, const AlignCall& c) {
   const int n = c.n;
   if (n <= 0 || !c.records) return PWN_HIP_OK;
   const bool dev = is_device_ptr(c.records);
-  const int rlen = c.match_records ? kMatchRecordFloats : kRecordFloats;
-  if (!dev) HIPCHK(ctx, ctx->records_ws.ensure((size_t)std::max(n, 64) * kMatchRecordFloats), PWN_HIP_ERR_ALLOCATION);
+  const int rlen = c.closure_records ? kClosureRecordFloats : c.match_records ? kMatchRecordFloats : kRecordFloats;
+  if (!dev) HIPCHK(ctx, ctx->records_ws.ensure((size_t)std::max(n, 64) * (c.closure_records ? kClosureRecordFloats : kMatchRecordFloats)), PWN_HIP_ERR_ALLOCATION);
   if (c.pair_ids) {
     HIPCHK(ctx, ctx->ids_dev.ensure((size_t)std::max(n, 64)), PWN_HIP_ERR_ALLOCATION);
     HIPCHK(ctx, copy_any(ctx->ids_dev, c.pair_ids, sizeof(int) * n, ctx->stream), PWN_HIP_ERR_COPY);
   }
   float* dst = dev ? c.records : ctx->records_ws;
-  hipLaunchKernelGGL(k_pack_records, dim3(n), dim3(c.match_records ? 128 : 64), 0, ctx->stream, ctx->pairs_dev, c.pair_ids ? (const int*)ctx->ids_dev : nullptr, c.first_pair_id, dst,
-                     c.match_records ? (const MatchAcc*)ctx->match_dev : nullptr);
+  if (c.closure_records)
+    hipLaunchKernelGGL(k_pack_closure_records, dim3(n), dim3(kClosureRecordFloats), 0, ctx->stream, ctx->pairs_dev, c.pair_ids ? (const int*)ctx->ids_dev : nullptr, c.first_pair_id, dst,
+                       (const MatchAcc*)ctx->match_dev, c.p->outer_iterations > 0 ? (const PairStats*)ctx->pairstats_dev : nullptr);
+  else
+    hipLaunchKernelGGL(k_pack_records, dim3(n), dim3(c.match_records ? 128 : 64), 0, ctx->stream, ctx->pairs_dev, c.pair_ids ? (const int*)ctx->ids_dev : nullptr, c.first_pair_id, dst,
+                       c.match_records ? (const MatchAcc*)ctx->match_dev : nullptr);
   if (!dev) HIPCHK(ctx, hipMemcpyAsync(c.records, ctx->records_ws, sizeof(float) * rlen * n, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
   return PWN_HIP_OK;
 }
@@ -2677,6 +2716,8 @@ static int align_enqueue_copybacks(pwn_hip_ctx* ctx, const AlignCall& c, const A
   const int n = c.n;
   if (n > 0 && c.scores) HIPCHK(ctx, hipMemcpyAsync(ctx->match_host, ctx->match_dev, sizeof(MatchAcc) * n, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
   if (n > 0 && c.statistics) HIPCHK(ctx, hipMemcpyAsync(ctx->stats_host, ctx->stats_dev, sizeof(SolveOut) * n, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
+  if (n > 0 && c.statistics && c.closure_records && c.p->outer_iterations > 0)
+    HIPCHK(ctx, hipMemcpyAsync(ctx->pairstats_host, ctx->pairstats_dev, sizeof(PairStats) * n, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
   // direct_state: T, it and the traces of state_host[i] were written by the last k_solve_update of each pair (PairDesc::state_out); with no
   // iterations it still holds the initial state
   if (n > 0 && !run.direct_state && c.results) HIPCHK(ctx, hipMemcpyAsync(ctx->state_host, ctx->state_ws, sizeof(PairState) * n, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
@@ -2709,6 +2750,14 @@ static void fill_statistics(pwn_hip_align_statistics& q, const SolveOut* so, con
   std::memcpy(q.H, so->H, sizeof(q.H)); std::memcpy(q.b, so->b, sizeof(q.b)); q.error = so->chi2; q.inliers = so->inliers;
   compute_statistics(so->H, T, q.mean, q.omega, &q.translational_eigen_ratio, &q.rotational_eigen_ratio);
 }
+// the same from the record k_pair_statistics wrote for the pair (the closure records: no 6x6 math on the host)
+static void fill_statistics_from_device(pwn_hip_align_statistics& q, const SolveOut* so, const PairStats* ps) {
+  std::memset(&q, 0, sizeof(q));
+  if (!so) return;
+  std::memcpy(q.H, so->H, sizeof(q.H)); std::memcpy(q.b, so->b, sizeof(q.b)); q.error = so->chi2; q.inliers = so->inliers;
+  std::memcpy(q.mean, ps->mean, sizeof(q.mean)); std::memcpy(q.omega, ps->omega, sizeof(q.omega));
+  q.translational_eigen_ratio = ps->translationalRatio; q.rotational_eigen_ratio = ps->rotationalRatio;
+}
 // Finish after the wait.  The streams are idle: the fault word is digested, scores, results and statistics are filled in, the finder's images are this call's.
 static int align_finish(pwn_hip_ctx* ctx, const AlignCall& c, const AlignRun& run) {
   const int n = c.n;
@@ -2718,8 +2767,10 @@ static int align_finish(pwn_hip_ctx* ctx, const AlignCall& c, const AlignRun& ru
   float ms = 0.f; (void)hipEventElapsedTime(&ms, ctx->t0, ctx->t1);
   for (int i = 0; i < n && c.results; ++i) {
     fill_result(c.results[i], ctx->state_host[i], c.refs[i], c.curs[i], ms / n);
-    if (c.statistics) fill_statistics(c.statistics[i], c.p->outer_iterations > 0 ? ctx->stats_host + i : nullptr, ctx->state_host[i].T);
+    if (c.statistics && !c.closure_records) fill_statistics(c.statistics[i], c.p->outer_iterations > 0 ? ctx->stats_host + i : nullptr, ctx->state_host[i].T);
   }
+  for (int i = 0; i < n && c.statistics && c.closure_records; ++i)      // with or without `results`
+    fill_statistics_from_device(c.statistics[i], c.p->outer_iterations > 0 ? ctx->stats_host + i : nullptr, ctx->pairstats_host + i);
   // batches: no current z-buffer after a skipped projection; a single alignment makes it on demand
   ctx->img.set(run.ap, run.slot0, n > 0 && (!run.any_own || n == 1), n == 1 && run.any_own);
   ctx->last_pairs = n; ctx->last_states_on_host = run.direct_state || c.results != nullptr;
@@ -2887,6 +2938,15 @@ int pwn_hip_match_batch_records(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* 
   if (!records) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null records");
   AlignCall call = align_call(p, n, refs, curs, guesses, results);
   call.scores = scores; call.match_threshold = threshold; call.records = records; call.match_records = true; call.pair_ids = pair_ids; call.first_pair_id = first_pair_id;
+  return align_batch_impl(ctx, call);
+}
+int pwn_hip_closure_batch_records(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs,
+                                  const float* guesses, float threshold, const int* pair_ids, int first_pair_id, pwn_hip_align_result* results,
+                                  pwn_hip_match_result* scores, pwn_hip_align_statistics* statistics, float* records) {
+  if (!records) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null records");
+  AlignCall call = align_call(p, n, refs, curs, guesses, results);
+  call.scores = scores; call.match_threshold = threshold; call.statistics = statistics;
+  call.records = records; call.closure_records = true; call.pair_ids = pair_ids; call.first_pair_id = first_pair_id;
   return align_batch_impl(ctx, call);
 }
 // The one-submission step: the reference frames (`ref`) and the current frames (`cur`, the same request but for frames and clouds) converted in

@@ -24,6 +24,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "pwn_math.h"
+#include "pwn_stats.h"
 
 namespace pwnhip {
 
@@ -2186,16 +2187,13 @@ __global__ void __launch_bounds__(256) k_solve_update(const PairDesc* __restrict
 // match != nullptr: a record has kMatchRecordFloats words, [64:68] = PwnMatcherBase::MatcherResult's image fields of the pair (nonZeros, outliers,
 // inliers, reprojection distance: pwn_matcher_base.cpp:175-181) from its MatchAcc, [68:72] = 0.  block = 64, or 128 for the long records.
 constexpr int kRecordFloats = 64, kRecordTrace = 10, kMatchRecordFloats = 72;
-__global__ void __launch_bounds__(128) k_pack_records(const PairDesc* __restrict__ pairs, const int* __restrict__ pair_ids, int first_id, float* __restrict__ out,
-                                                      const MatchAcc* __restrict__ match) {
-  const PairDesc& pd = pairs[blockIdx.x];
+// word t < kMatchRecordFloats of pair `pair`'s record (match: its score accumulators, read for t >= kRecordFloats only)
+__device__ __forceinline__ float record_word(const PairDesc& pd, int pair, int t, const int* __restrict__ pair_ids, int first_id, const MatchAcc* __restrict__ match) {
   const PairState& st = *pd.state;
-  const int t = threadIdx.x, it = st.it, m = it < kRecordTrace ? it : kRecordTrace;
-  const int len = match ? kMatchRecordFloats : kRecordFloats;
-  if (t >= len) return;
+  const int it = st.it, m = it < kRecordTrace ? it : kRecordTrace;
   float v = 0.f;
   if (t >= kRecordFloats) {
-    const MatchAcc a = match[blockIdx.x];
+    const MatchAcc a = match[pair];
     if (t == 64) v = (float)(int)a.nonZeros;
     else if (t == 65) v = (float)((int)a.nonZeros - (int)a.inliers);
     else if (t == 66) v = (float)(int)a.inliers;
@@ -2205,7 +2203,7 @@ __global__ void __launch_bounds__(128) k_pack_records(const PairDesc* __restrict
   else if (t == 16) v = it > 0 ? st.chi2[it - 1] : 0.f;
   else if (t == 17) v = it > 0 ? (float)st.inliers[it - 1] : 0.f;
   else if (t == 18) v = (float)it;
-  else if (t == 19) v = (float)(pair_ids ? pair_ids[blockIdx.x] : first_id + (int)blockIdx.x);
+  else if (t == 19) v = (float)(pair_ids ? pair_ids[pair] : first_id + pair);
   else if (t < 30) v = (t - 20 < m) ? st.chi2[t - 20] : 0.f;
   else if (t < 40) v = (t - 30 < m) ? (float)st.inliers[t - 30] : 0.f;
   else if (t < 50) v = (t - 40 < m) ? (float)st.ncorr[t - 40] : 0.f;
@@ -2214,7 +2212,47 @@ __global__ void __launch_bounds__(128) k_pack_records(const PairDesc* __restrict
   else if (t == 61) v = (float)*pd.cur.count;
   else if (t == 62) v = (float)m;
   else if (t == 63) v = (float)__hip_atomic_load(pd.fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // 1 = the call's fault word is up (see the layout above)
-  out[(size_t)blockIdx.x * len + t] = v;
+  return v;
+}
+__global__ void __launch_bounds__(128) k_pack_records(const PairDesc* __restrict__ pairs, const int* __restrict__ pair_ids, int first_id, float* __restrict__ out,
+                                                      const MatchAcc* __restrict__ match) {
+  const int t = threadIdx.x, len = match ? kMatchRecordFloats : kRecordFloats;
+  if (t >= len) return;
+  out[(size_t)blockIdx.x * len + t] = record_word(pairs[blockIdx.x], (int)blockIdx.x, t, pair_ids, first_id, match);
+}
+// Aligner::_computeStatistics' 6x6 math of one pair per workgroup (pwn_stats.h: the text the host entry points expand), from the H of the extra
+// update (so[pair], k_reduce_pairs) and the pair's final transform.  The team of that text is the workgroup's one wave: the independent turns of
+// its loops (at most 36) go to lanes, what is serial every lane computes for itself, every array is in LDS (StatsWork): no scratch, and every
+// element sees the host's operations in the host's order.  grid = pairs, block = 64
+//   record (kPairStatsFloats words): omega[36] column-major, mean[6], translational and rotational eigen ratio, error and inliers of the extra
+//   update (the count as float), 1 = computed, 0
+struct LaneTeam {
+  __device__ __forceinline__ int lane() const { return (int)threadIdx.x; }
+  __device__ __forceinline__ int size() const { return 64; }
+  __device__ __forceinline__ void sync() const { __syncthreads(); }
+};
+constexpr int kPairStatsFloats = 48;
+struct PairStats { float omega[36]; float mean[6]; float translationalRatio, rotationalRatio; float error, inliers; float computed, pad; };
+__global__ void __launch_bounds__(64) k_pair_statistics(const PairDesc* __restrict__ pairs, const SolveOut* __restrict__ so, PairStats* __restrict__ out) {
+  __shared__ StatsWork ws;
+  __shared__ PairStats rec;
+  const SolveOut& s = so[blockIdx.x];
+  const Mat4 T = pairs[blockIdx.x].state->T;
+  compute_statistics(LaneTeam(), s.H, T, rec.mean, rec.omega, &rec.translationalRatio, &rec.rotationalRatio, ws);
+  if (threadIdx.x == 0) { rec.error = s.chi2; rec.inliers = (float)s.inliers; rec.computed = 1.f; rec.pad = 0.f; }
+  __syncthreads();
+  if (threadIdx.x < kPairStatsFloats) reinterpret_cast<float*>(out + blockIdx.x)[threadIdx.x] = reinterpret_cast<const float*>(&rec)[threadIdx.x];
+}
+// The closure record (include/pwn_hip.h: PWN_HIP_CLOSURE_RECORD_FLOATS): [0:72] the match record word for word, [72:119] the pair's PairStats
+// up to its "computed" word (stats == nullptr: the call ran no iteration, zeros), [119:128] 0.  grid = pairs, block = 128
+constexpr int kClosureRecordFloats = 128, kClosureStatsWords = 47;
+__global__ void __launch_bounds__(128) k_pack_closure_records(const PairDesc* __restrict__ pairs, const int* __restrict__ pair_ids, int first_id, float* __restrict__ out,
+                                                              const MatchAcc* __restrict__ match, const PairStats* __restrict__ stats) {
+  const int t = threadIdx.x;
+  float v = 0.f;
+  if (t < kMatchRecordFloats) v = record_word(pairs[blockIdx.x], (int)blockIdx.x, t, pair_ids, first_id, match);
+  else if (stats && t < kMatchRecordFloats + kClosureStatsWords) v = reinterpret_cast<const float*>(stats + blockIdx.x)[t - kMatchRecordFloats];
+  out[(size_t)blockIdx.x * kClosureRecordFloats + t] = v;
 }
 // reduction only, one record per pair (Aligner::_computeStatistics' 11th update).  grid = pairs, block = 256
 __global__ void __launch_bounds__(256) k_reduce_pairs(const PairDesc* __restrict__ pairs, int nblocks, SolveOut* __restrict__ out) {

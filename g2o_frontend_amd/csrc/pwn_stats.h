@@ -1,8 +1,16 @@
-// pwn_stats.h -- host-side 6x6 math of Aligner::_computeStatistics (reference pwn_core/aligner.cpp:152-199,
+// pwn_stats.h -- the 6x6 math of Aligner::_computeStatistics (reference pwn_core/aligner.cpp:152-199,
 // pwn_core/unscented.h:23-65): covariance of the estimate from the final normal equations, unscented remap into the
 // (t, q) chart of the solution, information matrix and the translational / rotational eigen-ratios.
 // The reference uses Eigen's JacobiSVD / LLT / Matrix6f::inverse; symmetric cyclic Jacobi, Cholesky and Gauss-Jordan
-// stand in for them here (results agree to fp32 round-off).  Host only.
+// stand in for them here (results agree to fp32 round-off).
+// One text for the host (pwn_hip_compute_statistics, fill_statistics) and the device (k_pair_statistics).  It is written for a TEAM: the loops
+// whose turns do not depend on each other (the k loops of a Jacobi rotation, the rows of an elimination step, the 13 sigma points, the elements
+// of a 6x6 sum) are dealt over the team's lanes and closed by team.sync(); everything else -- the rotation's angle, the pivot search, a
+// Cholesky diagonal -- every lane computes for itself from the same stored values, so every branch is uniform.  On the host the team is one
+// thread (SerialTeam: the loops are the plain loops, sync does nothing); on the device it is the 64 lanes of a workgroup (LaneTeam,
+// pwn_kernels.h).  Every ELEMENT sees the same operations in the same order either way: the bits do not depend on the team.  Every array lives
+// in a StatsWork the caller provides -- the stack on the host, LDS on the device, where the run-time indices of the pivot search and of the
+// rotations would otherwise turn register arrays into scratch.  The SE(3) priors below are host only.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -11,10 +19,28 @@
 
 namespace pwnhip {
 
-// eigen-decomposition of a symmetric n x n matrix (column-major, n <= 6) by cyclic Jacobi rotations
-inline void sym_eigen(int n, float* A, float* V, float* w) {
-  for (int i = 0; i < n * n; ++i) V[i] = 0.f;
-  for (int i = 0; i < n; ++i) V[i + n * i] = 1.f;
+struct SerialTeam {
+  PWN_HD int lane() const { return 0; }
+  PWN_HD int size() const { return 1; }
+  PWN_HD void sync() const {}
+};
+
+// the arrays of compute_statistics and of the two solvers it calls (1.9 KB)
+struct StatsWork {
+  double wI[13], wP[13];
+  float H[36], V[36], sigma[36], L[36], C[36], cov[36], ga[36], gb[36];
+  float samples[13][6];
+  float w[6], gf[6];
+  float B[9], BtB[9], Vb[9], eb[3];
+};
+
+// eigen-decomposition of a symmetric n x n matrix (column-major, n <= 6) by cyclic Jacobi rotations; A must be in place for every lane (synced)
+template <class Team>
+PWN_HD void sym_eigen(const Team& tm, int n, float* A, float* V, float* w) {
+  for (int i = tm.lane(); i < n * n; i += tm.size()) V[i] = 0.f;
+  tm.sync();
+  for (int i = tm.lane(); i < n; i += tm.size()) V[i + n * i] = 1.f;
+  tm.sync();
   for (int sweep = 0; sweep < 30; ++sweep) {
     float off = 0.f;
     for (int p = 0; p < n; ++p) for (int q = p + 1; q < n; ++q) off += A[p + n * q] * A[p + n * q];
@@ -26,92 +52,152 @@ inline void sym_eigen(int n, float* A, float* V, float* w) {
         const float theta = (A[q + n * q] - A[p + n * p]) / (2.f * apq);
         const float t = (theta >= 0.f ? 1.f : -1.f) / (std::fabs(theta) + std::sqrt(theta * theta + 1.f));
         const float c = 1.f / std::sqrt(t * t + 1.f), s = t * c;
-        for (int k = 0; k < n; ++k) { const float x = A[k + n * p], y = A[k + n * q]; A[k + n * p] = c * x - s * y; A[k + n * q] = s * x + c * y; }
-        for (int k = 0; k < n; ++k) { const float x = A[p + n * k], y = A[q + n * k]; A[p + n * k] = c * x - s * y; A[q + n * k] = s * x + c * y; }
-        for (int k = 0; k < n; ++k) { const float x = V[k + n * p], y = V[k + n * q]; V[k + n * p] = c * x - s * y; V[k + n * q] = s * x + c * y; }
+        tm.sync();      // every lane has read the three entries (and the sweep's sum) before one of them changes
+        for (int k = tm.lane(); k < n; k += tm.size()) { const float x = A[k + n * p], y = A[k + n * q]; A[k + n * p] = c * x - s * y; A[k + n * q] = s * x + c * y; }
+        tm.sync();
+        for (int k = tm.lane(); k < n; k += tm.size()) { const float x = A[p + n * k], y = A[q + n * k]; A[p + n * k] = c * x - s * y; A[q + n * k] = s * x + c * y; }
+        for (int k = tm.lane(); k < n; k += tm.size()) { const float x = V[k + n * p], y = V[k + n * q]; V[k + n * p] = c * x - s * y; V[k + n * q] = s * x + c * y; }
+        tm.sync();
       }
   }
-  for (int i = 0; i < n; ++i) w[i] = A[i + n * i];
+  for (int i = tm.lane(); i < n; i += tm.size()) w[i] = A[i + n * i];
+  tm.sync();
 }
-inline bool gauss_jordan_inverse(int n, const float* Ain, float* out) {
-  float a[36], b[36];
-  for (int i = 0; i < n * n; ++i) { a[i] = Ain[i]; b[i] = 0.f; }
-  for (int i = 0; i < n; ++i) b[i + n * i] = 1.f;
+// a, b: n * n floats of work space each, f: n floats; Ain must be in place for every lane
+template <class Team>
+PWN_HD bool gauss_jordan_inverse(const Team& tm, int n, const float* Ain, float* out, float* a, float* b, float* f) {
+  for (int i = tm.lane(); i < n * n; i += tm.size()) { a[i] = Ain[i]; b[i] = 0.f; }
+  tm.sync();
+  for (int i = tm.lane(); i < n; i += tm.size()) b[i + n * i] = 1.f;
+  tm.sync();
   for (int c = 0; c < n; ++c) {
     int piv = c; float best = std::fabs(a[c + n * c]);
     for (int r = c + 1; r < n; ++r) if (std::fabs(a[r + n * c]) > best) { best = std::fabs(a[r + n * c]); piv = r; }
     if (best == 0.f) return false;
-    if (piv != c) for (int k = 0; k < n; ++k) { std::swap(a[c + n * k], a[piv + n * k]); std::swap(b[c + n * k], b[piv + n * k]); }
-    const float d = a[c + n * c];
-    for (int k = 0; k < n; ++k) { a[c + n * k] /= d; b[c + n * k] /= d; }
-    for (int r = 0; r < n; ++r) if (r != c) {
-      const float f = a[r + n * c];
-      if (f != 0.f) for (int k = 0; k < n; ++k) { a[r + n * k] -= f * a[c + n * k]; b[r + n * k] -= f * b[c + n * k]; }
+    tm.sync();      // the search is over for every lane
+    if (piv != c) {
+      for (int k = tm.lane(); k < n; k += tm.size()) {
+        const float ta = a[c + n * k]; a[c + n * k] = a[piv + n * k]; a[piv + n * k] = ta;
+        const float tb = b[c + n * k]; b[c + n * k] = b[piv + n * k]; b[piv + n * k] = tb;
+      }
+      tm.sync();
     }
+    const float d = a[c + n * c];
+    for (int r = tm.lane(); r < n; r += tm.size()) f[r] = a[r + n * c];      // the factors of the rows below and above, before column c is cleared
+    tm.sync();
+    for (int k = tm.lane(); k < n; k += tm.size()) { a[c + n * k] /= d; b[c + n * k] /= d; }
+    tm.sync();
+    for (int e = tm.lane(); e < n * n; e += tm.size()) {
+      const int r = e % n, k = e / n;
+      if (r != c && f[r] != 0.f) { a[r + n * k] -= f[r] * a[c + n * k]; b[r + n * k] -= f[r] * b[c + n * k]; }
+    }
+    tm.sync();
   }
-  for (int i = 0; i < n * n; ++i) out[i] = b[i];
+  for (int i = tm.lane(); i < n * n; i += tm.size()) out[i] = b[i];
+  tm.sync();
   return true;
 }
+inline bool gauss_jordan_inverse(int n, const float* Ain, float* out) {
+  float a[36], b[36], f[6];
+  return gauss_jordan_inverse(SerialTeam(), n, Ain, out, a, b, f);
+}
 
-// H: Linearizer::H() at the final transform (no damping), column-major; T: Aligner::_T.
-inline void compute_statistics(const float Hin[36], const Mat4& T, float mean[6], float omega[36], float* translationalRatio, float* rotationalRatio) {
+// H: Linearizer::H() at the final transform (no damping), column-major; T: Aligner::_T.  mean, omega and the two ratios are written for the
+// whole team to read (mean and omega by the lanes their elements were dealt to, a ratio by lane 0).
+template <class Team>
+PWN_HD void compute_statistics(const Team& tm, const float Hin[36], const Mat4& T, float mean[6], float omega[36], float* translationalRatio,
+                               float* rotationalRatio, StatsWork& ws) {
   const int n = 6;
-  float H[36], V[36], w[6];
-  for (int i = 0; i < 36; ++i) H[i] = Hin[i];
-  for (int i = 0; i < n; ++i) H[i + n * i] += 1.0f;                       // aligner.cpp:169
-  sym_eigen(n, H, V, w);                                                  // :172 (JacobiSVD of a symmetric PSD matrix)
+  float* H = ws.H; float* V = ws.V; float* w = ws.w;
+  for (int i = tm.lane(); i < 36; i += tm.size()) H[i] = Hin[i];
+  tm.sync();
+  for (int i = tm.lane(); i < n; i += tm.size()) H[i + n * i] += 1.0f;    // aligner.cpp:169
+  tm.sync();
+  sym_eigen(tm, n, H, V, w);                                              // :172 (JacobiSVD of a symmetric PSD matrix)
   float smax = 0.f;
   for (int i = 0; i < n; ++i) smax = std::max(smax, std::fabs(w[i]));
-  float sigma[36];
-  for (int i = 0; i < 36; ++i) sigma[i] = 0.f;
-  for (int k = 0; k < n; ++k) {                                           // :173 svd.solve(Identity): pseudo-inverse
-    if (std::fabs(w[k]) <= FLT_EPSILON * n * smax) continue;
-    const float inv = 1.0f / w[k];
-    for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) sigma[i + n * j] += V[i + n * k] * inv * V[j + n * k];
+  float* sigma = ws.sigma;
+  for (int e = tm.lane(); e < 36; e += tm.size()) {                       // :173 svd.solve(Identity): pseudo-inverse
+    const int i = e % n, j = e / n;
+    float sg = 0.f;
+    for (int k = 0; k < n; ++k) {
+      if (std::fabs(w[k]) <= FLT_EPSILON * n * smax) continue;
+      const float inv = 1.0f / w[k];
+      sg += V[i + n * k] * inv * V[j + n * k];
+    }
+    sigma[e] = sg;
   }
+  tm.sync();
   // unscented.h:23-50
   const double alpha = 1e-3, beta = 2., lambda = alpha * alpha * n;
   const double wi = 1. / (2. * (n + lambda));
-  float L[36], C[36];
-  for (int i = 0; i < 36; ++i) { L[i] = 0.f; C[i] = sigma[i] * (float)(n + lambda); }
+  float* L = ws.L; float* C = ws.C;
+  for (int i = tm.lane(); i < 36; i += tm.size()) { L[i] = 0.f; C[i] = sigma[i] * (float)(n + lambda); }
+  tm.sync();
   for (int j = 0; j < n; ++j) {
     float d = C[j + n * j];
     for (int k = 0; k < j; ++k) d -= L[j + n * k] * L[j + n * k];
     d = std::sqrt(d);
-    L[j + n * j] = d;
-    for (int i = j + 1; i < n; ++i) { float v = C[i + n * j]; for (int k = 0; k < j; ++k) v -= L[i + n * k] * L[j + n * k]; L[i + n * j] = v / d; }
+    if (tm.lane() == 0) L[j + n * j] = d;
+    for (int i = j + 1 + tm.lane(); i < n; i += tm.size()) { float v = C[i + n * j]; for (int k = 0; k < j; ++k) v -= L[i + n * k] * L[j + n * k]; L[i + n * j] = v / d; }
+    tm.sync();
   }
-  float samples[13][6]; double wI[13], wP[13];
-  for (int r = 0; r < n; ++r) samples[0][r] = 0.f;
-  wI[0] = lambda / (n + lambda); wP[0] = lambda / (n + lambda) + (1. - alpha * alpha + beta);
-  for (int i = 0, k = 1; i < n; ++i, k += 2) {
-    for (int r = 0; r < n; ++r) { samples[k][r] = L[r + n * i]; samples[k + 1][r] = -L[r + n * i]; }
-    wI[k] = wP[k] = wi; wI[k + 1] = wP[k + 1] = wi;
-  }
-  for (int k = 0; k < 13; ++k) {                                          // aligner.cpp:182-185
-    const Mat4 X = iso_mul(T, iso_inverse(v2t(samples[k])));
+  float (*samples)[6] = ws.samples; double* wI = ws.wI; double* wP = ws.wP;
+  for (int k = tm.lane(); k < 13; k += tm.size()) {                       // sigma point k: 0 the mean, 2 i + 1 and 2 i + 2 = +- column i of L
+    if (k == 0) {
+      for (int r = 0; r < n; ++r) samples[0][r] = 0.f;
+      wI[0] = lambda / (n + lambda); wP[0] = lambda / (n + lambda) + (1. - alpha * alpha + beta);
+    } else {
+      const int i = (k - 1) / 2;
+      for (int r = 0; r < n; ++r) samples[k][r] = ((k - 1) & 1) ? -L[r + n * i] : L[r + n * i];
+      wI[k] = wP[k] = wi;
+    }
+    const Mat4 X = iso_mul(T, iso_inverse(v2t(samples[k])));              // aligner.cpp:182-185
     t2v(X, samples[k]);
   }
-  float cov[36];                                                          // unscented.h:52-65
-  for (int r = 0; r < n; ++r) mean[r] = 0.f;
-  for (int i = 0; i < 36; ++i) cov[i] = 0.f;
-  for (int k = 0; k < 13; ++k) for (int r = 0; r < n; ++r) mean[r] += (float)wI[k] * samples[k][r];
-  for (int k = 0; k < 13; ++k) {
-    float d[6];
-    for (int r = 0; r < n; ++r) d[r] = samples[k][r] - mean[r];
-    for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) cov[i + n * j] += (float)wP[k] * (d[i] * d[j]);
+  tm.sync();
+  float* cov = ws.cov;                                                    // unscented.h:52-65
+  for (int r = tm.lane(); r < n; r += tm.size()) {
+    float m = 0.f;
+    for (int k = 0; k < 13; ++k) m += (float)wI[k] * samples[k][r];
+    mean[r] = m;
   }
-  if (!gauss_jordan_inverse(n, cov, omega)) for (int i = 0; i < 36; ++i) omega[i] = 0.f;      // aligner.cpp:190
+  tm.sync();
+  for (int e = tm.lane(); e < 36; e += tm.size()) {
+    const int i = e % n, j = e / n;
+    float cv = 0.f;
+    for (int k = 0; k < 13; ++k) {
+      const float di = samples[k][i] - mean[i], dj = samples[k][j] - mean[j];
+      cv += (float)wP[k] * (di * dj);
+    }
+    cov[e] = cv;
+  }
+  tm.sync();
+  if (!gauss_jordan_inverse(tm, n, cov, omega, ws.ga, ws.gb, ws.gf)) {    // aligner.cpp:190
+    for (int i = tm.lane(); i < 36; i += tm.size()) omega[i] = 0.f;
+    tm.sync();
+  }
   for (int blk = 0; blk < 2; ++blk) {                                     // :193-198
-    float B[9], BtB[9], Vb[9], eb[3];
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) B[i + 3 * j] = omega[(i + 3 * blk) + n * (j + 3 * blk)];
-    for (int i = 0; i < 9; ++i) BtB[i] = 0.f;
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) for (int k = 0; k < 3; ++k) BtB[i + 3 * j] += B[k + 3 * i] * B[k + 3 * j];
-    sym_eigen(3, BtB, Vb, eb);
+    float* B = ws.B; float* BtB = ws.BtB; float* Vb = ws.Vb; float* eb = ws.eb;
+    for (int e = tm.lane(); e < 9; e += tm.size()) { const int i = e % 3, j = e / 3; B[i + 3 * j] = omega[(i + 3 * blk) + n * (j + 3 * blk)]; }
+    tm.sync();
+    for (int e = tm.lane(); e < 9; e += tm.size()) {
+      const int i = e % 3, j = e / 3;
+      float acc = 0.f;
+      for (int k = 0; k < 3; ++k) acc += B[k + 3 * i] * B[k + 3 * j];
+      BtB[e] = acc;
+    }
+    tm.sync();
+    sym_eigen(tm, 3, BtB, Vb, eb);
     float s0 = 0.f, s2 = FLT_MAX;
     for (int i = 0; i < 3; ++i) { const float sv = std::sqrt(std::max(eb[i], 0.f)); s0 = std::max(s0, sv); s2 = std::min(s2, sv); }
-    (blk == 0 ? *translationalRatio : *rotationalRatio) = s0 / s2;
+    if (tm.lane() == 0) (blk == 0 ? *translationalRatio : *rotationalRatio) = s0 / s2;
+    tm.sync();
   }
+}
+inline void compute_statistics(const float Hin[36], const Mat4& T, float mean[6], float omega[36], float* translationalRatio, float* rotationalRatio) {
+  StatsWork ws;
+  compute_statistics(SerialTeam(), Hin, T, mean, omega, translationalRatio, rotationalRatio, ws);
 }
 
 // ---- SE(3) priors (reference pwn_core/se3_prior.{h,cpp}, consumed by aligner.cpp:96-108) ---------------------------

@@ -778,6 +778,37 @@ struct PwnMatcherBase {
                                             results ? sc.data() : nullptr, records));
     if (results) { results->resize((size_t)n); for (int i = 0; i < n; ++i) fill((*results)[(size_t)i], res[(size_t)i], sc[(size_t)i]); }
   }
+  // the same with PWN_HIP_CLOSURE_RECORD_FLOATS-float records, which also carry Aligner::omega() computed on the device: a result's
+  // informationMatrix is then that omega cast to double (pwn_tracker2/pwn_matcher_base.cpp:158-163), not v1's 100 * I
+  void matchCloudsBatchClosureRecords(float* records, const std::vector<Cloud*>& fromClouds, const std::vector<Cloud*>& toClouds,
+                                      const Isometry3f& fromOffset, const Isometry3f& toOffset, const Matrix3f& toCameraMatrix, int toRows, int toCols,
+                                      const std::vector<Isometry3f>& initialGuesses = std::vector<Isometry3f>(), const std::vector<int>& pairIds = std::vector<int>(),
+                                      int firstPairId = 0, std::vector<MatcherResult>* results = nullptr) {
+    configure(fromOffset, toOffset, toCameraMatrix, toRows, toCols, Isometry3f::Identity());
+    const int n = (int)fromClouds.size();
+    std::vector<float> g((size_t)n * 16);
+    for (int i = 0; i < n; ++i) {
+      Isometry3f t; if (!initialGuesses.empty()) t = initialGuesses[(size_t)i];
+      t(2,3) = 0.f; t.forceLastRow();
+      std::memcpy(&g[(size_t)i * 16], t.data(), 16 * sizeof(float));
+    }
+    std::vector<pwn_hip_cloud*> r((size_t)n), c((size_t)n);
+    for (int i = 0; i < n; ++i) { r[(size_t)i] = fromClouds[(size_t)i]->handle(); c[(size_t)i] = toClouds[(size_t)i]->handle(); }
+    std::vector<pwn_hip_align_result> res(results ? (size_t)n : 0);
+    std::vector<pwn_hip_match_result> sc(results ? (size_t)n : 0);
+    std::vector<pwn_hip_align_statistics> st(results ? (size_t)n : 0);
+    const pwn_hip_aligner_params p = _aligner->params();
+    _ctx->check(pwn_hip_closure_batch_records(_ctx->handle(), &p, n, r.data(), c.data(), g.data(), _frameInlierDepthThreshold,
+                                              pairIds.empty() ? nullptr : pairIds.data(), firstPairId, results ? res.data() : nullptr,
+                                              results ? sc.data() : nullptr, results ? st.data() : nullptr, records));
+    if (results) {
+      results->resize((size_t)n);
+      for (int i = 0; i < n; ++i) {
+        fill((*results)[(size_t)i], res[(size_t)i], sc[(size_t)i]);
+        for (int k = 0; k < 36; ++k) (*results)[(size_t)i].informationMatrix[k] = (double)st[(size_t)i].omega[k];
+      }
+    }
+  }
   int numCalls = 0;
  protected:
   void configure(const Isometry3f& fromOffset, const Isometry3f& toOffset, const Matrix3f& toCameraMatrix, int toRows, int toCols, const Isometry3f& initialGuess) {

@@ -61,6 +61,29 @@ def pack_results_raw(results: np.ndarray, pair_ids) -> np.ndarray:
     return out
 
 
+# The closure record (include/pwn_hip.h: PWN_HIP_CLOSURE_RECORD_FLOATS), 128 floats = 512 bytes: [0:64] as above, [64:68] MatcherResult's image
+# fields (nonZeros, outliers, inliers, reprojection distance), [72:108] Aligner::omega() column-major, [108:114] the remapped mean,
+# [114] translational and [115] rotational eigen ratio, [116] error and [117] inliers of the extra update, [118] 1 = statistics computed.
+CLOSURE_RECORD_FLOATS = 128
+
+
+def unpack_closure_records(records, rotationalMinEigenRatio: float = 50.0, translationalMinEigenRatio: float = 50.0):
+    """Relation dicts (what PwnCloser::matchFrames stores in a PwnCloserRelation, pwn_tracker2) from [n, CLOSURE_RECORD_FLOATS] closure records:
+    transform and informationMatrix as float64 (convertScalar of T and of Aligner::omega()), the score fields, both eigen ratios, and
+    solutionValid by Aligner.solutionValid()'s rule (aligner.cpp:128-129) on the given bounds (the reference class defaults)."""
+    rec = np.asarray(records, np.float32).reshape(-1, CLOSURE_RECORD_FLOATS)
+    out = []
+    for q in rec:
+        tr, rr = float(q[114]), float(q[115])
+        out.append(dict(pair_id=int(q[19]), transform=q[:16].reshape(4, 4).T.astype(np.float64),
+                        informationMatrix=q[72:108].reshape(6, 6).T.astype(np.float64), mean=q[108:114].copy(),
+                        cloud_inliers=int(q[17]), image_nonZeros=int(q[64]), image_outliers=int(q[65]), image_inliers=int(q[66]),
+                        image_reprojectionDistance=float(q[67]), translationalEigenRatio=tr, rotationalEigenRatio=rr,
+                        statisticsComputed=bool(q[118] != 0),
+                        solutionValid=not (rr > rotationalMinEigenRatio or tr > translationalMinEigenRatio)))
+    return out
+
+
 def all_gather_into(out: "torch.Tensor", local: "torch.Tensor"):
     """dist.all_gather_into_tensor; with the gloo backend (CPU tests, the one-device rehearsal) the list form on views of `out`, which gloo
     implements for host and device tensors alike"""

@@ -472,7 +472,8 @@ int pwn_hip_match_batch(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n
 /* Everything Aligner::align() does for n pairs in one call: the Gauss-Newton loop, optionally the matcher's depth-agreement
  * score (scores != NULL) and optionally Aligner::_computeStatistics (statistics != NULL; aligner.cpp:127,152-199: one more
  * linearizer update at the final transform on the finder's last correspondences, then the 6x6 covariance / unscented math
- * on the host).  pwn_hip_align_batch / pwn_hip_match_batch are this call with the optional outputs left NULL. */
+ * on the host; pwn_hip_closure_batch_records runs that math on the device and returns it in the pair's record).
+ * pwn_hip_align_batch / pwn_hip_match_batch are this call with the optional outputs left NULL. */
 int pwn_hip_align_batch_ex(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* references,
                            pwn_hip_cloud* const* currents, const float* initial_guesses, pwn_hip_align_result* results,
                            float frame_inlier_depth_threshold, pwn_hip_match_result* scores, pwn_hip_align_statistics* statistics);
@@ -504,6 +505,24 @@ int pwn_hip_match_batch_records(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* 
                                 pwn_hip_cloud* const* currents, const float* initial_guesses, float frame_inlier_depth_threshold,
                                 const int* pair_ids, int first_pair_id, pwn_hip_align_result* results, pwn_hip_match_result* scores,
                                 float* records);
+/* pwn_hip_match_batch_records whose records carry the one field of a closure relation the match record lacks: MatcherResult::informationMatrix =
+ * Aligner::omega() (pwn_tracker2/pwn_matcher_base.cpp:158-163, stored in the PwnCloserRelation by pwn_closer.cpp).  The extra linearizer update of
+ * Aligner::_computeStatistics runs on the device as for pwn_hip_align_batch_ex, and so does its 6x6 math (k_pair_statistics, one pair per
+ * workgroup, directly behind that update on the sub-batch's stream): the same bits as pwn_hip_compute_statistics, no per-pair host math.
+ * A record has PWN_HIP_CLOSURE_RECORD_FLOATS floats (512 bytes):
+ *   [0:72]    the record of pwn_hip_match_batch_records, word for word
+ *   [72:108]  Aligner::omega(), column-major   [108:114] the remapped mean   [114] translational, [115] rotational eigen ratio
+ *   [116] error, [117] inliers of the extra update (the count as float)
+ *   [118]     1 = the statistics were computed; 0 when outer_iterations == 0, and then [72:118] are 0 (as pwn_hip_align_batch_ex leaves them)
+ *   [119:128] 0
+ * H and b of the extra update are not in the record: a caller who wants them passes `statistics` (host, n entries, may be NULL), which is filled
+ * from the device's record and sums.  `records`: device or host, n * PWN_HIP_CLOSURE_RECORD_FLOATS floats; results and scores may be NULL.
+ * Ordering, the enqueued callback and word 63 as for the other record calls. */
+#define PWN_HIP_CLOSURE_RECORD_FLOATS 128
+int pwn_hip_closure_batch_records(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* references,
+                                  pwn_hip_cloud* const* currents, const float* initial_guesses, float frame_inlier_depth_threshold,
+                                  const int* pair_ids, int first_pair_id, pwn_hip_align_result* results, pwn_hip_match_result* scores,
+                                  pwn_hip_align_statistics* statistics, float* records);
 /* One candidate batch from raw frames as ONE submission: per pair i, DepthImageConverter::compute of ref_frames[i] -> references[i] and
  * cur_frames[i] -> currents[i] (PwnMatcherBase::makeCloud, pwn_matcher_base.cpp:77-85), then Aligner::align of the pair
  * (pwn_matcher_base.cpp:120-128).  The conversion of a sub-batch's frames is queued in front of its alignment on the same stream, so one

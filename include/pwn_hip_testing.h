@@ -88,6 +88,11 @@ int pwn_hip_debug_front_end(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p,
 /* The eigensolver's three trig values (theta = atan2(y, x) / 3, cos theta, sin theta as floats) evaluated on the device for n host arguments
  * y = sqrt(q) >= 0, x = half_b: the lines of the stats kernel's eigensolver that compute them (one macro, expanded in both places). */
 int pwn_hip_debug_trig_eval(pwn_hip_ctx* ctx, int n, const float* y, const float* x, float* theta, float* cos_theta, float* sin_theta);
+/* The kernel behind pwn_hip_closure_batch_records' statistics words (k_pair_statistics, as shipped, one system per workgroup, through the
+ * context's own pair arrays, which grow to n) on n injected systems: H n x 36 (column-major Linearizer::H() without damping), T n x 16
+ * (column-major Aligner::T()); out n x 44 = omega[36] column-major, mean[6], the translational and the rotational eigen ratio -- what
+ * pwn_hip_compute_statistics returns for the same system on the host. */
+int pwn_hip_debug_statistics_eval(pwn_hip_ctx* ctx, int n, const float* H, const float* T, float* out);
 
 /* A cloud's Gaussian vector (Cloud::gaussians()) set from host arrays in the layout pwn_hip_cloud_download_gaussians returns: mean n x 3,
  * cov n x 9 (column-major 3x3), info_vec n x 3, info n x 9, flags n (1 = moments valid, 2 = information form valid; any of 0..3).  The
