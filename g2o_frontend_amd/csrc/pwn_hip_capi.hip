@@ -3128,6 +3128,63 @@ int pwn_hip_align_images(pwn_hip_ctx* ctx, int* ref_index, float* ref_depth, int
   }
   return PWN_HIP_OK;
 }
+// Test hook: the aligner's projection launch (launch_project: its grid, its choice of kernel by n, its AlignParams with the context's settle guard)
+// on n injected clouds, each under its own projector transform, through the context's own pair descriptors, states and z-buffer slots (pair i:
+// slot i), with a tag from the running supply (the slots are not cleared), and every pair's images as k_pair_images reads them back.  No repeat:
+// *gave_up is the call's settle word.  Everything is checked before anything is written.
+int pwn_hip_debug_project_pairs(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* clouds, const float* transforms, int which,
+                                int form, int* index_out, float* depth_out, int* gave_up) {
+  if (!ctx || !p || !clouds || !transforms || !gave_up) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (n < 1 || n > ctx->max_batch) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "pairs outside 1 .. max_batch");
+  if ((which != 0 && which != 1) || (form != 0 && form != 1)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "which and form must be 0 or 1");
+  if (p->min_distance < 0.f) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "min_distance must be >= 0");
+  if (int rc = check_image(ctx, p->rows, p->cols)) return rc;
+  int capacity = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!clouds[i]) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null cloud");
+    if (clouds[i]->owner != ctx) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "cloud of another context");
+    if (std::min(clouds[i]->content.n, clouds[i]->d.capacity) > kMaxAlignerPoints)
+      return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "a cloud holds more than 2^21 points (index field of the aligner's z-buffer word)");
+    capacity = std::max(capacity, clouds[i]->d.capacity);
+  }
+  if (int rc = absorb_copies(ctx)) return rc;
+  if (int rc = ensure_desc(ctx, n)) return rc;
+  const bool robust = form == 1;
+  if (int rc = start_align_attempt(ctx, robust)) return rc;
+  ctx->img.invalidate();
+  ctx->last_pairs = 0;
+  const AlignParams ap = make_align_params(ctx, p);
+  const size_t N = (size_t)p->rows * p->cols;
+  hipStream_t st = ctx->stream;
+  for (int i = 0; i < n; ++i) {
+    fill_pair(ctx, i, i, clouds[i], clouds[i], nullptr, robust);
+    PairState& hs = ctx->state_host[i];
+    std::memset(&hs, 0, sizeof(hs));
+    Mat4 iKRt; Mat3 iK;
+    projector_matrices(ap.K, mat4_from(transforms + 16 * (size_t)i), hs.KRt, iKRt, iK);
+    hs.KRtLast = hs.KRt; hs.KRtCur = hs.KRt;
+  }
+  HIPCHK(ctx, hipMemcpyAsync(ctx->pairs_dev, ctx->pairs_host, sizeof(PairDesc) * n, hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->state_ws, ctx->state_host, sizeof(PairState) * n, hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
+  unsigned tag = kZ32Tag0;
+  if (int rc = take_tags32(ctx, 1, &tag)) return rc;
+  const PairLaunch L = { &ap, align_nblocks((int)N), clouds[0]->d.omSym, n, st, ctx->pairs_dev, robust ? (unsigned*)ctx->zdepth_ws : nullptr, nullptr };
+  if (int rc = launch_project(ctx, L, capacity, which, tag)) return rc;
+  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  for (int i = 0; i < n && (index_out || depth_out); ++i) {
+    int* di = index_out ? ctx->index_ws + (size_t)i * N : nullptr;
+    float* dd = depth_out ? ctx->depth_ws + (size_t)i * N : nullptr;
+    hipLaunchKernelGGL(k_pair_images, dim3((unsigned)std::min<size_t>((N + 255) / 256, 2048)), dim3(256), 0, st, ctx->pairs_dev + i, which, tag, (int)N, di, dd);
+  }
+  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  if (index_out) HIPCHK(ctx, copy_any(index_out, ctx->index_ws, (size_t)n * N * 4, st), PWN_HIP_ERR_COPY);
+  if (depth_out) HIPCHK(ctx, copy_any(depth_out, ctx->depth_ws, (size_t)n * N * 4, st), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
+  // the settle word, read and cleared here: a give-up is this call's result, not an error (take_align_fault would leave its message behind an OK)
+  *gave_up = *(volatile int*)ctx->align_fault_host != 0 ? 1 : 0;
+  *(volatile int*)ctx->align_fault_host = 0;
+  return PWN_HIP_OK;
+}
 
 // ------------------------------------------------------------------------------------------------------- helpers
 void pwn_hip_projector_matrices(const float K[9], const float T[16], float KRt[16], float iKRt[16], float iK[9]) {
@@ -3146,10 +3203,12 @@ int pwn_hip_project_point(const float K[9], const float T[16], float min_distanc
   if (!depth_in_range(ip.z, min_distance, max_distance)) return 0;
   float fx, fy;
   round_to_pixel(ip, fx, fy);
-  // the reference converts whatever comes out to int (undefined for values an int cannot hold); saturate instead
+  // the reference converts whatever comes out to int (undefined for values an int cannot hold); saturate instead, and give a NaN the
+  // smallest int (the conversion of a NaN is as undefined as that of a large value: no pixel of any image either way)
   const float lim = 2147483520.0f;
-  if (x) *x = (int)(fx > lim ? lim : (fx < -lim ? -lim : fx));
-  if (y) *y = (int)(fy > lim ? lim : (fy < -lim ? -lim : fy));
+  const auto to_int = [lim](float f) { return f != f ? -2147483647 - 1 : (int)(f > lim ? lim : (f < -lim ? -lim : f)); };
+  if (x) *x = to_int(fx);
+  if (y) *y = to_int(fy);
   return 1;
 }
 int pwn_hip_unproject_pixel(const float K[9], const float T[16], float min_distance, float max_distance, int x, int y, float d, float p[3]) {

@@ -630,7 +630,8 @@ void pwn_hip_projector_matrices(const float K[9], const float T[16], float KRt[1
 /* The single-point forms of the projector (host code; the very expressions the kernels evaluate, so a point projected here lands on the pixel
  * pwn_hip_project gives it):
  *   PinholePointProjector::project(x, y, f, p)      (pinholepointprojector.h:174, _project :224-233): 1 = valid (depth inside [min, max]); the image
- *                                                   bounds are the caller's test, as in the reference (pinholepointprojector.cpp:51-55)
+ *                                                   bounds are the caller's test, as in the reference (pinholepointprojector.cpp:51-55);
+ *                                                   a rounded coordinate an int cannot hold is returned as +-2147483520, a NaN as INT_MIN
  *   PinholePointProjector::unProject(p, x, y, d)    (:187, _unProject :246-251): 1 = valid; x = column, y = row (pinholepointprojector.cpp:112)
  *   PinholePointProjector::projectInterval(x,y,d,R) (:200, _projectInterval :264-274): -1 for a depth outside [min, max] */
 int pwn_hip_project_point(const float K[9], const float T[16], float min_distance, float max_distance, const float p[3], int* x, int* y, float* d);

@@ -33,6 +33,20 @@ int pwn_hip_debug_set_index_shortcut(pwn_hip_ctx* ctx, int enabled);
  * Number of calls repeated so far: */
 int pwn_hip_debug_set_settle_guard(pwn_hip_ctx* ctx, int rounds);
 int pwn_hip_debug_projection_fallbacks(pwn_hip_ctx* ctx, int* calls);
+/* The aligner's projection launch on injected clouds: clouds[i], i < n, projected under the projector transform transforms[16 i ..] (column-major,
+ * what pwn_hip_project takes); camera matrix, image size and range from p, as an alignment takes them.  The launch is the function an alignment
+ * calls, with its grid, its choice of kernel by n (fewer than 8 pairs: one point per thread; from 8 on: four) and the context's settle guard,
+ * through the context's own pair descriptors, states and z-buffer slots (pair i uses slot i).  which = 0: the reference side (its buffers, its
+ * matrix); which = 1: the current side.  The epoch tag comes from the context's running supply, so the slots are NOT cleared first.  form = 0:
+ * what an alignment of n pairs launches; form = 1: the two-pass projection of a repeated call.  index_out / depth_out (host or device, either
+ * may be NULL) receive every pair's images, n x rows x cols, read from the pair's words and points as pwn_hip_align_images reads slot 0's:
+ * empty pixels -1 / FLT_MAX.  *gave_up = 1 if a thread's settle loop ran out of rounds (the images are then not the reference's; the call is
+ * not repeated), else 0.  The images of the context's last alignment are no longer available afterwards.  Refused with
+ * PWN_HIP_ERR_INVALID_ARGUMENT, nothing written: a null ctx, p, clouds, transforms, gave_up or cloud; n outside 1 .. max_batch; which or form
+ * outside {0, 1}; min_distance < 0; a cloud of another context or of more than 2^21 points; with PWN_HIP_ERR_CAPACITY: an image larger than
+ * the context's. */
+int pwn_hip_debug_project_pairs(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* clouds, const float* transforms,
+                                int which, int form, int* index_out, float* depth_out, int* gave_up);
 
 /* The one-call step (pwn_hip_convert_align_batch_u16) aligns clouds it has just converted from frames that are still on the device.  Where every
  * pair of a sub-batch takes the current cloud's own index image (see pwn_hip_debug_set_index_shortcut), the frames are the caller's resident

@@ -13,7 +13,14 @@ pytestmark = pytest.mark.gpu
 
 
 def _hip():
-    h = C.CDLL("libamdhip64.so")
+    """The HIP runtime libpwn_hip.so itself runs on: the file the loader resolves the library's own dependency to (ldd), loaded by path -- the
+    same object, so the same handle.  A load by bare name binds to whatever copy of that name the process holds already: once torch is imported
+    (api's record checks do that), the one torch ships, a second runtime whose streams mean nothing to the library."""
+    import subprocess
+    from g2o_frontend_amd import _lib
+    deps = subprocess.run(["ldd", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    path = next(line.split("=>")[1].split()[0] for line in deps.splitlines() if line.strip().startswith("libamdhip64") and "=>" in line)
+    h = C.CDLL(path)
     h.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
     h.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
     h.hipStreamSynchronize.argtypes = [C.c_void_p]

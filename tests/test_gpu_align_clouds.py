@@ -12,6 +12,9 @@ injected clouds of tests/align_clouds.py, uploaded through pwn_hip_cloud_upload 
   4. mat2quat's trace <= 0 branches inside k_solve_update: `empty` cases (dx = 0) under rotations of 125 .. 180 degrees, bitwise against the oracle;
   5. the two kernel shapes: single pairs (latency shape) against batches (throughput shape), result records bitwise equal.
 """
+import functools
+import sys
+
 import numpy as np
 import pytest
 
@@ -211,13 +214,23 @@ def test_mat2quat_branches_on_the_device(rig, oracle, storage):
 RESULT_FIELDS = ("T", "error", "inliers", "iterations", "chi2", "iter_inliers", "iter_correspondences", "iter_candidates", "n_reference", "n_current")
 
 
+@functools.lru_cache(maxsize=None)
+def _compute_units():
+    """Multiprocessor count of device 0 as torch reports it, asked in a process of its own: torch ships its own HIP runtime, and that runtime finds
+    no device in a process where the library's runtime was initialised first (the other order, bench.py's, works)."""
+    import subprocess
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.get_device_properties(0).multi_processor_count)"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-600:]
+    return int(r.stdout.split()[-1])
+
+
 @pytest.mark.parametrize("storage", STORAGES)
 def test_both_kernel_shapes_give_the_same_records(rig, oracle, storage):
     """a launch of tiles x pairs <= CU count workgroups runs k_corr_linearize_lat, a larger one k_corr_linearize: single pairs against batches of
     the same pairs, in both orders and mixed with `empty` pairs, result records bitwise equal"""
-    import torch
     from g2o_frontend_amd import api
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    cus = _compute_units()
     ctx = rig(storage)
     shapes = set()
     groups = []
