@@ -30,7 +30,10 @@ namespace pwnhip {
 
 constexpr int kMaxIter = 64;
 constexpr int kIntegralChannels = 10;
-constexpr int kAccN = 37;              // Htt9 Htr9 Hrr9 bt3 br3 chi2 inliers C K
+// The H/b sum record, one per thread, per block (fp64 partials) and per pair: the column-major 3x3 blocks Htt, Htr, Hrr of H, the halves bt, br
+// of b and chi2 -- what linearize_term adds to (kAccTerms slots) -- then the counts: inliers, correspondences C, candidates K.
+constexpr int kAccHtt = 0, kAccHtr = 9, kAccHrr = 18, kAccBt = 27, kAccBr = 30, kAccChi2 = 33, kAccTerms = kAccChi2 + 1;
+constexpr int kAccInliers = kAccTerms, kAccCorr = kAccInliers + 1, kAccCand = kAccCorr + 1, kAccN = kAccCand + 1;
 constexpr int kPixPerThread = 8;
 constexpr int kAlignBlock = 256;
 constexpr unsigned long long kZEmpty = ~0ull;
@@ -1542,19 +1545,24 @@ struct RegAcc {
   __device__ __forceinline__ void add(int k, float v) const { a[k] += v; }
 };
 // The Gauss-Newton step solves with Matrix6f::ldlt(), which reads the LOWER triangle of H only (aligner.cpp:112; Eigen's LDLT
-// default): the strictly upper entries of the Htt and Hrr blocks (sums 3, 6, 7 and 21, 24, 25) are never looked at, so the
-// iteration kernels do not accumulate them (FULL = false: 28 sums).  Aligner::_computeStatistics inverts the full H, the pass
-// that feeds it runs with FULL = true (34 sums).
-__host__ __device__ constexpr bool acc_is_upper(int k) { return k == 3 || k == 6 || k == 7 || k == 21 || k == 24 || k == 25; }
-__host__ __device__ constexpr int acc_slot_lower(int k) { return k - (k > 3) - (k > 6) - (k > 7) - (k > 21) - (k > 24) - (k > 25); }
+// default): the strictly upper entries of the Htt and Hrr blocks (acc_is_upper) are never looked at, so the iteration kernels
+// do not accumulate them (FULL = false) and their LDS columns have no slot for them (acc_slot_lower).  Aligner::_computeStatistics
+// inverts the full H, the pass that feeds it runs with FULL = true (all kAccTerms sums).
+__host__ __device__ constexpr bool acc_block_upper(int k, int base) { return k >= base && k < base + 9 && (k - base) % 3 < (k - base) / 3; }   // row < column
+__host__ __device__ constexpr bool acc_is_upper(int k) { return acc_block_upper(k, kAccHtt) || acc_block_upper(k, kAccHrr); }
+__host__ __device__ constexpr int acc_upper_below(int k) { int n = 0; for (int j = 0; j < k; ++j) n += acc_is_upper(j); return n; }
+__host__ __device__ constexpr int acc_slot_lower(int k) { return k - acc_upper_below(k); }
 template <bool FULL> struct LdsAcc {
-  static constexpr int kSlots = FULL ? 34 : 28;
+  static constexpr int kSlots = kAccTerms - (FULL ? 0 : acc_upper_below(kAccTerms));
   float* base;      // &lds[threadIdx.x], stride kAlignBlock
   __device__ __forceinline__ void add(int k, float v) const {
     if (!FULL && acc_is_upper(k)) return;
     base[(FULL ? k : acc_slot_lower(k)) * kAlignBlock] += v;
   }
 };
+static_assert(kAccN == 37 && LdsAcc<true>::kSlots == 34 && LdsAcc<false>::kSlots == 28 && acc_slot_lower(kAccChi2) == 27, "the sum record's sizes");
+static_assert(acc_is_upper(3) && acc_is_upper(6) && acc_is_upper(7) && acc_is_upper(21) && acc_is_upper(24) && acc_is_upper(25) &&
+              acc_upper_below(kAccN) == 6, "the strictly upper entries of Htt and Hrr, and no other slot");
 // a*b + c*d of the H / b products: two roundings of the products and one of the sum, as the CPU path evaluates them (no FMA)
 #define MAD2(a, b, c, d) ((a) * (b) + (c) * (d))
 // returns false if the term is rejected (non-robust kernel and chi2 above threshold)
@@ -1582,14 +1590,14 @@ __device__ __forceinline__ bool linearize_term(const float3 rp, const float3 rn,
   const float s1 = (MAD2(ptz, ep[0], (-ptx), ep[2])) + (MAD2(ntz, en[0], (-ntx), en[2]));
   const float s2 = (MAD2((-pty), ep[0], ptx, ep[1])) + (MAD2((-nty), en[0], ntx, en[1]));
   // Row by row (keeps few values live): Htt += omegaP ; Htr += omegaP*Sp ; Hrr += (Sp^T omegaP Sp + Sn^T omegaN Sn).
-  // accumulators are column-major 3x3 blocks: acc[base + i + 3*j]
+  // accumulators are column-major 3x3 blocks: acc[kAccH.. + i + 3*j]
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
     const float a0 = oP[3 * i], a1 = oP[3 * i + 1], a2 = oP[3 * i + 2];
-    acc.add(0 + i, a0); acc.add(0 + i + 3, a1); acc.add(0 + i + 6, a2);
-    acc.add(9 + i, MAD2(a1, (-ptz), a2, pty));                    // (omegaP * Sp)(i, 0..2)
-    acc.add(9 + i + 3, MAD2(a0, ptz, a2, (-ptx)));
-    acc.add(9 + i + 6, MAD2(a0, (-pty), a1, ptx));
+    acc.add(kAccHtt + i, a0); acc.add(kAccHtt + i + 3, a1); acc.add(kAccHtt + i + 6, a2);
+    acc.add(kAccHtr + i, MAD2(a1, (-ptz), a2, pty));                    // (omegaP * Sp)(i, 0..2)
+    acc.add(kAccHtr + i + 3, MAD2(a0, ptz, a2, (-ptx)));
+    acc.add(kAccHtr + i + 6, MAD2(a0, (-pty), a1, ptx));
     // row i of Sp^T*omegaP and of Sn^T*omegaN
     float p0, p1, p2, q0, q1, q2;
     if (i == 0) {
@@ -1602,13 +1610,13 @@ __device__ __forceinline__ bool linearize_term(const float3 rp, const float3 rn,
       p0 = MAD2((-pty), oP[0], ptx, oP[3]); p1 = MAD2((-pty), oP[1], ptx, oP[4]); p2 = MAD2((-pty), oP[2], ptx, oP[5]);
       q0 = MAD2((-nty), oN[0], ntx, oN[3]); q1 = MAD2((-nty), oN[1], ntx, oN[4]); q2 = MAD2((-nty), oN[2], ntx, oN[5]);
     }
-    acc.add(18 + i, (MAD2(p1, (-ptz), p2, pty)) + (MAD2(q1, (-ntz), q2, nty)));
-    acc.add(18 + i + 3, (MAD2(p0, ptz, p2, (-ptx))) + (MAD2(q0, ntz, q2, (-ntx))));
-    acc.add(18 + i + 6, (MAD2(p0, (-pty), p1, ptx)) + (MAD2(q0, (-nty), q1, ntx)));
+    acc.add(kAccHrr + i, (MAD2(p1, (-ptz), p2, pty)) + (MAD2(q1, (-ntz), q2, nty)));
+    acc.add(kAccHrr + i + 3, (MAD2(p0, ptz, p2, (-ptx))) + (MAD2(q0, ntz, q2, (-ntx))));
+    acc.add(kAccHrr + i + 6, (MAD2(p0, (-pty), p1, ptx)) + (MAD2(q0, (-nty), q1, ntx)));
   }
-  acc.add(27, kscale * ep[0]); acc.add(28, kscale * ep[1]); acc.add(29, kscale * ep[2]);
-  acc.add(30, kscale * s0); acc.add(31, kscale * s1); acc.add(32, kscale * s2);
-  acc.add(33, kscale * localError);
+  acc.add(kAccBt, kscale * ep[0]); acc.add(kAccBt + 1, kscale * ep[1]); acc.add(kAccBt + 2, kscale * ep[2]);
+  acc.add(kAccBr, kscale * s0); acc.add(kAccBr + 1, kscale * s1); acc.add(kAccBr + 2, kscale * s2);
+  acc.add(kAccChi2, kscale * localError);
   return true;
 }
 __device__ __forceinline__ void load_omegas(const CloudDev& cur, int ci, int cls, float* oP, float* oN) {
@@ -1662,19 +1670,30 @@ __device__ __forceinline__ bool correspondence_test(const AlignParams& ap, const
   return true;
 }
 
-// block-level reduction of kAccN fp32 accumulators -> fp64 partial record of the block
+// the record of the thread that owns column `col` of the LDS sums (LdsAcc<FULL>) and counted K candidates, C correspondences and the inliers
+template <bool FULL>
+__device__ __forceinline__ void acc_from_lds(const float* lds, int col, float K, float C, float inliers, float* acc) {
+#pragma unroll
+  for (int k = 0; k < kAccTerms; ++k)
+    acc[k] = (FULL || !acc_is_upper(k)) ? lds[(FULL ? k : acc_slot_lower(k)) * kAlignBlock + col] : 0.f;
+  acc[kAccCand] = K; acc[kAccCorr] = C; acc[kAccInliers] = inliers;
+}
+// block-level reduction of kAccN fp32 accumulators -> fp64 partial record of the block: a wave tree per sum, the kAlignBlock / 64 wave sums in
+// order, in double.  contributes: this thread is one of the block's first kAlignBlock and acc is its record (whole waves; the rest only meet the barrier)
 template <bool FULL = true>
-__device__ __forceinline__ void block_reduce_store(float* acc, double* out_generic) {
+__device__ __forceinline__ void block_reduce_store(const float* acc, double* out_generic, bool contributes) {
   const gptr<double> out = as_global(out_generic);
   __shared__ float red[kAlignBlock / 64][kAccN];
+  if (contributes) {
 #pragma unroll
-  for (int k = 0; k < kAccN; ++k) {
-    if (!FULL && k < 34 && acc_is_upper(k)) {            // sums the lower-triangle passes do not accumulate: exact zeros, no reduction
-      if (lane_id() == 63) red[threadIdx.x >> 6][k] = 0.f;
-      continue;
+    for (int k = 0; k < kAccN; ++k) {
+      if (!FULL && acc_is_upper(k)) {            // sums the lower-triangle passes do not accumulate: exact zeros, no reduction
+        if (lane_id() == 63) red[threadIdx.x >> 6][k] = 0.f;
+        continue;
+      }
+      const float v = wave_sum_dpp_lane63(acc[k]);
+      if (lane_id() == 63) red[threadIdx.x >> 6][k] = v;
     }
-    const float v = wave_sum_dpp_lane63(acc[k]);
-    if (lane_id() == 63) red[threadIdx.x >> 6][k] = v;
   }
   __syncthreads();
   if (threadIdx.x < kAccN) {
@@ -1719,22 +1738,17 @@ __device__ __forceinline__ PairPtrs pair_ptrs(const PairDesc& pd) {
   q.cap = (unsigned)pd.cur.capacity;
   return q;
 }
-__device__ __forceinline__ void candidate_load(const PairPtrs& q, int ri, int ci, int nref, int ncur, Candidate& c) {
+// CUR_DEPTH: without the load of the current point: craw, the raw depth of the candidate's pixel (it arrived with the indices), is kept in its place
+template <bool CUR_DEPTH = false>
+__device__ __forceinline__ void candidate_load(const PairPtrs& q, int ri, int ci, int nref, int ncur, Candidate& c, unsigned craw = 0u) {
   c.valid = !(ri < 0 || ci < 0 || ri >= nref || ci >= ncur);
   c.ci = ci;
+  if constexpr (CUR_DEPTH) c.craw = craw;
   if (c.valid) {
     // 12 + 16 bytes per side; the rest of the pass keeps the (point, curvature) / (normal, -) records it was written for
-    c.rP = load_xyz(q.refP, (unsigned)ri); c.cP = load_xyz(q.curP, (unsigned)ci); c.cN = load4(q.curN + (unsigned)ci);
-    c.rN = load4(q.refN + (unsigned)ri);
-    c.rP.w = c.rN.w; c.cP.w = c.cN.w;
-  }
-}
-// the same without the load of the current point: craw, the raw depth of the candidate's pixel (it arrived with the indices), is kept in its place
-__device__ __forceinline__ void candidate_load_depth(const PairPtrs& q, int ri, int ci, unsigned craw, int nref, int ncur, Candidate& c) {
-  c.valid = !(ri < 0 || ci < 0 || ri >= nref || ci >= ncur);
-  c.ci = ci; c.craw = craw;
-  if (c.valid) {
-    c.rP = load_xyz(q.refP, (unsigned)ri); c.cN = load4(q.curN + (unsigned)ci);
+    c.rP = load_xyz(q.refP, (unsigned)ri);
+    if constexpr (!CUR_DEPTH) c.cP = load_xyz(q.curP, (unsigned)ci);
+    c.cN = load4(q.curN + (unsigned)ci);
     c.rN = load4(q.refN + (unsigned)ri);
     c.rP.w = c.rN.w; c.cP.w = c.cN.w;
   }
@@ -1822,13 +1836,11 @@ __global__ void __launch_bounds__(kAlignBlock, 1) k_corr_linearize(const PairDes
   load_indices(0, ri1, ci1, cr1);
   load_indices(1, ri2, ci2, cr2);
   Candidate nxt;
-  if constexpr (CUR_DEPTH) candidate_load_depth(q, ri1, ci1, cr1, nref, ncur, nxt);
-  else candidate_load(q, ri1, ci1, nref, ncur, nxt);
+  candidate_load<CUR_DEPTH>(q, ri1, ci1, nref, ncur, nxt, cr1);
 #pragma unroll 1
   for (int j = 0; j < PPT; ++j) {
     Candidate cur = nxt;
-    if constexpr (CUR_DEPTH) candidate_load_depth(q, ri2, ci2, cr2, nref, ncur, nxt);
-    else candidate_load(q, ri2, ci2, nref, ncur, nxt);    // gathers of pixel j+1: in flight during the arithmetic below
+    candidate_load<CUR_DEPTH>(q, ri2, ci2, nref, ncur, nxt, cr2);      // gathers of pixel j+1: in flight during the arithmetic below
     load_indices(j + 2, ri2, ci2, cr2);                   // indices of pixel j+2
     if constexpr (CUR_DEPTH) {                            // the current point of pixel j = (row, col), as the converter stored it
       if (cur.valid) {
@@ -1843,11 +1855,8 @@ __global__ void __launch_bounds__(kAlignBlock, 1) k_corr_linearize(const PairDes
     }
   }
   float acc[kAccN];
-#pragma unroll
-  for (int k = 0; k < 34; ++k)
-    acc[k] = (FULL_H || !acc_is_upper(k)) ? lacc[(FULL_H ? k : acc_slot_lower(k)) * kAlignBlock + threadIdx.x] : 0.f;
-  acc[36] = cnt[0]; acc[35] = cnt[1]; acc[34] = cnt[2];
-  block_reduce_store<FULL_H>(acc, pd.partials + (size_t)blockIdx.x * kAccN);
+  acc_from_lds<FULL_H>(lacc, threadIdx.x, cnt[0], cnt[1], cnt[2], acc);
+  block_reduce_store<FULL_H>(acc, pd.partials + (size_t)blockIdx.x * kAccN, true);
 }
 
 // Latency shape of the fused pass for small launches (sequential odometry: PwnTracker::processFrame aligns one pair at a time).  A pair is
@@ -1855,7 +1864,7 @@ __global__ void __launch_bounds__(kAlignBlock, 1) k_corr_linearize(const PairDes
 // a workgroup has 1024 threads for the same 2048-pixel tile: thread (q, col) = (tid / 256, tid % 256) takes pixels q and q + 4 of column col, so
 // the gathers and the arithmetic of all eight pixels of a column run side by side.  The sums stay bit-identical to k_corr_linearize: the
 // per-pixel terms are added to the column's LDS accumulator in the same order, pixel 0, 1, ... 7 -- eight ordered turns, a workgroup barrier
-// between turns -- and the block reduction is the same tree on the same 256 columns.  (Putting the four threads of a column into one wave
+// between turns -- and the block reduction is block_reduce_store on the same 256 columns.  (Putting the four threads of a column into one wave
 // needs no barriers but makes every wave walk all eight turns and quarters the gathers' coalescing: measured 19 vs 16 us per launch.)
 // grid = (ceil(N / 2048), pairs), block = 1024.
 constexpr int kLatBlock = 4 * kAlignBlock;
@@ -1903,6 +1912,7 @@ __global__ void __launch_bounds__(kLatBlock) k_corr_linearize_lat(const PairDesc
     c3[r][0] = c3[r][1] = c3[r][2] = 0.f;
     candidate_consume<SAME_T, SYM>(pd, pp, ap, Tc, Tl, cand[r], RegAcc{ t[r] }, c3[r], omNtab);
   }
+  const LdsAcc<FULL_H> sums = { &lacc[col] };
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
     const bool has = c3[r][2] > 0.f;              // linearize_term added this pixel's terms
@@ -1911,37 +1921,18 @@ __global__ void __launch_bounds__(kLatBlock) k_corr_linearize_lat(const PairDesc
       if (q == turn) {
         if (has) {
 #pragma unroll
-          for (int k = 0; k < 34; ++k)
-            if (FULL_H || !acc_is_upper(k)) lacc[(FULL_H ? k : acc_slot_lower(k)) * kAlignBlock + col] += t[r][k];
+          for (int k = 0; k < kAccTerms; ++k) sums.add(k, t[r][k]);
         }
         lcnt[col] += c3[r][0]; lcnt[kAlignBlock + col] += c3[r][1]; lcnt[2 * kAlignBlock + col] += c3[r][2];     // counts: integers, exact in any order
       }
       __syncthreads();
     }
   }
-  // block reduction: the tree of block_reduce_store on the 256 columns (waves 0..3), the other waves only meet the barrier
-  __shared__ float red[kAlignBlock / 64][kAccN];
-  if (tid < kAlignBlock) {
-    float acc[kAccN];
-#pragma unroll
-    for (int k = 0; k < 34; ++k)
-      acc[k] = (FULL_H || !acc_is_upper(k)) ? lacc[(FULL_H ? k : acc_slot_lower(k)) * kAlignBlock + tid] : 0.f;
-    acc[36] = lcnt[tid]; acc[35] = lcnt[kAlignBlock + tid]; acc[34] = lcnt[2 * kAlignBlock + tid];
-#pragma unroll
-    for (int k = 0; k < kAccN; ++k) {
-      if (!FULL_H && k < 34 && acc_is_upper(k)) { if (lane_id() == 63) red[tid >> 6][k] = 0.f; continue; }
-      const float v = wave_sum_dpp_lane63(acc[k]);
-      if (lane_id() == 63) red[tid >> 6][k] = v;
-    }
-  }
-  __syncthreads();
-  if (tid < kAccN) {
-    const gptr<double> out = as_global(pd.partials + (size_t)blockIdx.x * kAccN);
-    double sum = 0.0;
-#pragma unroll
-    for (int w = 0; w < kAlignBlock / 64; ++w) sum += (double)red[w][tid];
-    out[tid] = sum;
-  }
+  // the records of the 256 columns (waves 0..3) into the block's
+  const bool owns_column = tid < kAlignBlock;
+  float acc[kAccN];
+  if (owns_column) acc_from_lds<FULL_H>(lacc, tid, lcnt[tid], lcnt[kAlignBlock + tid], lcnt[2 * kAlignBlock + tid], acc);
+  block_reduce_store<FULL_H>(acc, pd.partials + (size_t)blockIdx.x * kAccN, owns_column);
 }
 
 // CorrespondenceFinder::compute as a per-pixel pair image (compacted on the host in row-major order).
@@ -1976,15 +1967,15 @@ __global__ void __launch_bounds__(kAlignBlock) k_linearize_list(CloudDev ref, Cl
     if (i >= C) continue;
     const int2 c = corr[i];
     if (c.x < 0 || c.y < 0 || c.x >= nref || c.y >= ncur) continue;
-    acc[35] += 1.f;
+    acc[kAccCorr] += 1.f;
     float4 rP, rN, cP, cN;
     cloud_get(ref, c.x, rP, rN); cloud_get(cur, c.y, cP, cN);
     float oP[9], oN[9];
     load_omegas(cur, c.y, __float_as_int(cN.w) & kClsMask, oP, oN);
     const float3 rp = iso_point(Tl, rP), rn = iso_normal(Tl, rN);
-    if (linearize_term(rp, rn, make_float3(cP.x, cP.y, cP.z), make_float3(cN.x, cN.y, cN.z), oP, oN, ap.maxChi2, ap.robust, RegAcc{ acc })) acc[34] += 1.f;
+    if (linearize_term(rp, rn, make_float3(cP.x, cP.y, cP.z), make_float3(cN.x, cN.y, cN.z), oP, oN, ap.maxChi2, ap.robust, RegAcc{ acc })) acc[kAccInliers] += 1.f;
   }
-  block_reduce_store(acc, partials + (size_t)blockIdx.x * kAccN);
+  block_reduce_store(acc, partials + (size_t)blockIdx.x * kAccN, true);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -2094,16 +2085,28 @@ __device__ __forceinline__ void assemble_Hb(const double* s, float* H, float* b)
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      H[i + 6 * j] = (float)s[0 + i + 3 * j];
-      H[i + 6 * (j + 3)] = (float)s[9 + i + 3 * j];
-      H[(i + 3) + 6 * (j + 3)] = (float)s[18 + i + 3 * j];
+      H[i + 6 * j] = (float)s[kAccHtt + i + 3 * j];
+      H[i + 6 * (j + 3)] = (float)s[kAccHtr + i + 3 * j];
+      H[(i + 3) + 6 * (j + 3)] = (float)s[kAccHrr + i + 3 * j];
     }
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) H[(i + 3) + 6 * j] = H[j + 6 * (i + 3)];
 #pragma unroll
-  for (int i = 0; i < 3; ++i) { b[i] = (float)s[27 + i]; b[i + 3] = (float)s[30 + i]; }
+  for (int i = 0; i < 3; ++i) { b[i] = (float)s[kAccBt + i]; b[i + 3] = (float)s[kAccBr + i]; }
+}
+// the four trace entries of iteration `it`
+__device__ __forceinline__ void trace_put(PairState& s, int it, const double* sums) {
+  s.chi2[it] = (float)sums[kAccChi2]; s.inliers[it] = (int)sums[kAccInliers]; s.ncorr[it] = (int)sums[kAccCorr]; s.ncand[it] = (int)sums[kAccCand];
+}
+// reduction only: the block records of one pair -> its H, b and the four scalars.  blockDim.x must be 256
+__device__ __forceinline__ void reduce_to_solve_out(const double* partials, int nblocks, SolveOut* o) {
+  __shared__ double sums[kAccN];
+  reduce_partials(partials, nblocks, sums);
+  if (threadIdx.x != 0) return;
+  assemble_Hb(sums, o->H, o->b);
+  o->chi2 = (float)sums[kAccChi2]; o->inliers = (int)sums[kAccInliers]; o->ncorr = (int)sums[kAccCorr]; o->ncand = (int)sums[kAccCand];
 }
 // The step is written out in the kernel, on registers with constant indices only.  (Round 3 had it as a pure function returning the new state in a
 // struct, for two experiments that evaluated it inside other kernels: the struct cost the kernel 29 VGPRs, 68 bytes of scratch and a 16 KB
@@ -2126,11 +2129,8 @@ __global__ void __launch_bounds__(256) k_solve_update(const PairDesc* __restrict
   assemble_Hb(sums, H, b);
   const int it = st.it;
   if (it < kMaxIter) {
-    st.chi2[it] = (float)sums[33];
-    st.inliers[it] = (int)sums[34];
-    st.ncorr[it] = (int)sums[35];
-    st.ncand[it] = (int)sums[36];
-    if (so) { so->chi2[it] = (float)sums[33]; so->inliers[it] = (int)sums[34]; so->ncorr[it] = (int)sums[35]; so->ncand[it] = (int)sums[36]; }
+    trace_put(st, it, sums);
+    if (so) trace_put(*so, it, sums);
   }
   st.it = it + 1;
 #pragma unroll
@@ -2254,22 +2254,13 @@ __global__ void __launch_bounds__(128) k_pack_closure_records(const PairDesc* __
   else if (stats && t < kMatchRecordFloats + kClosureStatsWords) v = reinterpret_cast<const float*>(stats + blockIdx.x)[t - kMatchRecordFloats];
   out[(size_t)blockIdx.x * kClosureRecordFloats + t] = v;
 }
-// reduction only, one record per pair (Aligner::_computeStatistics' 11th update).  grid = pairs, block = 256
+// one record per pair (Aligner::_computeStatistics' 11th update).  grid = pairs, block = 256
 __global__ void __launch_bounds__(256) k_reduce_pairs(const PairDesc* __restrict__ pairs, int nblocks, SolveOut* __restrict__ out) {
-  __shared__ double sums[kAccN];
-  reduce_partials(pairs[blockIdx.x].partials, nblocks, sums);
-  if (threadIdx.x != 0) return;
-  SolveOut* o = out + blockIdx.x;
-  assemble_Hb(sums, o->H, o->b);
-  o->chi2 = (float)sums[33]; o->inliers = (int)sums[34]; o->ncorr = (int)sums[35]; o->ncand = (int)sums[36];
+  reduce_to_solve_out(pairs[blockIdx.x].partials, nblocks, out + blockIdx.x);
 }
-// reduction only (pwn_hip_linearize)
+// one record (pwn_hip_linearize).  grid = 1, block = 256
 __global__ void __launch_bounds__(256) k_reduce_only(const double* __restrict__ partials, int nblocks, SolveOut* __restrict__ out) {
-  __shared__ double sums[kAccN];
-  reduce_partials(partials, nblocks, sums);
-  if (threadIdx.x != 0) return;
-  assemble_Hb(sums, out->H, out->b);
-  out->chi2 = (float)sums[33]; out->inliers = (int)sums[34]; out->ncorr = (int)sums[35]; out->ncand = (int)sums[36];
+  reduce_to_solve_out(partials, nblocks, out);
 }
 
 }  // namespace pwnhip
