@@ -76,6 +76,10 @@ class Prior(C.Structure):
     _fields_ = [("kind", C.c_int), ("mean", C.c_float * 16), ("reference_transform", C.c_float * 16), ("information", C.c_float * 36)]
 
 
+class PairPriors(C.Structure):
+    _fields_ = [("first", C.POINTER(C.c_int)), ("priors", C.POINTER(Prior))]
+
+
 # name -> (restype, argtypes); every symbol include/pwn_hip.h declares
 _VP, _I, _F = C.c_void_p, C.c_int, C.c_float
 PROTOTYPES = {
@@ -149,6 +153,8 @@ PROTOTYPES = {
     "pwn_hip_convert_align_batch_u16": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _F, _I, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
     "pwn_hip_convert_align_batch_u16_scaled": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _F, _I, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _I, _F]),
     "pwn_hip_compute_statistics": (None, [_VP, _VP, _VP, _VP, _VP, _VP]),
+    "pwn_hip_prior_terms": (None, [_VP, _VP, _VP, _VP, C.POINTER(_I)]),
+    "pwn_hip_align_batch_priors": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _F, _VP, _I, _VP, _VP, _VP, _VP, _I]),
     "pwn_hip_match_score": (_I, [_VP, _F, _VP]),
     "pwn_hip_match_batch": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _F, _VP, _VP]),
     "pwn_hip_match_batch_records": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _F, _VP, _I, _VP, _VP, _VP]),
@@ -187,6 +193,7 @@ PROTOTYPES = {
     "pwn_hip_debug_front_end": (_I, [_VP, _VP, _VP, _F, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_debug_trig_eval": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_debug_statistics_eval": (_I, [_VP, _I, _VP, _VP, _VP]),
+    "pwn_hip_debug_prior_terms_eval": (_I, [_VP, _I, _VP, _VP, _VP, _VP]),
     "pwn_hip_debug_cloud_set_gaussians": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_debug_cloud_expose_gaussians": (_I, [_VP, _VP, _I]),
     "pwn_hip_debug_set_manifold_chunk": (_I, [_VP, _I]),

@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AlignerParams, AlignResult, AlignSteps, AlignStatistics, Convergence, ConvertExtras, ConverterParams, MatchResult, Prior, PwnHipError
+from ._lib import AlignerParams, AlignResult, AlignSteps, AlignStatistics, Convergence, ConvertExtras, ConverterParams, MatchResult, PairPriors, Prior, PwnHipError
 
 
 def _ptr(x):
@@ -1055,10 +1055,27 @@ class Aligner:
             f._images = dict(ref_index=ri, ref_depth=rd, cur_index=ci, cur_depth=cd)
         return self._result
 
-    def alignBatch(self, references, currents, initialGuesses=None, raw=False, prepared=None):
+    @staticmethod
+    def _pair_priors(priors, n):
+        """pwn_hip_pair_priors of a list per pair of (kind, mean, referenceTransform, information) tuples (what addRelativePrior / addAbsolutePrior
+        store); the returned objects own the arrays the struct points into"""
+        if len(priors) != n:
+            raise ValueError("priors: one list per pair")
+        first = np.zeros(n + 1, np.int32)
+        first[1:] = np.cumsum([len(q) for q in priors])
+        arr = (Prior * max(int(first[n]), 1))()
+        for a, (kind, mean, reft, info) in zip(arr, [t for q in priors for t in q]):
+            a.kind = int(kind); _set(a.mean, np.asarray(mean, np.float32), 4); _set(a.reference_transform, np.asarray(reft, np.float32), 4)
+            _set(a.information, np.asarray(info, np.float32), 6)
+        pp = PairPriors(first.ctypes.data_as(C.POINTER(C.c_int)), C.cast(arr, C.POINTER(Prior)))
+        return pp, (first, arr)
+
+    def alignBatch(self, references, currents, initialGuesses=None, raw=False, prepared=None, priors=None):
         """n independent alignments with this aligner's parameters (the loop-closure candidate batch,
         pwn_tracker/pwn_closer.cpp:92-111).  raw=True returns the results as one numpy structured array
-        (ALIGN_RESULT_DTYPE, T column-major) instead of a list of dicts; prepared = (refs, curs, n) handle arrays."""
+        (ALIGN_RESULT_DTYPE, T column-major) instead of a list of dicts; prepared = (refs, curs, n) handle arrays.
+        priors = per pair a list of (kind, mean, referenceTransform, information): the device-resident loop with the SE(3) priors of
+        aligner.cpp:96-108 (pwn_hip_align_batch_priors); this aligner's own prior list (addRelativePrior) belongs to align() and is not used."""
         p = self.params()
         if prepared is not None:
             refs, curs, n = prepared
@@ -1070,14 +1087,20 @@ class Aligner:
         g = None
         if initialGuesses is not None:
             g = np.ascontiguousarray(np.stack([_colmajor(self._iso(T), 4) for T in initialGuesses]), np.float32)
-        self.ctx.check(self.ctx._L.pwn_hip_align_batch(self.ctx.h, C.byref(p), n, refs, curs, _ptr(g), res))
+        if priors is not None:
+            pp, keep = self._pair_priors(priors, n)
+            self.ctx.check(self.ctx._L.pwn_hip_align_batch_priors(self.ctx.h, C.byref(p), n, refs, curs, _ptr(g), C.byref(pp), 0.0, None, 0, res, None, None, None, 0))
+        else:
+            self.ctx.check(self.ctx._L.pwn_hip_align_batch(self.ctx.h, C.byref(p), n, refs, curs, _ptr(g), res))
         if raw:
             return np.frombuffer(res, dtype=ALIGN_RESULT_DTYPE, count=n)
         return [self._unpack(r) for r in res]
 
-    def alignBatchRecords(self, references, currents, records, pair_ids=None, first_pair_id=0, initialGuesses=None, want_results=True, prepared=None):
+    def alignBatchRecords(self, references, currents, records, pair_ids=None, first_pair_id=0, initialGuesses=None, want_results=True, prepared=None,
+                          priors=None):
         """alignBatch whose results also (or only) leave as fixed-size records written on the device (include/pwn_hip.h: PWN_HIP_RECORD_FLOATS):
-        records = a float32 [n, 64] CUDA tensor (e.g. what an all-gather sends) or numpy array; returns the structured result array or None."""
+        records = a float32 [n, 64] CUDA tensor (e.g. what an all-gather sends) or numpy array; returns the structured result array or None.
+        priors: as for alignBatch."""
         p = self.params()
         refs, curs, n = prepared if prepared is not None else ((C.c_void_p * len(references))(*[c.h for c in references]),
                                                                (C.c_void_p * len(currents))(*[c.h for c in currents]), len(references))
@@ -1089,7 +1112,12 @@ class Aligner:
         _check_records(records, n, RECORD_FLOATS, self.ctx)
         if ids is not None and ids.size < n:
             raise ValueError("pair_ids shorter than the batch")
-        self.ctx.check(self.ctx._L.pwn_hip_align_batch_records(self.ctx.h, C.byref(p), n, refs, curs, _ptr(g), _ptr(ids), int(first_pair_id), res, _ptr(records)))
+        if priors is not None:
+            pp, keep = self._pair_priors(priors, n)
+            self.ctx.check(self.ctx._L.pwn_hip_align_batch_priors(self.ctx.h, C.byref(p), n, refs, curs, _ptr(g), C.byref(pp), 0.0, _ptr(ids), int(first_pair_id), res,
+                                                                  None, None, _ptr(records), RECORD_FLOATS))
+        else:
+            self.ctx.check(self.ctx._L.pwn_hip_align_batch_records(self.ctx.h, C.byref(p), n, refs, curs, _ptr(g), _ptr(ids), int(first_pair_id), res, _ptr(records)))
         return np.frombuffer(res, dtype=ALIGN_RESULT_DTYPE, count=n) if want_results else None
 
     def convertAlignBatch(self, converter, references, currents, refFrames, curFrames, raw_scale=0.001, records=None, pair_ids=None, first_pair_id=0,

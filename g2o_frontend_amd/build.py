@@ -108,6 +108,13 @@ def build_tools(force: bool = False) -> str:
     if force or (not os.path.exists(out12)) or any(os.path.getmtime(d) > os.path.getmtime(out12) for d in deps12):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src12, "-o", out12, "-L", _HERE, "-lpwn_hip",
                                "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
+    # batch alignment with SE(3) priors through the C++ mirror against the records the Python mirror wrote to a file (exit status 0 = equal byte for byte)
+    src13 = os.path.join(root, "tools", "pwn_hip_batch_priors_check.cpp")
+    out13 = os.path.join(root, "tools", "pwn_hip_batch_priors_check")
+    deps13 = [src13] + deps[1:]
+    if force or (not os.path.exists(out13)) or any(os.path.getmtime(d) > os.path.getmtime(out13) for d in deps13):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src13, "-o", out13, "-L", _HERE, "-lpwn_hip",
+                               "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
     # PwnCloser::processPartition over the GPUs of a node in native code: the mirror + RCCL (broadcast of the flat `current` cloud, all-gather of the
     # match records); the program's own streams and events come from the HIP runtime
     src5 = os.path.join(root, "tools", "pwn_hip_partition_app.cpp")

@@ -252,6 +252,11 @@ struct pwn_hip_ctx {
   HostBuf<char> flat_hdr_host;             // page-locked staging of a flat cloud's 256-byte header (pwn_hip_cloud_export / _import)
   DevBuf<float> records_ws;                              // result records of a batch on their way to host memory (k_pack_records)
   DevBuf<int> ids_dev;                                   // the caller's pair ids of those records
+  // pwn_hip_align_batch_priors: the call's prior list (pair i: [first[i], first[i + 1])), the device copies of the priors and one record of
+  // terms per prior (k_prior_terms); they grow with the call
+  DevBuf<int> prior_first_dev; HostBuf<int> prior_first_host;
+  DevBuf<PriorHost> priors_dev; HostBuf<PriorHost> priors_host;
+  DevBuf<PriorTerms> prior_terms_dev;
   // Projection fault path (z32_settle): a page-locked word the projection kernels raise when a pixel's settle loop gave up; the call is then
   // repeated with the two-pass projection (k_project_robust) and its depth images (allocated on first use)
   void (*enqueued_cb)(void*) = nullptr; void* enqueued_user = nullptr;      // pwn_hip_ctx_set_enqueued_callback
@@ -2484,6 +2489,7 @@ struct AlignCall {
   bool closure_records = false;                                // or the closure form: the score words and Aligner::_computeStatistics, computed on the device
   const int* pair_ids = nullptr; int first_pair_id = 0;        // record word 19: pair_ids[i] (host), else first_pair_id + i
   const CurDepthFrames* cur_depth = nullptr;                   // the one-call step: the frames curs[i] are being converted from
+  const pwn_hip_pair_priors* priors = nullptr;                 // SE(3) priors per pair (checked by the entry point); nullptr or an empty list: none
 };
 // What the phases of one attempt at a call share (on align_batch_once's stack)
 struct AlignRun {
@@ -2495,6 +2501,7 @@ struct AlignRun {
   int N = 0, nb = 0, omSym = 0;          // pixels; workgroups per pair of the linearize pass; storage of the current clouds' information matrices
   std::vector<char> sub_own, sub_ownref; // per sub-batch: every pair of it takes the current cloud's own index image / the reference cloud's in iteration 0
   bool any_own = false;
+  bool priors = false;                   // the call holds at least one prior: its list is on the device (align_describe_pairs)
   bool rolling = false; unsigned tagBase = kZ32Tag0, tagsPerSub = 1;      // sub-batch k draws the tags tagBase - k * tagsPerSub downwards; fixed tags: kZ32Tag0 for all
   Slot0Pair slot0;                       // the sub-batch that owns workspace slot 0 (what the finder's images will show)
 };
@@ -2536,6 +2543,38 @@ static void set_pose(PairState& st, const Mat4& T, const AlignParams& ap, const 
   projector_matrices(ap.K, iso_mul(T, ap.refOffset), st.KRt, iKRt, iK);
   st.KRtLast = st.KRt;
   st.KRtCur = KRtCur;
+}
+
+// the record the prior terms are computed from (pwn_stats.h): the inverse reference transform is taken here, once (se3_prior.h)
+static PriorHost prior_host_from(const pwn_hip_prior& q) {
+  PriorHost pr;
+  pr.kind = q.kind; pr.mean = mat4_from(q.mean);
+  pr.invReference = q.kind == 1 ? iso_inverse(mat4_from(q.reference_transform)) : mat4_identity();
+  std::memcpy(pr.information, q.information, sizeof(pr.information));
+  return pr;
+}
+// a prior list as pwn_hip_pair_priors describes it: first[0] = 0, non-decreasing, every kind 0 or 1
+static bool prior_list_ok(int n, const int* first, const pwn_hip_prior* priors) {
+  if (n < 0 || !first || first[0] != 0) return false;
+  for (int i = 0; i < n; ++i) if (first[i + 1] < first[i]) return false;
+  if (first[n] > 0 && !priors) return false;
+  for (int j = 0; j < first[n]; ++j) if (priors[j].kind != 0 && priors[j].kind != 1) return false;
+  return true;
+}
+// The list of a call on the device, queued on st: first[0 .. n] and the first[n] records; the terms get room.  The buffers grow with the call
+// (nothing of an earlier call is in flight: every call ends with a wait).
+static int upload_priors(pwn_hip_ctx* ctx, int n, const int* first, const pwn_hip_prior* priors, hipStream_t st) {
+  const size_t np = (size_t)first[n];
+  HIPCHK(ctx, ctx->prior_first_dev.ensure((size_t)n + 1), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->prior_first_host.ensure((size_t)n + 1), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->priors_dev.ensure(std::max<size_t>(np, 64)), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->priors_host.ensure(std::max<size_t>(np, 64)), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->prior_terms_dev.ensure(std::max<size_t>(np, 64)), PWN_HIP_ERR_ALLOCATION);
+  std::memcpy(ctx->prior_first_host.p, first, sizeof(int) * ((size_t)n + 1));
+  for (size_t j = 0; j < np; ++j) ctx->priors_host[j] = prior_host_from(priors[j]);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->prior_first_dev, ctx->prior_first_host, sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
+  if (np > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->priors_dev, ctx->priors_host, sizeof(PriorHost) * np, hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
+  return PWN_HIP_OK;
 }
 
 // ---- one attempt at a batch alignment, phase by phase (align_batch_once calls them in this order) ----
@@ -2608,6 +2647,8 @@ static int align_describe_pairs(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& 
     }
     if (run.want_scores) HIPCHK(ctx, hipMemsetAsync(ctx->match_dev, 0, sizeof(MatchAcc) * n, ctx->stream), PWN_HIP_ERR_COPY);
   }
+  run.priors = n > 0 && c.priors && c.priors->first[n] > 0;
+  if (run.priors) { if (int rc = upload_priors(ctx, n, c.priors->first, c.priors->priors, ctx->stream)) return rc; }
   return PWN_HIP_OK;
 }
 // Draw the tags.  On ctx->stream: the clearing of all z-buffer slots if the tag space had to start over, else nothing.
@@ -2652,6 +2693,9 @@ static int align_enqueue_sub(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& run
     run.slot0.cur_tag = tag0; run.slot0.ref_tag = lastRefTag;
   }
   if (c.hooks && c.hooks->pre_sub) { if (int rc = c.hooks->pre_sub(base, m, k, st)) return rc; }
+  // a sub-batch that holds a prior takes the priors form of the step, with the terms of this iteration's transforms in front of it
+  const bool subPriors = run.priors && c.priors->first[base + m] > c.priors->first[base];
+  const PairPriors pp = { ctx->prior_first_dev + base, ctx->prior_terms_dev };
   if (!run.sub_own[k]) {
     StageTimer t(ctx, "project_cur", st);
     if (int rc = launch_project_cur(ctx, L, maxcap_cur, tag0)) return rc; }
@@ -2666,9 +2710,13 @@ static int align_enqueue_sub(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& run
         // first inner pass: the linearizer's transform is bitwise the finder's (aligner.cpp:79,84)
         if (j == 0) launch_corr_linearize<true, false>(ctx, L, tag, 0, ownRef);
         else launch_corr_linearize<false, false>(ctx, L, tag, 0, ownRef); }
+      if (subPriors) { StageTimer t(ctx, "prior_terms", st);
+        hipLaunchKernelGGL(k_prior_terms, dim3(m), dim3(64), 0, st, L.pr, pp.first, (const PriorHost*)ctx->priors_dev, (PriorTerms*)ctx->prior_terms_dev,
+                           (const Mat4*)nullptr, ctx->stop); }
       { StageTimer t(ctx, "solve", st);
-        hipLaunchKernelGGL(k_solve_update, dim3(m), dim3(256), 0, st, L.pr, run.ap, run.nb, lastInner ? 1 : 0, (lastInner && i == p->outer_iterations - 1) ? 1 : 0,
-                           tag, ctx->stop); }
+        const int last = (lastInner && i == p->outer_iterations - 1) ? 1 : 0;
+        if (subPriors) hipLaunchKernelGGL(k_solve_update_priors, dim3(m), dim3(256), 0, st, L.pr, run.ap, run.nb, lastInner ? 1 : 0, last, tag, ctx->stop, pp);
+        else hipLaunchKernelGGL(k_solve_update, dim3(m), dim3(256), 0, st, L.pr, run.ap, run.nb, lastInner ? 1 : 0, last, tag, ctx->stop); }
     }
   }
   if ((c.statistics || c.closure_records) && p->outer_iterations > 0) {
@@ -2828,11 +2876,7 @@ static int align_with_priors_once(pwn_hip_ctx* ctx, const AlignCall& call, int n
   if (!ctx || !p || !ref || !cur || !priors || !call.results) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (int rc = check_align_params(ctx, p)) return rc;
   std::vector<PriorHost> pr(n_priors);
-  for (int i = 0; i < n_priors; ++i) {
-    pr[i].kind = priors[i].kind; pr[i].mean = mat4_from(priors[i].mean);
-    pr[i].invReference = priors[i].kind == 1 ? iso_inverse(mat4_from(priors[i].reference_transform)) : mat4_identity();
-    std::memcpy(pr[i].information, priors[i].information, sizeof(pr[i].information));
-  }
+  for (int i = 0; i < n_priors; ++i) pr[i] = prior_host_from(priors[i]);
   if (int rc = check_pair_points(ctx, ref, cur)) return rc;
   const AlignParams ap = make_align_params(ctx, p);
   hipStream_t st = ctx->stream;
@@ -2947,6 +2991,21 @@ int pwn_hip_closure_batch_records(pwn_hip_ctx* ctx, const pwn_hip_aligner_params
   AlignCall call = align_call(p, n, refs, curs, guesses, results);
   call.scores = scores; call.match_threshold = threshold; call.statistics = statistics;
   call.records = records; call.closure_records = true; call.pair_ids = pair_ids; call.first_pair_id = first_pair_id;
+  return align_batch_impl(ctx, call);
+}
+int pwn_hip_align_batch_priors(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs,
+                               const float* guesses, const pwn_hip_pair_priors* pair_priors, float threshold, const int* pair_ids, int first_pair_id,
+                               pwn_hip_align_result* results, pwn_hip_match_result* scores, pwn_hip_align_statistics* statistics, float* records,
+                               int record_floats) {
+  if (record_floats != 0 && record_floats != kRecordFloats && record_floats != kMatchRecordFloats && record_floats != kClosureRecordFloats)
+    return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "record_floats is none of 0 and the three record lengths");
+  if ((record_floats != 0) != (records != nullptr)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "records and record_floats must be given together");
+  if (pair_priors && !prior_list_ok(n, pair_priors->first, pair_priors->priors))
+    return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "bad prior list: first[0] = 0, first non-decreasing, first[n] records of kind 0 or 1");
+  AlignCall call = align_call(p, n, refs, curs, guesses, results);
+  call.scores = scores; call.match_threshold = threshold; call.statistics = statistics; call.priors = pair_priors;
+  call.records = records; call.match_records = record_floats == kMatchRecordFloats; call.closure_records = record_floats == kClosureRecordFloats;
+  call.pair_ids = pair_ids; call.first_pair_id = first_pair_id;
   return align_batch_impl(ctx, call);
 }
 // The one-submission step: the reference frames (`ref`) and the current frames (`cur`, the same request but for frames and clouds) converted in
@@ -3079,6 +3138,32 @@ int pwn_hip_last_align_steps(pwn_hip_ctx* ctx, int first, int n, pwn_hip_align_s
 }
 void pwn_hip_compute_statistics(const float H[36], const float T[16], float mean[6], float omega[36], float* tr, float* rr) {
   compute_statistics(H, mat4_from(T), mean, omega, tr, rr);
+}
+void pwn_hip_prior_terms(const float invT[16], const pwn_hip_prior* prior, float Hp[36], float bp[6], int* valid) {
+  PriorWork ws;
+  const bool ok = prior_terms(SerialTeam(), prior_host_from(*prior), mat4_from(invT), Hp, bp, ws);
+  if (!ok) { std::memset(Hp, 0, sizeof(float) * 36); std::memset(bp, 0, sizeof(float) * 6); }
+  if (valid) *valid = ok ? 1 : 0;
+}
+// Test hook: the shipped k_prior_terms on n injected transforms with their prior lists, through the context's own prior arrays
+int pwn_hip_debug_prior_terms_eval(pwn_hip_ctx* ctx, int n, const float* invT, const int* first, const pwn_hip_prior* priors, float* out) {
+  if (!ctx || n < 0 || !prior_list_ok(n, first, priors) || (n > 0 && !invT) || (n > 0 && first[n] > 0 && !out))
+    return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument or bad prior list");
+  if (n == 0 || first[n] == 0) return PWN_HIP_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device), PWN_HIP_ERR_NO_DEVICE);
+  static_assert(sizeof(Mat4) == 16 * sizeof(float), "a transform is 16 floats");
+  DevBuf<Mat4> T;
+  HIPCHK(ctx, T.alloc((size_t)n), PWN_HIP_ERR_ALLOCATION);
+  hipStream_t st = ctx->stream;
+  HIPCHK(ctx, hipMemcpyAsync(T, invT, sizeof(Mat4) * n, hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
+  if (int rc = upload_priors(ctx, n, first, priors, st)) return rc;
+  const StopRule off = { 0, 0.f, 0.f, 0 };
+  hipLaunchKernelGGL(k_prior_terms, dim3(n), dim3(64), 0, st, (const PairDesc*)nullptr, (const int*)ctx->prior_first_dev, (const PriorHost*)ctx->priors_dev,
+                     (PriorTerms*)ctx->prior_terms_dev, (const Mat4*)T, off);
+  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, hipMemcpyAsync(out, ctx->prior_terms_dev, sizeof(PriorTerms) * (size_t)first[n], hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
+  return PWN_HIP_OK;
 }
 int pwn_hip_match_score(pwn_hip_ctx* ctx, float threshold, pwn_hip_match_result* out) {
   if (!ctx || !out) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");

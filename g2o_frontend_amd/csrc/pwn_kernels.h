@@ -2116,8 +2116,19 @@ __device__ __forceinline__ void reduce_to_solve_out(const double* partials, int 
 // tag: the epoch of this outer iteration's reference projection.  At the end of an outer iteration the norms of the step just solved are recorded
 // (stepT / stepR, entry `outer`), and under an enabled StopRule the pair may freeze: its update is applied as usual, and with pd.state_out set the
 // pose goes to the host copy now, because the launch with `last` set will return for this pair like every other one.
-__global__ void __launch_bounds__(256) k_solve_update(const PairDesc* __restrict__ pairs, AlignParams ap, int nblocks, int outerEnd, int last, unsigned tag,
-                                                      StopRule stop) {
+// The terms of one prior at one pair's Linearizer::_T (k_prior_terms writes them, the priors form of the step adds them); valid = 0: the inverse
+// of the prior's Jz was refused, the prior is skipped (se3_prior.cpp's `return`), Hp and bp are zeros
+constexpr int kPriorTermsWords = 44;
+struct PriorTerms { float Hp[36]; float bp[6]; int valid; int pad; };
+// What a call with priors hands the step next to the descriptors (PairDesc, PairState and AlignParams keep their layout): pair y of the launch
+// carries the records terms[first[y] .. first[y + 1]), in list order.  NoPairPriors is what the plain step takes in its place.
+struct PairPriors { const int* first; const PriorTerms* terms; };
+struct NoPairPriors {};
+// One body for the two kernels below: PRIORS = false is k_solve_update as it was (the priors argument is an empty struct, nothing of it is compiled)
+template <bool PRIORS, class Priors>
+// (arguments by value, as the kernel takes them: by reference the compiler commuted a dozen additions of k_solve_update)
+__device__ __forceinline__ void solve_update(const PairDesc* __restrict__ pairs, AlignParams ap, int nblocks, int outerEnd, int last, unsigned tag,
+                                             StopRule stop, Priors priors) {
   const PairDesc& pd = pairs[blockIdx.x];
   if (stop.enabled && pair_frozen(pd.state)) return;      // workgroup-uniform, in front of reduce_partials' barriers
   __shared__ double sums[kAccN];
@@ -2137,6 +2148,17 @@ __global__ void __launch_bounds__(256) k_solve_update(const PairDesc* __restrict
   for (int d = 0; d < 6; ++d) H[d + 6 * d] = H[d + 6 * d] + 1.0f;        // aligner.cpp:92
 #pragma unroll
   for (int d = 0; d < 6; ++d) H[d + 6 * d] = H[d + 6 * d] + 1000.0f;     // aligner.cpp:94
+  if constexpr (PRIORS) {                                                // aligner.cpp:97-108, the valid terms in list order
+    const int j1 = priors.first[blockIdx.x + 1];
+    for (int j = priors.first[blockIdx.x]; j < j1; ++j) {
+      const PriorTerms& pt = priors.terms[j];
+      if (!pt.valid) continue;
+#pragma unroll
+      for (int i = 0; i < 36; ++i) H[i] = H[i] + pt.Hp[i];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) b[i] = b[i] + pt.bp[i];
+    }
+  }
   float nb[6], dx[6];
 #pragma unroll
   for (int d = 0; d < 6; ++d) nb[d] = -b[d];
@@ -2175,6 +2197,16 @@ __global__ void __launch_bounds__(256) k_solve_update(const PairDesc* __restrict
   }
   set_last_row(invT);
   st.invT = invT;
+}
+__global__ void __launch_bounds__(256) k_solve_update(const PairDesc* __restrict__ pairs, AlignParams ap, int nblocks, int outerEnd, int last, unsigned tag,
+                                                      StopRule stop) {
+  solve_update<false>(pairs, ap, nblocks, outerEnd, last, tag, stop, NoPairPriors());
+}
+// The priors form of the step (pwn_hip_align_batch_priors, a sub-batch that holds at least one prior): after the two damping additions it adds the
+// valid records k_prior_terms wrote for the pair at this iteration's st.invT, then solves and updates as k_solve_update does
+__global__ void __launch_bounds__(256) k_solve_update_priors(const PairDesc* __restrict__ pairs, AlignParams ap, int nblocks, int outerEnd, int last, unsigned tag,
+                                                             StopRule stop, PairPriors priors) {
+  solve_update<true>(pairs, ap, nblocks, outerEnd, last, tag, stop, priors);
 }
 // The result record of a pair as it travels between ranks (include/pwn_hip.h: PWN_HIP_RECORD_FLOATS): 64 floats =
 //   [0:16] T column-major  [16] chi2 of the last iteration  [17] its inliers  [18] iterations  [19] the caller's pair id
@@ -2242,6 +2274,39 @@ __global__ void __launch_bounds__(64) k_pair_statistics(const PairDesc* __restri
   if (threadIdx.x == 0) { rec.error = s.chi2; rec.inliers = (float)s.inliers; rec.computed = 1.f; rec.pad = 0.f; }
   __syncthreads();
   if (threadIdx.x < kPairStatsFloats) reinterpret_cast<float*>(out + blockIdx.x)[threadIdx.x] = reinterpret_cast<const float*>(&rec)[threadIdx.x];
+}
+// The prior terms of one pair per workgroup (pwn_stats.h: prior_terms, the text pwn_hip_prior_terms and the host-driven loop expand), for each
+// prior of the pair in list order, at the pair's Linearizer::_T as the last step stored it (after set_last_row, what the host loop passes).  The
+// 24 error evaluations of the numeric Jacobians, the rows of the elimination and the 36 elements of each product go to lanes; every array is in
+// LDS (PriorWork).  A pair without priors, and a frozen pair under an enabled StopRule, returns at once.  grid = pairs, block = 64
+//   first: per pair of the launch, as for PairPriors; priors: the device copies; terms: one record per prior
+//   invT != nullptr (pwn_hip_debug_prior_terms_eval): pair y takes invT[y] and `pairs` is not read
+// The team is LaneTeam under a name of its own: with one team type for both kernels the two shared gauss_jordan_inverse<LaneTeam>, and the
+// compiler then laid out k_pair_statistics' blocks differently (same operations, other code).  A type of its own keeps that kernel's code as it was.
+struct PriorLaneTeam : LaneTeam {};
+__global__ void __launch_bounds__(64) k_prior_terms(const PairDesc* __restrict__ pairs, const int* __restrict__ first, const PriorHost* __restrict__ priors,
+                                                    PriorTerms* __restrict__ terms, const Mat4* __restrict__ invT, StopRule stop) {
+  const int j0 = first[blockIdx.x], j1 = first[blockIdx.x + 1];
+  if (j0 >= j1) return;
+  if (!invT && stop.enabled && pair_frozen(pairs[blockIdx.x].state)) return;      // workgroup-uniform
+  __shared__ PriorWork ws;
+  __shared__ PriorHost pr;
+  __shared__ Mat4 T;
+  __shared__ PriorTerms rec;
+  static_assert(sizeof(PriorHost) % 4 == 0 && sizeof(PriorTerms) == 4 * kPriorTermsWords, "records are copied word by word");
+  constexpr int kPriorWords = (int)(sizeof(PriorHost) / 4);
+  const float* Tsrc = invT ? invT[blockIdx.x].m : pairs[blockIdx.x].state->invT.m;
+  if (threadIdx.x < 16) T.m[threadIdx.x] = Tsrc[threadIdx.x];
+  for (int j = j0; j < j1; ++j) {
+    __syncthreads();      // the record of the prior before this one is out, T is in
+    for (int w = threadIdx.x; w < kPriorWords; w += 64) reinterpret_cast<unsigned*>(&pr)[w] = reinterpret_cast<const unsigned*>(priors + j)[w];
+    __syncthreads();
+    const bool valid = prior_terms(PriorLaneTeam(), pr, T, rec.Hp, rec.bp, ws);
+    if (!valid && threadIdx.x < 42) reinterpret_cast<float*>(&rec)[threadIdx.x] = 0.f;
+    if (threadIdx.x == 0) { rec.valid = valid ? 1 : 0; rec.pad = 0; }
+    __syncthreads();
+    if (threadIdx.x < kPriorTermsWords) reinterpret_cast<unsigned*>(terms + j)[threadIdx.x] = reinterpret_cast<const unsigned*>(&rec)[threadIdx.x];
+  }
 }
 // The closure record (include/pwn_hip.h: PWN_HIP_CLOSURE_RECORD_FLOATS): [0:72] the match record word for word, [72:119] the pair's PairStats
 // up to its "computed" word (stats == nullptr: the call ran no iteration, zeros), [119:128] 0.  grid = pairs, block = 128

@@ -10,7 +10,7 @@
 // thread (SerialTeam: the loops are the plain loops, sync does nothing); on the device it is the 64 lanes of a workgroup (LaneTeam,
 // pwn_kernels.h).  Every ELEMENT sees the same operations in the same order either way: the bits do not depend on the team.  Every array lives
 // in a StatsWork the caller provides -- the stack on the host, LDS on the device, where the run-time indices of the pivot search and of the
-// rotations would otherwise turn register arrays into scratch.  The SE(3) priors below are host only.
+// rotations would otherwise turn register arrays into scratch.  The SE(3) prior terms below are the same kind of text (PriorWork).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -201,39 +201,75 @@ inline void compute_statistics(const float Hin[36], const Mat4& T, float mean[6]
 }
 
 // ---- SE(3) priors (reference pwn_core/se3_prior.{h,cpp}, consumed by aligner.cpp:96-108) ---------------------------
+// One text again: prior_terms is what pwn_hip_prior_terms and the host-driven loop (prior_accumulate) expand through SerialTeam and k_prior_terms
+// through LaneTeam.  The prior is the device copy too (the arrays of a batch call hold PriorHost records).
 struct PriorHost {
   int kind;            // 0: SE3RelativePrior (error = t2v(invT * mean)), 1: SE3AbsolutePrior (error = t2v(invT * ref^-1 * mean))
   Mat4 mean;           // _priorMean
   Mat4 invReference;   // _inverseReferenceTransform (identity for relative priors)
   float information[36];
 };
-inline void prior_error(const PriorHost& pr, const Mat4& mean, const Mat4& invT, float e[6]) {      // se3_prior.cpp:58-60,69-71
+// the arrays of prior_terms and of the inverse it calls (2.2 KB)
+struct PriorWork {
+  float ev[24][6];     // error 4 i + q of the numeric Jacobians: q = 0, 1 the +- steps of column i of J, q = 2, 3 those of Jz
+  float e[6];
+  float J[36], Jz[36], iJz[36], iJzT[36], t1[36], Om[36], Jt[36], t2[36];
+  float ga[36], gb[36], gf[6];
+};
+PWN_HD void prior_error(const PriorHost& pr, const Mat4& mean, const Mat4& invT, float e[6]) {      // se3_prior.cpp:58-60,69-71
   const Mat4 X = pr.kind == 0 ? iso_mul(invT, mean) : iso_mul(iso_mul(invT, pr.invReference), mean);
   t2v(X, e);
 }
-inline void mat6_mul(const float* A, const float* B, float* R) {      // column-major, left-to-right inner products
-  for (int j = 0; j < 6; ++j) for (int i = 0; i < 6; ++i) { float s = A[i] * B[6 * j]; for (int k = 1; k < 6; ++k) s = s + A[i + 6 * k] * B[k + 6 * j]; R[i + 6 * j] = s; }
+// element e of the column-major product A * B, the inner product left to right
+PWN_HD float mat6_mul_at(const float* A, const float* B, int e) {
+  const int i = e % 6, j = e / 6;
+  float s = A[i] * B[6 * j];
+  for (int k = 1; k < 6; ++k) s = s + A[i + 6 * k] * B[k + 6 * j];
+  return s;
 }
-inline void mat6_transpose(const float* A, float* R) { for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) R[i + 6 * j] = A[j + 6 * i]; }
-// Adds J^T * Omega' * J to H and J^T * Omega' * e to b (aligner.cpp:99-107) with the numeric Jacobians of se3_prior.cpp:8-52.
-inline void prior_accumulate(const PriorHost& pr, const Mat4& invT, float H[36], float b[6]) {
+template <class Team> PWN_HD void mat6_mul(const Team& tm, const float* A, const float* B, float* R) {
+  for (int e = tm.lane(); e < 36; e += tm.size()) R[e] = mat6_mul_at(A, B, e);
+  tm.sync();
+}
+template <class Team> PWN_HD void mat6_transpose(const Team& tm, const float* A, float* R) {
+  for (int e = tm.lane(); e < 36; e += tm.size()) { const int i = e % 6, j = e / 6; R[i + 6 * j] = A[j + 6 * i]; }
+  tm.sync();
+}
+// The terms one prior adds to the normal equations at Linearizer::_T = invT (aligner.cpp:99-107, the numeric Jacobians of se3_prior.cpp:8-52):
+// Hp = J^T Omega' J and bp = J^T Omega' e, for the whole team to read.  false: the inverse of Jz was refused, the reference's `return` skips the
+// prior, Hp and bp are not written.  pr and invT must be in place for every lane.
+template <class Team>
+PWN_HD bool prior_terms(const Team& tm, const PriorHost& pr, const Mat4& invT, float Hp[36], float bp[6], PriorWork& ws) {
   const float epsilon = 1e-3f, iEpsilon = 0.5f / epsilon;
-  float e[6]; prior_error(pr, pr.mean, invT, e);
-  float J[36], Jz[36];
-  for (int i = 0; i < 6; ++i) {
-    float up[6] = {0, 0, 0, 0, 0, 0}, dn[6] = {0, 0, 0, 0, 0, 0}, eu[6], ed[6];
-    up[i] = epsilon; dn[i] = -epsilon;
-    prior_error(pr, pr.mean, iso_mul(v2t(up), invT), eu); prior_error(pr, pr.mean, iso_mul(v2t(dn), invT), ed);        // jacobian
-    for (int r = 0; r < 6; ++r) J[r + 6 * i] = iEpsilon * (eu[r] - ed[r]);
-    prior_error(pr, iso_mul(pr.mean, v2t(up)), invT, eu); prior_error(pr, iso_mul(pr.mean, v2t(dn)), invT, ed);        // jacobianZ
-    for (int r = 0; r < 6; ++r) Jz[r + 6 * i] = iEpsilon * (eu[r] - ed[r]);
+  tm.sync();      // whoever read ws for the prior before this one is done
+  for (int t = tm.lane(); t < 25; t += tm.size()) {
+    if (t == 24) { prior_error(pr, pr.mean, invT, ws.e); continue; }
+    const int i = t / 4, q = t % 4;
+    float dv[6];
+    for (int k = 0; k < 6; ++k) dv[k] = k != i ? 0.f : (q & 1) ? -epsilon : epsilon;
+    if (q < 2) prior_error(pr, pr.mean, iso_mul(v2t(dv), invT), ws.ev[t]);      // jacobian
+    else prior_error(pr, iso_mul(pr.mean, v2t(dv)), invT, ws.ev[t]);            // jacobianZ
   }
-  float iJz[36], iJzT[36], t1[36], Om[36], Jt[36], t2[36], Hp[36];
-  if (!gauss_jordan_inverse(6, Jz, iJz)) return;
-  mat6_transpose(iJz, iJzT); mat6_mul(iJzT, pr.information, t1); mat6_mul(t1, iJz, Om);                                 // errorInformation
-  mat6_transpose(J, Jt); mat6_mul(Jt, Om, t2); mat6_mul(t2, J, Hp);
+  tm.sync();
+  for (int el = tm.lane(); el < 36; el += tm.size()) {
+    const int r = el % 6, i = el / 6;
+    ws.J[el] = iEpsilon * (ws.ev[4 * i][r] - ws.ev[4 * i + 1][r]);
+    ws.Jz[el] = iEpsilon * (ws.ev[4 * i + 2][r] - ws.ev[4 * i + 3][r]);
+  }
+  tm.sync();
+  if (!gauss_jordan_inverse(tm, 6, ws.Jz, ws.iJz, ws.ga, ws.gb, ws.gf)) return false;
+  mat6_transpose(tm, ws.iJz, ws.iJzT); mat6_mul(tm, ws.iJzT, pr.information, ws.t1); mat6_mul(tm, ws.t1, ws.iJz, ws.Om);      // errorInformation
+  mat6_transpose(tm, ws.J, ws.Jt); mat6_mul(tm, ws.Jt, ws.Om, ws.t2); mat6_mul(tm, ws.t2, ws.J, Hp);
+  for (int i = tm.lane(); i < 6; i += tm.size()) { float sacc = ws.t2[i] * ws.e[0]; for (int k = 1; k < 6; ++k) sacc = sacc + ws.t2[i + 6 * k] * ws.e[k]; bp[i] = sacc; }
+  tm.sync();
+  return true;
+}
+// Adds the terms of one prior to H and b (the host-driven loop of pwn_hip_align_with_priors*)
+inline void prior_accumulate(const PriorHost& pr, const Mat4& invT, float H[36], float b[6]) {
+  PriorWork ws; float Hp[36], bp[6];
+  if (!prior_terms(SerialTeam(), pr, invT, Hp, bp, ws)) return;
   for (int i = 0; i < 36; ++i) H[i] = H[i] + Hp[i];
-  for (int i = 0; i < 6; ++i) { float sacc = t2[i] * e[0]; for (int k = 1; k < 6; ++k) sacc = sacc + t2[i + 6 * k] * e[k]; b[i] = b[i] + sacc; }
+  for (int i = 0; i < 6; ++i) b[i] = b[i] + bp[i];
 }
 
 }  // namespace pwnhip

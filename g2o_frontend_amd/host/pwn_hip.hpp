@@ -569,6 +569,27 @@ class Aligner {
                                        frameInlierDepthThreshold, scores ? scores->data() : nullptr, nullptr));
     return results;
   }
+  // The same with SE(3) priors per pair, the loop on the device (pwn_hip_align_batch_priors; aligner.cpp:96-108): priors[i] is the list
+  // addRelativePrior / addAbsolutePrior would have queued for pair i (relativePrior / absolutePrior below make the records), in that order.
+  // This aligner's own list belongs to align() and is not used.
+  typedef std::vector<std::vector<pwn_hip_prior>> PairPriors;
+  static pwn_hip_prior relativePrior(const Isometry3f& mean, const Matrix6f& informationMatrix) { return makePrior(0, mean, Isometry3f::Identity(), informationMatrix); }
+  static pwn_hip_prior absolutePrior(const Isometry3f& referenceTransform, const Isometry3f& mean, const Matrix6f& informationMatrix) {
+    return makePrior(1, mean, referenceTransform, informationMatrix);
+  }
+  std::vector<pwn_hip_align_result> alignBatch(const std::vector<Cloud*>& references, const std::vector<Cloud*>& currents, const std::vector<Isometry3f>& initialGuesses,
+                                               const PairPriors& priors, std::vector<pwn_hip_match_result>* scores = nullptr, float frameInlierDepthThreshold = 50.f) {
+    return alignBatchPriors(references, currents, initialGuesses, priors, scores, frameInlierDepthThreshold, nullptr, 0, std::vector<int>(), 0);
+  }
+  // alignBatch whose results also leave as fixed-size records written on the device (PWN_HIP_RECORD_FLOATS floats each, device or host buffer;
+  // pair id = pairIds[i], else firstPairId + i); priors: empty, or one list per pair as above
+  std::vector<pwn_hip_align_result> alignBatchRecords(const std::vector<Cloud*>& references, const std::vector<Cloud*>& currents, float* records,
+                                                      const std::vector<Isometry3f>& initialGuesses = std::vector<Isometry3f>(),
+                                                      const PairPriors& priors = PairPriors(), const std::vector<int>& pairIds = std::vector<int>(),
+                                                      int firstPairId = 0) {
+    if (!records) throw Error(PWN_HIP_ERR_INVALID_ARGUMENT, "Aligner::alignBatchRecords: null records");
+    return alignBatchPriors(references, currents, initialGuesses, priors, nullptr, 0.f, records, PWN_HIP_RECORD_FLOATS, pairIds, firstPairId);
+  }
   // One candidate batch from raw uint16 frames as one submission (pwn_hip_convert_align_batch_u16): per pair PwnMatcherBase::makeCloud of both
   // frames (pwn_matcher_base.cpp:77-85), then align; `records` (optional): device or host buffer of n * PWN_HIP_RECORD_FLOATS floats that
   // receives the fixed-size result records (pair id = firstPairId + i) straight from the device.
@@ -615,6 +636,35 @@ class Aligner {
     std::memcpy(q.mean, mean.data(), sizeof(q.mean)); std::memcpy(q.reference_transform, referenceTransform.data(), sizeof(q.reference_transform));
     std::memcpy(q.information, info.data(), sizeof(q.information));
     return q;
+  }
+  // what the two batch calls with priors share: the handle, guess and prior arrays, and the one call (priors empty: no list is passed, the
+  // launches of the call without priors)
+  std::vector<pwn_hip_align_result> alignBatchPriors(const std::vector<Cloud*>& references, const std::vector<Cloud*>& currents, const std::vector<Isometry3f>& initialGuesses,
+                                                     const PairPriors& priors, std::vector<pwn_hip_match_result>* scores, float frameInlierDepthThreshold,
+                                                     float* records, int recordFloats, const std::vector<int>& pairIds, int firstPairId) {
+    const size_t n = references.size();
+    if (currents.size() != n || (!initialGuesses.empty() && initialGuesses.size() != n) || (!priors.empty() && priors.size() != n) ||
+        (!pairIds.empty() && pairIds.size() < n))
+      throw Error(PWN_HIP_ERR_INVALID_ARGUMENT, "Aligner::alignBatch: list sizes differ");
+    std::vector<pwn_hip_align_result> results(n);
+    if (n == 0) return results;
+    const pwn_hip_aligner_params p = params();
+    std::vector<pwn_hip_cloud*> r(n), c(n);
+    for (size_t i = 0; i < n; ++i) {
+      if (!references[i] || !currents[i]) throw Error(PWN_HIP_ERR_INVALID_ARGUMENT, "Aligner::alignBatch: null cloud");
+      r[i] = references[i]->handle(); c[i] = currents[i]->handle();
+    }
+    std::vector<float> g;
+    for (const Isometry3f& T : initialGuesses) { Isometry3f t = T; t.forceLastRow(); g.insert(g.end(), t.m, t.m + 16); }
+    std::vector<int> first(n + 1, 0);
+    std::vector<pwn_hip_prior> flat;
+    for (size_t i = 0; i < priors.size(); ++i) { flat.insert(flat.end(), priors[i].begin(), priors[i].end()); first[i + 1] = (int)flat.size(); }
+    const pwn_hip_pair_priors pp = { first.data(), flat.data() };
+    if (scores) scores->resize(n);
+    _ctx->check(pwn_hip_align_batch_priors(_ctx->handle(), &p, (int)n, r.data(), c.data(), g.empty() ? nullptr : g.data(), priors.empty() ? nullptr : &pp,
+                                           frameInlierDepthThreshold, pairIds.empty() ? nullptr : pairIds.data(), firstPairId, results.data(),
+                                           scores ? scores->data() : nullptr, nullptr, records, recordFloats));
+    return results;
   }
   Context* _ctx;
   PinholePointProjector* _projector = nullptr; Linearizer* _linearizer = nullptr; CorrespondenceFinder* _correspondenceFinder = nullptr;

@@ -205,7 +205,8 @@ int pwn_hip_cloud_omega_storage(pwn_hip_ctx* ctx, const pwn_hip_cloud* cloud, in
  *   traces), its record words, its matchClouds score, its statistics, and for the pair of slot 0 pwn_hip_align_images / pwn_hip_match_score -- equals
  *   bit for bit what the same call returns with outer_iterations = i + 1.  total_time_ms is exempt.
  * Every alignment entry point honours the setting.  The one exception is the host-driven loop with priors: pwn_hip_align_with_priors* with
- * n_priors > 0 returns PWN_HIP_ERR_INVALID_ARGUMENT while the setting is enabled, and touches nothing.
+ * n_priors > 0 returns PWN_HIP_ERR_INVALID_ARGUMENT while the setting is enabled, and touches nothing (pwn_hip_align_batch_priors, whose loop
+ * with priors runs on the device, honours it).
  * set: NULL or enabled == 0 switches it off; enabling is refused (INVALID_ARGUMENT, setting unchanged) unless both epsilons are finite and >= 0
  * and min_iterations >= 0. */
 typedef struct pwn_hip_convergence {
@@ -219,7 +220,8 @@ int pwn_hip_ctx_get_convergence(const pwn_hip_ctx* ctx, pwn_hip_convergence* set
 /* The step norms of the pairs [first, first + n) of the context's last alignment call: `iterations` OUTER iterations were executed (the entries
  * [0, iterations) of both traces, zeros behind them), `converged` = 1 when the pair froze under the setting above.  Reads what the call left
  * behind (a call that returned records only fetches the states from the device on the first such request); INVALID_ARGUMENT when the range
- * is not inside the last call's pairs.  After pwn_hip_align_with_priors* with n_priors > 0 the traces are empty. */
+ * is not inside the last call's pairs.  After pwn_hip_align_with_priors* with n_priors > 0 the traces are empty (the host drove that loop; after
+ * pwn_hip_align_batch_priors they are filled). */
 typedef struct pwn_hip_align_steps {
   int   iterations;
   int   converged;
@@ -542,10 +544,11 @@ int pwn_hip_convert_align_batch_u16_scaled(pwn_hip_ctx* ctx, const pwn_hip_conve
                                            int rows, int cols, pwn_hip_cloud* const* references, pwn_hip_cloud* const* currents,
                                            const float* initial_guesses, const int* pair_ids, int first_pair_id,
                                            pwn_hip_align_result* results, float* records, int step, float max_depth_cov);
-/* Aligner::align with priors (aligner.cpp:96-108).  The prior terms (numeric Jacobians, se3_prior.cpp:8-52) are 6x6 host math
- * that changes the normal equations of every iteration, so this entry point keeps the reference's host-driven loop: per
+/* Aligner::align with priors (aligner.cpp:96-108), one pair, the loop driven from the host.  The prior terms (numeric Jacobians,
+ * se3_prior.cpp:8-52) change the normal equations of every iteration; this entry point keeps the reference's shape: per
  * iteration the GPU projects, finds correspondences and reduces H, b; the host adds damping + priors, solves and updates.
- * n_priors = 0 is the device-resident loop of pwn_hip_align. */
+ * n_priors = 0 is the device-resident loop of pwn_hip_align.  The device-resident loop WITH priors is pwn_hip_align_batch_priors
+ * (below; n = 1 of it is this call without the host in the loop, the same bits). */
 int pwn_hip_align_with_priors(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, const pwn_hip_cloud* reference,
                               const pwn_hip_cloud* current, int n_priors, const pwn_hip_prior* priors, pwn_hip_align_result* result);
 /* The same with Aligner::_computeStatistics (aligner.cpp:127): the reference runs it after every align(), priors or not, on
@@ -557,6 +560,31 @@ int pwn_hip_align_with_priors_ex(pwn_hip_ctx* ctx, const pwn_hip_aligner_params*
 /* the host-side part alone: H = Linearizer::H() at the final transform, T = Aligner::T() */
 void pwn_hip_compute_statistics(const float H[36], const float T[16], float mean[6], float omega[36],
                                 float* translational_eigen_ratio, float* rotational_eigen_ratio);
+/* The terms one prior adds to the normal equations of an inner iteration (aligner.cpp:99-107), the host side alone: invT = Linearizer::_T of
+ * that iteration (column-major, last row 0 0 0 1), Hp = J^T Omega' J (column-major), bp = J^T Omega' e, with the numeric Jacobians of
+ * se3_prior.cpp:8-52.  *valid = 0: the inverse of the prior's Jz was refused, the reference skips such a prior, Hp and bp are zeros.  The
+ * text every alignment call with priors expands, on the host and on the device (the same bits). */
+void pwn_hip_prior_terms(const float invT[16], const pwn_hip_prior* prior, float Hp[36], float bp[6], int* valid);
+/* Batch alignment with SE(3) priors, device-resident: pwn_hip_align_batch_ex (records == NULL, record_floats == 0) or one of the three
+ * record calls (record_floats == PWN_HIP_RECORD_FLOATS, PWN_HIP_MATCH_RECORD_FLOATS or PWN_HIP_CLOSURE_RECORD_FLOATS; layouts unchanged)
+ * in which pair i carries the priors pair_priors->priors[first[i] .. first[i + 1]) in that order, as Aligner::addRelativePrior /
+ * addAbsolutePrior queued them.  Once per inner iteration a sub-batch that holds at least one prior runs a small kernel that computes the
+ * terms of its pairs' priors at the pair's Linearizer::_T, and its solve step adds the valid ones behind the two damping additions
+ * (aligner.cpp:92-108); the loop stays on the device, and so do traces, step norms and the convergence setting (honoured as everywhere: a
+ * stopped pair returns the result of that many outer iterations).  Statistics and omega come from the linearizer's H alone
+ * (aligner.cpp:165-170).  Every pair returns the bits pwn_hip_align_with_priors_ex returns for it.  pair_priors == NULL or first[n] == 0:
+ * the launches and the bits of the matching call without priors.  scores, statistics and results may be NULL as in those calls (results
+ * only when records are asked for).  Refused with PWN_HIP_ERR_INVALID_ARGUMENT, nothing touched: first == NULL, first[0] != 0, a decreasing
+ * first, priors == NULL with first[n] > 0, a kind outside {0, 1}, a record_floats outside the four values, records == NULL with
+ * record_floats != 0 (or the reverse). */
+typedef struct pwn_hip_pair_priors {   /* pair i carries priors[first[i] .. first[i+1]) in that order */
+  const int* first;                    /* n + 1 host ints, first[0] = 0, non-decreasing */
+  const pwn_hip_prior* priors;         /* first[n] host records */
+} pwn_hip_pair_priors;
+int pwn_hip_align_batch_priors(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* references,
+                               pwn_hip_cloud* const* currents, const float* initial_guesses, const pwn_hip_pair_priors* pair_priors,
+                               float frame_inlier_depth_threshold, const int* pair_ids, int first_pair_id, pwn_hip_align_result* results,
+                               pwn_hip_match_result* scores, pwn_hip_align_statistics* statistics, float* records, int record_floats);
 
 /* ---- scene maintenance (what follows the registration path in pwn_aligner.cpp:205-208 / pwn_merger.cpp:91-94) ---------------- */
 /* The Gaussian half of PinholePointProjector::unProject(points, gaussians, index, depth) (pinholepointprojector.cpp:104-123; baseline

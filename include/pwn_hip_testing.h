@@ -107,6 +107,11 @@ int pwn_hip_debug_trig_eval(pwn_hip_ctx* ctx, int n, const float* y, const float
  * (column-major Aligner::T()); out n x 44 = omega[36] column-major, mean[6], the translational and the rotational eigen ratio -- what
  * pwn_hip_compute_statistics returns for the same system on the host. */
 int pwn_hip_debug_statistics_eval(pwn_hip_ctx* ctx, int n, const float* H, const float* T, float* out);
+/* The kernel behind pwn_hip_align_batch_priors' prior terms (k_prior_terms, as shipped, one pair per workgroup) on n injected pairs: invT
+ * n x 16 (column-major Linearizer::_T), pair i carries priors[first[i] .. first[i + 1]) (first: n + 1 ints as in pwn_hip_pair_priors); out
+ * first[n] x 44 words = Hp[36] column-major, bp[6], valid (an int), 0 -- per prior what pwn_hip_prior_terms returns for (invT[i], prior) on
+ * the host. */
+int pwn_hip_debug_prior_terms_eval(pwn_hip_ctx* ctx, int n, const float* invT, const int* first, const pwn_hip_prior* priors, float* out);
 
 /* A cloud's Gaussian vector (Cloud::gaussians()) set from host arrays in the layout pwn_hip_cloud_download_gaussians returns: mean n x 3,
  * cov n x 9 (column-major 3x3), info_vec n x 3, info n x 9, flags n (1 = moments valid, 2 = information form valid; any of 0..3).  The
