@@ -187,6 +187,7 @@ PROTOTYPES = {
     "pwn_hip_debug_projection_fallbacks": (_I, [_VP, C.POINTER(_I)]),
     "pwn_hip_debug_project_pairs": (_I, [_VP, _VP, _I, _VP, _VP, _I, _I, _VP, _VP, C.POINTER(_I)]),
     "pwn_hip_debug_cur_depth_sub_batches": (_I, [_VP, C.POINTER(_I)]),
+    "pwn_hip_debug_strip_index_sub_batches": (_I, [_VP, C.POINTER(_I)]),
     "pwn_hip_debug_converter_points": (_I, [_VP, _I, _I, _VP, _F, _VP, _I, _VP]),
     "pwn_hip_debug_stats_from_integral": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _I]),
     "pwn_hip_debug_stats_from_integral_lean": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _F, _VP, _I]),

@@ -164,7 +164,7 @@ struct pwn_hip_cloud {
   }
   // the whole core, the size word and nothing else (but the index image): such a cloud may retire into the context's pool
   bool plain() const { return front.P3 && front.Nc && front.Om && count && front.held() == kArrCore && back.held() == 0; }
-  size_t core_bytes() const { return front.core_bytes() + idximg.cap * sizeof(int); }      // what the pool's budget counts
+  size_t core_bytes() const { return front.core_bytes() + (idximg.cap + stripoff.cap) * sizeof(int); }      // what the pool's budget counts
   // What the arrays mean right now; the owners above say nothing about that
   CloudContent content;
   CloudView view() const { CloudView v = { d, sb, content.n, sb.G ? content.n_gauss : 0 }; if (!content.stats) v.d.St = nullptr; return v; }
@@ -173,6 +173,14 @@ struct pwn_hip_cloud {
   // returns this image: every point falls back on its own pixel (the round trip moves it by < 0.01 pixel and its depth not at all), so batch
   // alignments take it as the current index image and skip that projection.  Anything that changes the points invalidates it.
   DevBuf<int> idximg;
+  // The strip offsets that index image was counted from: [rows][cols / 64] words, entry (r, s) = the index of the first valid pixel of columns
+  // [64 s, 64 s + 64) of row r.  The converter's single-pass front end writes them here (FrameDesc::rowoff) instead of into its workspace when
+  // cols is a multiple of 64 and the cloud receives its own index image; with them an index is a table word plus a rank among 64 depths
+  // (CurDepthSrc::strips).  stripoff_filled: the conversion that is making (or made) the index image fills the table -- set by convert_prepare,
+  // taken back by a launch that runs the three-kernel front end, cleared by every replace.  The table is no part of the flat form: an imported
+  // cloud has none.
+  DevBuf<int> stripoff; bool stripoff_filled = false;
+  bool strip_table() const { return content.idx_valid && stripoff_filled && stripoff; }      // valid exactly as long as the index image it belongs to
   const pwn_hip_ctx* owner = nullptr;    // the context it was created on (pwn_hip_project_merge_batch refuses another context's cloud)
 };
 
@@ -269,6 +277,10 @@ struct pwn_hip_ctx {
   // on them (pwn_hip_debug_cur_depth_sub_batches)
   DevBuf<const uint16_t*> cur_raw_dev; HostBuf<const uint16_t*> cur_raw_host;
   int cur_depth_subs = 0;
+  // the strip offsets of those clouds, per pair (CurDepthSrc::strips), and how many of those sub-batches ranked the current index from them
+  // (pwn_hip_debug_strip_index_sub_batches)
+  DevBuf<const int*> cur_strip_dev; HostBuf<const int*> cur_strip_host;
+  int strip_index_subs = 0;
   // The merged closure (pwn_hip_merge_depth_images, pwn_hip_project_merge_batch), allocated by the first such call: the staging images of
   // host-side `merged` / `weights` ([0, N) and [N, 2N)) and behind them merge_planes = min(max_batch, kMergePlanesMax) depth planes of N words;
   // a call with more images runs in chunks of that many.  Per image of a call: its plane's address, its cloud, its projector matrix; the
@@ -303,7 +315,8 @@ bool latency_shape(const pwn_hip_ctx* ctx, int nb, int m) { return (long long)nb
 template <bool SAME_T, bool FULL_H, bool SYM>
 void launch_corr_linearize_s(const pwn_hip_ctx* ctx, const PairLaunch& L, unsigned tag, int usePrevTc, int ownRef) {
   if (latency_shape(ctx, L.nb, L.m)) hipLaunchKernelGGL((k_corr_linearize_lat<SAME_T, FULL_H, SYM>), dim3(L.nb, L.m), dim3(kLatBlock), 0, L.st, L.pr, *L.ap, tag, usePrevTc, ownRef);
-  else if (L.cd) hipLaunchKernelGGL((k_corr_linearize<SAME_T, FULL_H, SYM, kPixPerThread, true>), dim3(L.nb, L.m), dim3(kAlignBlock), 0, L.st, L.pr, *L.ap, tag, usePrevTc, ownRef, *L.cd);
+  else if (L.cd && L.cd->strips) hipLaunchKernelGGL((k_corr_linearize<SAME_T, FULL_H, SYM, kPixPerThread, true, true>), dim3(L.nb, L.m), dim3(kAlignBlock), 0, L.st, L.pr, *L.ap, tag, usePrevTc, ownRef, *L.cd);
+  else if (L.cd) hipLaunchKernelGGL((k_corr_linearize<SAME_T, FULL_H, SYM, kPixPerThread, true>),dim3(L.nb, L.m), dim3(kAlignBlock), 0, L.st, L.pr, *L.ap, tag, usePrevTc, ownRef, *L.cd);
   else hipLaunchKernelGGL((k_corr_linearize<SAME_T, FULL_H, SYM>), dim3(L.nb, L.m), dim3(kAlignBlock), 0, L.st, L.pr, *L.ap, tag, usePrevTc, ownRef, NoCurDepthSrc());
 }
 template <bool SAME_T, bool FULL_H>
@@ -647,6 +660,8 @@ int ensure_desc(pwn_hip_ctx* ctx, int n) {
   HIPCHK(ctx, ctx->counts_host.ensure(B + 1), PWN_HIP_ERR_ALLOCATION);
   HIPCHK(ctx, ctx->cur_raw_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
   HIPCHK(ctx, ctx->cur_raw_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->cur_strip_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->cur_strip_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
   HIPCHK(ctx, ctx->match_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
   HIPCHK(ctx, ctx->match_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
   HIPCHK(ctx, ctx->stats_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
@@ -662,6 +677,7 @@ int ensure_desc(pwn_hip_ctx* ctx, int n) {
 // launches of at least this many frames take the single-pass strip kernel; measured on MI355X at VGA, three kernels vs single pass: 8 frames 0.20 vs
 // 0.27 ms, 16 frames 0.38 vs 0.35, 32 frames 0.74 vs 0.58
 constexpr int kSinglePassMinFrames = 16;
+bool single_pass_launch(int n) { return n >= kSinglePassMinFrames; }
 // the stats pass over n frames
 void launch_stats(const ConvertParams& cp, const FrameDesc* fr, int n, hipStream_t st) {
   const unsigned perFrame = (unsigned)cp.rows * (unsigned)((cp.cols + 255) / 256);
@@ -711,7 +727,7 @@ int launch_front_end(pwn_hip_ctx* ctx, const ConvertParams& cp, int base, int n,
   return PWN_HIP_OK;
 }
 int launch_convert(pwn_hip_ctx* ctx, const ConvertParams& cp, int base, int n, hipStream_t st, int* fault_out = nullptr) {
-  if (int rc = launch_front_end(ctx, cp, base, n, st, n >= kSinglePassMinFrames, fault_out)) return rc;
+  if (int rc = launch_front_end(ctx, cp, base, n, st, single_pass_launch(n), fault_out)) return rc;
   { StageTimer t(ctx, "stats", st);
     launch_stats(cp, ctx->frames_dev + base, n, st); }
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
@@ -747,6 +763,7 @@ int cloud_replace(pwn_hip_ctx* ctx, pwn_hip_cloud* c, bool keep_stats, bool plan
   if (!planes && c->d.OmN) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH); c->drop_omega_n(); }
   if (cls) { std::memcpy(c->d.omN, cls->omN, sizeof(cls->omN)); c->d.clsThr = cls->clsThr; }
   c->content.replace(keep_stats, key, promised);
+  c->stripoff_filled = false;      // the table went with the index image it belonged to; a conversion that fills it says so after this (convert_prepare)
   return PWN_HIP_OK;
 }
 // Commit: the new content has arrived, `n` points of it; with `key` the index image came with them, without it a promised one stands.  (The
@@ -952,6 +969,18 @@ int convert_prepare(pwn_hip_ctx* ctx, const ConvertCall& c, const std::vector<in
       HIPCHK(ctx, cl->idximg.ensure(N), PWN_HIP_ERR_ALLOCATION);
     }
     ctx->frames_host[i].index = cl->idximg;
+    // ... and so do the strip offsets it is counted from, where a single-pass launch will leave a table of 64-column strips that line up with
+    // the rows: the front end's kernels get the cloud's buffer for their workspace slot, and run the code they ran (a three-kernel launch
+    // writes its [rows] offsets there and takes the promise back: convert_enqueue)
+    if (cp.hasOffset == 0 && c.cols % kIR_Cols == 0) {
+      const size_t words = (size_t)c.rows * (size_t)strips_of(c.cols);
+      if (cl->stripoff.cap < words) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+        HIPCHK(ctx, cl->stripoff.ensure(words), PWN_HIP_ERR_ALLOCATION);
+      }
+      ctx->frames_host[i].rowoff = cl->stripoff;
+      cl->stripoff_filled = true;
+    }
     if (sc.step) { ctx->scale_host[i].src = src; ctx->scale_host[i].dst = scaled; }
     else if (raw) { ctx->frames_host[i].raw = static_cast<const uint16_t*>(src); ctx->frames_host[i].raw_scale = c.depth_scale; }      // converted on the fly by the kernels
   }
@@ -1002,7 +1031,10 @@ int launch_gaussians(pwn_hip_ctx* ctx, const ConvertJob& job, int base, int m, h
 }
 // the kernels of frames [base, base + m) of the job on st: the box mean into the frames' slots first when the job down-samples, the Gaussians last
 // when it makes them
+// the clouds of frames [base, base + m) get no strip table after all: their launch runs the three-kernel front end, whose offsets are per row
+void no_strip_tables(const ConvertJob& job, int base, int m) { for (int i = 0; i < m; ++i) job.clouds[(size_t)(base + i)]->stripoff_filled = false; }
 int convert_enqueue(pwn_hip_ctx* ctx, const ConvertJob& job, int base, int m, hipStream_t st, int* fault_out = nullptr) {
+  if (!single_pass_launch(m)) no_strip_tables(job, base, m);
   if (job.scale.step) { if (int rc = launch_depth_scale(ctx, job.scale, job.raw, job.depth_scale, base, m, st)) return rc; }
   if (int rc = launch_convert(ctx, job.cp, base, m, st, fault_out)) return rc;
   if (job.gauss.on) return launch_gaussians(ctx, job, base, m, st);
@@ -1112,6 +1144,7 @@ int debug_front_end_impl(pwn_hip_ctx* ctx, const ConvertCall& call, bool single_
   ConvertJob job;
   if (int rc = convert_prepare(ctx, call, slot, direct, job)) return rc;
   if (job.host_input) { if (int rc = convert_stage_frames(ctx, job, 0, n, ctx->stream)) return rc; }
+  if (!single_pass) no_strip_tables(job, 0, n);
   if (lean == PWN_HIP_FRONT_END_LEAN_PLANES) job.cp.lean = 1;      // ten planes; PWN_HIP_FRONT_END_LEAN_GROUPED keeps convert_prepare's kLeanGrouped and
                                                                    // integral_out receives the slot as stored (three arrays of records, ig_at)
   // The one thing queued here that a convert call does not queue (there k_stats writes normals and matrices): with lean = 0 the clouds get points
@@ -1563,6 +1596,12 @@ int pwn_hip_debug_projection_fallbacks(pwn_hip_ctx* ctx, int* calls) {
 int pwn_hip_debug_cur_depth_sub_batches(pwn_hip_ctx* ctx, int* sub_batches) {
   if (!ctx || !sub_batches) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   *sub_batches = ctx->cur_depth_subs;
+  return PWN_HIP_OK;
+}
+// Test hook: those of them that also ranked the current indices from the clouds' strip offsets (CurDepthSrc::strips)
+int pwn_hip_debug_strip_index_sub_batches(pwn_hip_ctx* ctx, int* sub_batches) {
+  if (!ctx || !sub_batches) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  *sub_batches = ctx->strip_index_subs;
   return PWN_HIP_OK;
 }
 // Test hook: the converter's stats pass (k_stats, launched as launch_convert launches it) on caller-supplied integral planes, index and
@@ -2583,7 +2622,7 @@ static int align_check_and_plan(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& 
   if (!ctx || !c.p || !c.refs || !c.curs || (!c.results && !c.records) || c.n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (int rc = check_image(ctx, c.p->rows, c.p->cols)) return rc;
   ctx->img.invalidate();                  // whatever happens below (set again on success)
-  ctx->last_pairs = 0; ctx->cur_depth_subs = 0;
+  ctx->last_pairs = 0; ctx->cur_depth_subs = 0; ctx->strip_index_subs = 0;
   if (int rc = check_align_params(ctx, c.p)) return rc;
   if (int rc = start_align_attempt(ctx, run.robust)) return rc;
   run.want_scores = c.scores != nullptr || (c.records && (c.match_records || c.closure_records));
@@ -2644,6 +2683,9 @@ static int align_describe_pairs(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& 
     if (c.cur_depth && run.any_own) {
       for (int i = 0; i < n; ++i) ctx->cur_raw_host[i] = static_cast<const uint16_t*>(c.cur_depth->frames[i]);
       HIPCHK(ctx, hipMemcpyAsync(ctx->cur_raw_dev, ctx->cur_raw_host, sizeof(const uint16_t*) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+      // the strip offsets beside them (whether a sub-batch reads them is decided when its conversions have been queued: align_enqueue_sub)
+      for (int i = 0; i < n; ++i) ctx->cur_strip_host[i] = c.curs[i]->stripoff;
+      HIPCHK(ctx, hipMemcpyAsync(ctx->cur_strip_dev, ctx->cur_strip_host, sizeof(const int*) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
     }
     if (run.want_scores) HIPCHK(ctx, hipMemsetAsync(ctx->match_dev, 0, sizeof(MatchAcc) * n, ctx->stream), PWN_HIP_ERR_COPY);
   }
@@ -2678,6 +2720,7 @@ static int align_enqueue_sub(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& run
   if (cur_depth) {
     const ConvertParams& cp = *c.cur_depth->cp;
     cd.raw = ctx->cur_raw_dev + base; cd.scale = c.cur_depth->scale; cd.iKRt = cp.iKRt; cd.hasOffset = cp.hasOffset; cd.offset = cp.offset;
+    cd.strips = nullptr; cd.minD = cp.minD; cd.maxD = cp.maxD;
     ++ctx->cur_depth_subs;
   }
   const PairLaunch L = { &run.ap, run.nb, run.omSym, m, st, ctx->pairs_dev + base, run.robust ? ctx->zdepth_ws + s0 * ctx->N : nullptr, cur_depth ? &cd : nullptr };
@@ -2693,6 +2736,13 @@ static int align_enqueue_sub(pwn_hip_ctx* ctx, const AlignCall& c, AlignRun& run
     run.slot0.cur_tag = tag0; run.slot0.ref_tag = lastRefTag;
   }
   if (c.hooks && c.hooks->pre_sub) { if (int rc = c.hooks->pre_sub(base, m, k, st)) return rc; }
+  // ... and the current indices from the strip offsets, when every current cloud's conversion -- queued by the hook above, which knows how it
+  // launched them -- leaves the table of its index image (L.cd points to cd)
+  if (cur_depth) {
+    bool tables = true;
+    for (int i = 0; i < m && tables; ++i) tables = c.curs[base + i]->strip_table();
+    if (tables) { cd.strips = ctx->cur_strip_dev + base; ++ctx->strip_index_subs; }
+  }
   // a sub-batch that holds a prior takes the priors form of the step, with the terms of this iteration's transforms in front of it
   const bool subPriors = run.priors && c.priors->first[base + m] > c.priors->first[base];
   const PairPriors pp = { ctx->prior_first_dev + base, ctx->prior_terms_dev };

@@ -203,11 +203,17 @@ struct AlignParams {
 // 2-byte raw depth, coalesced, instead of gathering the 12-byte point, and evaluates the converter's own expression (converter_point: the bits
 // k_stats stored).  raw[y] belongs to pair y of the launch, like pairs[y]; the other members are those of the step's conversions.  It sits next to
 // the descriptors, not in them: PairDesc and AlignParams keep their layout, and every other kernel its code.
+// STRIP_IDX: the index goes the same way.  The single-pass front end gave valid pixel (row, col) the index rowoff[row][col / 64] + (valid pixels of
+// the strip to its left), with cols a multiple of 64 (unproject_integral_body), and a cloud keeps that table of strip offsets beside its index
+// image.  A wave of the fused pass covers the 64 pixels of one (row, strip), entry pix >> 6 of the table, and holds their raw depths: one table
+// word, the converter's range test and one ballot stand for the 4-byte-per-pixel index stream.
 struct CurDepthSrc {
   const uint16_t* const* raw;   // per pair of the launch: the uint16 frame the current cloud was converted from (rows x cols, the aligner's size)
   float scale;                  // metres per raw unit
   Mat4 iKRt;                    // ConvertParams::iKRt
   int hasOffset; Mat4 offset;   // ConvertParams::hasOffset / offset
+  const int* const* strips;     // per pair of the launch: the current cloud's strip offsets [rows][cols / 64]; nullptr: the launch reads the index images
+  float minD, maxD;             // ConvertParams::minD / maxD: the range the converter counted a pixel valid in
 };
 struct NoCurDepthSrc {};        // what the other instantiations take in its place
 
@@ -1715,7 +1721,7 @@ struct Candidate {
   float4 rP, rN, cP, cN;
   int ci;
   bool valid;
-  unsigned craw;      // CUR_DEPTH: the pixel's raw depth stands for cP.xyz (CurDepthSrc), one register instead of three
+  unsigned craw;      // CUR_DEPTH: the pixel's raw depth (STRIP_IDX: its depth in metres, as bits) stands for cP.xyz (CurDepthSrc), one register instead of three
 };
 // The descriptor's pointers are generic to the compiler: flat_* loads, which count on BOTH the vector-memory and the LDS counter, so
 // every wait for an LDS accumulator update would also wait for the gathers of the next pixel that are meant to stay in flight.
@@ -1797,7 +1803,8 @@ __device__ __forceinline__ void candidate_consume(const PairDesc& pd, const Pair
 // the finder's existing correspondences at the final transform, aligner.cpp:165-170).
 // CUR_DEPTH: the pairs' current clouds own their index images (curidx) and their frames are at hand (cd, CurDepthSrc): the current point is
 // recomputed from the pixel's depth instead of loaded -- 2 coalesced bytes per pixel in place of a 12-byte gather per candidate, the same bits.
-template <bool SAME_T, bool FULL_H, bool SYM = false, int PPT = kPixPerThread, bool CUR_DEPTH = false>
+// STRIP_IDX (with CUR_DEPTH): the current index is ranked from the depths the wave holds and the cloud's strip offsets (cd.strips), curidx is not read.
+template <bool SAME_T, bool FULL_H, bool SYM = false, int PPT = kPixPerThread, bool CUR_DEPTH = false, bool STRIP_IDX = false>
 __global__ void __launch_bounds__(kAlignBlock, 1) k_corr_linearize(const PairDesc* __restrict__ pairs, AlignParams ap, unsigned tag, int usePrevTc, int ownRefIndex,
                                                                    std::conditional_t<CUR_DEPTH, CurDepthSrc, NoCurDepthSrc> cd) {
   const PairDesc& pd = pairs[blockIdx.y];
@@ -1822,13 +1829,40 @@ __global__ void __launch_bounds__(kAlignBlock, 1) k_corr_linearize(const PairDes
   gptr<const uint16_t> craw = nullptr;                    // CUR_DEPTH: the pair's current frame
   int row = 0, col = 0;                                   // CUR_DEPTH: row and column of pixel j
   if constexpr (CUR_DEPTH) { craw = as_global(as_global(cd.raw)[blockIdx.y]); row = pix0 / ap.cols; col = pix0 - row * ap.cols; }
+  static_assert(CUR_DEPTH || !STRIP_IDX, "the strip ranks are counted on the depths of the depth source");
+  // STRIP_IDX: the offsets of the tile's PPT * 4 strips, one per lane -- lane 4 j + w holds the offset (>= 0) of the strip wave w covers in turn j; the
+  // lanes behind them and the strips behind the image hold -1.  One 128-byte load per wave stands for the index stream of its 512 pixels.
+  constexpr int kWaves = kAlignBlock / 64;
+  static_assert((PPT + 1) * kWaves <= 64, "the strips of a tile and of the turn of look-ahead behind it are lanes of one wave");
+  int tileoff = -1;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if constexpr (STRIP_IDX) {
+    const unsigned lane = lane_id(), strip = blockIdx.x * (PPT * kWaves) + lane;
+    if (lane < (unsigned)(PPT * kWaves) && strip < ((unsigned)N >> 6)) tileoff = as_global(as_global(cd.strips)[blockIdx.y])[strip];
+  }
   auto load_indices = [&](int j, int& ri, int& ci, unsigned& cr) {
     const int pix = pix0 + j * kAlignBlock;
     ri = -1; ci = -1;
     if (j < PPT && pix < N) {
       ri = ownRefIndex ? q.refidx0[(unsigned)pix] : z32_index(q.zref[(unsigned)pix], tag);      // wave-uniform choice
-      ci = q.curidx[(unsigned)pix];
+      if constexpr (!STRIP_IDX) ci = q.curidx[(unsigned)pix];
       if constexpr (CUR_DEPTH) cr = craw[(unsigned)pix];    // 2 bytes per pixel, coalesced: what the 12-byte gather of the current point is traded for
+    }
+  };
+  // STRIP_IDX: the index of pixel j, whose raw depth has arrived -- the front end's expression (unproject_integral_body: the strip's offset + the valid
+  // pixels of the strip in the lanes below, -1 for a pixel out of range).  Every lane of the wave votes; a turn without pixels (offset -1) votes false.
+  // The depth in metres is handed on in cr (its bits): the point of the pixel is computed from it a turn later.
+  auto cur_index = [&](int j, int ci, unsigned& cr) {
+    if constexpr (STRIP_IDX) {
+      const int off = __builtin_amdgcn_readlane(tileoff, kWaves * j + wave);      // wave-uniform
+      const float d = raw_to_metres(cr, cd.scale);
+      const bool valid = off >= 0 && depth_in_range(d, cd.minD, cd.maxD);
+      const unsigned long long bal = __builtin_amdgcn_ballot_w64(valid);
+      const int idx = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, (unsigned)off));
+      cr = __float_as_uint(d);
+      return valid ? idx : -1;
+    } else {
+      return ci;
     }
   };
   int ri1, ci1, ri2, ci2;
@@ -1836,15 +1870,18 @@ __global__ void __launch_bounds__(kAlignBlock, 1) k_corr_linearize(const PairDes
   load_indices(0, ri1, ci1, cr1);
   load_indices(1, ri2, ci2, cr2);
   Candidate nxt;
+  ci1 = cur_index(0, ci1, cr1);
   candidate_load<CUR_DEPTH>(q, ri1, ci1, nref, ncur, nxt, cr1);
 #pragma unroll 1
   for (int j = 0; j < PPT; ++j) {
     Candidate cur = nxt;
+    ci2 = cur_index(j + 1, ci2, cr2);
     candidate_load<CUR_DEPTH>(q, ri2, ci2, nref, ncur, nxt, cr2);      // gathers of pixel j+1: in flight during the arithmetic below
     load_indices(j + 2, ri2, ci2, cr2);                   // indices of pixel j+2
     if constexpr (CUR_DEPTH) {                            // the current point of pixel j = (row, col), as the converter stored it
       if (cur.valid) {
-        const Vec3 p = converter_point(cd.iKRt, cd.hasOffset, cd.offset, col, row, raw_to_metres(cur.craw, cd.scale));
+        const float d = STRIP_IDX ? __uint_as_float(cur.craw) : raw_to_metres(cur.craw, cd.scale);
+        const Vec3 p = converter_point(cd.iKRt, cd.hasOffset, cd.offset, col, row, d);
         cur.cP.x = p.x; cur.cP.y = p.y; cur.cP.z = p.z;
       }
     }

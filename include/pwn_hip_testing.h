@@ -55,6 +55,11 @@ int pwn_hip_debug_project_pairs(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* 
  * bits.  Number of sub-batches of the context's last batch alignment that ran this way (0 after every other alignment call, after the _scaled
  * step, and after a step on host frames): */
 int pwn_hip_debug_cur_depth_sub_batches(pwn_hip_ctx* ctx, int* sub_batches);
+/* Of those sub-batches, the ones whose fused pass did not load the current clouds' index images either: where cols is a multiple of 64 and the
+ * conversions of the sub-batch's current frames ran the single-pass strip front end (launches of at least 16 frames), every current cloud keeps
+ * that front end's table of strip offsets, and a pixel's index is the table word of its 64-column strip plus its rank among the strip's valid
+ * depths -- the converter's expression, the same bits.  0 wherever the hook above reads 0, for other widths and for smaller launches: */
+int pwn_hip_debug_strip_index_sub_batches(pwn_hip_ctx* ctx, int* sub_batches);
 /* The expression that pass evaluates, on the host (no GPU, no context): for every pixel (r, c) of a rows x cols uint16 frame with
  * 0 <= index_image[r][c] < capacity, points[3 * index] = the point the converter stores for that pixel -- PinholePointProjector::unProject of
  * (c, r, depth_scale * raw), then p's sensor offset if it is not the identity.  Other entries of points are left alone. */
