@@ -1021,18 +1021,13 @@ class Aligner:
         p = self.params()
         r = AlignResult()
         q = AlignStatistics() if statistics else None
-        if self._priors:
-            # priors change the normal equations of every iteration (aligner.cpp:96-108); _computeStatistics still runs afterwards (:127)
-            arr = (Prior * len(self._priors))()
-            for a, (kind, mean, reft, info) in zip(arr, self._priors):
-                a.kind = kind; _set(a.mean, mean, 4); _set(a.reference_transform, reft, 4); _set(a.information, info, 6)
-            self.ctx.check(self.ctx._L.pwn_hip_align_with_priors_ex(self.ctx.h, C.byref(p), self._referenceCloud.h, self._currentCloud.h, len(arr), arr,
-                                                                    C.byref(r), C.byref(q) if statistics else None))
-        elif statistics:
-            refs = (C.c_void_p * 1)(self._referenceCloud.h); curs = (C.c_void_p * 1)(self._currentCloud.h)
-            self.ctx.check(self.ctx._L.pwn_hip_align_batch_ex(self.ctx.h, C.byref(p), 1, refs, curs, None, C.byref(r), 0.0, None, C.byref(q)))
-        else:
-            self.ctx.check(self.ctx._L.pwn_hip_align(self.ctx.h, C.byref(p), self._referenceCloud.h, self._currentCloud.h, C.byref(r)))
+        # the call the binding makes: priors change the normal equations of every iteration (aligner.cpp:96-108), _computeStatistics runs
+        # afterwards (:127); without priors it is pwn_hip_align_batch_ex for one pair
+        arr = (Prior * len(self._priors))() if self._priors else None
+        for a, (kind, mean, reft, info) in zip(arr or (), self._priors):
+            a.kind = kind; _set(a.mean, mean, 4); _set(a.reference_transform, reft, 4); _set(a.information, info, 6)
+        self.ctx.check(self.ctx._L.pwn_hip_align_with_priors_ex(self.ctx.h, C.byref(p), self._referenceCloud.h, self._currentCloud.h, len(self._priors), arr,
+                                                                C.byref(r), C.byref(q) if statistics else None))
         if statistics:
             self._omega = _from_colmajor(q.omega, 6); self._mean = np.array(list(q.mean), np.float32)
             self._translationalEigenRatio, self._rotationalEigenRatio = q.translational_eigen_ratio, q.rotational_eigen_ratio

@@ -2920,97 +2920,22 @@ int pwn_hip_align_with_priors(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p,
                               const pwn_hip_prior* priors, pwn_hip_align_result* result) {
   return pwn_hip_align_with_priors_ex(ctx, p, ref, cur, n_priors, priors, result, nullptr);
 }
-// n_priors > 0 (pwn_hip_align_with_priors_ex): the one pair of `call` with its result and (optional) statistics, the loop driven from the host; robust: see align_batch_once
-static int align_with_priors_once(pwn_hip_ctx* ctx, const AlignCall& call, int n_priors, const pwn_hip_prior* priors, bool robust) {
-  const pwn_hip_aligner_params* p = call.p; const pwn_hip_cloud* ref = call.refs[0]; const pwn_hip_cloud* cur = call.curs[0];
-  if (!ctx || !p || !ref || !cur || !priors || !call.results) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  if (int rc = check_align_params(ctx, p)) return rc;
-  std::vector<PriorHost> pr(n_priors);
-  for (int i = 0; i < n_priors; ++i) pr[i] = prior_host_from(priors[i]);
-  if (int rc = check_pair_points(ctx, ref, cur)) return rc;
-  const AlignParams ap = make_align_params(ctx, p);
-  hipStream_t st = ctx->stream;
-  if (int rc = start_align_attempt(ctx, robust)) return rc;
-  fill_pair(ctx, 0, 0, ref, cur, nullptr, robust);
-  const PairLaunch L = { &ap, align_nblocks(p->rows * p->cols), cur->d.omSym, 1, st, ctx->pairs_dev, ctx->pairs_host[0].zdepth };
-  ctx->img.invalidate();
-  PairState& hs = ctx->state_host[0];
-  std::memset(&hs, 0, sizeof(hs));
-  Mat4 T = mat4_from(p->initial_guess); set_last_row(T);
-  Mat4 KRtCur, iKRt; Mat3 iK;
-  projector_matrices(ap.K, mat4_from(p->current_sensor_offset), KRtCur, iKRt, iK);
-  set_pose(hs, T, ap, KRtCur);
-  HIPCHK(ctx, hipEventRecord(ctx->t0, st), PWN_HIP_ERR_LAUNCH);
-  HIPCHK(ctx, hipMemcpyAsync(ctx->pairs_dev, ctx->pairs_host, sizeof(PairDesc), hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipMemcpyAsync(ctx->state_ws, &hs, sizeof(PairState), hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
-  // z-buffer tags come from the context's running supply like the batch path's (a smaller tag wins atomicMin: fixed tags would
-  // leave words behind that beat a later call's)
-  Slot0Pair slot0; slot0.ref_cloud = ref; slot0.cur_cloud = cur;
-  if (int rc = take_tags32(ctx, (unsigned)std::max(1, p->outer_iterations), &slot0.cur_tag)) return rc;
-  const unsigned tag0 = slot0.cur_tag; slot0.ref_tag = tag0 - (unsigned)std::max(0, p->outer_iterations - 1);
-  if (int rc = launch_project_cur(ctx, L, cur->d.capacity, tag0)) return rc;
-  int it = 0;
-  for (int i = 0; i < p->outer_iterations; ++i) {
-    const unsigned tag = tag0 - (unsigned)i;
-    set_last_row(T);                                                                 // aligner.cpp:72
-    set_pose(hs, T, ap, KRtCur);                                                     // :73
-    Mat4 invT = iso_inverse(T);                                                      // :84
-    for (int k = 0; k < p->inner_iterations; ++k, ++it) {
-      set_last_row(invT);                                                            // :86
-      hs.invT = invT;
-      HIPCHK(ctx, hipMemcpyAsync(ctx->state_ws, &hs, sizeof(PairState), hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
-      if (k == 0) { if (int rc = launch_project(ctx, L, ref->d.capacity, 0, tag)) return rc; }
-      if (k == 0) launch_corr_linearize<true, true>(ctx, L, tag, 0, 0);
-      else launch_corr_linearize<false, true>(ctx, L, tag, 0, 0);
-      hipLaunchKernelGGL(k_reduce_pairs, dim3(1), dim3(256), 0, st, ctx->pairs_dev, L.nb, ctx->stats_dev);
-      HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
-      HIPCHK(ctx, hipMemcpyAsync(ctx->stats_host, ctx->stats_dev, sizeof(SolveOut), hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
-      HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
-      const SolveOut& so = ctx->stats_host[0];
-      hs.chi2[it] = so.chi2; hs.inliers[it] = so.inliers; hs.ncorr[it] = so.ncorr; hs.ncand[it] = so.ncand;      // the traces k_solve_update keeps
-      float H[36], b[6];
-      std::memcpy(H, so.H, sizeof(H)); std::memcpy(b, so.b, sizeof(b));
-      for (int d = 0; d < 6; ++d) H[d + 6 * d] = H[d + 6 * d] + 1.0f;                // :92
-      for (int d = 0; d < 6; ++d) H[d + 6 * d] = H[d + 6 * d] + 1000.0f;             // :94
-      for (int j = 0; j < n_priors; ++j) prior_accumulate(pr[j], invT, H, b);        // :97-108
-      float nbv[6], dx[6];
-      for (int d = 0; d < 6; ++d) nbv[d] = -b[d];
-      ldlt_solve6(H, nbv, dx);                                                       // :110
-      invT = iso_mul(v2t(dx), invT);                                                 // :111-112
-    }
-    T = iso_inverse(invT);                                                           // :115-117
-    float v[6]; t2v(T, v); T = v2t(v); set_last_row(T);
-  }
-  if (call.statistics && p->outer_iterations > 0) {
-    // Aligner::_computeStatistics (aligner.cpp:127,152-199) runs after the loop whether or not priors exist: H + I without the prior terms (:168-170)
-    hs.invTcorrPrev = hs.invTcorr;
-    hs.invT = iso_inverse(T); set_last_row(hs.invT);                                  // :165-167
-    HIPCHK(ctx, hipMemcpyAsync(ctx->state_ws, &hs, sizeof(PairState), hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
-    launch_statistics(ctx, L, slot0.ref_tag, ctx->stats_dev);
-    HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->stats_host, ctx->stats_dev, sizeof(SolveOut), hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
-    HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
-  }
-  HIPCHK(ctx, hipEventRecord(ctx->t1, st), PWN_HIP_ERR_LAUNCH);
-  HIPCHK(ctx, hipEventSynchronize(ctx->t1), PWN_HIP_ERR_LAUNCH);
-  if (int rc = take_align_fault(ctx)) return rc;
-  float ms = 0.f; (void)hipEventElapsedTime(&ms, ctx->t0, ctx->t1);
-  hs.T = T; hs.it = it;
-  fill_result(*call.results, hs, ref, cur, ms);
-  if (call.statistics) fill_statistics(*call.statistics, p->outer_iterations > 0 ? ctx->stats_host : nullptr, T);
-  ctx->img.set(ap, slot0, true, false);
-  ctx->last_pairs = 1; ctx->last_states_on_host = true;      // the host drove the loop: no step traces (outer = 0)
-  return PWN_HIP_OK;
-}
+// One pair of pwn_hip_align_batch_priors: the caller's n_priors records are the pair's list.  With priors the call is refused while the convergence
+// setting is on (include/pwn_hip.h: a stated limit of this entry point) and for the null arguments it always refused, nothing touched.
 int pwn_hip_align_with_priors_ex(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, const pwn_hip_cloud* ref, const pwn_hip_cloud* cur, int n_priors,
                                  const pwn_hip_prior* priors, pwn_hip_align_result* result, pwn_hip_align_statistics* statistics) {
+  if (n_priors > 0 && ctx && ctx->stop.enabled) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "a single call with priors runs a fixed iteration count: switch the convergence setting off");
   pwn_hip_cloud* r[1] = { const_cast<pwn_hip_cloud*>(ref) };
   pwn_hip_cloud* c[1] = { const_cast<pwn_hip_cloud*>(cur) };
   AlignCall call = align_call(p, 1, r, c, nullptr, result);
   call.statistics = statistics;
   if (n_priors <= 0) return align_batch_impl(ctx, call);
-  if (ctx && ctx->stop.enabled) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "the loop with priors runs a fixed iteration count: switch the convergence setting off");
-  return repeat_once(ctx, kSettleFault, [&](bool robust) { return align_with_priors_once(ctx, call, n_priors, priors, robust); });
+  if (!ctx || !p || !ref || !cur || !priors || !result) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  const int first[2] = { 0, n_priors };
+  pwn_hip_pair_priors list; list.first = first; list.priors = priors;
+  if (!prior_list_ok(1, list.first, list.priors)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "bad prior list: n_priors records of kind 0 or 1");
+  call.priors = &list;
+  return align_batch_impl(ctx, call);
 }
 int pwn_hip_align_batch_ex(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, int n, pwn_hip_cloud* const* refs, pwn_hip_cloud* const* curs,
                            const float* guesses, pwn_hip_align_result* results, float threshold, pwn_hip_match_result* scores,

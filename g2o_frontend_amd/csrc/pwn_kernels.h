@@ -2312,8 +2312,8 @@ __global__ void __launch_bounds__(64) k_pair_statistics(const PairDesc* __restri
   __syncthreads();
   if (threadIdx.x < kPairStatsFloats) reinterpret_cast<float*>(out + blockIdx.x)[threadIdx.x] = reinterpret_cast<const float*>(&rec)[threadIdx.x];
 }
-// The prior terms of one pair per workgroup (pwn_stats.h: prior_terms, the text pwn_hip_prior_terms and the host-driven loop expand), for each
-// prior of the pair in list order, at the pair's Linearizer::_T as the last step stored it (after set_last_row, what the host loop passes).  The
+// The prior terms of one pair per workgroup (pwn_stats.h: prior_terms, the text pwn_hip_prior_terms and prior_accumulate expand on the host), for each
+// prior of the pair in list order, at the pair's Linearizer::_T as the last step stored it (after set_last_row, aligner.cpp:86).  The
 // 24 error evaluations of the numeric Jacobians, the rows of the elimination and the 36 elements of each product go to lanes; every array is in
 // LDS (PriorWork).  A pair without priors, and a frozen pair under an enabled StopRule, returns at once.  grid = pairs, block = 64
 //   first: per pair of the launch, as for PairPriors; priors: the device copies; terms: one record per prior

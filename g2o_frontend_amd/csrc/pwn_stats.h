@@ -201,8 +201,7 @@ inline void compute_statistics(const float Hin[36], const Mat4& T, float mean[6]
 }
 
 // ---- SE(3) priors (reference pwn_core/se3_prior.{h,cpp}, consumed by aligner.cpp:96-108) ---------------------------
-// One text again: prior_terms is what pwn_hip_prior_terms and the host-driven loop (prior_accumulate) expand through SerialTeam and k_prior_terms
-// through LaneTeam.  The prior is the device copy too (the arrays of a batch call hold PriorHost records).
+// One text again: prior_terms is what pwn_hip_prior_terms and prior_accumulate expand through SerialTeam and k_prior_terms through LaneTeam.  The prior is the device copy too (the arrays of a batch call hold PriorHost records).
 struct PriorHost {
   int kind;            // 0: SE3RelativePrior (error = t2v(invT * mean)), 1: SE3AbsolutePrior (error = t2v(invT * ref^-1 * mean))
   Mat4 mean;           // _priorMean
@@ -264,7 +263,8 @@ PWN_HD bool prior_terms(const Team& tm, const PriorHost& pr, const Mat4& invT, f
   tm.sync();
   return true;
 }
-// Adds the terms of one prior to H and b (the host-driven loop of pwn_hip_align_with_priors*)
+// Adds the terms of one prior to H and b: the host statement of "terms, then add in list order", which the step on the device
+// (k_solve_update_priors) is held against (tests/test_prior_terms_cpu.py); no alignment call runs it
 inline void prior_accumulate(const PriorHost& pr, const Mat4& invT, float H[36], float b[6]) {
   PriorWork ws; float Hp[36], bp[6];
   if (!prior_terms(SerialTeam(), pr, invT, Hp, bp, ws)) return;

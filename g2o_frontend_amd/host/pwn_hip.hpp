@@ -521,15 +521,10 @@ class Aligner {
     if (!_referenceCloud || !_currentCloud) throw Error(PWN_HIP_ERR_INVALID_ARGUMENT, "Aligner: missing cloud");
     const pwn_hip_aligner_params p = params();
     pwn_hip_align_statistics q;
-    if (!_priors.empty()) {                                                       // aligner.cpp:96-108: host-driven loop with the prior terms;
-      _ctx->check(pwn_hip_align_with_priors_ex(_ctx->handle(), &p, _referenceCloud->handle(), _currentCloud->handle(), (int)_priors.size(), _priors.data(),
-                                               &_result, _computeStatistics ? &q : nullptr));     // _computeStatistics runs after it as always (:127)
-    } else if (_computeStatistics) {
-      pwn_hip_cloud* r = _referenceCloud->handle(); pwn_hip_cloud* c = _currentCloud->handle();
-      _ctx->check(pwn_hip_align_batch_ex(_ctx->handle(), &p, 1, &r, &c, nullptr, &_result, 0.f, nullptr, &q));
-    } else {
-      _ctx->check(pwn_hip_align(_ctx->handle(), &p, _referenceCloud->handle(), _currentCloud->handle(), &_result));
-    }
+    // the call the binding makes: the prior terms in every iteration (aligner.cpp:96-108), _computeStatistics after the loop as always (:127);
+    // without priors it is pwn_hip_align_batch_ex for one pair
+    _ctx->check(pwn_hip_align_with_priors_ex(_ctx->handle(), &p, _referenceCloud->handle(), _currentCloud->handle(), (int)_priors.size(),
+                                             _priors.empty() ? nullptr : _priors.data(), &_result, _computeStatistics ? &q : nullptr));
     if (_computeStatistics) {
       std::memcpy(_omega.m, q.omega, sizeof(q.omega)); std::memcpy(_mean.v, q.mean, sizeof(q.mean));
       _translationalEigenRatio = q.translational_eigen_ratio; _rotationalEigenRatio = q.rotational_eigen_ratio;

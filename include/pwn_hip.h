@@ -151,9 +151,9 @@ int pwn_hip_ctx_wait_stream(pwn_hip_ctx* ctx, void* hip_stream);
 /* The other direction: what the caller queues on `hip_stream` from now on runs after everything the context has queued so far.  With
  * pwn_hip_ctx_set_enqueued_callback this lets a collective that sends a call's device `records` be queued while the call's kernels still run. */
 int pwn_hip_ctx_signal_stream(pwn_hip_ctx* ctx, void* hip_stream);
-/* fn(user) is called on the calling thread by every alignment batch call of the context (pwn_hip_align_batch*, pwn_hip_match_batch*,
- * pwn_hip_convert_align_batch_u16; n > 0) after ALL device work of the call has been queued -- records packed, copies back queued -- and before
- * the call waits for it.  The reference's closer loop (pwn_tracker/pwn_closer.cpp:85-111) is sequential; on a GPU the host's share of a step
+/* fn(user) is called on the calling thread by every alignment call of the context (pwn_hip_align_batch*, pwn_hip_match_batch*,
+ * pwn_hip_convert_align_batch_u16 with n > 0; pwn_hip_align and pwn_hip_align_with_priors*, with priors or without) after ALL device work
+ * of the call has been queued -- records packed, copies back queued -- and before the call waits for it.  The reference's closer loop (pwn_tracker/pwn_closer.cpp:85-111) is sequential; on a GPU the host's share of a step
  * (queueing the exchange of the results, fetching and replicating the next `current` cloud) would otherwise run with the device idle between two
  * calls.  Inside fn: other streams and other contexts freely; on THIS context only pwn_hip_ctx_signal_stream, pwn_hip_ctx_wait_stream,
  * pwn_hip_convert_export_begin / _end, pwn_hip_convert_scaled_begin / pwn_hip_convert_end -- no call that converts, aligns or waits on it.  The
@@ -204,9 +204,10 @@ int pwn_hip_cloud_omega_storage(pwn_hip_ctx* ctx, const pwn_hip_cloud* cloud, in
  *   Contract: everything the call returns for a pair frozen after iteration i -- its pwn_hip_align_result (T, error, inliers, iterations, the
  *   traces), its record words, its matchClouds score, its statistics, and for the pair of slot 0 pwn_hip_align_images / pwn_hip_match_score -- equals
  *   bit for bit what the same call returns with outer_iterations = i + 1.  total_time_ms is exempt.
- * Every alignment entry point honours the setting.  The one exception is the host-driven loop with priors: pwn_hip_align_with_priors* with
- * n_priors > 0 returns PWN_HIP_ERR_INVALID_ARGUMENT while the setting is enabled, and touches nothing (pwn_hip_align_batch_priors, whose loop
- * with priors runs on the device, honours it).
+ * Every alignment entry point honours the setting.  The one exception is a stated limit of one entry point: pwn_hip_align_with_priors* with
+ * n_priors > 0 returns PWN_HIP_ERR_INVALID_ARGUMENT while the setting is enabled, and touches nothing.  The loop it runs is the one of
+ * pwn_hip_align_batch_priors, which honours the setting (n = 1 of that call is the way to a single pair with priors under it); lifting the
+ * refusal is left to a change of its own.
  * set: NULL or enabled == 0 switches it off; enabling is refused (INVALID_ARGUMENT, setting unchanged) unless both epsilons are finite and >= 0
  * and min_iterations >= 0. */
 typedef struct pwn_hip_convergence {
@@ -220,8 +221,8 @@ int pwn_hip_ctx_get_convergence(const pwn_hip_ctx* ctx, pwn_hip_convergence* set
 /* The step norms of the pairs [first, first + n) of the context's last alignment call: `iterations` OUTER iterations were executed (the entries
  * [0, iterations) of both traces, zeros behind them), `converged` = 1 when the pair froze under the setting above.  Reads what the call left
  * behind (a call that returned records only fetches the states from the device on the first such request); INVALID_ARGUMENT when the range
- * is not inside the last call's pairs.  After pwn_hip_align_with_priors* with n_priors > 0 the traces are empty (the host drove that loop; after
- * pwn_hip_align_batch_priors they are filled). */
+ * is not inside the last call's pairs.  Every alignment call fills them, pwn_hip_align_with_priors* with n_priors > 0 included (the traces
+ * pwn_hip_align_batch_priors leaves for that pair). */
 typedef struct pwn_hip_align_steps {
   int   iterations;
   int   converged;
@@ -544,11 +545,16 @@ int pwn_hip_convert_align_batch_u16_scaled(pwn_hip_ctx* ctx, const pwn_hip_conve
                                            int rows, int cols, pwn_hip_cloud* const* references, pwn_hip_cloud* const* currents,
                                            const float* initial_guesses, const int* pair_ids, int first_pair_id,
                                            pwn_hip_align_result* results, float* records, int step, float max_depth_cov);
-/* Aligner::align with priors (aligner.cpp:96-108), one pair, the loop driven from the host.  The prior terms (numeric Jacobians,
- * se3_prior.cpp:8-52) change the normal equations of every iteration; this entry point keeps the reference's shape: per
- * iteration the GPU projects, finds correspondences and reduces H, b; the host adds damping + priors, solves and updates.
- * n_priors = 0 is the device-resident loop of pwn_hip_align.  The device-resident loop WITH priors is pwn_hip_align_batch_priors
- * (below; n = 1 of it is this call without the host in the loop, the same bits). */
+/* Aligner::align with priors (aligner.cpp:96-108), one pair: one pair of pwn_hip_align_batch_priors (below), the loop on the device.  The
+ * prior terms (numeric Jacobians, se3_prior.cpp:8-52) change the normal equations of every iteration; the initial guess is p->initial_guess,
+ * the pair's list the n_priors records of `priors` in that order.  n_priors <= 0 is pwn_hip_align.  Like every alignment call it leaves the
+ * step traces (pwn_hip_last_align_steps), with profiling on the stage times (pwn_hip_last_stage_ms), the finder's images of the pair
+ * (pwn_hip_align_images, pwn_hip_match_score), runs a set enqueued callback, takes the current cloud's own index image where it may, and waits
+ * for the device once.  Result, statistics, a following score and the following images are bit for bit those of the loop the host once
+ * drove behind this entry point (one wait per iteration, no traces, no stage times, no callback), for every call that loop accepted.
+ * Refused with PWN_HIP_ERR_INVALID_ARGUMENT, nothing touched: a NULL ctx, p, cloud or result; with n_priors > 0 also NULL priors, a kind
+ * outside {0, 1} (never defined; it used to be read half as a relative, half as an absolute prior), and the convergence setting enabled
+ * (see pwn_hip_ctx_set_convergence). */
 int pwn_hip_align_with_priors(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, const pwn_hip_cloud* reference,
                               const pwn_hip_cloud* current, int n_priors, const pwn_hip_prior* priors, pwn_hip_align_result* result);
 /* The same with Aligner::_computeStatistics (aligner.cpp:127): the reference runs it after every align(), priors or not, on
@@ -572,7 +578,7 @@ void pwn_hip_prior_terms(const float invT[16], const pwn_hip_prior* prior, float
  * terms of its pairs' priors at the pair's Linearizer::_T, and its solve step adds the valid ones behind the two damping additions
  * (aligner.cpp:92-108); the loop stays on the device, and so do traces, step norms and the convergence setting (honoured as everywhere: a
  * stopped pair returns the result of that many outer iterations).  Statistics and omega come from the linearizer's H alone
- * (aligner.cpp:165-170).  Every pair returns the bits pwn_hip_align_with_priors_ex returns for it.  pair_priors == NULL or first[n] == 0:
+ * (aligner.cpp:165-170).  A batch of n equals n single calls: pwn_hip_align_with_priors_ex is one pair of this call.  pair_priors == NULL or first[n] == 0:
  * the launches and the bits of the matching call without priors.  scores, statistics and results may be NULL as in those calls (results
  * only when records are asked for).  Refused with PWN_HIP_ERR_INVALID_ARGUMENT, nothing touched: first == NULL, first[0] != 0, a decreasing
  * first, priors == NULL with first[n] > 0, a kind outside {0, 1}, a record_floats outside the four values, records == NULL with

@@ -1,7 +1,7 @@
-"""Batch alignment with SE(3) priors on the device (pwn_hip_align_batch_priors) against the host-driven loop (pwn_hip_align_with_priors_ex), pair by
-pair and bit for bit: every stage of the two is either the same accumulators through the same reduction or the same text (pwn_stats.h), so a
-difference is a bug, not a tolerance.  Also: a call without priors against the existing calls, record packing, the convergence setting, the
-settle-fault repeat, the refusals and the mirrors."""
+"""Batch alignment with SE(3) priors on the device (pwn_hip_align_batch_priors) against the single call (pwn_hip_align_with_priors_ex, one pair of
+it), pair by pair and bit for bit -- the header's contract: a batch of n equals n single calls, through every sub-batch and stream plan, with the
+cloud's own index image or a projection, so a difference is a bug, not a tolerance.  Also: a call without priors against the existing calls,
+record packing, the convergence setting, the settle-fault repeat, the refusals and the mirrors."""
 import ctypes as C
 import os
 import subprocess
@@ -103,7 +103,7 @@ class Rig:
             self.refs.append(r); self.curs.append(c)
         self.guesses = [E.guess_for(s, KINDS[i % 3]) for i, s in enumerate(seeds)]
         self.lists = prior_lists(seeds)
-        self._host = {}
+        self._single = {}
 
     def args(self, idx):
         n = len(idx)
@@ -133,25 +133,33 @@ class Rig:
             out["res"] = r
         return out
 
-    def host_driven(self, i, outer=None):
+    def single_call(self, i, outer=None):
         """pwn_hip_align_with_priors_ex of pair i (no priors: pwn_hip_align_batch_ex for one pair) and pwn_hip_match_score behind it; cached"""
+        if (i, outer) not in self._single:
+            self._single[(i, outer)] = self.single_call_of(self.refs[i], self.curs[i], i, outer)
+        return self._single[(i, outer)]
+
+    def single_call_of(self, ref, cur, i, outer=None, images=False):
+        """the same call for the clouds ref, cur with pair i's guess and prior list; images: pwn_hip_align_images behind the score"""
         from g2o_frontend_amd import api
         from g2o_frontend_amd._lib import AlignStatistics, MatchResult, Prior
         import prior_cases as pc
-        if (i, outer) in self._host:
-            return self._host[(i, outer)]
         ctx, p = self.ctx, self.params(outer)
         C.memmove(p.initial_guess, _cm(self.guesses[i]).ctypes.data, 64)
         arr = (Prior * max(len(self.lists[i]), 1))()
         for j, prior in enumerate(self.lists[i]):
             arr[j] = pc.prior_struct(prior)
         res = api.AlignResult(); st = (AlignStatistics * 1)(); sc = MatchResult()
-        ctx.check(ctx._L.pwn_hip_align_with_priors_ex(ctx.h, C.byref(p), self.refs[i].h, self.curs[i].h, len(self.lists[i]), arr, C.byref(res), st))
+        ctx.check(ctx._L.pwn_hip_align_with_priors_ex(ctx.h, C.byref(p), ref.h, cur.h, len(self.lists[i]), arr, C.byref(res), st))
         ctx.check(ctx._L.pwn_hip_match_score(ctx.h, THRESHOLD, C.byref(sc)))
         r = np.frombuffer(bytes(res), dtype=api.ALIGN_RESULT_DTYPE, count=1).copy(); r["total_time_ms"] = 0
         out = dict(res=r[0], sc=np.frombuffer(bytes(sc), np.int32).copy(), scf=np.frombuffer(bytes(sc), np.float32).copy(), stw=stat_words(st)[0],
                    H=bytes(st[0].H), b=bytes(st[0].b))
-        self._host[(i, outer)] = out
+        if images:
+            ri = np.empty((p.rows, p.cols), np.int32); ci = np.empty((p.rows, p.cols), np.int32)
+            rd = np.empty((p.rows, p.cols), np.float32); cd = np.empty((p.rows, p.cols), np.float32)
+            ctx.check(ctx._L.pwn_hip_align_images(ctx.h, _vp(ri), _vp(rd), _vp(ci), _vp(cd)))
+            out["images"] = (ri, rd.view(np.uint32), ci, cd.view(np.uint32))
         return out
 
     def close(self):
@@ -159,7 +167,7 @@ class Rig:
 
 
 def same_pair(got, k, want, what):
-    """pair k of a batch call against a host-driven call: T, chi2, inliers, ncorr, ncand, iterations (the whole result), score, statistics"""
+    """pair k of a batch call against a single call: T, chi2, inliers, ncorr, ncand, iterations (the whole result), score, statistics"""
     assert got["res"][k].tobytes() == want["res"].tobytes(), (what, "result", got["res"][k]["T"], want["res"]["T"], got["res"][k]["chi2"][:10], want["res"]["chi2"][:10])
     assert np.array_equal(got["sc"][k], want["sc"]), (what, "score")
     assert np.array_equal(_bits(got["stw"][k]), _bits(want["stw"])), (what, "statistics")
@@ -175,9 +183,10 @@ def rig(request):
 
 @pytest.mark.parametrize("n", [1, 5, 9])
 def test_every_pair_equals_the_host_driven_loop(rig, n):
-    """sub-batches of 4 (9 runs as 4 + 4 + 1) on 1 and on 4 streams, and the default plan"""
+    """a batch of n equals n single calls (once the loop the host drove, now one pair of the batch call): sub-batches of 4 (9 runs as
+    4 + 4 + 1) on 1 and on 4 streams, and the default plan"""
     idx = list(range(n))
-    want = [rig.host_driven(i) for i in idx]
+    want = [rig.single_call(i) for i in idx]
     for sub, streams in ((4, 1), (4, 4), (64, 4)):
         rig.ctx.set_subbatch(64, sub); rig.ctx.set_concurrency(streams)
         try:
@@ -252,9 +261,10 @@ def test_batch_of_nine_equals_nine_calls_of_one(rig):
 
 
 def test_records_in_all_three_forms_equal_host_packing_of_the_host_results(rig):
+    """the host results: what the single calls returned to the host"""
     idx = list(range(9))
     ids = np.arange(100, 109, dtype=np.int32)
-    want = [rig.host_driven(i) for i in idx]
+    want = [rig.single_call(i) for i in idx]
     for floats in (64, 72, 128):
         got = rig.batch(idx, record_floats=floats, ids=ids, results=(floats != 72))
         for k in idx:
@@ -262,8 +272,73 @@ def test_records_in_all_three_forms_equal_host_packing_of_the_host_results(rig):
             score = None if floats == 64 else np.array([w["sc"][0], w["sc"][1], w["sc"][2], w["scf"][3]], np.float32)
             ref = packed(w["res"], ids[k], score, w["stw"] if floats == 128 else None)
             assert np.array_equal(_bits(got["rec"][k]), _bits(ref)), (floats, k, np.where(_bits(got["rec"][k]) != _bits(ref))[0][:8])
-    # the closure record's statistics words are the host-driven call's statistics
+    # the closure record's statistics words are the single call's statistics
     assert all(np.array_equal(_bits(got["rec"][k, 72:119]), _bits(want[k]["stw"])) for k in idx)
+
+
+def _same_single(a, b, what):
+    assert a["res"].tobytes() == b["res"].tobytes(), (what, "result")
+    assert a["sc"].tobytes() == b["sc"].tobytes() and a["scf"].tobytes() == b["scf"].tobytes(), (what, "score")
+    assert np.array_equal(_bits(a["stw"]), _bits(b["stw"])) and a["H"] == b["H"] and a["b"] == b["b"], (what, "statistics")
+
+
+@pytest.mark.parametrize("i", [1, 3])
+def test_single_call_with_the_index_shortcut_equals_the_projection(rig, i):
+    """pair 1 carries a relative prior, pair 3 an absolute and a relative one.  The rig's clouds carry their converter's index image, so the single
+    call takes it in place of projecting the current cloud (pwn_hip_debug_set_index_shortcut); result, statistics, the score behind it and the
+    finder's four images are those of the call that projects"""
+    ctx = rig.ctx
+    assert [len(rig.lists[k]) for k in (1, 3)] == [1, 2] and [q[0] for q in rig.lists[3]] == [1, 0]
+    try:
+        ctx.check(ctx._L.pwn_hip_debug_set_index_shortcut(ctx.h, 1))
+        on = rig.single_call_of(rig.refs[i], rig.curs[i], i, images=True)
+        ctx.check(ctx._L.pwn_hip_debug_set_index_shortcut(ctx.h, 0))
+        off = rig.single_call_of(rig.refs[i], rig.curs[i], i, images=True)
+    finally:
+        ctx.check(ctx._L.pwn_hip_debug_set_index_shortcut(ctx.h, 1))
+    _same_single(on, off, i)
+    for a, b, name in zip(on["images"], off["images"], ("reference index", "reference depth", "current index", "current depth")):
+        assert np.array_equal(a, b), (i, name)
+    assert (on["images"][2] >= 0).sum() > 1000       # the images are not empty
+
+
+def test_single_call_with_priors_leaves_stage_times_and_takes_the_index_shortcut(rig):
+    """with profiling on a single call with priors has stage times like every alignment call, and they say whether the current cloud was
+    projected: not with the shortcut (the comparison above is not one of a call with itself), once without"""
+    ctx = rig.ctx
+    ms, launches = C.c_float(0), C.c_int(0)
+    p = rig.params()
+    ctx._L.pwn_hip_set_profiling(ctx.h, 1)
+    try:
+        for shortcut, projections in ((1, 0), (0, 1)):
+            ctx.check(ctx._L.pwn_hip_debug_set_index_shortcut(ctx.h, shortcut))
+            rig.single_call_of(rig.refs[3], rig.curs[3], 3)
+            ctx.check(ctx._L.pwn_hip_last_stage_ms(ctx.h, b"project_cur", C.byref(ms), C.byref(launches)))
+            assert launches.value == projections, shortcut
+            ctx.check(ctx._L.pwn_hip_last_stage_ms(ctx.h, b"prior_terms", C.byref(ms), C.byref(launches)))
+            assert launches.value == p.outer_iterations * p.inner_iterations and ms.value > 0
+    finally:
+        ctx.check(ctx._L.pwn_hip_debug_set_index_shortcut(ctx.h, 1)); ctx._L.pwn_hip_set_profiling(ctx.h, 0)
+
+
+def test_single_call_on_uploaded_clouds_equals_one_pair_of_the_batch(rig):
+    """uploaded clouds have no index image of their own: the current cloud is projected; single call and n = 1 of the batch call, the same bits"""
+    from g2o_frontend_amd import api
+    i = 3
+    up = []
+    for src in (rig.refs[i], rig.curs[i]):
+        a = src.arrays()
+        c = api.Cloud(rig.ctx, rig.rows * rig.cols)
+        c.upload(a["points"], a["normals"], a["curvature"], a["omega_p"], a["omega_n"])
+        up.append(c)
+    one = rig.single_call_of(up[0], up[1], i)
+    refs, curs = rig.refs[i], rig.curs[i]
+    rig.refs[i], rig.curs[i] = up
+    try:
+        got = rig.batch([i])
+    finally:
+        rig.refs[i], rig.curs[i] = refs, curs
+    same_pair(got, 0, one, "uploaded")
 
 
 @pytest.mark.parametrize("kind", [0, 1])
@@ -320,7 +395,7 @@ def test_convergence_setting_is_honoured(rig):
         want = rig.batch([k], record_floats=128, first=k, outer=stops[k])
         assert want["res"][0].tobytes() == got["res"][k].tobytes(), k
         assert np.array_equal(_bits(want["rec"][0]), _bits(got["rec"][k])) and np.array_equal(want["sc"][0], got["sc"][k]), k
-        same_pair(got, k, rig.host_driven(k, outer=stops[k]), ("stopped", k))
+        same_pair(got, k, rig.single_call(k, outer=stops[k]), ("stopped", k))
 
 
 def test_settle_fault_repeat_returns_the_same_bits(rig):

@@ -553,8 +553,14 @@ def test_priors_with_the_setting_enabled_are_refused_and_touch_nothing(small):
             aligner.align()
         assert e.value.code == INVALID
         ctx.clear_convergence()
-        assert aligner.align()["iterations"] == E.OUTER               # off again: the host-driven loop runs
-        assert aligner.lastSteps()[0]["iterations"] == 0              # ... and records no steps
+        assert aligner.align()["iterations"] == E.OUTER               # off again: the call runs, one pair of pwn_hip_align_batch_priors
+        single = aligner.lastSteps()[0]                               # ... and leaves its step traces
+        assert single["iterations"] == E.OUTER and len(single["step_translation"]) == E.OUTER
+        assert np.all(single["step_translation"] > 0) and np.all(single["step_rotation"] > 0)
+        # bit for bit the traces n = 1 of the batch call leaves for the same pair and prior
+        prior = (0, np.eye(4, dtype=np.float32), np.eye(4, dtype=np.float32), np.eye(6, dtype=np.float32) * 10.0)
+        aligner.alignBatch([ref], [cur], priors=[[prior]])
+        assert _same_steps(single, aligner.lastSteps()[0])
     finally:
         aligner.clearPriors(); ctx.clear_convergence()
 

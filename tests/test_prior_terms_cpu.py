@@ -1,6 +1,6 @@
 """The SE(3) prior terms on the host (pwn_hip_prior_terms: the text of pwn_stats.h through SerialTeam), no GPU: the families of
 tests/prior_cases.py reach what they claim, the terms agree with the float64 model where that is well conditioned, and adding them to an H, b is
-what prior_accumulate (the host-driven loop of pwn_hip_align_with_priors*) does, bit for bit and in list order."""
+what prior_accumulate (pwn_stats.h: the host statement of the addition the step on the device makes) does, bit for bit and in list order."""
 import ctypes as C
 import os
 import subprocess
@@ -145,7 +145,7 @@ int main(int argc, char** argv) {
 
 
 def test_adding_the_terms_is_prior_accumulate_in_list_order(tmp_path):
-    """prior_accumulate itself -- the function the host-driven loop calls, compiled for the host into a stand-alone program with the library's
+    """prior_accumulate itself -- the host statement of "terms, then add in list order", compiled for the host into a stand-alone program with the library's
     flags -- on lists of 1, 2 and 3 priors, against H[i] + Hp[i], b[i] + bp[i] of pwn_hip_prior_terms added in list order in float32.  The lists
     mix magnitudes (information 1e-3 .. 1e12), so the reversed order gives other bits for some: the check is order-sensitive."""
     from g2o_frontend_amd import build as B

@@ -1,5 +1,6 @@
 """What SE(3) priors cost a candidate batch on one MI355X: the device-resident loop with priors (include/pwn_hip.h: pwn_hip_align_batch_priors)
-against the same batch without priors and against the one route that existed before, a host-driven loop per pair.
+against the same batch without priors and against one single call per pair (pwn_hip_align_with_priors_ex: one pair of the batch call on this
+tree's library; on a library from before that, the loop the host drove).
 
     python tools/bench_batch_priors.py [--pairs 128] [--reps 20] [--warmup 3] [--parent-lib PATH] [--out profiles/batch_priors_bench.jsonl]
 
@@ -9,11 +10,14 @@ absolute and one relative prior, in that order (pwn_tracker2 adds the IMU prior,
 pose.  Host clock around calls that end in the library's wait for the device, median of --reps calls, the routes timed alternately:
   (a) `closure_batch_records`: pwn_hip_closure_batch_records, 128-word device records, no priors;
   (b) `batch_priors_closure`: the new call with closure records and the priors;
-  (c) `host_driven_loop`: per pair pwn_hip_align_with_priors_ex(statistics) + pwn_hip_match_score -- with --parent-lib in a child process of the
-      same session on THAT library (the parent commit's build), and on this tree's;
-  (d) one VGA pair (480 x 640): `one_pair_host_driven` against `one_pair_batch_priors` (n = 1 of the new call, results + statistics + score);
+  (c) `single_call_loop`: per pair pwn_hip_align_with_priors_ex(statistics) + pwn_hip_match_score on this tree's library -- and with --parent-lib
+      in a child process of the same session on THAT library (the parent commit's build), where the route keeps its name there, `host_driven_loop`;
+  (d) one VGA pair (480 x 640): `one_pair_single_call` (`one_pair_host_driven` in the child) against `one_pair_batch_priors` (n = 1 of the batch
+      call, results + statistics + score);
   `prior_terms`: k_prior_terms alone, the stage timer of one profiled call of (b), with its launches.
-One JSON line per workload.  Needs a GPU: there is no CPU fallback."""
+Both processes feed what the per-pair route returns -- every pwn_hip_align_result with total_time_ms zeroed, every pwn_hip_align_statistics, every
+pwn_hip_match_result -- into a CRC32 per workload (`per_pair_route_crc32`); with --parent-lib the line says whether the two are equal
+(`single_call_equals_parent_host_driven_loop`).  One JSON line per workload.  Needs a GPU: there is no CPU fallback."""
 import argparse
 import ctypes as C
 import json
@@ -22,6 +26,7 @@ import statistics
 import subprocess
 import sys
 import time
+import zlib
 from concurrent.futures import ProcessPoolExecutor
 
 import numpy as np
@@ -85,7 +90,7 @@ def run(args, only_existing):
         matcher._configure(I, I, Km, ROWS, COLS, None)
         p = aligner.params()
         per_pair = []
-        for i in range(m):                                           # the host-driven call takes its guess from the parameters
+        for i in range(m):                                           # the single call takes its guess from the parameters
             q = aligner.params(); C.memmove(q.initial_guess, g[i].ctypes.data, 64); per_pair.append(q)
         hr = (C.c_void_p * m)(*[c.h for c in refs]); hc = (C.c_void_p * m)(*[c.h for c in curs])
         gp = g[:m].ctypes.data_as(C.c_void_p)
@@ -102,17 +107,18 @@ def run(args, only_existing):
         def one_pair_batch_priors():
             ctx.check(L.pwn_hip_align_batch_priors(ctx.h, C.byref(p), m, hr, hc, gp, C.byref(pp), 50.0, None, 0, res, scores, stats, None, 0))
 
-        def host_driven():
+        def single_calls():
             for i in range(m):
                 ctx.check(L.pwn_hip_align_with_priors_ex(ctx.h, C.byref(per_pair[i]), hr[i], hc[i], 2, C.byref(arr[2 * i]), C.byref(res[i]), C.byref(stats[i])))
                 ctx.check(L.pwn_hip_match_score(ctx.h, 50.0, C.byref(scores[i])))
 
+        single = "host_driven" if only_existing else "single_call"      # what the per-pair route is on the library it runs on
         if scale == 2:
-            routes = (("host_driven_loop", host_driven),) if only_existing else \
-                     (("closure_batch_records", closure), ("batch_priors_closure", batch_priors), ("host_driven_loop", host_driven))
+            routes = ((single + "_loop", single_calls),) if only_existing else \
+                     (("closure_batch_records", closure), ("batch_priors_closure", batch_priors), (single + "_loop", single_calls))
         else:
-            routes = (("one_pair_host_driven", host_driven),) if only_existing else \
-                     (("one_pair_host_driven", host_driven), ("one_pair_batch_priors", one_pair_batch_priors))
+            routes = (("one_pair_" + single, single_calls),) if only_existing else \
+                     (("one_pair_" + single, single_calls), ("one_pair_batch_priors", one_pair_batch_priors))
         for _, call in routes:
             for _ in range(args.warmup):
                 call()
@@ -123,9 +129,13 @@ def run(args, only_existing):
         line = dict(workload="matcher_scale_2" if scale == 2 else "one_vga_pair", pairs=m, rows=p.rows, cols=p.cols, omega_storage=ctx.omega_storage,
                     outer_iterations=p.outer_iterations, priors_per_pair=2, reps=args.reps, library="PWN_HIP_LIB" if "PWN_HIP_LIB" in os.environ else "this tree")
         line.update(_median_line(times))
+        # everything the per-pair route returns, for the comparison across the two libraries
+        single_calls()
+        r = np.frombuffer(res, dtype=api.ALIGN_RESULT_DTYPE, count=m).copy(); r["total_time_ms"] = 0
+        line["per_pair_route_crc32"] = zlib.crc32(bytes(scores), zlib.crc32(bytes(stats), zlib.crc32(r.tobytes())))
         if not only_existing:
-            # the two routes return the same bits (T of every pair)
-            host_driven(); want = np.frombuffer(res, dtype=api.ALIGN_RESULT_DTYPE, count=m)["T"].copy()
+            # the two routes of this library return the same bits (T of every pair)
+            want = r["T"].copy()
             res2 = (AlignResult * m)()
             ctx.check(L.pwn_hip_align_batch_priors(ctx.h, C.byref(p), m, hr, hc, gp, C.byref(pp), 50.0, None, 0, res2, None, None, None, 0))
             same = np.array_equal(want.view(np.uint32), np.frombuffer(res2, dtype=api.ALIGN_RESULT_DTYPE, count=m)["T"].view(np.uint32))
@@ -133,7 +143,7 @@ def run(args, only_existing):
             ms, launches = ctx.stage_ms("prior_terms"); solve_ms, solve_launches = ctx.stage_ms("solve")
             ctx.set_profiling(False)
             line.update(prior_terms_ms=round(ms, 4), prior_terms_launches=launches, prior_terms_us_per_launch=round(1e3 * ms / max(launches, 1), 3),
-                        solve_ms=round(solve_ms, 4), solve_launches=solve_launches, device_loop_equals_host_driven_loop=bool(same))
+                        solve_ms=round(solve_ms, 4), solve_launches=solve_launches, batch_priors_equals_single_call_loop=bool(same))
         lines.append(line)
     ctx.close()
     return lines
@@ -144,7 +154,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=128)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--parent-lib", default=None, help="libpwn_hip.so built from the parent commit: the host-driven route is timed on it in a child process")
+    ap.add_argument("--parent-lib", default=None, help="libpwn_hip.so built from the parent commit: the per-pair route is timed on it in a child process, and its results compared")
     ap.add_argument("--existing-route-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -160,14 +170,16 @@ def main():
             for k, v in ch.items():
                 if k.endswith("_ms") and ("host_driven" in k):
                     ln["parent_library_" + k] = v
+            ln["parent_library_per_pair_route_crc32"] = ch["per_pair_route_crc32"]
+            ln["single_call_equals_parent_host_driven_loop"] = ln["per_pair_route_crc32"] == ch["per_pair_route_crc32"]
     for ln in lines:
         if "batch_priors_closure_ms" in ln:
-            ref = ln.get("parent_library_host_driven_loop_ms", ln["host_driven_loop_ms"])
+            ref = ln.get("parent_library_host_driven_loop_ms", ln["single_call_loop_ms"])
             ln["priors_over_no_priors_ms"] = round(ln["batch_priors_closure_ms"] - ln["closure_batch_records_ms"], 3)
-            ln["host_driven_loop_over_batch_priors"] = round(ref / ln["batch_priors_closure_ms"], 2)
+            ln[("host_driven" if args.parent_lib else "single_call") + "_loop_over_batch_priors"] = round(ref / ln["batch_priors_closure_ms"], 2)
         if "one_pair_batch_priors_ms" in ln:
-            ref = ln.get("parent_library_one_pair_host_driven_ms", ln["one_pair_host_driven_ms"])
-            ln["one_pair_host_driven_over_batch_priors"] = round(ref / ln["one_pair_batch_priors_ms"], 2)
+            ref = ln.get("parent_library_one_pair_host_driven_ms", ln["one_pair_single_call_ms"])
+            ln["one_pair_" + ("host_driven" if args.parent_lib else "single_call") + "_over_batch_priors"] = round(ref / ln["one_pair_batch_priors_ms"], 2)
         print(json.dumps(ln), flush=True)
     if args.out:
         with open(args.out, "w") as f:

@@ -33,7 +33,7 @@ def kernels(path):
             continue
         ins = re.sub(r"//.*$", "", line).strip()
         ins = re.sub(r"^\s*[0-9a-f]+:\s*", "", ins)
-        if ins:
+        if ins and ins != "...":      # "...": objdump's mark for the zero bytes between one kernel's end and the next one's aligned start, no instruction
             out[cur].append(ins)
     return out
 
