@@ -98,8 +98,10 @@ __host__ __device__ constexpr int sym_slot(int k) { return k == 0 ? 0 : (k == 1 
 __host__ __device__ constexpr bool om_is_lower(int k) { return k == 3 || k == 6 || k == 7; }
 __host__ __device__ __forceinline__ size_t omp_at(size_t cap, size_t i, int k, int sym) { return om_at(cap, i, sym ? sym_slot(k) : k); }
 __host__ __device__ __forceinline__ int om_planes(int sym) { return sym ? 2 : 3; }
+// The reference tests squaredNorm() > 0 (informationmatrixcalculator.cpp:46): a normal whose squares all underflow (components near 1e-30,
+// which only an imported or a scene cloud can carry) is a zero normal.  The sum is formed as correspondence_test forms it.
 __host__ __device__ __forceinline__ int normal_class(float nx, float ny, float nz, float curvature, float thr) {
-  return (nx != 0.f || ny != 0.f || nz != 0.f) ? ((curvature < thr) ? 1 : 2) : 0;
+  return (dot4seq(nx, nx, ny, ny, nz, nz, 0.f, 0.f) > 0.0f) ? ((curvature < thr) ? 1 : 2) : 0;
 }
 
 struct FrameDesc {

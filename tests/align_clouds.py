@@ -12,7 +12,9 @@ variant at the wanted ulp distance from the threshold is kept.  Under another gu
 float64 and rounded, and thresholds are met by log-spaced ladders (1e-7.5 .. 1e-3 either side).  Points are stored in a random permutation.
 
 Families (FAMILIES): zero_normal, normal_angle, distance, ratio, chi2_edge, omega_range, cancel, index_edges, empty; their sub-kinds are the
-`sub` labels.  Every Omega is positive semi-definite up to rounding, every point finite.
+`sub` labels.  Every Omega is positive semi-definite up to rounding, every point finite.  class_edge (the last family, in no mixed case) is for
+clouds of the converter's form (tests/flat_clouds.py), whose Omega_n is a class matrix chosen by the current point's curvature against the
+cloud's threshold cls_thr: current curvatures at cls_thr, reference curvatures on its other side.
 """
 from __future__ import annotations
 
@@ -24,7 +26,7 @@ CHAIN = 8                        # kPixPerThread
 PARAMS = dict(min_distance=0.5, max_distance=4.5, inlier_distance_threshold=1.0, inlier_normal_angular_threshold=0.95,
               flat_curvature_threshold=0.02, inlier_curvature_ratio_threshold=1.3, inlier_max_chi2=9000.0, robust_kernel=1,
               outer_iterations=1, inner_iterations=1)
-FAMILIES = ("zero_normal", "normal_angle", "distance", "ratio", "chi2_edge", "omega_range", "cancel", "index_edges", "empty")
+FAMILIES = ("zero_normal", "normal_angle", "distance", "ratio", "chi2_edge", "omega_range", "cancel", "index_edges", "empty", "class_edge")
 VARIANTS = 48
 WANT = np.array([0, -1, 1, 0, -2, 2, 0, -3, 3, -4, 4])      # ulp distances from a threshold, dealt round-robin (equality three times as often)
 
@@ -122,8 +124,8 @@ class Case:
 
 
 class _Builder:
-    def __init__(self, rng, rows, cols, K, exact, params):
-        self.rng, self.rows, self.cols, self.K, self.exact, self.params = rng, rows, cols, K, exact, params
+    def __init__(self, rng, rows, cols, K, exact, params, cls_thr=0.02):
+        self.rng, self.rows, self.cols, self.K, self.exact, self.params, self.cls_thr = rng, rows, cols, K, exact, params, cls_thr
         self.N = rows * cols
         self.free = np.ones(self.N, bool)
         self.family = np.full(self.N, "", object); self.sub = np.full(self.N, "", object); self.expect = np.full(self.N, -1, np.int8)
@@ -386,6 +388,27 @@ class _Builder:
         b = self.base(pix); b["rn"] = -b["cn"]; b["sub"][:] = "rejected"; b["expect"][:] = 0
         return b
 
+    def class_edge(self, pix):
+        """the current curvature at cls_thr, at equality and 1 .. 4 ulps either side (curvatures are stored bits: no variants needed, under any
+        guess); in every second pixel the reference curvature on the OTHER side of cls_thr, by 1 ulp .. 5 % (sub "across"), else equal to the
+        current one ("same").  Omega_n is the shipped table by the class rule, so the uploaded form of the case is the same cloud.  Every pair is
+        a correspondence: the curvatures differ by 5 % at the most, the ratio stays near 1."""
+        b = self.base(pix); n = len(pix); rng = self.rng
+        thr = F32(self.cls_thr); tb = int(thr.view(np.int32))
+        want = WANT[np.arange(n) % len(WANT)]
+        cc = (tb + want).astype(np.int32).view(F32)
+        below = cc < thr                                           # class 1 (flat); equality is class 2
+        across = (np.arange(n) // len(WANT)) % 2 == 0
+        steps = np.where(rng.random(n) < 0.4, rng.integers(1, 4, n), 0)                       # 1 .. 3 ulps, else a relative offset 1e-6 .. 5e-2
+        rel = 10.0 ** rng.uniform(-6.0, np.log10(0.05), n)
+        up = np.where(steps > 0, (tb + steps - 1).astype(np.int32).view(F32), (float(thr) * (1 + rel)).astype(F32))      # >= thr: class 2
+        dn = np.where(steps > 0, (tb - steps).astype(np.int32).view(F32), (float(thr) * (1 - rel)).astype(F32))          # < thr: class 1
+        rc = np.where(across, np.where(below, up, dn), cc).astype(F32)
+        b["ccurv"] = cc.astype(F32); b["rcurv"] = rc
+        b["On"] = np.where(below[:, None, None], (np.eye(3) * 100.0).astype(F32), np.eye(3, dtype=F32)).astype(F32)
+        b["sub"][:] = np.where(across, "across", "same"); b["expect"][:] = 1
+        return b
+
 
 def _zbuffer(pix, key, visible, N):
     """the intended index image: nearest visible point per pixel, ties to the lowest index"""
@@ -397,7 +420,7 @@ def _zbuffer(pix, key, visible, N):
     return out
 
 
-def make_case(name, rows, cols, guess, counts, seed, tiles=None, lone_tile=None, params=None):
+def make_case(name, rows, cols, guess, counts, seed, tiles=None, lone_tile=None, params=None, cls_thr=0.02):
     """counts: family -> number of pixels (cancel: pairs; empty: "none" or "rejected" pixels through the keys empty_none / empty_rejected).
     tiles: restrict the candidates to these 2048-pixel tiles; lone_tile: a tile whose only candidate is its last pixel."""
     rng = np.random.default_rng(seed)
@@ -405,7 +428,7 @@ def make_case(name, rows, cols, guess, counts, seed, tiles=None, lone_tile=None,
     G = np.asarray(GUESSES[guess] if isinstance(guess, str) else guess, np.float64)
     exact = bool(np.array_equal(G, np.eye(4)))
     K = camera(rows, cols)
-    B = _Builder(rng, rows, cols, K, exact, p)
+    B = _Builder(rng, rows, cols, K, exact, p, cls_thr)
     N = rows * cols
     tile_of = np.arange(N) // TILE
     allowed = np.ones(N, bool) if tiles is None else np.isin(tile_of, list(tiles))
@@ -424,7 +447,7 @@ def make_case(name, rows, cols, guess, counts, seed, tiles=None, lone_tile=None,
         if lone_tile is not None:
             special(min(N, (lone_tile + 1) * TILE) - 1, "tile_last")
         B.index_edges(B.take(counts["index_edges"], allowed), (np.array(sp, np.int64), kinds))
-    for fam in ("cancel", "zero_normal", "normal_angle", "distance", "ratio", "chi2_edge", "omega_range", "empty_none", "empty_rejected"):
+    for fam in ("cancel", "zero_normal", "normal_angle", "distance", "ratio", "chi2_edge", "omega_range", "empty_none", "empty_rejected", "class_edge"):
         n = counts.get(fam, 0)
         if not n:
             continue
@@ -460,7 +483,7 @@ def make_case(name, rows, cols, guess, counts, seed, tiles=None, lone_tile=None,
         index[side] = _zbuffer(cat["pix"].astype(np.int64), key, cat["visible"].astype(bool), N).reshape(rows, cols)
     T = G.astype(F32); T[3] = (0, 0, 0, 1)
     return Case(name=name, rows=rows, cols=cols, K=K, guess=T, guess_name=guess if isinstance(guess, str) else name, params=p, ref=clouds["ref"], cur=clouds["cur"],
-                family=B.family, sub=B.sub, expect=B.expect, ref_index=index["ref"], cur_index=index["cur"])
+                family=B.family, sub=B.sub, expect=B.expect, ref_index=index["ref"], cur_index=index["cur"], cls_thr=cls_thr)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the case sets
@@ -518,6 +541,33 @@ def cpu_case_set():
     out = [family_case(f, g) for f in SMALL_SIZES for g in GUESSES]
     out += [empty_case("none"), empty_case("rejected"), empty_case("none", "moderate"), empty_case("rejected", "small")]
     out += [mixed_case(r, c) for r, c in ((64, 32), (3, 683), (17, 65)) + LARGE_SIZES] + [mixed_case(480, 640, "moderate")]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- the converter-form case sets
+CLASS_EDGE_SIZES = ((17, 65), (64, 32))
+CLASS_THRESHOLDS = (0.02, 0.01, 0.03)            # the shipped default = flat_curvature_threshold; below and above it
+CONVERTER_MIXED_SIZES = ((64, 32), (3, 683), (17, 65), (480, 640))
+
+
+def class_edge_case(rows, cols, guess="identity", cls_thr=0.02):
+    """class_edge alone: 900 pixels of 1105 (a partial tile) or of 2048 (one tile)"""
+    def mk():
+        return make_case(f"class_edge{rows}x{cols}/{guess}/{cls_thr:g}", rows, cols, guess, {"class_edge": 900},
+                         seed=3000 + rows + 7 * sorted(GUESSES).index(guess) + int(round(cls_thr * 1000)), cls_thr=cls_thr)
+    return _cached(("class_edge", rows, cols, guess, cls_thr), mk)
+
+
+def class_edge_cases():
+    return [class_edge_case(r, c, g, t) for r, c in CLASS_EDGE_SIZES for g in GUESSES for t in CLASS_THRESHOLDS]
+
+
+def converter_form_cases():
+    """(case, cls_thr, table name) of every case run in the converter's form: the x 3 threshold, x 2 table product on the class_edge cases and on
+    one mixed case per size; the existing family cases under (0.02, rotated)"""
+    out = [(c, c.cls_thr, t) for c in class_edge_cases() for t in ("shipped", "rotated")]
+    out += [(mixed_case(r, c), thr, t) for r, c in CONVERTER_MIXED_SIZES for thr in CLASS_THRESHOLDS for t in ("shipped", "rotated")]
+    out += [(family_case(f, g), 0.02, "rotated") for f in SMALL_SIZES for g in GUESSES]
     return out
 
 

@@ -13,12 +13,12 @@ PwnMatcherBase::makeCloud's data path in one call (pwn_hip_convert_batch[_u16]_s
 """
 import ctypes as C
 import os
-import struct
 import subprocess
 
 import numpy as np
 import pytest
 
+import flat_clouds as FC
 import scaled_frames as S
 
 pytestmark = pytest.mark.gpu
@@ -111,21 +111,7 @@ def make_aligner(ctx, K, rows, cols):
     return aligner
 
 
-def flat_bytes(cloud):
-    """the cloud as pwn_hip_cloud_export writes it: every array, the stored index image and what it was made with"""
-    buf = np.zeros(cloud.flatSize(), np.uint8)
-    assert cloud.exportFlat(buf) == buf.size
-    return buf
-
-
-def stored_index(cloud):
-    """(rows, cols, camera matrix, index image) the cloud keeps for the aligner's projection shortcuts, read from its flat form"""
-    b = flat_bytes(cloud).tobytes()
-    valid, rows, cols = struct.unpack_from("<iii", b, 20)
-    assert valid == 1
-    K = np.frombuffer(b, np.float32, 9, 116)
-    off, = struct.unpack_from("<Q", b, 184)
-    return rows, cols, K, np.frombuffer(b, np.int32, rows * cols, off).reshape(rows, cols)
+flat_bytes, stored_index = FC.flat_bytes, FC.stored_index      # the flat form and its header are read in tests/flat_clouds.py
 
 
 def scaled_call(ctx, p, kind, args, rows, cols, step, clouds, cov=COV):
