@@ -80,6 +80,16 @@ class PairPriors(C.Structure):
     _fields_ = [("first", C.POINTER(C.c_int)), ("priors", C.POINTER(Prior))]
 
 
+class SceneStepParams(C.Structure):
+    _fields_ = [("distance_threshold", C.c_float), ("normal_threshold", C.c_float), ("max_point_depth", C.c_float), ("baseline", C.c_float),
+                ("alpha", C.c_float), ("step", C.c_int), ("max_depth_cov", C.c_float)]
+
+
+class SceneStepResult(C.Structure):
+    _fields_ = [("align", AlignResult), ("scene_T", C.c_float * 16), ("n_cloud", C.c_int), ("n_subscene", C.c_int), ("size_after_add", C.c_int),
+                ("size_after_merge", C.c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/pwn_hip.h declares
 _VP, _I, _F = C.c_void_p, C.c_int, C.c_float
 PROTOTYPES = {
@@ -174,6 +184,8 @@ PROTOTYPES = {
     "pwn_hip_cloud_add": (_I, [_VP, _VP, _VP, _VP]),
     "pwn_hip_merge": (_I, [_VP, _VP, _VP, _VP, _F, _F, _I, _I, _F, _F, _F, C.POINTER(_I), _VP]),
     "pwn_hip_merge_clouds": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _F, _F, _I, _I, _VP, _VP, _VP, _VP]),
+    "pwn_hip_default_scene_step_params": (None, [_VP]),
+    "pwn_hip_scene_step": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _F, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_manifold_image": (_I, [_VP, _I, _VP, _VP, _F, _I, _I, _F, _I, _VP, _VP]),
     "pwn_hip_voxelize": (_I, [_VP, _VP, _F, C.POINTER(_I), _VP]),
     "pwn_hip_cloud_save": (_I, [_VP, _VP, C.c_char_p, _VP, _I, _I]),

@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AlignerParams, AlignResult, AlignSteps, AlignStatistics, Convergence, ConvertExtras, ConverterParams, MatchResult, PairPriors, Prior, PwnHipError
+from ._lib import AlignerParams, AlignResult, AlignSteps, AlignStatistics, Convergence, ConvertExtras, ConverterParams, MatchResult, PairPriors, Prior, PwnHipError, SceneStepParams, SceneStepResult
 
 
 def _ptr(x):
@@ -825,6 +825,90 @@ class Merger:
                                        self._maxPointDepth, C.byref(k), _ptr(collapsed)))
         self._collapsedIndices = collapsed[:n]
         return k.value
+
+
+def scene_step(ctx: Context, cp: ConverterParams, ap: AlignerParams, sp: SceneStepParams, frame, sceneT, scene: Cloud, cloud: Cloud, subscene: Cloud,
+               raw_scale=None, collapsed=None) -> SceneStepResult:
+    """pwn_hip_scene_step: one frame of the mapping loop in one submission.  frame: float32 metres, or uint16 with raw_scale; numpy array or
+    device buffer.  collapsed: optional int32 array of size(scene) + converted pixels entries."""
+    rows, cols = frame.shape
+    res = SceneStepResult()
+    ctx.check(ctx._L.pwn_hip_scene_step(ctx.h, C.byref(cp), C.byref(ap), C.byref(sp), _ptr(frame), 0 if raw_scale is None else 1, raw_scale or 0.0, rows, cols,
+                                        _ptr(_colmajor(sceneT, 4)), scene.h, cloud.h, subscene.h, C.byref(res), _ptr(collapsed)))
+    return res
+
+
+class SceneAligner:
+    """The mapping loop of pwn_aligner.cpp:166-209 (pwn_odometry_sequential_controller.cpp:124-171), a frame per processFrame and a submission
+    per frame (pwn_hip_scene_step): the frame is converted, tracked against the rendering of the scene and fused into it.  The chunk's
+    Cloud::save is the caller's: save scene() under sceneT().inverse() * globalT(), then newChunk()."""
+
+    def __init__(self, ctx: Context, converter: DepthImageConverterIntegralImage, aligner: "Aligner", merger: Merger, capacity: int,
+                 sensorOffset=None, imageScale: int = 0, maxDepthCov: float = 0.01, raw_scale=None):
+        self.ctx, self._converter, self._aligner, self._merger = ctx, converter, aligner, merger
+        self._capacity, self._sensorOffset = int(capacity), sensorOffset
+        self._imageScale, self._maxDepthCov, self._raw_scale = int(imageScale), float(maxDepthCov), raw_scale
+        self._scene = Cloud(ctx, self._capacity)
+        self._cloud = self._subscene = None
+        self._sceneT = np.eye(4, dtype=np.float32)
+        self._globalT = np.eye(4, dtype=np.float32)
+        self._result = None
+        self._collapsedIndices = None
+
+    def scene(self): return self._scene
+    def cloud(self): return self._cloud                                         # the last frame's cloud, scene-ready
+    def subscene(self): return self._subscene                                   # what it was tracked against
+    def sceneT(self): return self._sceneT
+    def globalT(self): return self._globalT
+    def result(self): return self._result
+    def collapsedIndices(self): return self._collapsedIndices
+
+    def stepParams(self) -> SceneStepParams:
+        sp = SceneStepParams()
+        _lib.lib().pwn_hip_default_scene_step_params(C.byref(sp))
+        m, pr = self._merger, self._converter.projector()
+        sp.distance_threshold, sp.normal_threshold, sp.max_point_depth = m._distanceThreshold, m._normalThreshold, m._maxPointDepth
+        sp.baseline, sp.alpha = pr._baseline, pr._alpha
+        sp.step, sp.max_depth_cov = self._imageScale, self._maxDepthCov
+        return sp
+
+    def processFrame(self, depth):
+        """one frame -> Aligner::T() of its alignment against the scene (the identity for the first frame of a chunk)"""
+        rows, cols = depth.shape
+        if self._imageScale:
+            rows, cols = rows // self._imageScale, cols // self._imageScale
+        if self._cloud is None or self._cloud.capacity < rows * cols:
+            self._cloud, self._subscene = Cloud(self.ctx, rows * cols), Cloud(self.ctx, rows * cols)
+        pr = self._aligner.projector()
+        pr.setImageSize(rows, cols)
+        self._merger.setImageSize(rows, cols)
+        self._aligner.setInitialGuess(np.eye(4, dtype=np.float32))
+        if self._sensorOffset is not None:
+            self._aligner.setSensorOffset(self._sensorOffset)
+        collapsed = np.empty(self._scene.size() + rows * cols, np.int32)
+        res = scene_step(self.ctx, self._converter.params(self._sensorOffset), self._aligner.params(), self.stepParams(), depth, self._sceneT, self._scene,
+                         self._cloud, self._subscene, raw_scale=self._raw_scale, collapsed=collapsed)
+        self._result = Aligner._unpack(res.align)
+        T = self._result["T"]
+        G = np.empty(16, np.float32)
+        _lib.lib().pwn_hip_iso_mul(_ptr(_colmajor(self._globalT, 4)), _ptr(_colmajor(T, 4)), _ptr(G))
+        self._globalT = _from_colmajor(G, 4); self._globalT[3] = (0, 0, 0, 1)
+        self._sceneT = _from_colmajor(res.scene_T, 4)
+        self._collapsedIndices = collapsed[:res.size_after_add]
+        self._sizes = (res.n_cloud, res.n_subscene, res.size_after_add, res.size_after_merge)
+        return T
+
+    def newChunk(self):
+        """pwn_aligner.cpp:188-199: a new scene that holds the last frame's cloud at the identity; the one it replaces is returned (it holds
+        that frame too: the reference saves its chunk before the frame is added)."""
+        old = self._scene
+        self._scene = Cloud(self.ctx, self._capacity)
+        self._sceneT = np.eye(4, dtype=np.float32)
+        if self._cloud is not None:
+            self._scene.add(self._cloud, self._sceneT)
+            so = np.eye(4, dtype=np.float32) if self._sensorOffset is None else np.asarray(self._sensorOffset, np.float32)
+            self._merger.merge(self._scene, so)
+        return old
 
 
 class VoxelCalculator:

@@ -115,6 +115,13 @@ def build_tools(force: bool = False) -> str:
     if force or (not os.path.exists(out13)) or any(os.path.getmtime(d) > os.path.getmtime(out13) for d in deps13):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src13, "-o", out13, "-L", _HERE, "-lpwn_hip",
                                "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
+    # SceneAligner (pwn_hip_scene_step per frame) through the C++ mirror against what the Python mirror wrote to a file (exit status 0 = equal byte for byte)
+    src14 = os.path.join(root, "tools", "pwn_hip_scene_step_check.cpp")
+    out14 = os.path.join(root, "tools", "pwn_hip_scene_step_check")
+    deps14 = [src14] + deps[1:]
+    if force or (not os.path.exists(out14)) or any(os.path.getmtime(d) > os.path.getmtime(out14) for d in deps14):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src14, "-o", out14, "-L", _HERE, "-lpwn_hip",
+                               "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
     # PwnCloser::processPartition over the GPUs of a node in native code: the mirror + RCCL (broadcast of the flat `current` cloud, all-gather of the
     # match records); the program's own streams and events come from the HIP runtime
     src5 = os.path.join(root, "tools", "pwn_hip_partition_app.cpp")

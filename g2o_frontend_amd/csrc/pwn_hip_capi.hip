@@ -296,6 +296,8 @@ struct pwn_hip_ctx {
   DevBuf<ManifoldCloud> manifold_dev; HostBuf<ManifoldCloud> manifold_host;
   DevBuf<uint16_t> manifold_img_dev; HostBuf<uint16_t> manifold_img_host;
   int manifold_chunk = kMaxCloudPoints;
+  // pwn_hip_scene_step (allocated by the first such call): the rendering of the scene, the step record on the device and its page-locked copy
+  DevBuf<float> scene_depth_ws; DevBuf<SceneStepRecord> step_dev; HostBuf<SceneStepRecord> step_host;
 };
 
 namespace {
@@ -909,6 +911,8 @@ struct ConvertCall {
   pwn_hip_cloud* const* clouds = nullptr;
   int keep_stats = 0; bool want_interval = false;              // the interval image stays readable (pwn_hip_convert(..., interval_image))
   ScaleSpec scale; GaussSpec gauss;                            // DepthImage_scale in front of every conversion; the sensor-noise Gaussians beside the points
+  int first_entry = 0;                                         // the job's descriptors are entries [first_entry, first_entry + n) of the context's arrays: a call
+                                                               // that holds two jobs of different kinds at once (the mapping step) puts the second behind the first
 };
 // The members every entry point fills, and where the typed ones hand their frame arrays over: behind it the frame type is ConvertCall::raw
 template <typename T>
@@ -922,6 +926,7 @@ struct ConvertJob {
   ConvertParams cp;
   GaussSpec gauss;
   int n = 0, rows = 0, cols = 0;
+  int entry0 = 0;                        // ConvertCall::first_entry: frame i of the job is entry entry0 + i of frames_dev / gauss_dev / scale_dev / counts_host
   size_t N = 0;
   size_t srcN = 0;                       // pixels of a frame as the caller hands it over (= N unless the job down-samples)
   ScaleSpec scale;
@@ -942,9 +947,10 @@ int convert_prepare(pwn_hip_ctx* ctx, const ConvertCall& c, const std::vector<in
   // the interval image leaves the converter only through pwn_hip_convert(..., interval_image); nothing outside the library sees a lean call's
   // integral image: grouped storage (ig_at)
   cp.lean = c.want_interval ? 0 : kLeanGrouped;
-  if (int rc = ensure_desc(ctx, n)) return rc;
-  if (gs.on) { if (int rc = ensure_gauss_desc(ctx, n)) return rc; }
-  job.gauss = gs;
+  const int e0 = c.first_entry;
+  if (int rc = ensure_desc(ctx, e0 + n)) return rc;
+  if (gs.on) { if (int rc = ensure_gauss_desc(ctx, e0 + n)) return rc; }
+  job.gauss = gs; job.entry0 = e0;
   job.n = n; job.rows = c.rows; job.cols = c.cols; job.N = N; job.raw = raw; job.depth_scale = c.depth_scale; job.slot = slot; job.direct = direct;
   job.scale = sc; job.srcN = sc.step ? (size_t)sc.srows * sc.scols : N;
   job.src.assign(n, nullptr);
@@ -958,17 +964,17 @@ int convert_prepare(pwn_hip_ctx* ctx, const ConvertCall& c, const std::vector<in
     pwn_hip_cloud* cl = c.clouds[i];
     if (int rc = cloud_replace(ctx, cl, c.keep_stats != 0, false, &cls, &key, cp.hasOffset == 0, gs.on)) return rc;
     job.clouds.push_back(cl);
-    if (gs.on) ctx->gauss_host[i] = cl->sb;
+    if (gs.on) ctx->gauss_host[e0 + i] = cl->sb;
     job.src[i] = c.frames[i];
     const void* src = c.frames[i];      // where the kernels find the frame
     if (job.host_input) src = raw ? (const void*)(ctx->raw_ws + (size_t)slot[i] * ctx->N) : (const void*)(ctx->depth_ws + (size_t)slot[i] * ctx->N);
     float* scaled = sc.step ? ctx->scaled_ws + (size_t)slot[i] * ctx->N : nullptr;      // a down-sampling job: the box kernel writes, the front end reads the slot's frame
-    fill_frame(ctx, i, slot[i], sc.step ? scaled : raw ? nullptr : static_cast<const float*>(src), cl->d);
+    fill_frame(ctx, e0 + i, slot[i], sc.step ? scaled : raw ? nullptr : static_cast<const float*>(src), cl->d);
     if (cl->idximg.cap < N) {
       HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
       HIPCHK(ctx, cl->idximg.ensure(N), PWN_HIP_ERR_ALLOCATION);
     }
-    ctx->frames_host[i].index = cl->idximg;
+    ctx->frames_host[e0 + i].index = cl->idximg;
     // ... and so do the strip offsets it is counted from, where a single-pass launch will leave a table of 64-column strips that line up with
     // the rows: the front end's kernels get the cloud's buffer for their workspace slot, and run the code they ran (a three-kernel launch
     // writes its [rows] offsets there and takes the promise back: convert_enqueue)
@@ -978,17 +984,17 @@ int convert_prepare(pwn_hip_ctx* ctx, const ConvertCall& c, const std::vector<in
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
         HIPCHK(ctx, cl->stripoff.ensure(words), PWN_HIP_ERR_ALLOCATION);
       }
-      ctx->frames_host[i].rowoff = cl->stripoff;
+      ctx->frames_host[e0 + i].rowoff = cl->stripoff;
       cl->stripoff_filled = true;
     }
-    if (sc.step) { ctx->scale_host[i].src = src; ctx->scale_host[i].dst = scaled; }
-    else if (raw) { ctx->frames_host[i].raw = static_cast<const uint16_t*>(src); ctx->frames_host[i].raw_scale = c.depth_scale; }      // converted on the fly by the kernels
+    if (sc.step) { ctx->scale_host[e0 + i].src = src; ctx->scale_host[e0 + i].dst = scaled; }
+    else if (raw) { ctx->frames_host[e0 + i].raw = static_cast<const uint16_t*>(src); ctx->frames_host[e0 + i].raw_scale = c.depth_scale; }      // converted on the fly by the kernels
   }
-  if (sc.step) HIPCHK(ctx, hipMemcpyAsync(ctx->scale_dev, ctx->scale_host, sizeof(ScaleDesc) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
-  if (gs.on && n > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->gauss_dev, ctx->gauss_host, sizeof(SceneBuffers) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+  if (sc.step) HIPCHK(ctx, hipMemcpyAsync(ctx->scale_dev + e0, ctx->scale_host + e0, sizeof(ScaleDesc) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+  if (gs.on && n > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->gauss_dev + e0, ctx->gauss_host + e0, sizeof(SceneBuffers) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
   // a call of a few frames (latency path, one launch): counts and fault flag land in page-locked host words straight from the kernels
-  if (direct) for (int i = 0; i < n; ++i) ctx->frames_host[i].count_out = ctx->counts_host + i;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev, ctx->frames_host, sizeof(FrameDesc) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+  if (direct) for (int i = 0; i < n; ++i) ctx->frames_host[e0 + i].count_out = ctx->counts_host + e0 + i;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev + e0, ctx->frames_host + e0, sizeof(FrameDesc) * n, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
   job.cp = cp;
   return PWN_HIP_OK;
 }
@@ -1023,7 +1029,7 @@ int launch_gaussians(pwn_hip_ctx* ctx, const ConvertJob& job, int base, int m, h
   if (m <= 0) return PWN_HIP_OK;
   StageTimer t(ctx, "gaussians", st);
   const dim3 grid((unsigned)((job.N + 255) / 256), (unsigned)m);
-  const FrameDesc* fr = ctx->frames_dev + base; const SceneBuffers* sbs = ctx->gauss_dev + base;
+  const FrameDesc* fr = ctx->frames_dev + job.entry0 + base; const SceneBuffers* sbs = ctx->gauss_dev + job.entry0 + base;
   if (ctx->gauss_staged) hipLaunchKernelGGL(k_gaussians_batch<true>, grid, dim3(256), 0, st, fr, sbs, job.cp, job.gauss.iK, job.gauss.fB, job.gauss.alpha);
   else hipLaunchKernelGGL(k_gaussians_batch<false>, grid, dim3(256), 0, st, fr, sbs, job.cp, job.gauss.iK, job.gauss.fB, job.gauss.alpha);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
@@ -1035,8 +1041,8 @@ int launch_gaussians(pwn_hip_ctx* ctx, const ConvertJob& job, int base, int m, h
 void no_strip_tables(const ConvertJob& job, int base, int m) { for (int i = 0; i < m; ++i) job.clouds[(size_t)(base + i)]->stripoff_filled = false; }
 int convert_enqueue(pwn_hip_ctx* ctx, const ConvertJob& job, int base, int m, hipStream_t st, int* fault_out = nullptr) {
   if (!single_pass_launch(m)) no_strip_tables(job, base, m);
-  if (job.scale.step) { if (int rc = launch_depth_scale(ctx, job.scale, job.raw, job.depth_scale, base, m, st)) return rc; }
-  if (int rc = launch_convert(ctx, job.cp, base, m, st, fault_out)) return rc;
+  if (job.scale.step) { if (int rc = launch_depth_scale(ctx, job.scale, job.raw, job.depth_scale, job.entry0 + base, m, st)) return rc; }
+  if (int rc = launch_convert(ctx, job.cp, job.entry0 + base, m, st, fault_out)) return rc;
   if (job.gauss.on) return launch_gaussians(ctx, job, base, m, st);
   return PWN_HIP_OK;
 }

@@ -243,6 +243,147 @@ int pwn_hip_merge(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, const float K[9], cons
   return PWN_HIP_OK;
 }
 
+void pwn_hip_default_scene_step_params(pwn_hip_scene_step_params* p) {
+  if (!p) return;
+  p->distance_threshold = 0.1f; p->normal_threshold = std::cos(10 * (float)M_PI / 180.0f); p->max_point_depth = 10.0f;      // merger.cpp:6-8
+  p->baseline = 0.075f; p->alpha = 0.1f;                                                                                     // pinholepointprojector.cpp:10-11
+  p->step = 0; p->max_depth_cov = 0.01f;
+}
+// The mapping step (pwn_aligner.cpp:166-209) in one submission: the two conversions and the rendering go in front of the alignment's kernels on its
+// stream (AlignHooks::pre_sub), k_scene_pose, the add and the merge behind them (before_sync); the host waits once (align_batch_once) and does the
+// bookkeeping of pwn_hip_cloud_add / pwn_hip_merge afterwards.  Everything that can refuse the call is looked at before a cloud is touched.
+int pwn_hip_scene_step(pwn_hip_ctx* ctx, const pwn_hip_converter_params* cp, const pwn_hip_aligner_params* ap, const pwn_hip_scene_step_params* sp,
+                       const void* frame, int raw_u16, float depth_scale, int rows, int cols, const float scene_T[16], pwn_hip_cloud* scene,
+                       pwn_hip_cloud* cloud, pwn_hip_cloud* subscene, pwn_hip_scene_step_result* result, int* collapsed) {
+  if (!ctx || !cp || !ap || !sp || !frame || !scene_T || !scene || !cloud || !subscene || !result) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (scene == cloud || scene == subscene || cloud == subscene) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "the three clouds of a mapping step must be distinct");
+  if (scene->owner != ctx || cloud->owner != ctx || subscene->owner != ctx) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "cloud of another context");
+  if (scene->d.omSym != cloud->d.omSym || scene->d.omSym != subscene->d.omSym) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "clouds with different omega storages");
+  if (sp->step < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "DepthImage_scale: step < 0");
+  if (!std::isfinite(sp->baseline) || !std::isfinite(sp->alpha)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "baseline or alpha is not finite");
+  if (cp->min_distance < 0.f) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "min_distance must be >= 0");
+  ConvertCall frameCall; frameCall.p = cp; frameCall.n = 1; frameCall.rows = rows; frameCall.cols = cols;
+  frameCall.raw = raw_u16 != 0; frameCall.depth_scale = frameCall.raw ? depth_scale : 0.f; frameCall.keep_stats = 1;
+  if (sp->step) {
+    if (int rc = make_scale_spec(ctx, rows, cols, sp->step, sp->max_depth_cov, frameCall.scale)) return rc;
+    frameCall.rows = frameCall.scale.orows; frameCall.cols = frameCall.scale.ocols;
+  }
+  const int vrows = frameCall.rows, vcols = frameCall.cols;      // the view: what is converted, rendered, aligned and merged
+  if (int rc = check_image(ctx, vrows, vcols)) return rc;
+  if (ap->rows != vrows || ap->cols != vcols) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "aligner image size differs from the converted frame's");
+  if (int rc = check_align_params(ctx, ap)) return rc;
+  const int pixels = vrows * vcols;
+  if (pixels > kMaxAlignerPoints) return fail(ctx, PWN_HIP_ERR_CAPACITY, "Aligner::align: frames of more than 2^21 pixels (index field of the aligner's z-buffer word)");
+  const int k0 = scene->content.n;
+  if (!(scene->sb.G ? scene->content.n_gauss >= k0 : k0 == 0)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "Merger::merge needs the scene's Gaussians (fewer Gaussians than points)");
+  const size_t bound = (size_t)k0 + (size_t)pixels;              // what the scene can hold after the add
+  if (bound > (size_t)scene->d.capacity) return fail(ctx, PWN_HIP_ERR_CAPACITY, "scene capacity smaller than its size plus the pixels of the frame");
+  if (bound > (size_t)kMaxCloudPoints) return fail(ctx, PWN_HIP_ERR_CAPACITY, "the scene could exceed what the z-buffer index field holds (2^25)");
+  if (cloud->d.capacity < pixels || subscene->d.capacity < pixels) return fail(ctx, PWN_HIP_ERR_CAPACITY, "cloud capacity smaller than the pixels of the converted frame");
+  HIPCHK(ctx, hipSetDevice(ctx->device), PWN_HIP_ERR_NO_DEVICE);
+  if (int rc = absorb_copies(ctx)) return rc;      // caller pointers may be the destination of a queued pwn_hip_copy_async
+  // ---- allocations and whatever waits for the stream: before anything of the step is queued
+  if (int rc = ensure_desc(ctx, 2)) return rc;
+  if (sp->step) { if (int rc = ensure_scale(ctx, 2)) return rc; }
+  HIPCHK(ctx, ctx->scene_depth_ws.ensure(ctx->N), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->step_dev.ensure(1), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->step_host.ensure(1), PWN_HIP_ERR_ALLOCATION);
+  cloud_changes(ctx, scene);
+  if (int rc = ensure_scene(ctx, scene, true)) return rc;
+  CloudDev back; SceneBuffers sback;
+  HIPCHK(ctx, scene->own_back(back, sback), PWN_HIP_ERR_ALLOCATION);
+  // the scene grows by a frame per call: when the scratch is too small it is made for twice the bound (within the capacity), so that growing it --
+  // a wait for the stream, a free and an allocation per array -- happens once in a while, not once per frame
+  size_t scratch = bound;
+  for (const auto& b : ctx->scene_i) if (b.cap < bound + 1024) scratch = std::min((size_t)scene->d.capacity, 2 * bound);
+  if (int rc = scene_scratch(ctx, scratch, 0)) return rc;
+  int* d_collapsed = ctx->scene_i[0]; int* d_head = ctx->scene_i[1]; int* d_next = ctx->scene_i[2]; int* d_keep = ctx->scene_i[3];
+  int* d_offs = ctx->scene_i[4]; int* d_sums = ctx->scene_i[5];
+  // ---- the two conversions: entries 0 and 1 of the descriptor arrays, both in workspace slot 0 (they follow each other on one stream)
+  const void* frames[1] = { frame }; pwn_hip_cloud* frameCloud[1] = { cloud };
+  frameCall.frames = frames; frameCall.clouds = frameCloud;
+  { Mat4 KRt, iKRt; projector_matrices(mat3_from(cp->K), mat4_identity(), KRt, iKRt, frameCall.gauss.iK); }
+  frameCall.gauss.on = true; frameCall.gauss.fB = sp->baseline * cp->K[0]; frameCall.gauss.alpha = sp->alpha;
+  const float* rendering[1] = { ctx->scene_depth_ws }; pwn_hip_cloud* subCloud[1] = { subscene };
+  ConvertCall subCall = convert_call(cp, rendering, 0.f, 1, vrows, vcols, subCloud);
+  subCall.first_entry = 1;
+  const std::vector<int> slot(1, 0);
+  ConvertJob frameJob, subJob;
+  if (int rc = convert_prepare(ctx, frameCall, slot, true, frameJob)) return rc;
+  if (int rc = convert_prepare(ctx, subCall, slot, true, subJob)) return rc;
+  int* faultWord = ctx->counts_host + 2;           // behind the two counts: what counts_check reads for a call of two frames
+  const Mat3 K = mat3_from(cp->K);
+  const Mat4 sceneT0 = mat4_from(scene_T), offset = forced(cp->sensor_offset);
+  Mat4 renderKRt;
+  { Mat4 iKRt; Mat3 iK; projector_matrices(K, iso_mul(sceneT0, offset), renderKRt, iKRt, iK); }
+  const MergeView view = { cp->min_distance, cp->max_distance, sp->max_point_depth, vrows, vcols, sp->distance_threshold, sp->normal_threshold };
+  SceneStepRecord* rec = ctx->step_dev; SceneStepRecord* host = ctx->step_host;
+  const unsigned nbPix = (unsigned)((pixels + 255) / 256), nbBound = (unsigned)((bound + 255) / 256);
+  AlignHooks hooks;
+  hooks.pre_sub = [&](int, int, int, hipStream_t st) -> int {
+    *faultWord = 0;
+    if (frameJob.host_input) { if (int rc = convert_stage_frames(ctx, frameJob, 0, 1, st)) return rc; }
+    if (int rc = convert_enqueue(ctx, frameJob, 0, 1, st, faultWord)) return rc;
+    { StageTimer t(ctx, "scene_render", st);      // pwn_hip_project's launches, the depth image alone, on the size the device holds
+      HIPCHK(ctx, hipMemsetAsync(ctx->zref_ws, 0xFF, (size_t)pixels * 8, st), PWN_HIP_ERR_COPY);
+      if (k0 > 0) hipLaunchKernelGGL(k_project_single, dim3((unsigned)((k0 + 255) / 256)), dim3(256), 0, st, scene->d, renderKRt, cp->min_distance, cp->max_distance, vrows, vcols,
+                                     ctx->zref_ws, kZTag0);
+      hipLaunchKernelGGL(k_zbuf_resolve, dim3(std::min(nbPix, 2048u)), dim3(256), 0, st, ctx->zref_ws, pixels, (int*)nullptr, (float*)ctx->scene_depth_ws, kZTag0); }
+    return convert_enqueue(ctx, subJob, 0, 1, st, faultWord);
+  };
+  hooks.before_sync = [&]() -> int {
+    hipStream_t st = ctx->stream;
+    { StageTimer t(ctx, "scene_pose");
+      hipLaunchKernelGGL(k_scene_pose, dim3(1), dim3(1), 0, st, (const PairState*)ctx->state_ws, sceneT0, K, offset, (const int*)ctx->fault_dev,
+                         (const int*)ctx->align_fault_host, (const int*)scene->d.count, scene->d.capacity, rec, host); }
+    { StageTimer t(ctx, "scene_add");
+      hipLaunchKernelGGL(k_scene_append, dim3(nbPix), dim3(256), 0, st, scene->d, scene->sb, cloud->d, cloud->sb, (const SceneStepRecord*)rec);
+      hipLaunchKernelGGL(k_scene_grow, dim3(1), dim3(1), 0, st, scene->d, cloud->d, rec, host); }
+    unsigned tag = kZTag0;
+    if (int rc = take_tags(ctx, 1, &tag)) return rc;
+    { StageTimer t(ctx, "scene_merge");
+      const SceneStepRecord* r = rec;
+      hipLaunchKernelGGL(k_scene_merge_project, dim3(nbBound), dim3(256), 0, st, scene->d, r, cp->min_distance, cp->max_distance, vrows, vcols, ctx->zref_ws, tag);
+      HIPCHK(ctx, hipMemsetAsync(d_head, 0xFF, sizeof(int) * bound, st), PWN_HIP_ERR_COPY);
+      hipLaunchKernelGGL(k_scene_merge_classify, dim3(nbBound), dim3(256), 0, st, scene->d, r, view, (const unsigned long long*)ctx->zref_ws, tag, d_collapsed, d_head, d_next);
+      hipLaunchKernelGGL(k_scene_merge_accumulate, dim3(nbBound), dim3(256), 0, st, scene->d, scene->sb, r, (const int*)d_collapsed, (const int*)d_head, (const int*)d_next);
+      hipLaunchKernelGGL(k_scene_merge_keep_flags, dim3(nbBound), dim3(256), 0, st, scene->d, r, d_collapsed, (int)bound, d_keep);
+      if (int rc = exclusive_scan(ctx, d_keep, d_offs, (int)bound, d_sums, ctx->scene_total)) return rc;
+      hipLaunchKernelGGL(k_scene_merge_compact, dim3(nbBound), dim3(256), 0, st, scene->d, scene->sb, back, sback, r, (const int*)d_keep, (const int*)d_offs);
+      hipLaunchKernelGGL(k_scene_gauss_tail, dim3(nbBound), dim3(256), 0, st, scene->d, scene->sb, sback, r, (const int*)ctx->scene_total);
+      hipLaunchKernelGGL(k_scene_merge_count, dim3(1), dim3(1), 0, st, scene->d, (const int*)ctx->scene_total, rec, host); }
+    HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+    if (collapsed) HIPCHK(ctx, hipMemcpyAsync(collapsed, d_collapsed, sizeof(int) * bound, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
+    return PWN_HIP_OK;
+  };
+  // after the wait: an attempt whose projection gave up commits nothing (align_finish digests the fault word, the repeat converts again); else
+  // the two conversions end as a batch of two frames ends
+  hooks.after_sync = [&]() -> int {
+    if (*(volatile int*)ctx->align_fault_host != 0) return PWN_HIP_OK;
+    pwn_hip_cloud* both[2] = { cloud, subscene };
+    if (int rc = counts_check(ctx, both, 2)) return rc;
+    cloud_commit_with_gaussians(cloud, ctx->counts_host[0]); frameJob.committed = true;
+    cloud_commit(subscene, ctx->counts_host[1]); subJob.committed = true;
+    return PWN_HIP_OK;
+  };
+  pwn_hip_cloud* refs[1] = { subscene }; pwn_hip_cloud* curs[1] = { cloud };
+  const Mat4 I = mat4_identity();
+  AlignCall call = align_call(ap, 1, refs, curs, I.m, &result->align);
+  call.hooks = &hooks;
+  if (int rc = align_batch_impl(ctx, call)) return rc;
+  ctx->img.invalidate();                  // slot 0 of the z-buffer was used
+  if (host->skipped) return fail(ctx, PWN_HIP_ERR_LAUNCH, "mapping step: skipped on the device without a fault on the host");
+  // ---- the bookkeeping of pwn_hip_cloud_add and pwn_hip_merge
+  const int nAdd = host->sizeAdd, nMerge = host->sizeMerge;
+  scene->content.set_gaussians(nAdd);     // _gaussians.resize(k + cloud.gaussians().size()) (cloud.cpp:153); the merge does not resize it
+  if (nAdd > 0) scene->swap_sides();
+  if (int rc = cloud_edit(ctx, scene, nMerge, false)) return rc;      // edit: the kernels have set the device's word
+  std::memcpy(result->scene_T, host->sceneT.m, sizeof(result->scene_T));
+  result->n_cloud = cloud->content.n; result->n_subscene = subscene->content.n;
+  result->size_after_add = nAdd; result->size_after_merge = nMerge;
+  return PWN_HIP_OK;
+}
+
 // Merger2::merge (pwn_tracker2/merger2.cpp:106-183) for the clouds of a node list (PwnMerger::mergeNodeList, pwn_tracker2/pwn_merger.cpp:44-54) in one
 // submission: per cloud the two projections, the pixel loop's decisions and in-place fuses, the ordered compaction of the appended pixels and the
 // appends (pwn_scene_kernels.h).  The total's size stays on the device between the clouds (CloudDev::count); the grids are sized by the host's upper

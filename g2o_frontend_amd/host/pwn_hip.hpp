@@ -675,6 +675,72 @@ class Aligner {
   pwn_hip_align_result _result;
 };
 
+// The mapping loop of pwn_aligner.cpp:166-209 (pwn_odometry_sequential_controller.cpp:124-171), a frame per processFrame and a submission per
+// frame (pwn_hip_scene_step): the frame is converted, tracked against the rendering of the scene and fused into it.  The chunk's Cloud::save is
+// the caller's: save scene() under sceneT().inverse() * globalT(), then newChunk().
+class SceneAligner {
+ public:
+  SceneAligner(Context* ctx, DepthImageConverter* converter, Aligner* aligner, Merger* merger, int capacity, const Isometry3f& sensorOffset = Isometry3f::Identity(),
+               int imageScale = 0, float maxDepthCov = 0.01f)
+      : _ctx(ctx), _converter(converter), _aligner(aligner), _merger(merger), _capacity(capacity), _sensorOffset(sensorOffset), _imageScale(imageScale),
+        _maxDepthCov(maxDepthCov), _scene(new Cloud(*ctx, capacity)) { _sensorOffset.forceLastRow(); }
+  Cloud* scene() { return _scene.get(); }
+  Cloud* cloud() { return _cloud.get(); }            // the last frame's cloud, scene-ready
+  Cloud* subscene() { return _subscene.get(); }      // what it was tracked against
+  const Isometry3f& sceneT() const { return _sceneT; }
+  const Isometry3f& globalT() const { return _globalT; }
+  const pwn_hip_scene_step_result& result() const { return _result; }
+  const std::vector<int>& collapsedIndices() const { return _collapsedIndices; }
+  pwn_hip_scene_step_params stepParams() const {
+    pwn_hip_scene_step_params sp; pwn_hip_default_scene_step_params(&sp);
+    sp.distance_threshold = _merger->distanceThreshold(); sp.normal_threshold = _merger->normalThreshold(); sp.max_point_depth = _merger->maxPointDepth();
+    sp.baseline = _converter->projector()->baseline(); sp.alpha = _converter->projector()->alpha();
+    sp.step = _imageScale; sp.max_depth_cov = _maxDepthCov;
+    return sp;
+  }
+  // one frame -> Aligner::T() of its alignment against the scene (the identity for the first frame of a chunk)
+  Isometry3f processFrame(const DepthImage& depth) { return step(depth.data.data(), 0, 0.f, depth.rows, depth.cols); }
+  Isometry3f processFrame(const RawDepthImage& raw, float depthScale) { return step(raw.data.data(), 1, depthScale, raw.rows, raw.cols); }
+  // pwn_aligner.cpp:188-199: a new scene that holds the last frame's cloud at the identity; the one it replaces is returned (it holds that
+  // frame too: the reference saves its chunk before the frame is added)
+  std::unique_ptr<Cloud> newChunk() {
+    std::unique_ptr<Cloud> old(new Cloud(*_ctx, _capacity));
+    old.swap(_scene);
+    _sceneT.setIdentity();
+    if (_cloud) {
+      _scene->add(*_cloud, _sceneT);
+      _merger->merge(_scene.get(), _sceneT * _sensorOffset);
+      _converter->projector()->setTransform(Isometry3f::Identity());
+    }
+    return old;
+  }
+ private:
+  Isometry3f step(const void* frame, int raw, float depthScale, int rows, int cols) {
+    const int vrows = _imageScale ? rows / _imageScale : rows, vcols = _imageScale ? cols / _imageScale : cols;
+    if (!_cloud || _pixels < vrows * vcols) { _cloud.reset(new Cloud(*_ctx, vrows * vcols)); _subscene.reset(new Cloud(*_ctx, vrows * vcols)); _pixels = vrows * vcols; }
+    _aligner->projector()->setImageSize(vrows, vcols);
+    _merger->setImageSize(vrows, vcols);
+    _aligner->setInitialGuess(Isometry3f::Identity()); _aligner->setSensorOffset(_sensorOffset);      // pwn_aligner.cpp:183-184
+    const pwn_hip_converter_params cp = _converter->params(_sensorOffset);
+    const pwn_hip_aligner_params ap = _aligner->params();
+    const pwn_hip_scene_step_params sp = stepParams();
+    _collapsedIndices.assign(_scene->size() + (size_t)vrows * vcols, -1);
+    _ctx->check(pwn_hip_scene_step(_ctx->handle(), &cp, &ap, &sp, frame, raw, depthScale, rows, cols, _sceneT.data(), _scene->handle(), _cloud->handle(),
+                                   _subscene->handle(), &_result, _collapsedIndices.data()));
+    _collapsedIndices.resize((size_t)_result.size_after_add);
+    const Isometry3f T(_result.align.T);
+    _globalT = _globalT * T; _globalT.forceLastRow();
+    _sceneT = Isometry3f(_result.scene_T);
+    return T;
+  }
+  Context* _ctx; DepthImageConverter* _converter; Aligner* _aligner; Merger* _merger;
+  int _capacity; Isometry3f _sensorOffset; int _imageScale; float _maxDepthCov; int _pixels = 0;
+  std::unique_ptr<Cloud> _scene, _cloud, _subscene;
+  Isometry3f _sceneT, _globalT;
+  pwn_hip_scene_step_result _result;
+  std::vector<int> _collapsedIndices;
+};
+
 // pwn_tracker/pwn_matcher_base.{h,cpp}: makeCloud + matchClouds with the reference's quirks kept (guess z zeroed :114,
 // projector re-configured and scaled per call :117-119, information matrix = 100*I :147-148).
 struct PwnMatcherBase {

@@ -658,6 +658,45 @@ int pwn_hip_voxelize(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, float resolution, i
 int pwn_hip_cloud_save(pwn_hip_ctx* ctx, const pwn_hip_cloud* cloud, const char* filename, const float T[16], int step, int binary);
 int pwn_hip_cloud_load(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, const char* filename, float T_out[16]);
 
+/* ---- the mapping step (pwn_aligner.cpp:166-209, pwn_odometry_sequential_controller.cpp:124-171) ------------------------------ */
+/* One frame of the mapping loop in one submission: the host queues everything on the context's stream and waits once.  In stream order:
+ *   1. the frame is converted into `cloud`, scene-ready (Stats and sensor-noise Gaussians: pwn_hip_convert_batch_ex with both extras), behind
+ *      DepthImage_scale when sp->step != 0 (step and max_depth_cov as in pwn_hip_convert_batch_ex);
+ *   2. `scene` is rendered under scene_T * cp->sensor_offset (pwn_hip_iso_mul) into a depth image on the device (pwn_hip_project);
+ *   3. that image is converted into `subscene` (pwn_hip_convert_batch);
+ *   4. `subscene` (reference) is aligned against `cloud` (current) from the identity, as pwn_hip_align does it with the context's settings;
+ *   5. one thread forms scene_T' = scene_T * Aligner::T() with the last row forced, the projector matrices of scene_T' * cp->sensor_offset and
+ *      Cloud::add's identity test;
+ *   6. Cloud::add(cloud, scene_T') on `scene` (pwn_hip_cloud_add) with the size of `cloud` read on the device;
+ *   7. Merger::merge on `scene` (pwn_hip_merge) under scene_T' * cp->sensor_offset, with the projector of cp, the image size that was converted
+ *      and sp's thresholds, on the size the add left.
+ * The result is, byte for byte, what those seven calls give one after the other (total_time_ms apart).  rows, cols: the frame as the caller
+ * holds it; ap->rows, ap->cols must be the size that is converted (rows / step, cols / step).  frame: float metres, or uint16 with depth_scale
+ * when raw_u16 != 0; host or device memory.  scene_T: host, the scene pose before the frame.  collapsed (optional, host,
+ * size(scene) + converted pixels ints): Merger::_collapsedIndices for the size the add left, -1 behind it.
+ * A scene of size 0 is allowed (the reference's first frame: nothing is rendered, the pose stays the identity of the alignment).  If a
+ * projection of the alignment gave up on a pixel the step leaves `scene` alone on the device and the call runs once more with the two-pass
+ * projection, as pwn_hip_align does; after a converter time-out `scene` is untouched as well and the call returns PWN_HIP_ERR_LAUNCH.
+ * Refused, the three clouds untouched: PWN_HIP_ERR_INVALID_ARGUMENT for a null argument, a scene that has fewer Gaussians than points, two
+ * equal handles, a cloud of another context, clouds of different omega storages, an aligner image size that is not the converted one;
+ * PWN_HIP_ERR_CAPACITY when size(scene) + converted pixels exceeds the scene's capacity or 2^25, or `cloud` / `subscene` hold fewer points
+ * than the converted image has pixels. */
+typedef struct pwn_hip_scene_step_params {
+  float distance_threshold, normal_threshold, max_point_depth;   /* Merger (merger.cpp:6-8) */
+  float baseline, alpha;                                         /* the Gaussians of `cloud`, as in pwn_hip_convert_extras */
+  int step; float max_depth_cov;                                 /* DepthImage_scale in front of the conversion; step 0: the frame as it is */
+} pwn_hip_scene_step_params;
+typedef struct pwn_hip_scene_step_result {
+  pwn_hip_align_result align;
+  float scene_T[16];                                             /* the scene pose after the frame */
+  int n_cloud, n_subscene;                                       /* points of `cloud` and `subscene` */
+  int size_after_add, size_after_merge;                          /* points of `scene` */
+} pwn_hip_scene_step_result;
+void pwn_hip_default_scene_step_params(pwn_hip_scene_step_params* p);
+int pwn_hip_scene_step(pwn_hip_ctx* ctx, const pwn_hip_converter_params* cp, const pwn_hip_aligner_params* ap, const pwn_hip_scene_step_params* sp,
+                       const void* frame, int raw_u16, float depth_scale, int rows, int cols, const float scene_T[16], pwn_hip_cloud* scene,
+                       pwn_hip_cloud* cloud, pwn_hip_cloud* subscene, pwn_hip_scene_step_result* result, int* collapsed);
+
 /* ------------------------------------------------------------------ helpers ------------------ */
 /* PinholePointProjector::_updateMatrices (pinholepointprojector.cpp:17-31): KRt, iKRt (4x4), iK (3x3) */
 void pwn_hip_projector_matrices(const float K[9], const float T[16], float KRt[16], float iKRt[16], float iK[9]);

@@ -6,6 +6,10 @@
 // Differences from the reference harness: depth images are binary PGM (P5, maxval 65535) instead of PNG (no OpenCV here); the
 // configuration keys are the reference's (pwn_aligner.cpp:295-327) plus chunkStep.
 //
+// --one-call (opt-in, after the three arguments): every frame is one pwn_hip_scene_step (SceneAligner of the mirror) instead of the seven calls
+// composed here.  The trajectory file is the same byte for byte.  At a chunk boundary the saved scene holds the boundary frame as well (the step
+// fuses the frame it tracked; the reference saves the chunk before the add), and the new scene starts from that frame as in the reference.
+//
 //   g++ -O2 -std=c++17 -I. tools/pwn_hip_scene_aligner.cpp -o tools/pwn_hip_scene_aligner -Lg2o_frontend_amd -lpwn_hip -Wl,-rpath,$ORIGIN/../g2o_frontend_amd
 #include <cstdio>
 #include <fstream>
@@ -49,7 +53,7 @@ static bool fillInputParametersMap(std::map<std::string, float>& m, const std::s
 
 int main(int argc, char** argv) {
   if (argc < 4) {
-    std::cout << "USAGE: pwn_hip_scene_aligner configuration.txt depthImageList.txt outputPrefix" << std::endl;
+    std::cout << "USAGE: pwn_hip_scene_aligner configuration.txt depthImageList.txt outputPrefix [--one-call]" << std::endl;
     return 0;
   }
   std::map<std::string, float> P;
@@ -59,6 +63,7 @@ int main(int argc, char** argv) {
   const int imageScale = (int)get("imageScale", 1.f);
   const int chunkStep = (int)get("chunkStep", 1000.f);
   const std::string prefix = argv[3];
+  const bool oneCall = argc > 4 && std::string(argv[4]) == "--one-call";
   try {
     std::ifstream list(argv[2]);
     if (!list) { std::cerr << "cannot open " << argv[2] << std::endl; return 1; }
@@ -105,6 +110,26 @@ int main(int argc, char** argv) {
     std::ofstream os((prefix + "_trajectory.txt").c_str());
     os.precision(9);
     int counter = 0; bool firstDepth = true;
+    SceneAligner mapper(&ctx, &converter, &aligner, &merger, sceneCapacity, sensorOffset, imageScale, 0.01f);
+    for (size_t fi = 0; fi < files.size() && oneCall; ++fi) {
+      if (!readPGM16(files[fi], raw)) { std::cerr << "cannot read " << files[fi] << std::endl; return 1; }
+      mapper.processFrame(raw, depthScale);
+      if (!firstDepth && counter++ % chunkStep == 0) {
+        char buffer[1024];
+        std::snprintf(buffer, sizeof(buffer), "%s_scene-%03d.pwn", prefix.c_str(), counter);
+        mapper.scene()->save(buffer, mapper.sceneT().inverse() * mapper.globalT(), 1, true);
+        mapper.newChunk();
+      }
+      float v[6]; t2v(mapper.globalT(), v);
+      os << fi << " " << v[0] << " " << v[1] << " " << v[2] << " " << v[3] << " " << v[4] << " " << v[5] << " " << mapper.scene()->size() << std::endl;
+      firstDepth = false;
+    }
+    if (oneCall) {
+      char buffer[1024];
+      std::snprintf(buffer, sizeof(buffer), "%s_scene-%03d.pwn", prefix.c_str(), counter);
+      mapper.scene()->save(buffer, mapper.sceneT().inverse() * mapper.globalT(), 1, true);
+      return 0;
+    }
     for (size_t fi = 0; fi < files.size(); ++fi) {
       if (!readPGM16(files[fi], raw)) { std::cerr << "cannot read " << files[fi] << std::endl; return 1; }
       depth.create(raw.rows, raw.cols);
