@@ -90,6 +90,10 @@ class SceneStepResult(C.Structure):
                 ("size_after_merge", C.c_int)]
 
 
+class ConsensusParams(C.Structure):
+    _fields_ = [("inlier_translational_threshold", C.c_float), ("inlier_rotational_threshold", C.c_float), ("min_times_checked", C.c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/pwn_hip.h declares
 _VP, _I, _F = C.c_void_p, C.c_int, C.c_float
 PROTOTYPES = {
@@ -169,6 +173,10 @@ PROTOTYPES = {
     "pwn_hip_match_batch": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _F, _VP, _VP]),
     "pwn_hip_match_batch_records": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _F, _VP, _I, _VP, _VP, _VP]),
     "pwn_hip_closure_batch_records": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _F, _VP, _I, _VP, _VP, _VP, _VP]),
+    "pwn_hip_default_consensus_params": (None, [_VP]),
+    "pwn_hip_validate_relation": (None, [_I, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
+    "pwn_hip_validate_relations_host": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(_I)]),
+    "pwn_hip_validate_relations": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_projector_matrices": (None, [_VP, _VP, _VP, _VP, _VP]),
     "pwn_hip_project_point": (_I, [_VP, _VP, _F, _F, _VP, C.POINTER(_I), C.POINTER(_I), C.POINTER(_F)]),
     "pwn_hip_unproject_pixel": (_I, [_VP, _VP, _F, _F, _I, _I, _F, _VP]),

@@ -1786,6 +1786,94 @@ class PwnCloserWithMerger:
         return relations
 
 
+class MapCloser:
+    """The part of boss_map_building::MapCloser (map_closer.{h,cpp}) behind processPartition: the pool of relations and validatePartitions
+    (:286-417), the consensus vote that commits or removes the relations joining two partitions (pwn_hip_validate_relations; with ctx = None
+    the host call, pwn_hip_validate_relations_host: the same bits).  A relation is the dict processPartition returns -- nodes (a pair of
+    MapNode), transform (double 4x4) -- extended by the ClosureInfo fields consensusTimeChecked, consensusCumInlier,
+    consensusCumOutlierTimes and accepted.  The reference walks std::sets of pointers, whose order is not defined; here the relations of a
+    call come in the order they were added.
+    consistent (not in the reference, off by default): every transform is inverted before use.  The closers store nodes[0]^-1 * nodes[1] with
+    nodes[0] in the current partition, and validateRelation's rule is a consistency check only for the inverse of that (docs/parity.md)."""
+
+    def __init__(self, ctx: Context | None = None, consistent: bool = False):
+        self.ctx, self.consistent = ctx, bool(consistent)
+        p = _lib.ConsensusParams()
+        _lib.lib().pwn_hip_default_consensus_params(C.byref(p))
+        self._params = p
+        self._relations = []
+
+    def setConsensusInlierTranslationalThreshold(self, v): self._params.inlier_translational_threshold = float(v)
+    def setConsensusInlierRotationalThreshold(self, v): self._params.inlier_rotational_threshold = float(v)
+    def setConsensusMinTimesCheckedThreshold(self, v): self._params.min_times_checked = int(v)
+    def consensusInlierTranslationalThreshold(self): return self._params.inlier_translational_threshold
+    def consensusInlierRotationalThreshold(self): return self._params.inlier_rotational_threshold
+    def consensusMinTimesCheckedThreshold(self): return self._params.min_times_checked
+
+    def addRelation(self, r):
+        """:111-112"""
+        r.setdefault("consensusTimeChecked", 0); r.setdefault("consensusCumInlier", 0); r.setdefault("consensusCumOutlierTimes", 0)
+        r.setdefault("accepted", False)
+        self._relations.append(r)
+
+    def relations(self): return list(self._relations)
+
+    def joining(self, other, current):
+        """:289-306 -> (the relations that join a node of `other` with a node of `current`, in insertion order; the flag of each: 1 = its
+        nodes[1] is the one in current, the transform is inverted before use, :211-214)"""
+        inOther = lambda n: any(n is o for o in other)
+        inCurrent = lambda n: any(n is o for o in current)
+        rels, flags = [], []
+        for r in self._relations:
+            n0, n1 = r["nodes"]
+            if (inOther(n0) or inOther(n1)) and (inCurrent(n0) or inCurrent(n1)):
+                rels.append(r); flags.append(0 if inCurrent(n0) else 1)
+        return rels, flags
+
+    def validatePartitions(self, other, current, records=None):
+        """:286-417 -> (committed, removed).  records (optional): the records a closer call wrote for exactly these relations, in their order
+        ([n, 64 | 72 | 128] float32, host array or device tensor / DeviceBuffer): the transforms are then taken from them, words [0:16].
+        The removed relations leave the store; "no inliers" (:362) raises PwnHipError and changes nothing."""
+        rels, flags = self.joining(other, current)
+        n = len(rels)
+        if n == 0:
+            return [], []
+        cm = lambda T: np.asarray(T, np.float64).reshape(4, 4).T.reshape(16)
+        tc = np.ascontiguousarray(np.stack([cm(r["nodes"][f].transform()) for r, f in zip(rels, flags)]))
+        to = np.ascontiguousarray(np.stack([cm(r["nodes"][1 - f].transform()) for r, f in zip(rels, flags)]))
+        fl = np.asarray(flags, np.int32) ^ (1 if self.consistent else 0)
+        cnt = [np.array([r[k] for r in rels], np.int32) for k in ("consensusTimeChecked", "consensusCumInlier", "consensusCumOutlierTimes")]
+        dec = np.zeros(n, np.int32)
+        L = _lib.lib()
+        tr, rf = None, 0
+        if records is None:
+            tr = np.ascontiguousarray(np.stack([cm(r["transform"]) for r in rels]))
+        else:
+            if tuple(records.shape)[0] != n:
+                raise ValueError("validatePartitions: %d records for %d relations" % (tuple(records.shape)[0], n))
+            rf = int(tuple(records.shape)[1])
+        if self.ctx is None:
+            if records is not None:
+                tr = np.ascontiguousarray(np.asarray(records, np.float32)[:, :16].astype(np.float64)); tr[:, [3, 7, 11]] = 0.0; tr[:, 15] = 1.0
+            empty = C.c_int(-1)
+            rc = L.pwn_hip_validate_relations_host(C.byref(self._params), n, _ptr(tc), _ptr(to), _ptr(tr), _ptr(fl), _ptr(cnt[0]), _ptr(cnt[1]), _ptr(cnt[2]),
+                                                   _ptr(dec), None, None, C.byref(empty))
+            if rc:
+                raise PwnHipError(rc, L.pwn_hip_last_error_string(None).decode())
+        else:
+            self.ctx.check(L.pwn_hip_validate_relations(self.ctx.h, C.byref(self._params), n, _ptr(tc), _ptr(to), _ptr(tr), _ptr(records), rf, _ptr(fl),
+                                                        _ptr(cnt[0]), _ptr(cnt[1]), _ptr(cnt[2]), _ptr(dec), None, None))
+        committed, removed = [], []
+        for i, r in enumerate(rels):
+            r["consensusTimeChecked"], r["consensusCumInlier"], r["consensusCumOutlierTimes"] = int(cnt[0][i]), int(cnt[1][i]), int(cnt[2][i])
+            if dec[i] == 1:
+                r["accepted"] = True; committed.append(r)
+            elif dec[i] == 2:
+                removed.append(r)
+        self._relations = [r for r in self._relations if not any(r is q for q in removed)]
+        return committed, removed
+
+
 class PwnMerger:
     """pwn_tracker2/pwn_merger.{h,cpp}: mergeNodeList (:28-62), what MapMerger::process (boss_map_building/map_merger.cpp:43-82) calls every
     listSize + 1 key nodes -- the cached clouds of the list fused, one after the other, into one local-map cloud in the frame of the first

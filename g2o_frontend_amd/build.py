@@ -6,7 +6,7 @@ import subprocess
 import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("pwn_hip_capi.hip", "pwn_buffers.h", "pwn_kernels.h", "pwn_math.h", "pwn_scene_kernels.h", "pwn_scene_capi.h", "pwn_stats.h")]
+SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("pwn_hip_capi.hip", "pwn_buffers.h", "pwn_kernels.h", "pwn_math.h", "pwn_scene_kernels.h", "pwn_scene_capi.h", "pwn_stats.h", "pwn_consensus.h")]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pwn_hip.h")
 TEST_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pwn_hip_testing.h")
 OUT = os.path.join(_HERE, "libpwn_hip.so")
@@ -121,6 +121,13 @@ def build_tools(force: bool = False) -> str:
     deps14 = [src14] + deps[1:]
     if force or (not os.path.exists(out14)) or any(os.path.getmtime(d) > os.path.getmtime(out14) for d in deps14):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src14, "-o", out14, "-L", _HERE, "-lpwn_hip",
+                               "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
+    # MapCloser::validatePartitions of the C++ mirror against the decisions and counters the Python mirror wrote to a file (exit status 0 = no difference)
+    src15 = os.path.join(root, "tools", "pwn_hip_consensus_check.cpp")
+    out15 = os.path.join(root, "tools", "pwn_hip_consensus_check")
+    deps15 = [src15] + deps[1:]
+    if force or (not os.path.exists(out15)) or any(os.path.getmtime(d) > os.path.getmtime(out15) for d in deps15):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src15, "-o", out15, "-L", _HERE, "-lpwn_hip",
                                "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
     # PwnCloser::processPartition over the GPUs of a node in native code: the mirror + RCCL (broadcast of the flat `current` cloud, all-gather of the
     # match records); the program's own streams and events come from the HIP runtime

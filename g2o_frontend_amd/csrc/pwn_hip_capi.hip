@@ -13,6 +13,7 @@
 #include "pwn_kernels.h"
 #include "pwn_scene_kernels.h"
 #include "pwn_stats.h"
+#include "pwn_consensus.h"
 
 #include <algorithm>
 #include <chrono>
@@ -298,6 +299,10 @@ struct pwn_hip_ctx {
   int manifold_chunk = kMaxCloudPoints;
   // pwn_hip_scene_step (allocated by the first such call): the rendering of the scene, the step record on the device and its page-locked copy
   DevBuf<float> scene_depth_ws; DevBuf<SceneStepRecord> step_dev; HostBuf<SceneStepRecord> step_host;
+  // pwn_hip_validate_relations (they grow with the call): per relation its four transforms, the isIn bit matrix, the column counts and behind
+  // them the empty-column word, the staging of the call's host-side arrays, and the page-locked copy of the empty-column word
+  DevBuf<ConsensusRel> consensus_rel; DevBuf<unsigned long long> consensus_bits; DevBuf<int> consensus_counts;
+  DevBuf<char> consensus_stage; HostBuf<int> consensus_flag_host;
 };
 
 namespace {
@@ -3314,6 +3319,145 @@ void pwn_hip_iso_mul(const float A[16], const float B[16], float out[16]) { cons
 void pwn_hip_v2t(const float v[6], float T[16]) { const Mat4 t = v2t(v); std::memcpy(T, t.m, sizeof(t.m)); }
 void pwn_hip_t2v(const float T[16], float v[6]) { t2v(mat4_from(T), v); }
 void pwn_hip_ldlt_solve6(const float H[36], const float b[6], float x[6]) { ldlt_solve6(H, b, x); }
+
+// ---------------------------------------------------------------------------------------------------- consensus validation of closures
+void pwn_hip_default_consensus_params(pwn_hip_consensus_params* p) {
+  if (!p) return;
+  p->inlier_translational_threshold = 0.5 * 0.5;                             // map_closer.cpp:63
+  p->inlier_rotational_threshold = (float)(15.0f * M_PI / 180.0f);           // :64
+  p->min_times_checked = 5;                                                  // :65
+}
+static const char* consensus_params_refused(const pwn_hip_consensus_params* p) {
+  if (!p) return "null params";
+  if (!(p->inlier_translational_threshold > 0.f)) return "the translational threshold must be positive";
+  if (!(p->inlier_rotational_threshold > 0.f && (double)p->inlier_rotational_threshold <= kConsensusMaxRotThreshold))
+    return "the rotational threshold must lie in (0, 2 pi / 3]: beyond it the decision depends on the Eigen version";
+  return nullptr;
+}
+static ConsensusRel consensus_rel_host(const double* tc, const double* to, const double* tr, const int* flags, int i) {
+  ConsensusRel r;
+  consensus_prepare(tc + (size_t)16 * i, to + (size_t)16 * i, tr + (size_t)16 * i, nullptr, flags ? flags[i] : 0, r);
+  return r;
+}
+void pwn_hip_validate_relation(int n, const double* tc, const double* to, const double* tr, const int* flags, int i, float* translational_errors,
+                               float* rotational_errors) {
+  if (n <= 0 || !tc || !to || !tr || i < 0 || i >= n || !translational_errors || !rotational_errors) return;
+  const ConsensusRel ri = consensus_rel_host(tc, to, tr, flags, i);
+  for (int j = 0; j < n; ++j) {
+    const ConsensusRel rj = consensus_rel_host(tc, to, tr, flags, j);
+    consensus_pair(ri.tfix, rj.tc, rj.toInv, rj.trInv, translational_errors[j], rotational_errors[j]);
+  }
+}
+int pwn_hip_validate_relations_host(const pwn_hip_consensus_params* p, int n, const double* tc, const double* to, const double* tr, const int* flags,
+                                    int* times_checked, int* cum_inlier, int* cum_outlier_times, int* decisions, float* translational_errors,
+                                    float* rotational_errors, int* empty_column) {
+  if (empty_column) *empty_column = -1;
+  if (const char* why = consensus_params_refused(p)) return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, why);
+  if (n < 0) return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, "negative n");
+  if (n > PWN_HIP_CONSENSUS_MAX_RELATIONS) return fail(nullptr, PWN_HIP_ERR_CAPACITY, "more than PWN_HIP_CONSENSUS_MAX_RELATIONS relations");
+  if (n == 0) return PWN_HIP_OK;
+  if (!tc || !to || !tr || !times_checked || !cum_inlier || !cum_outlier_times || !decisions)
+    return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  const float thrT = p->inlier_translational_threshold, thrR = p->inlier_rotational_threshold;
+  std::vector<ConsensusRel> rel((size_t)n);
+  for (int i = 0; i < n; ++i) rel[i] = consensus_rel_host(tc, to, tr, flags, i);
+  const int W = (n + kConsensusTile - 1) / kConsensusTile;
+  std::vector<unsigned long long> bits((size_t)W * n, 0ull);               // the device's layout: word (tile row a, column i) at a * n + i
+  std::vector<int> counts((size_t)n, 0);
+  int empty = -1;
+  for (int i = 0; i < n; ++i) {
+    for (int j = 0; j < n; ++j) {
+      float te, re;
+      consensus_pair(rel[i].tfix, rel[j].tc, rel[j].toInv, rel[j].trInv, te, re);
+      if (translational_errors) translational_errors[(size_t)j + (size_t)n * i] = te;
+      if (rotational_errors) rotational_errors[(size_t)j + (size_t)n * i] = re;
+      if (consensus_is_in(te, re, thrT, thrR)) { bits[(size_t)(j / kConsensusTile) * n + i] |= 1ull << (j % kConsensusTile); counts[i] += 1; }
+    }
+    if (counts[i] == 0 && empty < 0) empty = i;
+  }
+  if (empty >= 0) {
+    if (empty_column) *empty_column = empty;
+    return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, "no inliers in column " + std::to_string(empty));
+  }
+  for (int j = 0; j < n; ++j) {
+    int in = 0, out = 0;
+    for (int i = 0; i < n; ++i) { if ((bits[(size_t)(j / kConsensusTile) * n + i] >> (j % kConsensusTile)) & 1ull) in += counts[i]; else out += 1; }
+    times_checked[j] += 1; cum_inlier[j] += in; cum_outlier_times[j] += out;
+    decisions[j] = consensus_decision(times_checked[j], cum_inlier[j], cum_outlier_times[j], p->min_times_checked);
+  }
+  return PWN_HIP_OK;
+}
+int pwn_hip_validate_relations(pwn_hip_ctx* ctx, const pwn_hip_consensus_params* p, int n, const double* tc, const double* to, const double* tr,
+                               const float* records, int record_floats, const int* flags, int* times_checked, int* cum_inlier,
+                               int* cum_outlier_times, int* decisions, float* translational_errors, float* rotational_errors) {
+  if (!ctx) return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, "null ctx");
+  if (const char* why = consensus_params_refused(p)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, why);
+  if (n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "negative n");
+  if (n > PWN_HIP_CONSENSUS_MAX_RELATIONS) return fail(ctx, PWN_HIP_ERR_CAPACITY, "more than PWN_HIP_CONSENSUS_MAX_RELATIONS relations");
+  if ((tr != nullptr) == (records != nullptr)) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "exactly one of tr and records must be given");
+  if (records && record_floats != PWN_HIP_RECORD_FLOATS && record_floats != PWN_HIP_MATCH_RECORD_FLOATS && record_floats != PWN_HIP_CLOSURE_RECORD_FLOATS)
+    return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "record_floats is not one of the three record sizes");
+  if (n == 0) return PWN_HIP_OK;
+  if (!tc || !to || !times_checked || !cum_inlier || !cum_outlier_times || !decisions) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  HIPCHK(ctx, hipSetDevice(ctx->device), PWN_HIP_ERR_NO_DEVICE);
+  if (int rc = absorb_copies(ctx)) return rc;
+  hipStream_t st = ctx->stream;
+  const int W = (n + kConsensusTile - 1) / kConsensusTile;
+  const size_t nn = (size_t)n * n;
+  // host-side arrays pass through the staging block: inputs go up in front of the kernels, outputs come down behind them
+  // (tc, to, tr, records, flags: up; the three counters and decisions: up and down; the two matrices, up to 256 MB each: down)
+  struct Staged { void* user; size_t bytes; bool up, down; bool staged; size_t off; void* dev; };
+  auto arg = [](const void* user, size_t bytes, bool up, bool down) { return Staged{ const_cast<void*>(user), bytes, up, down, false, 0, const_cast<void*>(user) }; };
+  Staged a[11] = { arg(tc, sizeof(double) * 16 * n, true, false), arg(to, sizeof(double) * 16 * n, true, false), arg(tr, sizeof(double) * 16 * n, true, false),
+                   arg(records, sizeof(float) * (size_t)record_floats * n, true, false), arg(flags, sizeof(int) * n, true, false),
+                   arg(times_checked, sizeof(int) * n, true, true), arg(cum_inlier, sizeof(int) * n, true, true),
+                   arg(cum_outlier_times, sizeof(int) * n, true, true), arg(decisions, sizeof(int) * n, true, true),
+                   arg(translational_errors, sizeof(float) * nn, false, true), arg(rotational_errors, sizeof(float) * nn, false, true) };
+  size_t need = 256;
+  for (Staged& s : a)
+    if (s.user && !is_device_ptr(s.user)) { s.staged = true; s.off = need; need += (s.bytes + 255) & ~(size_t)255; }
+  HIPCHK(ctx, ctx->consensus_stage.ensure(need), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->consensus_rel.ensure((size_t)n), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->consensus_bits.ensure((size_t)W * n), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->consensus_counts.ensure((size_t)n + 1), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->consensus_flag_host.ensure(1), PWN_HIP_ERR_ALLOCATION);
+  for (Staged& s : a) {
+    if (!s.staged) continue;
+    s.dev = ctx->consensus_stage.p + s.off;
+    if (s.up) HIPCHK(ctx, hipMemcpyAsync(s.dev, s.user, s.bytes, hipMemcpyHostToDevice, st), PWN_HIP_ERR_COPY);
+  }
+  ctx->stages.clear();
+  int* emptyDev = ctx->consensus_counts + n;
+  {
+    StageTimer t(ctx, "consensus_prepare");
+    hipLaunchKernelGGL(k_consensus_prepare, dim3((n + 63) / 64), dim3(64), 0, st, n, (const double*)a[0].dev, (const double*)a[1].dev, (const double*)a[2].dev,
+                       (const float*)a[3].dev, record_floats, (const int*)a[4].dev, (ConsensusRel*)ctx->consensus_rel, emptyDev);
+  }
+  {
+    StageTimer t(ctx, "consensus_errors");
+    hipLaunchKernelGGL(k_consensus_errors, dim3(W, W), dim3(kConsensusTile), 0, st, (const ConsensusRel*)ctx->consensus_rel, n, p->inlier_translational_threshold,
+                       p->inlier_rotational_threshold, (unsigned long long*)ctx->consensus_bits, (float*)a[9].dev, (float*)a[10].dev);
+  }
+  {
+    StageTimer t(ctx, "consensus_count");
+    hipLaunchKernelGGL(k_consensus_count, dim3((n + 255) / 256), dim3(256), 0, st, (const unsigned long long*)ctx->consensus_bits, n, W, (int*)ctx->consensus_counts, emptyDev);
+  }
+  {
+    StageTimer t(ctx, "consensus_commit");
+    hipLaunchKernelGGL(k_consensus_commit, dim3(W), dim3(kConsensusTile), 0, st, (const unsigned long long*)ctx->consensus_bits, (const int*)ctx->consensus_counts,
+                       (const int*)emptyDev, n, p->min_times_checked, (int*)a[5].dev, (int*)a[6].dev, (int*)a[7].dev, (int*)a[8].dev);
+  }
+  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  // a call that found an empty column committed nothing: its staged counters come back as they went up
+  for (Staged& s : a)
+    if (s.staged && s.down) HIPCHK(ctx, hipMemcpyAsync(s.user, s.dev, s.bytes, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->consensus_flag_host, emptyDev, sizeof(int), hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
+  collect_stage_times(ctx);
+  const int empty = ctx->consensus_flag_host[0];
+  if (empty != kConsensusNoEmptyColumn) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "no inliers in column " + std::to_string(empty));
+  return PWN_HIP_OK;
+}
 
 }  // extern "C"
 

@@ -1211,7 +1211,11 @@ struct MapNode { int key = 0; Isometry3d transform; Isometry3d sensorOffset; };
 // reference walks a std::set of pointers, whose order is not defined; here the order is the caller's vector.
 class PwnCloserWithMerger {
  public:
-  struct Relation { const MapNode* nodes[2]; Isometry3d transform; double informationMatrix[36]; PwnMatcherBase::MatcherResult result; };
+  // the last four fields are ClosureInfo's (boss_map_building/map_closer.h): what MapCloser::validatePartitions counts and decides
+  struct Relation {
+    const MapNode* nodes[2]; Isometry3d transform; double informationMatrix[36]; PwnMatcherBase::MatcherResult result;
+    int consensusTimeChecked = 0, consensusCumInlier = 0, consensusCumOutlierTimes = 0; bool accepted = false;
+  };
   PwnCloserWithMerger(Context* ctx, Merger2* merger, CloudCache* cache) : _ctx(ctx), _merger(merger), _cache(cache) {}
   int frameMinNonZeroThreshold = 3000, frameMaxOutliersThreshold = 100, frameMinInliersThreshold = 1000;
   static int som(size_t size) { const int s = (int)(size / 8); return s == 0 ? 1 : s; }                     // :134-135
@@ -1277,6 +1281,77 @@ class PwnCloserWithMerger {
   const MapNode* _current = nullptr;
   std::vector<const MapNode*> _currentPartitionActive, _nodeList;
   std::unique_ptr<DeviceImage> _currentPartitionImage, _otherPartitionImage;
+};
+
+// The part of boss_map_building::MapCloser (map_closer.{h,cpp}) behind processPartition: the pool of relations and validatePartitions
+// (:286-417), the consensus vote that commits or removes the relations joining two partitions (pwn_hip_validate_relations; without a context
+// the host call: the same bits).  The reference walks std::sets of pointers, whose order is not defined; here the relations of a call come in
+// the order they were added.  consistent (not in the reference, off by default): every transform is inverted before use -- the closers store
+// nodes[0]^-1 * nodes[1] with nodes[0] in the current partition, and validateRelation's rule is a consistency check only for the inverse of
+// that (docs/parity.md).
+class MapCloser {
+ public:
+  typedef PwnCloserWithMerger::Relation Relation;
+  explicit MapCloser(Context* ctx = nullptr, bool consistent_ = false) : consistent(consistent_), _ctx(ctx) { pwn_hip_default_consensus_params(&_params); }
+  bool consistent;
+  void setConsensusInlierTranslationalThreshold(float v) { _params.inlier_translational_threshold = v; }
+  void setConsensusInlierRotationalThreshold(float v) { _params.inlier_rotational_threshold = v; }
+  void setConsensusMinTimesCheckedThreshold(int v) { _params.min_times_checked = v; }
+  const pwn_hip_consensus_params& params() const { return _params; }
+  Relation* addRelation(const Relation& r) { _relations.push_back(r); return &_relations.back(); }      // :111-112
+  const std::list<Relation>& relations() const { return _relations; }
+  struct Validation { std::vector<Relation*> committed; std::vector<Relation> removed; };
+  // :286-417.  records (optional, host or device): the records a closer call wrote for exactly the joining relations, in their order; the
+  // transforms are then words [0:16] of them.  The removed relations leave the store (returned by value); "no inliers" (:362) throws Error.
+  Validation validatePartitions(const std::vector<const MapNode*>& other, const std::vector<const MapNode*>& current, const float* records = nullptr,
+                                int record_floats = 0) {
+    auto in = [](const std::vector<const MapNode*>& s, const MapNode* n) { for (const MapNode* o : s) if (o == n) return true; return false; };
+    std::vector<Relation*> rels; std::vector<int> flags;
+    for (Relation& r : _relations)                                                                        // :289-306
+      if ((in(other, r.nodes[0]) || in(other, r.nodes[1])) && (in(current, r.nodes[0]) || in(current, r.nodes[1]))) {
+        rels.push_back(&r); flags.push_back(in(current, r.nodes[0]) ? 0 : 1);                             // :206-214
+      }
+    Validation v;
+    const int n = (int)rels.size();
+    if (n == 0) return v;
+    std::vector<double> tc((size_t)16 * n), to((size_t)16 * n), tr((size_t)16 * n);
+    std::vector<int> fl(n), cnt[3], dec(n, 0);
+    for (auto& c : cnt) c.resize(n);
+    for (int k = 0; k < n; ++k) {
+      const Relation& r = *rels[k];
+      for (int row = 0; row < 4; ++row)
+        for (int col = 0; col < 4; ++col) {
+          tc[(size_t)16 * k + row + 4 * col] = r.nodes[flags[k]]->transform(row, col);
+          to[(size_t)16 * k + row + 4 * col] = r.nodes[1 - flags[k]]->transform(row, col);
+          tr[(size_t)16 * k + row + 4 * col] = r.transform(row, col);
+        }
+      fl[k] = flags[k] ^ (consistent ? 1 : 0);
+      cnt[0][k] = r.consensusTimeChecked; cnt[1][k] = r.consensusCumInlier; cnt[2][k] = r.consensusCumOutlierTimes;
+    }
+    if (_ctx)
+      _ctx->check(pwn_hip_validate_relations(_ctx->handle(), &_params, n, tc.data(), to.data(), records ? nullptr : tr.data(), records, record_floats, fl.data(),
+                                             cnt[0].data(), cnt[1].data(), cnt[2].data(), dec.data(), nullptr, nullptr));
+    else {
+      if (records) throw Error(PWN_HIP_ERR_INVALID_ARGUMENT, "MapCloser: records need a context");
+      int empty = -1;
+      const int rc = pwn_hip_validate_relations_host(&_params, n, tc.data(), to.data(), tr.data(), fl.data(), cnt[0].data(), cnt[1].data(), cnt[2].data(),
+                                                     dec.data(), nullptr, nullptr, &empty);
+      if (rc) throw Error(rc, pwn_hip_last_error_string(nullptr));
+    }
+    for (int k = 0; k < n; ++k) {
+      Relation& r = *rels[k];
+      r.consensusTimeChecked = cnt[0][k]; r.consensusCumInlier = cnt[1][k]; r.consensusCumOutlierTimes = cnt[2][k];
+      if (dec[k] == 1) { r.accepted = true; v.committed.push_back(&r); }
+    }
+    for (int k = 0; k < n; ++k)
+      if (dec[k] == 2) {
+        v.removed.push_back(*rels[k]);
+        for (auto it = _relations.begin(); it != _relations.end(); ++it) if (&*it == rels[k]) { _relations.erase(it); break; }
+      }
+    return v;
+  }
+ private:
+  Context* _ctx; pwn_hip_consensus_params _params; std::list<Relation> _relations;
 };
 
 // pwn_tracker2/pwn_merger.{h,cpp}: mergeNodeList (:28-62), what MapMerger::process (boss_map_building/map_merger.cpp:43-82) calls every

@@ -526,6 +526,52 @@ int pwn_hip_closure_batch_records(pwn_hip_ctx* ctx, const pwn_hip_aligner_params
                                   pwn_hip_cloud* const* currents, const float* initial_guesses, float frame_inlier_depth_threshold,
                                   const int* pair_ids, int first_pair_id, pwn_hip_align_result* results, pwn_hip_match_result* scores,
                                   pwn_hip_align_statistics* statistics, float* records);
+
+/* ---- consensus validation of closures (boss_map_building/map_closer.cpp:200-253, :286-417) -----------------------------------
+ * What MapCloser::process runs after every processPartition: validatePartitions(other, current).  For the n relations that join the two
+ * partitions, reference relation i predicts where every relation j should land; the n x n pose errors of validateRelation become two integer
+ * votes, and the votes decide which relations are committed (ClosureFoundMessage) and which are removed.
+ *   relation i = (tc_i, to_i, tr_i): the pose of its node in the current partition, of its node in the other partition, and its transform
+ *   TR_i = tr_i, or tr_i^-1 when bit 0 of flags[i] is set (the reference's `else` branch, :211-214 / :231-234);  tfix_i = (to_i TR_i) tc_i^-1
+ *   pair (j, i): te = TR_j^-1 (to_j^-1 (tfix_i tc_j));  transErr = (float)|te.translation|^2;  rotErr = (float)AngleAxisd(te.linear()).angle()
+ *   isIn(j, i) = transErr < inlier_translational_threshold && fabs(rotErr) < inlier_rotational_threshold
+ * Order of effects: every times_checked goes up by one; for each column i with c_i = sum_j isIn(j, i): cum_inlier[j] += c_i where isIn(j, i),
+ * else cum_outlier_times[j] += 1; then decisions[j] = 0 (skipped: times_checked[j] < min_times_checked), 1 (accepted: cum_inlier[j] >
+ * cum_outlier_times[j]) or 2 (removed).  The three counters are ClosureInfo::consensusTimeChecked / consensusCumInlier /
+ * consensusCumOutlierTimes, in / out.
+ * All arithmetic is double in a fixed order, one text for the host and the device: the device call returns the host call's bits.  The angle is
+ * Eigen 3.3's (2 atan2(|vec|, |w|) of the unnormalised quaternion); Eigen <= 3.2 (2 acos(w)) takes the same decision for every rotational
+ * threshold up to 2 pi / 3, and a larger threshold is refused.
+ * tc, to: n x 16 doubles, column-major.  The transforms: tr (n x 16 doubles), or the records a closer call wrote (record_floats = 64, 72 or 128;
+ * T = words [0:16], each of the twelve upper entries converted to double, the last row forced) -- exactly one of the two.  flags may be NULL.
+ * The error matrices are optional: n x n floats, column-major, element (j, i) at j + n i (translationalErrors.col(i)).  Every array of the
+ * device call is host or device memory.
+ * A column without an inlier is the reference's throw "no inliers" (a NaN pose produces one): PWN_HIP_ERR_INVALID_ARGUMENT, the column named in
+ * pwn_hip_last_error_string (and in *empty_column by the host call, else -1), counters and decisions exactly as they were.  n == 0 is a
+ * no-op; n > PWN_HIP_CONSENSUS_MAX_RELATIONS returns PWN_HIP_ERR_CAPACITY; a NULL required argument, both or neither of tr and records,
+ * another record_floats, a translational threshold that is not positive or a rotational one outside (0, 2 pi / 3] return
+ * PWN_HIP_ERR_INVALID_ARGUMENT with nothing written. */
+typedef struct pwn_hip_consensus_params {
+  float inlier_translational_threshold;   /* 0.5*0.5, squared metres           map_closer.cpp:63 */
+  float inlier_rotational_threshold;      /* (float)(15.0f*M_PI/180.0f)        :64; must lie in (0, 2*pi/3] */
+  int   min_times_checked;                /* 5                                 :65 */
+} pwn_hip_consensus_params;
+void pwn_hip_default_consensus_params(pwn_hip_consensus_params* p);
+#define PWN_HIP_CONSENSUS_MAX_RELATIONS 8192
+/* host, no context: column i of both error matrices (n floats each), what validateRelation(..., rels[i], ...) writes */
+void pwn_hip_validate_relation(int n, const double* tc, const double* to, const double* tr, const int* flags, int i,
+                               float* translational_errors, float* rotational_errors);
+/* host, no context: all of validatePartitions from the same text, serially */
+int pwn_hip_validate_relations_host(const pwn_hip_consensus_params* p, int n, const double* tc, const double* to, const double* tr,
+                                    const int* flags, int* times_checked, int* cum_inlier, int* cum_outlier_times, int* decisions,
+                                    float* translational_errors, float* rotational_errors, int* empty_column);
+/* device: four launches on the context's stream and one host wait (stages consensus_prepare, consensus_errors, consensus_count,
+ * consensus_commit in pwn_hip_last_stage_ms); the empty-column condition is a word a kernel writes and the committing kernel reads */
+int pwn_hip_validate_relations(pwn_hip_ctx* ctx, const pwn_hip_consensus_params* p, int n, const double* tc, const double* to,
+                               const double* tr, const float* records, int record_floats, const int* flags,
+                               int* times_checked, int* cum_inlier, int* cum_outlier_times, int* decisions,
+                               float* translational_errors, float* rotational_errors);
+
 /* One candidate batch from raw frames as ONE submission: per pair i, DepthImageConverter::compute of ref_frames[i] -> references[i] and
  * cur_frames[i] -> currents[i] (PwnMatcherBase::makeCloud, pwn_matcher_base.cpp:77-85), then Aligner::align of the pair
  * (pwn_matcher_base.cpp:120-128).  The conversion of a sub-batch's frames is queued in front of its alignment on the same stream, so one
