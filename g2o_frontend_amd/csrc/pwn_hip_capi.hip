@@ -2328,6 +2328,16 @@ int pwn_hip_convert_batch_ex(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p
 }
 
 // ------------------------------------------------------------------------------------------------ aligner stages
+// A cloud rendered into index and / or depth image (either may be null; device pointers): the z-buffer cleared, the cloud's points projected -- the
+// kernel reads the size; bound: what the grid covers -- and the winners resolved.  pwn_hip_project and the mapping step's rendering of the scene.
+static int render_enqueue(pwn_hip_ctx* ctx, hipStream_t st, const CloudDev& cl, int bound, const Mat4& KRt, float min_distance, float max_distance, int rows, int cols,
+                          int* index, float* depth) {
+  const size_t N = (size_t)rows * cols;
+  HIPCHK(ctx, hipMemsetAsync(ctx->zref_ws, 0xFF, N * 8, st), PWN_HIP_ERR_COPY);
+  if (bound > 0) hipLaunchKernelGGL(k_project_single, dim3((unsigned)((bound + 255) / 256)), dim3(256), 0, st, cl, KRt, min_distance, max_distance, rows, cols, ctx->zref_ws, kZTag0);
+  hipLaunchKernelGGL(k_zbuf_resolve, dim3((unsigned)std::min<size_t>((N + 255) / 256, 2048)), dim3(256), 0, st, ctx->zref_ws, (int)N, index, depth, kZTag0);
+  return PWN_HIP_OK;
+}
 int pwn_hip_project(pwn_hip_ctx* ctx, const float K[9], const float T[16], float min_distance, float max_distance, int rows, int cols,
                     const pwn_hip_cloud* cloud, int* index_image, float* depth_image) {
   if (!ctx || !K || !T || !cloud) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
@@ -2336,12 +2346,10 @@ int pwn_hip_project(pwn_hip_ctx* ctx, const float K[9], const float T[16], float
   const size_t N = (size_t)rows * cols;
   Mat4 KRt, iKRt; Mat3 iK;
   projector_matrices(mat3_from(K), mat4_from(T), KRt, iKRt, iK);
-  HIPCHK(ctx, hipMemsetAsync(ctx->zref_ws, 0xFF, N * 8, ctx->stream), PWN_HIP_ERR_COPY);
-  { StageTimer t(ctx, "project");
-    hipLaunchKernelGGL(k_project_single, dim3((cloud->d.capacity + 255) / 256), dim3(256), 0, ctx->stream, cloud->d, KRt, min_distance, max_distance, rows, cols, ctx->zref_ws, kZTag0); }
   int* di = index_image ? (is_device_ptr(index_image) ? index_image : ctx->index_ws) : nullptr;
   float* dd = depth_image ? (is_device_ptr(depth_image) ? depth_image : ctx->depth_ws) : nullptr;
-  hipLaunchKernelGGL(k_zbuf_resolve, dim3((unsigned)std::min<size_t>((N + 255) / 256, 2048)), dim3(256), 0, ctx->stream, ctx->zref_ws, (int)N, di, dd, kZTag0);
+  { StageTimer t(ctx, "project");
+    if (int rc = render_enqueue(ctx, ctx->stream, cloud->d, cloud->d.capacity, KRt, min_distance, max_distance, rows, cols, di, dd)) return rc; }
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   if (index_image && di != index_image) HIPCHK(ctx, hipMemcpyAsync(index_image, di, N * 4, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
   if (depth_image && dd != depth_image) HIPCHK(ctx, hipMemcpyAsync(depth_image, dd, N * 4, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);

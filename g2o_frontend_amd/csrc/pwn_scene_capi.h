@@ -49,6 +49,9 @@ int scene_scratch(pwn_hip_ctx* ctx, size_t n_int, size_t n_u64) {
   HIPCHK(ctx, ctx->scene_total.ensure(4), PWN_HIP_ERR_ALLOCATION);
   return PWN_HIP_OK;
 }
+// the int arrays of that scratch as Merger::merge uses them
+struct MergeScratch { int* collapsed; int* head; int* next; int* keep; int* offs; int* sums; };
+MergeScratch merge_scratch(pwn_hip_ctx* ctx) { return { ctx->scene_i[0], ctx->scene_i[1], ctx->scene_i[2], ctx->scene_i[3], ctx->scene_i[4], ctx->scene_i[5] }; }
 // out[i] = sum of in[0..i), *total = sum of all; sums: scratch of >= n/1024 + 1 ints
 int exclusive_scan(pwn_hip_ctx* ctx, const int* in, int* out, int n, int* sums, int* total) {
   const int nb = (n + 1023) / 1024;
@@ -58,6 +61,41 @@ int exclusive_scan(pwn_hip_ctx* ctx, const int* in, int* out, int n, int* sums, 
   hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(1024), 0, ctx->stream, out, n, (const int*)sums);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
+}
+// The scene record of a stand-alone call (pwn_scene_kernels.h): the host fills it and sends it to the device in front of the call's kernels, through
+// the page-locked copy that the kernels write their sizes back to
+int record_send(pwn_hip_ctx* ctx, const SceneStepRecord& r) {
+  HIPCHK(ctx, ctx->step_dev.ensure(1), PWN_HIP_ERR_ALLOCATION);
+  HIPCHK(ctx, ctx->step_host.ensure(1), PWN_HIP_ERR_ALLOCATION);
+  *ctx->step_host.p = r;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->step_dev.p, ctx->step_host.p, sizeof(SceneStepRecord), hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
+  return PWN_HIP_OK;
+}
+// Merger::merge queued on st, steps 1-4 of pwn_scene_kernels.h on the size the device holds with the record's view; the survivors go to the back
+// set, the new size into the device's word and both copies of the record.  bound / gaussBound: the host's upper bounds of the cloud's size and of
+// its Gaussian vector's length (grids, fill, scan); scene_scratch has been made for the bound.  collapsed[0, bound) is ready for the host behind it.
+int merge_enqueue(pwn_hip_ctx* ctx, hipStream_t st, const pwn_hip_cloud* cloud, const CloudDev& back, const SceneBuffers& sback, SceneStepRecord* rec,
+                  SceneStepRecord* host, const MergeView& v, size_t bound, size_t gaussBound, unsigned tag) {
+  const MergeScratch s = merge_scratch(ctx);
+  const SceneStepRecord* r = rec;
+  const dim3 nb((unsigned)((bound + 255) / 256));
+  hipLaunchKernelGGL(k_scene_merge_project, nb, dim3(256), 0, st, cloud->d, r, v.minD, v.maxD, v.rows, v.cols, ctx->zref_ws, tag);
+  HIPCHK(ctx, hipMemsetAsync(s.head, 0xFF, sizeof(int) * bound, st), PWN_HIP_ERR_COPY);
+  hipLaunchKernelGGL(k_scene_merge_classify, nb, dim3(256), 0, st, cloud->d, r, v, (const unsigned long long*)ctx->zref_ws, tag, s.collapsed, s.head, s.next);
+  hipLaunchKernelGGL(k_scene_merge_accumulate, nb, dim3(256), 0, st, cloud->d, cloud->sb, r, (const int*)s.collapsed, (const int*)s.head, (const int*)s.next);
+  hipLaunchKernelGGL(k_scene_merge_keep_flags, nb, dim3(256), 0, st, cloud->d, r, s.collapsed, (int)bound, s.keep);
+  if (int rc = exclusive_scan(ctx, s.keep, s.offs, (int)bound, s.sums, ctx->scene_total)) return rc;
+  hipLaunchKernelGGL(k_scene_merge_compact, nb, dim3(256), 0, st, cloud->d, cloud->sb, back, sback, r, (const int*)s.keep, (const int*)s.offs);
+  hipLaunchKernelGGL(k_scene_gauss_tail, dim3((unsigned)((gaussBound + 255) / 256)), dim3(256), 0, st, cloud->d, cloud->sb, sback, r, (const int*)ctx->scene_total);
+  hipLaunchKernelGGL(k_scene_merge_count, dim3(1), dim3(1), 0, st, cloud->d, (const int*)ctx->scene_total, rec, host);
+  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
+  return PWN_HIP_OK;
+}
+// after the wait: a merge of `before` points has left `after` of them in the back set, which becomes the front (an empty cloud moved nothing), and
+// has set the device's word
+int merge_commit(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, int before, int after) {
+  if (before > 0) cloud->swap_sides();
+  return cloud_edit(ctx, cloud, after, false);
 }
 // Stable LSD radix sort of m (key, value) records by the low `bits` bits of the key, 8 bits per pass (k_sort_hist, the scan of the histogram,
 // k_sort_scatter), from (key[0], val[0]) to and fro between the two pairs; *in says which pair holds the result.  hist: 256 ints per block of
@@ -211,33 +249,20 @@ int pwn_hip_merge(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, const float K[9], cons
   CloudDev back; SceneBuffers sback;      // the second array set: the stable compaction / reordering writes there, then the two sets change places
   HIPCHK(ctx, cloud->own_back(back, sback), PWN_HIP_ERR_ALLOCATION);
   if (int rc = scene_scratch(ctx, (size_t)n, 0)) return rc;
-  int* d_collapsed = ctx->scene_i[0]; int* d_head = ctx->scene_i[1]; int* d_next = ctx->scene_i[2]; int* d_keep = ctx->scene_i[3];
-  int* d_offs = ctx->scene_i[4]; int* d_sums = ctx->scene_i[5];
-  Mat4 KRt, iKRt; Mat3 iK;
-  projector_matrices(mat3_from(K), mat4_from(T), KRt, iKRt, iK);
   unsigned tag = kZTag0;
   if (int rc = take_tags(ctx, 1, &tag)) return rc;
+  SceneStepRecord r;                      // nothing skipped, no add in front: the sizes as the host knows them
+  r.sceneT = mat4_identity(); r.identity = 1; r.skipped = 0; r.sizeAdd = r.sizeMerge = n; r.gaussLen = ngauss;
+  { Mat4 iKRt; Mat3 iK; projector_matrices(mat3_from(K), mat4_from(T), r.mergeKRt, iKRt, iK); }
+  if (int rc = record_send(ctx, r)) return rc;
+  SceneStepRecord* host = ctx->step_host;
   hipStream_t st = ctx->stream;
-  const int nb = (n + 255) / 256;
-  hipLaunchKernelGGL(k_project_single, dim3(nb), dim3(256), 0, st, cloud->d, KRt, min_distance, max_distance, rows, cols, ctx->zref_ws, tag);
-  HIPCHK(ctx, hipMemsetAsync(d_head, 0xFF, sizeof(int) * (size_t)n, st), PWN_HIP_ERR_COPY);
-  hipLaunchKernelGGL(k_merge_classify, dim3(nb), dim3(256), 0, st, cloud->d, n, KRt, min_distance, max_distance, max_point_depth, rows, cols,
-                     (const unsigned long long*)ctx->zref_ws, tag, distance_threshold, normal_threshold, d_collapsed, d_head, d_next);
-  hipLaunchKernelGGL(k_merge_accumulate, dim3(nb), dim3(256), 0, st, cloud->d, cloud->sb, n, (const int*)d_collapsed, (const int*)d_head, (const int*)d_next);
-  hipLaunchKernelGGL(k_merge_keep_flags, dim3(nb), dim3(256), 0, st, (const int*)d_collapsed, n, d_keep);
-  if (int rc = exclusive_scan(ctx, d_keep, d_offs, n, d_sums, ctx->scene_total)) return rc;
-  hipLaunchKernelGGL(k_merge_compact, dim3(nb), dim3(256), 0, st, cloud->d, cloud->sb, back, sback, n, ngauss, (const int*)d_keep, (const int*)d_offs);
-  hipLaunchKernelGGL(k_set_count, dim3(1), dim3(1), 0, st, cloud->d.count, (const int*)ctx->scene_total);
-  HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
-  int k = 0;
-  HIPCHK(ctx, hipMemcpyAsync(&k, ctx->scene_total, sizeof(int), hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
-  if (collapsed) HIPCHK(ctx, hipMemcpyAsync(collapsed, d_collapsed, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
+  const MergeView view = { min_distance, max_distance, max_point_depth, rows, cols, distance_threshold, normal_threshold };
+  if (int rc = merge_enqueue(ctx, st, cloud, back, sback, ctx->step_dev, host, view, (size_t)n, (size_t)ngauss, tag)) return rc;
+  if (collapsed) HIPCHK(ctx, hipMemcpyAsync(collapsed, merge_scratch(ctx).collapsed, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
-  // the Gaussian vector is compacted but not resized (merger.cpp:108-112): its tail keeps the old entries
-  if (ngauss > k) hipLaunchKernelGGL(k_gauss_copy_tail, dim3((ngauss - k + 255) / 256), dim3(256), 0, st, cloud->sb, sback, k, ngauss);
-  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
-  cloud->swap_sides();
-  if (int rc = cloud_edit(ctx, cloud, k, false)) return rc;      // edit: k_set_count has set the device's word
+  const int k = host->sizeMerge;
+  if (int rc = merge_commit(ctx, cloud, n, k)) return rc;
   ctx->img.invalidate();                  // slot 0 of the z-buffer was used
   if (new_size) *new_size = k;
   return PWN_HIP_OK;
@@ -297,8 +322,6 @@ int pwn_hip_scene_step(pwn_hip_ctx* ctx, const pwn_hip_converter_params* cp, con
   size_t scratch = bound;
   for (const auto& b : ctx->scene_i) if (b.cap < bound + 1024) scratch = std::min((size_t)scene->d.capacity, 2 * bound);
   if (int rc = scene_scratch(ctx, scratch, 0)) return rc;
-  int* d_collapsed = ctx->scene_i[0]; int* d_head = ctx->scene_i[1]; int* d_next = ctx->scene_i[2]; int* d_keep = ctx->scene_i[3];
-  int* d_offs = ctx->scene_i[4]; int* d_sums = ctx->scene_i[5];
   // ---- the two conversions: entries 0 and 1 of the descriptor arrays, both in workspace slot 0 (they follow each other on one stream)
   const void* frames[1] = { frame }; pwn_hip_cloud* frameCloud[1] = { cloud };
   frameCall.frames = frames; frameCall.clouds = frameCloud;
@@ -318,17 +341,13 @@ int pwn_hip_scene_step(pwn_hip_ctx* ctx, const pwn_hip_converter_params* cp, con
   { Mat4 iKRt; Mat3 iK; projector_matrices(K, iso_mul(sceneT0, offset), renderKRt, iKRt, iK); }
   const MergeView view = { cp->min_distance, cp->max_distance, sp->max_point_depth, vrows, vcols, sp->distance_threshold, sp->normal_threshold };
   SceneStepRecord* rec = ctx->step_dev; SceneStepRecord* host = ctx->step_host;
-  const unsigned nbPix = (unsigned)((pixels + 255) / 256), nbBound = (unsigned)((bound + 255) / 256);
   AlignHooks hooks;
   hooks.pre_sub = [&](int, int, int, hipStream_t st) -> int {
     *faultWord = 0;
     if (frameJob.host_input) { if (int rc = convert_stage_frames(ctx, frameJob, 0, 1, st)) return rc; }
     if (int rc = convert_enqueue(ctx, frameJob, 0, 1, st, faultWord)) return rc;
-    { StageTimer t(ctx, "scene_render", st);      // pwn_hip_project's launches, the depth image alone, on the size the device holds
-      HIPCHK(ctx, hipMemsetAsync(ctx->zref_ws, 0xFF, (size_t)pixels * 8, st), PWN_HIP_ERR_COPY);
-      if (k0 > 0) hipLaunchKernelGGL(k_project_single, dim3((unsigned)((k0 + 255) / 256)), dim3(256), 0, st, scene->d, renderKRt, cp->min_distance, cp->max_distance, vrows, vcols,
-                                     ctx->zref_ws, kZTag0);
-      hipLaunchKernelGGL(k_zbuf_resolve, dim3(std::min(nbPix, 2048u)), dim3(256), 0, st, ctx->zref_ws, pixels, (int*)nullptr, (float*)ctx->scene_depth_ws, kZTag0); }
+    { StageTimer t(ctx, "scene_render", st);      // pwn_hip_project's commands, the depth image alone, on the size the device holds
+      if (int rc = render_enqueue(ctx, st, scene->d, k0, renderKRt, cp->min_distance, cp->max_distance, vrows, vcols, nullptr, ctx->scene_depth_ws)) return rc; }
     return convert_enqueue(ctx, subJob, 0, 1, st, faultWord);
   };
   hooks.before_sync = [&]() -> int {
@@ -337,23 +356,13 @@ int pwn_hip_scene_step(pwn_hip_ctx* ctx, const pwn_hip_converter_params* cp, con
       hipLaunchKernelGGL(k_scene_pose, dim3(1), dim3(1), 0, st, (const PairState*)ctx->state_ws, sceneT0, K, offset, (const int*)ctx->fault_dev,
                          (const int*)ctx->align_fault_host, (const int*)scene->d.count, scene->d.capacity, rec, host); }
     { StageTimer t(ctx, "scene_add");
-      hipLaunchKernelGGL(k_scene_append, dim3(nbPix), dim3(256), 0, st, scene->d, scene->sb, cloud->d, cloud->sb, (const SceneStepRecord*)rec);
+      hipLaunchKernelGGL(k_scene_append, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, st, scene->d, scene->sb, cloud->d, cloud->sb, (const SceneStepRecord*)rec);
       hipLaunchKernelGGL(k_scene_grow, dim3(1), dim3(1), 0, st, scene->d, cloud->d, rec, host); }
     unsigned tag = kZTag0;
     if (int rc = take_tags(ctx, 1, &tag)) return rc;
     { StageTimer t(ctx, "scene_merge");
-      const SceneStepRecord* r = rec;
-      hipLaunchKernelGGL(k_scene_merge_project, dim3(nbBound), dim3(256), 0, st, scene->d, r, cp->min_distance, cp->max_distance, vrows, vcols, ctx->zref_ws, tag);
-      HIPCHK(ctx, hipMemsetAsync(d_head, 0xFF, sizeof(int) * bound, st), PWN_HIP_ERR_COPY);
-      hipLaunchKernelGGL(k_scene_merge_classify, dim3(nbBound), dim3(256), 0, st, scene->d, r, view, (const unsigned long long*)ctx->zref_ws, tag, d_collapsed, d_head, d_next);
-      hipLaunchKernelGGL(k_scene_merge_accumulate, dim3(nbBound), dim3(256), 0, st, scene->d, scene->sb, r, (const int*)d_collapsed, (const int*)d_head, (const int*)d_next);
-      hipLaunchKernelGGL(k_scene_merge_keep_flags, dim3(nbBound), dim3(256), 0, st, scene->d, r, d_collapsed, (int)bound, d_keep);
-      if (int rc = exclusive_scan(ctx, d_keep, d_offs, (int)bound, d_sums, ctx->scene_total)) return rc;
-      hipLaunchKernelGGL(k_scene_merge_compact, dim3(nbBound), dim3(256), 0, st, scene->d, scene->sb, back, sback, r, (const int*)d_keep, (const int*)d_offs);
-      hipLaunchKernelGGL(k_scene_gauss_tail, dim3(nbBound), dim3(256), 0, st, scene->d, scene->sb, sback, r, (const int*)ctx->scene_total);
-      hipLaunchKernelGGL(k_scene_merge_count, dim3(1), dim3(1), 0, st, scene->d, (const int*)ctx->scene_total, rec, host); }
-    HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
-    if (collapsed) HIPCHK(ctx, hipMemcpyAsync(collapsed, d_collapsed, sizeof(int) * bound, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
+      if (int rc = merge_enqueue(ctx, st, scene, back, sback, rec, host, view, bound, bound, tag)) return rc; }
+    if (collapsed) HIPCHK(ctx, hipMemcpyAsync(collapsed, merge_scratch(ctx).collapsed, sizeof(int) * bound, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
     return PWN_HIP_OK;
   };
   // after the wait: an attempt whose projection gave up commits nothing (align_finish digests the fault word, the repeat converts again); else
@@ -376,8 +385,7 @@ int pwn_hip_scene_step(pwn_hip_ctx* ctx, const pwn_hip_converter_params* cp, con
   // ---- the bookkeeping of pwn_hip_cloud_add and pwn_hip_merge
   const int nAdd = host->sizeAdd, nMerge = host->sizeMerge;
   scene->content.set_gaussians(nAdd);     // _gaussians.resize(k + cloud.gaussians().size()) (cloud.cpp:153); the merge does not resize it
-  if (nAdd > 0) scene->swap_sides();
-  if (int rc = cloud_edit(ctx, scene, nMerge, false)) return rc;      // edit: the kernels have set the device's word
+  if (int rc = merge_commit(ctx, scene, nAdd, nMerge)) return rc;
   std::memcpy(result->scene_T, host->sceneT.m, sizeof(result->scene_T));
   result->n_cloud = cloud->content.n; result->n_subscene = subscene->content.n;
   result->size_after_add = nAdd; result->size_after_merge = nMerge;

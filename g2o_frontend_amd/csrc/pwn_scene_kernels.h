@@ -162,8 +162,43 @@ __global__ void __launch_bounds__(256) k_gaussians_batch(const FrameDesc* __rest
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// The scene record.  Cloud::add and Merger::merge run on sizes that the device holds (CloudDev::count) and on a transform and a view that they read
+// from this record, which lies in device memory in front of their kernels: written by the host (pwn_hip_merge) or by k_scene_pose
+// (the mapping step, pwn_aligner.cpp:166-209; pwn_hip_scene_step: what the host does between pwn_hip_align, pwn_hip_cloud_add and pwn_hip_merge).
+// The grids are sized by the host's upper bound of the sizes; every kernel reads the sizes itself and clamps them to the capacities.  A skipped step
+// (the converter timed out, or a projection of the alignment gave up on a pixel: the host repeats or reports it) touches nothing of the scene.
+// Every dependency is a kernel boundary.
+struct SceneStepRecord {
+  Mat4 sceneT;             // scene_T' = scene_T * Aligner::T(), last row forced: the transform of Cloud::add (pwn_aligner.cpp:199, :205)
+  Mat4 mergeKRt;           // the projector matrix of scene_T' * sensor offset: the view of Merger::merge (pwn_aligner.cpp:206-208)
+  int identity;            // Cloud::add's test of scene_T' (cloud.cpp:176)
+  int skipped;
+  int sizeAdd, sizeMerge;  // the cloud's size after Cloud::add and after Merger::merge (a skipped step: the size it had)
+  int gaussLen;            // the length of the cloud's Gaussian vector, which Merger::merge does not resize (merger.cpp:108-112)
+};
+__device__ __forceinline__ int clamped_count(const int* count, int capacity) { return max(0, min(*count, capacity)); }
+// one thread.  state: the pair's final state (PairState::T is the aligner's result); convFault: the converter's time-out word (device memory);
+// alignFault: the projections' give-up word (page-locked host memory).  The record is written twice: for the kernels behind, and for the host.
+__global__ void k_scene_pose(const PairState* __restrict__ state, Mat4 sceneT, Mat3 K, Mat4 offset, const int* __restrict__ convFault,
+                             const int* alignFault, const int* __restrict__ sceneCount, int sceneCapacity, SceneStepRecord* __restrict__ rec,
+                             SceneStepRecord* host) {
+  SceneStepRecord r;
+  r.sceneT = iso_mul(sceneT, state->T);
+  set_last_row(r.sceneT);
+  Mat4 iKRt; Mat3 iK;
+  projector_matrices(K, iso_mul(r.sceneT, offset), r.mergeKRt, iKRt, iK);
+  const Mat4 I = mat4_identity();
+  r.identity = 1;
+  for (int q = 0; q < 16; ++q) if (r.sceneT.m[q] != I.m[q]) r.identity = 0;
+  r.skipped = (*convFault != 0 || *(const volatile int*)alignFault != 0) ? 1 : 0;
+  r.sizeAdd = r.sizeMerge = r.gaussLen = clamped_count(sceneCount, sceneCapacity);
+  *rec = r;
+  *host = r;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // Cloud::add (cloud.cpp:145-171): dst[k + i] = transformInPlace(T)(src[i]).  The scene cloud keeps per-point normal information
-// matrices (9 planes): clouds appended with different transforms have different class matrices.  grid = ceil(n/256), block = 256.
+// matrices (9 planes): clouds appended with different transforms have different class matrices.
 __device__ __forceinline__ void omega_transform(const Mat4& m, float* om /* row-major 3x3, in place */) {
   float t1[9];
 #pragma unroll
@@ -192,7 +227,7 @@ __device__ __forceinline__ void gauss_store_default(const SceneBuffers& sb, int 
   sb.G[o] = g; sb.Gf[o] = 0;
 }
 // Point i of src, transformed by m (not at all when `identity`), stored as point o of dst: every per-point array Cloud::add carries.  The one
-// definition of that arithmetic: k_cloud_append (Cloud::add) and k_merge_clouds_append (Merger2::merge's push_backs) both call it.
+// definition of that arithmetic: k_cloud_append / k_scene_append (Cloud::add) and k_merge_clouds_append (Merger2::merge's push_backs) both call it.
 __device__ __forceinline__ void cloud_append_point(const CloudDev& dst, const SceneBuffers& dsb, const CloudDev& src, const SceneBuffers& ssb, int i, int o,
                                                    int ngauss, const Mat4& m, int identity) {
   float4 P, Nm;                    // old-format view: (x, y, z, curvature), (normal, class word)
@@ -246,11 +281,30 @@ __device__ __forceinline__ void cloud_append_point(const CloudDev& dst, const Sc
     dsb.G[o] = g; dsb.Gf[o] = flags;
   }
 }
+// sizes, Gaussian count and transform from the host (pwn_hip_cloud_add; the record form costs that call a copy and a launch more: measured 0.056 ms
+// against 0.051 ms per VGA frame, profiles/one_merge_chain_ab.txt).  grid = ceil(n / 256), block = 256
 __global__ void __launch_bounds__(256) k_cloud_append(CloudDev dst, SceneBuffers dsb, CloudDev src, SceneBuffers ssb, int k, int n, int ngauss,
                                                       Mat4 m, int identity) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n || k + i >= dst.capacity) return;
   cloud_append_point(dst, dsb, src, ssb, i, k + i, ngauss, m, identity);
+}
+// the same at sizes the device holds: src appended at *dst.count under the record's transform.  grid = ceil(pixels of the frame / 256), block = 256
+__global__ void __launch_bounds__(256) k_scene_append(CloudDev dst, SceneBuffers dsb, CloudDev src, SceneBuffers ssb, const SceneStepRecord* __restrict__ rec) {
+  if (*as_global(&rec->skipped)) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int m = clamped_count(src.count, src.capacity), k = clamped_count(dst.count, dst.capacity);
+  if (i >= m || i >= dst.capacity - k) return;
+  const Mat4 T = uniform_iso_global(as_global((const float*)rec->sceneT.m));
+  cloud_append_point(dst, dsb, src, ssb, i, k + i, m, T, *as_global(&rec->identity));
+}
+// one thread: the destination's size word follows (the append read it), and with it the length of its Gaussian vector
+__global__ void k_scene_grow(CloudDev dst, CloudDev src, SceneStepRecord* __restrict__ rec, SceneStepRecord* host) {
+  if (rec->skipped) return;
+  const int k = clamped_count(dst.count, dst.capacity);
+  const int n = k + min(clamped_count(src.count, src.capacity), dst.capacity - k);
+  *dst.count = n;
+  rec->sizeAdd = rec->gaussLen = n; host->sizeAdd = host->gaussLen = n;
 }
 // Cloud::transformInPlace on the Gaussians and Stats of an existing cloud (k_cloud_transform handles the other arrays)
 __global__ void __launch_bounds__(256) k_scene_transform(CloudDev cl, SceneBuffers sb, int n, int ngauss, Mat4 m) {
@@ -269,17 +323,19 @@ __global__ void __launch_bounds__(256) k_expand_omega_n(CloudDev cl, float* __re
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Merger::merge (merger.cpp:15-119).
-// 1. k_project_single: z-buffer of the whole cloud (index + depth image of merger.cpp:21-23).
-// 2. k_merge_classify: the per-point tests of merger.cpp:42-76 -> _collapsedIndices; a point that merges into target t is pushed on
+// Merger::merge (merger.cpp:15-119) on the size the device holds (*cl.count), with the view of the scene record.
+// 1. k_scene_merge_project: z-buffer of the whole cloud (index + depth image of merger.cpp:21-23).
+// 2. k_scene_merge_classify: the per-point tests of merger.cpp:42-76 -> _collapsedIndices; a point that merges into target t is pushed on
 //    t's list (head/next, order of arrival).
-// 3. k_merge_accumulate: one thread per target walks its list in ASCENDING point index -- the order in which the reference's
+// 3. k_scene_merge_accumulate: one thread per target walks its list in ASCENDING point index -- the order in which the reference's
 //    sequential loop calls addInformation, so the fp32 sums carry the same bits -- then mean() moves the point (merger.cpp:91-93).
-// 4. exclusive scan of the keep flags + k_merge_compact: stable compaction of every per-point array (merger.cpp:88-104).
+// 4. k_scene_merge_keep_flags, exclusive scan of the keep flags over the host's bound + k_scene_merge_compact: stable compaction of every
+//    per-point array (merger.cpp:88-104); k_scene_gauss_tail: what the Gaussian vector, never resized, keeps behind the survivors
+//    (merger.cpp:108-112); k_scene_merge_count: the new size.
+// grids = ceil(bound / 256), block = 256.
 // The merger's thresholds and view as the classification reads them (merger.cpp:6-8, :20-23)
 struct MergeView { float minD, maxD, maxPointDepth; int rows, cols; float distanceThreshold, normalThreshold; };
-// Point i of the merge: the one definition of steps 2 and 3 per point, which k_merge_classify / k_merge_accumulate (size and view from the host) and
-// k_scene_merge_classify / k_scene_merge_accumulate (size and view from the device: the mapping step) both call.
+// Point i of the merge: step 2 for one point
 __device__ __forceinline__ void merge_classify_point(const CloudDev& cl, int i, const Mat4& KRt, float minD, float maxD, float maxPointDepth, int rows, int cols,
                                                      const unsigned long long* __restrict__ z, unsigned tag, float distanceThreshold, float normalThreshold,
                                                      int* __restrict__ collapsed, int* __restrict__ head, int* __restrict__ next) {
@@ -310,12 +366,22 @@ __device__ __forceinline__ void merge_classify_point(const CloudDev& cl, int i, 
   }
   collapsed[i] = res;
 }
-__global__ void __launch_bounds__(256) k_merge_classify(CloudDev cl, int n, Mat4 KRt, float minD, float maxD, float maxPointDepth, int rows, int cols,
-                                                        const unsigned long long* __restrict__ z, unsigned tag, float distanceThreshold,
-                                                        float normalThreshold, int* __restrict__ collapsed, int* __restrict__ head, int* __restrict__ next) {
+__global__ void __launch_bounds__(256) k_scene_merge_project(CloudDev cl, const SceneStepRecord* __restrict__ rec, float minD, float maxD, int rows, int cols,
+                                                             unsigned long long* z, unsigned tag) {
+  if (*as_global(&rec->skipped)) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  merge_classify_point(cl, i, KRt, minD, maxD, maxPointDepth, rows, cols, z, tag, distanceThreshold, normalThreshold, collapsed, head, next);
+  if (i >= clamped_count(cl.count, cl.capacity)) return;
+  const Mat4 KRt = uniform_iso_global(as_global((const float*)rec->mergeKRt.m));
+  project_point(KRt, minD, maxD, rows, cols, load_xyz(cl.P3, i), i, z, tag);
+}
+__global__ void __launch_bounds__(256) k_scene_merge_classify(CloudDev cl, const SceneStepRecord* __restrict__ rec, MergeView v,
+                                                              const unsigned long long* __restrict__ z, unsigned tag, int* __restrict__ collapsed,
+                                                              int* __restrict__ head, int* __restrict__ next) {
+  if (*as_global(&rec->skipped)) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= clamped_count(cl.count, cl.capacity)) return;
+  const Mat4 KRt = uniform_iso_global(as_global((const float*)rec->mergeKRt.m));
+  merge_classify_point(cl, i, KRt, v.minD, v.maxD, v.maxPointDepth, v.rows, v.cols, z, tag, v.distanceThreshold, v.normalThreshold, collapsed, head, next);
 }
 // target t (collapsed[t] == t) takes the points on its list
 __device__ __forceinline__ void merge_accumulate_target(const CloudDev& cl, const SceneBuffers& sb, int t, const int* __restrict__ head, const int* __restrict__ next) {
@@ -343,15 +409,21 @@ __device__ __forceinline__ void merge_accumulate_target(const CloudDev& cl, cons
   sb.G[t] = g; sb.Gf[t] = flags;
   store_xyz(cl.P3, t, g.mean[0], g.mean[1], g.mean[2]);
 }
-__global__ void __launch_bounds__(256) k_merge_accumulate(CloudDev cl, SceneBuffers sb, int n, const int* __restrict__ collapsed,
-                                                          const int* __restrict__ head, const int* __restrict__ next) {
+__global__ void __launch_bounds__(256) k_scene_merge_accumulate(CloudDev cl, SceneBuffers sb, const SceneStepRecord* __restrict__ rec,
+                                                                const int* __restrict__ collapsed, const int* __restrict__ head, const int* __restrict__ next) {
+  if (*as_global(&rec->skipped)) return;
   const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= n || collapsed[t] != t) return;
+  if (t >= clamped_count(cl.count, cl.capacity) || collapsed[t] != t) return;
   merge_accumulate_target(cl, sb, t, head, next);
 }
-__global__ void __launch_bounds__(256) k_merge_keep_flags(const int* __restrict__ collapsed, int n, int* __restrict__ keep) {
+// the keep flags of the n points, and 0 for every index of [n, bound): the scan runs over the bound.  collapsed gets -1 there (what the host copies back)
+__global__ void __launch_bounds__(256) k_scene_merge_keep_flags(CloudDev cl, const SceneStepRecord* __restrict__ rec, int* __restrict__ collapsed, int bound,
+                                                                int* __restrict__ keep) {
   const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= bound) return;
+  const int n = *as_global(&rec->skipped) ? 0 : clamped_count(cl.count, cl.capacity);
   if (i < n) { const int c = collapsed[i]; keep[i] = (c < 0 || c == i) ? 1 : 0; }
+  else { keep[i] = 0; collapsed[i] = -1; }
 }
 // Record i of one array set becomes record o of another, unchanged: the optional arrays where both sets have them, the Gaussian when `gauss`.
 // What the compaction of a merge and the gather of a voxelization do to a point.
@@ -370,16 +442,30 @@ __device__ __forceinline__ void cloud_move_point(const CloudDev& src, const Scen
   if (gauss) { dsb.G[o] = ssb.G[i]; dsb.Gf[o] = ssb.Gf[i]; }
 }
 // stable compaction: point i with keep[i] moves to offs[i] in the destination arrays
-__global__ void __launch_bounds__(256) k_merge_compact(CloudDev src, SceneBuffers ssb, CloudDev dst, SceneBuffers dsb, int n, int ngauss,
-                                                       const int* __restrict__ keep, const int* __restrict__ offs) {
+__global__ void __launch_bounds__(256) k_scene_merge_compact(CloudDev src, SceneBuffers ssb, CloudDev dst, SceneBuffers dsb, const SceneStepRecord* __restrict__ rec,
+                                                             const int* __restrict__ keep, const int* __restrict__ offs) {
+  if (*as_global(&rec->skipped)) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n || !keep[i]) return;
-  cloud_move_point(src, ssb, i, dst, dsb, offs[i], ssb.G && dsb.G && i < ngauss);
+  if (i >= clamped_count(src.count, src.capacity) || !keep[i]) return;
+  const int o = offs[i];
+  if (o < 0 || o > i) return;        // a compaction only moves a point down
+  cloud_move_point(src, ssb, i, dst, dsb, o, ssb.G && dsb.G);
 }
-// the reference does not resize the Gaussian vector after a merge (merger.cpp:108-112): entries [k, ngauss) keep their old values
-__global__ void __launch_bounds__(256) k_gauss_copy_tail(SceneBuffers ssb, SceneBuffers dsb, int from, int to) {
-  const int i = from + blockIdx.x * 256 + threadIdx.x;
-  if (i < to) { dsb.G[i] = ssb.G[i]; dsb.Gf[i] = ssb.Gf[i]; }
+// the Gaussian tail [k, gaussLen), k = *total: the reference does not resize the Gaussian vector after a merge (merger.cpp:108-112), so these entries keep
+// their old values.  After a Cloud::add the vector has the cloud's size; a cloud that was merged before holds more.  grid = ceil(bound of gaussLen / 256)
+__global__ void __launch_bounds__(256) k_scene_gauss_tail(CloudDev cl, SceneBuffers ssb, SceneBuffers dsb, const SceneStepRecord* __restrict__ rec,
+                                                          const int* __restrict__ total) {
+  if (*as_global(&rec->skipped)) return;
+  const int n = clamped_count(&rec->gaussLen, cl.capacity);
+  const int i = clamped_count(total, clamped_count(cl.count, cl.capacity)) + blockIdx.x * 256 + threadIdx.x;
+  if (i < n) { dsb.G[i] = ssb.G[i]; dsb.Gf[i] = ssb.Gf[i]; }
+}
+// one thread: the merged size becomes the cloud's
+__global__ void k_scene_merge_count(CloudDev cl, const int* __restrict__ total, SceneStepRecord* __restrict__ rec, SceneStepRecord* host) {
+  if (rec->skipped) return;
+  const int k = clamped_count(total, clamped_count(cl.count, cl.capacity));
+  *cl.count = k;
+  rec->sizeMerge = k; host->sizeMerge = k;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -427,115 +513,6 @@ __global__ void __launch_bounds__(1024) k_scan_sums(int* __restrict__ sums, int 
 __global__ void __launch_bounds__(1024) k_scan_add(int* __restrict__ out, int n, const int* __restrict__ sums) {
   const int i = blockIdx.x * 1024 + threadIdx.x;
   if (i < n) out[i] += sums[blockIdx.x];
-}
-__global__ void k_set_count(int* count, const int* total) { *count = *total; }
-
-// ------------------------------------------------------------------------------------------------------------------
-// The mapping step (pwn_aligner.cpp:166-209; pwn_hip_scene_step): what the host does between pwn_hip_align, pwn_hip_cloud_add and pwn_hip_merge,
-// and those two calls' kernels on sizes and transforms that only the device knows.  The step record carries them from kernel to kernel; the grids
-// are sized by the host's upper bound (scene size + pixels of the frame), every kernel reads the sizes itself and clamps them to the capacities.
-// A skipped step (the converter timed out, or a projection of the alignment gave up on a pixel: the host repeats or reports it) touches nothing
-// of the scene.  Every dependency is a kernel boundary.
-struct SceneStepRecord {
-  Mat4 sceneT;             // scene_T' = scene_T * Aligner::T(), last row forced: the transform of Cloud::add (pwn_aligner.cpp:199, :205)
-  Mat4 mergeKRt;           // the projector matrix of scene_T' * sensor offset: the view of Merger::merge (pwn_aligner.cpp:206-208)
-  int identity;            // Cloud::add's test of scene_T' (cloud.cpp:176)
-  int skipped;
-  int sizeAdd, sizeMerge;  // the scene's size after Cloud::add and after Merger::merge (a skipped step: the size it had)
-};
-__device__ __forceinline__ int clamped_count(const int* count, int capacity) { return max(0, min(*count, capacity)); }
-// one thread.  state: the pair's final state (PairState::T is the aligner's result); convFault: the converter's time-out word (device memory);
-// alignFault: the projections' give-up word (page-locked host memory).  The record is written twice: for the kernels behind, and for the host.
-__global__ void k_scene_pose(const PairState* __restrict__ state, Mat4 sceneT, Mat3 K, Mat4 offset, const int* __restrict__ convFault,
-                             const int* alignFault, const int* __restrict__ sceneCount, int sceneCapacity, SceneStepRecord* __restrict__ rec,
-                             SceneStepRecord* host) {
-  SceneStepRecord r;
-  r.sceneT = iso_mul(sceneT, state->T);
-  set_last_row(r.sceneT);
-  Mat4 iKRt; Mat3 iK;
-  projector_matrices(K, iso_mul(r.sceneT, offset), r.mergeKRt, iKRt, iK);
-  const Mat4 I = mat4_identity();
-  r.identity = 1;
-  for (int q = 0; q < 16; ++q) if (r.sceneT.m[q] != I.m[q]) r.identity = 0;
-  r.skipped = (*convFault != 0 || *(const volatile int*)alignFault != 0) ? 1 : 0;
-  r.sizeAdd = r.sizeMerge = clamped_count(sceneCount, sceneCapacity);
-  *rec = r;
-  *host = r;
-}
-// Cloud::add at a size the device knows: src appended at *dst.count under the record's transform.  grid = ceil(pixels of the frame / 256), block = 256
-__global__ void __launch_bounds__(256) k_scene_append(CloudDev dst, SceneBuffers dsb, CloudDev src, SceneBuffers ssb, const SceneStepRecord* __restrict__ rec) {
-  if (*as_global(&rec->skipped)) return;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const int m = clamped_count(src.count, src.capacity), k = clamped_count(dst.count, dst.capacity);
-  if (i >= m || i >= dst.capacity - k) return;
-  const Mat4 T = uniform_iso_global(as_global((const float*)rec->sceneT.m));
-  cloud_append_point(dst, dsb, src, ssb, i, k + i, m, T, *as_global(&rec->identity));
-}
-// one thread: the destination's size word follows (the append read it)
-__global__ void k_scene_grow(CloudDev dst, CloudDev src, SceneStepRecord* __restrict__ rec, SceneStepRecord* host) {
-  if (rec->skipped) return;
-  const int k = clamped_count(dst.count, dst.capacity);
-  const int n = k + min(clamped_count(src.count, src.capacity), dst.capacity - k);
-  *dst.count = n;
-  rec->sizeAdd = n; host->sizeAdd = n;
-}
-// Merger::merge on that size, steps 1-4 (above) with the record's view.  grids = ceil(bound / 256), block = 256
-__global__ void __launch_bounds__(256) k_scene_merge_project(CloudDev cl, const SceneStepRecord* __restrict__ rec, float minD, float maxD, int rows, int cols,
-                                                             unsigned long long* z, unsigned tag) {
-  if (*as_global(&rec->skipped)) return;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= clamped_count(cl.count, cl.capacity)) return;
-  const Mat4 KRt = uniform_iso_global(as_global((const float*)rec->mergeKRt.m));
-  project_point(KRt, minD, maxD, rows, cols, load_xyz(cl.P3, i), i, z, tag);
-}
-__global__ void __launch_bounds__(256) k_scene_merge_classify(CloudDev cl, const SceneStepRecord* __restrict__ rec, MergeView v,
-                                                              const unsigned long long* __restrict__ z, unsigned tag, int* __restrict__ collapsed,
-                                                              int* __restrict__ head, int* __restrict__ next) {
-  if (*as_global(&rec->skipped)) return;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= clamped_count(cl.count, cl.capacity)) return;
-  const Mat4 KRt = uniform_iso_global(as_global((const float*)rec->mergeKRt.m));
-  merge_classify_point(cl, i, KRt, v.minD, v.maxD, v.maxPointDepth, v.rows, v.cols, z, tag, v.distanceThreshold, v.normalThreshold, collapsed, head, next);
-}
-__global__ void __launch_bounds__(256) k_scene_merge_accumulate(CloudDev cl, SceneBuffers sb, const SceneStepRecord* __restrict__ rec,
-                                                                const int* __restrict__ collapsed, const int* __restrict__ head, const int* __restrict__ next) {
-  if (*as_global(&rec->skipped)) return;
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= clamped_count(cl.count, cl.capacity) || collapsed[t] != t) return;
-  merge_accumulate_target(cl, sb, t, head, next);
-}
-// the keep flags of the n points, and 0 for every index of [n, bound): the scan runs over the bound.  collapsed gets -1 there (what the host copies back)
-__global__ void __launch_bounds__(256) k_scene_merge_keep_flags(CloudDev cl, const SceneStepRecord* __restrict__ rec, int* __restrict__ collapsed, int bound,
-                                                                int* __restrict__ keep) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= bound) return;
-  const int n = *as_global(&rec->skipped) ? 0 : clamped_count(cl.count, cl.capacity);
-  if (i < n) { const int c = collapsed[i]; keep[i] = (c < 0 || c == i) ? 1 : 0; }
-  else { keep[i] = 0; collapsed[i] = -1; }
-}
-__global__ void __launch_bounds__(256) k_scene_merge_compact(CloudDev src, SceneBuffers ssb, CloudDev dst, SceneBuffers dsb, const SceneStepRecord* __restrict__ rec,
-                                                             const int* __restrict__ keep, const int* __restrict__ offs) {
-  if (*as_global(&rec->skipped)) return;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= clamped_count(src.count, src.capacity) || !keep[i]) return;
-  const int o = offs[i];
-  if (o < 0 || o > i) return;        // a compaction only moves a point down
-  cloud_move_point(src, ssb, i, dst, dsb, o, ssb.G && dsb.G);
-}
-// the Gaussian tail [k, n): after the add the vector has the scene's size n, after the merge it still has (merger.cpp:108-112); k = *total
-__global__ void __launch_bounds__(256) k_scene_gauss_tail(CloudDev cl, SceneBuffers ssb, SceneBuffers dsb, const SceneStepRecord* __restrict__ rec,
-                                                          const int* __restrict__ total) {
-  if (*as_global(&rec->skipped)) return;
-  const int n = clamped_count(cl.count, cl.capacity);
-  const int i = clamped_count(total, n) + blockIdx.x * 256 + threadIdx.x;
-  if (i < n) { dsb.G[i] = ssb.G[i]; dsb.Gf[i] = ssb.Gf[i]; }
-}
-// one thread: the merged size becomes the scene's
-__global__ void k_scene_merge_count(CloudDev cl, const int* __restrict__ total, SceneStepRecord* __restrict__ rec, SceneStepRecord* host) {
-  if (rec->skipped) return;
-  const int k = clamped_count(total, clamped_count(cl.count, cl.capacity));
-  *cl.count = k;
-  rec->sizeMerge = k; host->sizeMerge = k;
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -49,6 +49,7 @@ def isometry(v6):
 
 T_A = isometry((0.3, -0.2, 0.1, 0.2, -0.1, 0.3))
 T_B = isometry((-0.05, 0.4, 0.02, -1.1, 0.7, 0.2))
+T_FILL = isometry((0.0, 0.0, 0.002, 0.0, 0.0, 0.001))      # hardly a move: what it appends stays in its pixels, 2 mm behind
 
 
 # ------------------------------------------------------------------------------------------------------------ arrays of a cloud
@@ -431,6 +432,35 @@ def sizes_case(n, every_second, seed=16):
     case = b.finish()
     idx = np.arange(n)
     assert np.array_equal(case["expect"], idx - (idx % 2) if every_second else idx)
+    return case
+
+
+# A used cloud against a fresh one (tests/test_gpu_scene_sizes.py): the stand-alone calls read their sizes from the device's word while their
+# grids come from the host's bound.  JUNK_N is the smallest content that leaves a third block of 256 stale records behind a content of 257.
+JUNK_N, JUNK_CAPACITY = 600, 640
+USED_SIZES = (1, 255, 256, 257)          # the block boundaries of a 256-thread grid
+USED_SOURCES = (1, 256, 257)
+
+
+def junk_case():
+    """what the used cloud held first: JUNK_N points inside the view, two per pixel, the second merging into the first"""
+    case = sizes_case(JUNK_N, True, seed=41)
+    assert (case["r"] >= 0).all() and (case["expect"] != np.arange(JUNK_N)).sum() == JUNK_N // 2
+    return case
+
+
+@functools.lru_cache(maxsize=None)
+def mirrored_case(n, seed=42):
+    """n points inside the view: point i < n // 2 wins pixel i and point n - 1 - i merges into it (the middle one of an odd n stands alone), so
+    the members of a pair lie as far apart as the size allows: (0, 256) of n = 257 in two blocks of 256; n = 256 is one block, and there the
+    pairs span its waves"""
+    b = Builder(seed + n)
+    for i in range(n):
+        j = min(i, n - 1 - i)
+        b.add(j // COLS, j % COLS, F(1.0 + 0.04 * (i > j)), flags=1 + i % 3, tag="member" if i > j else "winner", at=i)
+    case = b.finish()
+    idx = np.arange(n)
+    assert (case["r"] >= 0).all() and np.array_equal(case["expect"], np.minimum(idx, n - 1 - idx))
     return case
 
 
