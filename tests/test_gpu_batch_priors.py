@@ -1,7 +1,10 @@
-"""Batch alignment with SE(3) priors on the device (pwn_hip_align_batch_priors) against the single call (pwn_hip_align_with_priors_ex, one pair of
-it), pair by pair and bit for bit -- the header's contract: a batch of n equals n single calls, through every sub-batch and stream plan, with the
-cloud's own index image or a projection, so a difference is a bug, not a tolerance.  Also: a call without priors against the existing calls,
-record packing, the convergence setting, the settle-fault repeat, the refusals and the mirrors."""
+"""Batch alignment with SE(3) priors on the device (pwn_hip_align_batch_priors) against the single call (pwn_hip_align_with_priors_ex), pair by
+pair and bit for bit -- the header's contract: a batch of n equals n single calls, through every sub-batch and stream plan, with the cloud's
+own index image or a projection, so a difference is a bug, not a tolerance.  The single call is ONE PAIR OF THE SAME BATCH CALL (the loop the
+host once drove behind it is gone): these comparisons hold the call to itself across batch sizes, sub-batch and stream plans -- they find a
+pair that reads another pair's list or state, not a loop that is wrong for every pair alike.  What the loop computes is held to the CPU oracle
+in tests/test_gpu_prior_steps.py.  Also: a call without priors against the existing calls, record packing, the convergence setting, the
+settle-fault repeat, the refusals and the mirrors."""
 import ctypes as C
 import os
 import subprocess
@@ -182,9 +185,9 @@ def rig(request):
 
 
 @pytest.mark.parametrize("n", [1, 5, 9])
-def test_every_pair_equals_the_host_driven_loop(rig, n):
-    """a batch of n equals n single calls (once the loop the host drove, now one pair of the batch call): sub-batches of 4 (9 runs as
-    4 + 4 + 1) on 1 and on 4 streams, and the default plan"""
+def test_every_pair_equals_one_pair_of_the_same_call(rig, n):
+    """a batch of n equals n single calls, each of them one pair of the batch call itself (no independent loop is left to compare with: the
+    oracle holds the loop in tests/test_gpu_prior_steps.py): sub-batches of 4 (9 runs as 4 + 4 + 1) on 1 and on 4 streams, and the default plan"""
     idx = list(range(n))
     want = [rig.single_call(i) for i in idx]
     for sub, streams in ((4, 1), (4, 4), (64, 4)):
