@@ -90,6 +90,16 @@ class SceneStepResult(C.Structure):
                 ("size_after_merge", C.c_int)]
 
 
+class TrackerState(C.Structure):
+    _fields_ = [("globalT", C.c_float * 16), ("previous_cloud_transform", C.c_float * 16), ("sensor_offset", C.c_float * 16), ("counter", C.c_int),
+                ("num_keyframes", C.c_int), ("key_slot", C.c_int), ("reserved", C.c_int)]
+
+
+class TrackResult(C.Structure):
+    _fields_ = [("new_frame", C.c_int), ("aligned", C.c_int), ("inliers", C.c_int), ("error", C.c_float), ("T", C.c_float * 16),
+                ("globalT", C.c_float * 16), ("inliers_fraction", C.c_float), ("n_points", C.c_int)]
+
+
 class ConsensusParams(C.Structure):
     _fields_ = [("inlier_translational_threshold", C.c_float), ("inlier_rotational_threshold", C.c_float), ("min_times_checked", C.c_int)]
 
@@ -194,6 +204,13 @@ PROTOTYPES = {
     "pwn_hip_merge_clouds": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _F, _F, _I, _I, _VP, _VP, _VP, _VP]),
     "pwn_hip_default_scene_step_params": (None, [_VP]),
     "pwn_hip_scene_step": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _F, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pwn_hip_tracker_create": (_I, [_VP, _I, _I, _I, _I, _I, C.POINTER(_VP)]),
+    "pwn_hip_tracker_destroy": (_I, [_VP]),
+    "pwn_hip_tracker_get_state": (_I, [_VP, _I, _I, _VP]),
+    "pwn_hip_tracker_set_state": (_I, [_VP, _I, _I, _VP]),
+    "pwn_hip_tracker_key_cloud": (_I, [_VP, _I, C.POINTER(_VP)]),
+    "pwn_hip_track_frames": (_I, [_VP, _VP, _VP, _VP, _I, _VP, _F, _F, _VP, _F, _VP]),
+    "pwn_hip_track_pose_update": (None, [_VP, _VP, _VP, _I, _I, _F, _I, _VP]),
     "pwn_hip_manifold_image": (_I, [_VP, _I, _VP, _VP, _F, _I, _I, _F, _I, _VP, _VP]),
     "pwn_hip_voxelize": (_I, [_VP, _VP, _F, C.POINTER(_I), _VP]),
     "pwn_hip_cloud_save": (_I, [_VP, _VP, C.c_char_p, _VP, _I, _I]),
@@ -204,6 +221,7 @@ PROTOTYPES = {
     "pwn_hip_debug_set_index_shortcut": (_I, [_VP, _I]),
     "pwn_hip_debug_convert_retries": (_I, [_VP, C.POINTER(_I)]),
     "pwn_hip_debug_set_settle_guard": (_I, [_VP, _I]),
+    "pwn_hip_debug_host_waits": (_I, [_VP, C.POINTER(_I)]),
     "pwn_hip_debug_projection_fallbacks": (_I, [_VP, C.POINTER(_I)]),
     "pwn_hip_debug_project_pairs": (_I, [_VP, _VP, _I, _VP, _VP, _I, _I, _VP, _VP, C.POINTER(_I)]),
     "pwn_hip_debug_cur_depth_sub_batches": (_I, [_VP, C.POINTER(_I)]),

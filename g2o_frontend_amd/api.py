@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AlignerParams, AlignResult, AlignSteps, AlignStatistics, Convergence, ConvertExtras, ConverterParams, MatchResult, PairPriors, Prior, PwnHipError, SceneStepParams, SceneStepResult
+from ._lib import AlignerParams, AlignResult, AlignSteps, AlignStatistics, Convergence, ConvertExtras, ConverterParams, MatchResult, PairPriors, Prior, PwnHipError, SceneStepParams, SceneStepResult, TrackerState, TrackResult
 
 
 def _ptr(x):
@@ -2121,6 +2121,165 @@ class PwnTracker(PwnMatcherBase):
         self._counter += 1
         out["globalT"] = self._globalT.copy()
         return out
+
+
+class _BorrowedCloud(Cloud):
+    """a handle somebody else owns (PwnTrackerBatch.keyCloud): every reading method of Cloud, no destruction"""
+
+    def __init__(self, ctx: Context, handle, capacity: int):
+        self.ctx, self.h, self.capacity = ctx, handle, capacity
+
+    def __del__(self):
+        self.h = None
+
+
+class PwnTrackerBatch(PwnMatcherBase):
+    """S PwnTrackers that advance in lock-step (pwn_hip_tracker / pwn_hip_track_frames): processFrames runs processFrame
+    (pwn_tracker/pwn_tracker.cpp:106-215) for frame 0 of every stream, then frame 1 of every stream, ... as ONE submission with one host wait --
+    guess, pose chain, key-cloud decision and the switch of the reference cloud happen on the device.  Per stream the results, globalT and the key
+    cloud are PwnTracker's, bit for bit.  The streams share camera matrix, image size, parameters and ONE sensor offset (given to every call, like
+    processFrame's); they differ in frames and state.  Frames are raw uint16 images (depth = raw_scale * raw), numpy arrays or CUDA tensors -- all
+    of one call of one kind."""
+
+    def __init__(self, aligner, converter, streams: int, framesPerCallMax: int, rows: int, cols: int, scale: int = 2):
+        super().__init__(aligner, converter)
+        self._scale = int(scale)
+        self._streams, self._framesPerCallMax, self._rows, self._cols = int(streams), int(framesPerCallMax), int(rows), int(cols)
+        self._newFrameInliersFraction = 0.4          # pwn_tracker.cpp:36
+        self.ctx = aligner.ctx
+        h = C.c_void_p()
+        self.ctx.check(self.ctx._L.pwn_hip_tracker_create(self.ctx.h, self._streams, self._framesPerCallMax, self._rows, self._cols, self._scale, C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):      # a context that went first left the handle valid for this call
+                self.ctx._L.pwn_hip_tracker_destroy(self.h)
+            self.h = None
+        except Exception:
+            pass
+
+    def streams(self): return self._streams
+    def framesPerCallMax(self): return self._framesPerCallMax
+    def setNewFrameInliersFraction(self, v): self._newFrameInliersFraction = float(v)
+    def newFrameInliersFraction(self): return self._newFrameInliersFraction
+
+    def states(self):
+        st = (TrackerState * self._streams)()
+        self.ctx.check(self.ctx._L.pwn_hip_tracker_get_state(self.h, 0, self._streams, st))
+        return st
+
+    def state(self, s: int):
+        """the stream's state as a dict (what PwnTracker keeps in _globalT, _previousCloudTransform, _counter, _numKeyframes)"""
+        st = TrackerState()
+        self.ctx.check(self.ctx._L.pwn_hip_tracker_get_state(self.h, int(s), 1, C.byref(st)))
+        return dict(globalT=_from_colmajor(st.globalT, 4), previousCloudTransform=_from_colmajor(st.previous_cloud_transform, 4),
+                    sensorOffset=_from_colmajor(st.sensor_offset, 4), counter=st.counter, numKeyframes=st.num_keyframes, keySlot=st.key_slot)
+
+    def setState(self, s: int, globalT=None, previousCloudTransform=None, counter=None, numKeyframes=None, keySlot=None):
+        st = TrackerState()
+        self.ctx.check(self.ctx._L.pwn_hip_tracker_get_state(self.h, int(s), 1, C.byref(st)))
+        if globalT is not None: _set(st.globalT, globalT, 4)
+        if previousCloudTransform is not None: _set(st.previous_cloud_transform, previousCloudTransform, 4)
+        if counter is not None: st.counter = int(counter)
+        if numKeyframes is not None: st.num_keyframes = int(numKeyframes)
+        if keySlot is not None: st.key_slot = int(keySlot)
+        self.ctx.check(self.ctx._L.pwn_hip_tracker_set_state(self.h, int(s), 1, C.byref(st)))
+
+    def init(self, s: int = None):
+        """pwn_tracker.cpp:38-49 for stream s, or for every stream"""
+        I = _colmajor(np.eye(4, dtype=np.float32), 4)
+        which = range(self._streams) if s is None else [int(s)]
+        for k in which:
+            st = TrackerState()
+            for f in (st.globalT, st.previous_cloud_transform, st.sensor_offset):
+                f[:] = I.tolist()
+            st.key_slot = -1
+            self.ctx.check(self.ctx._L.pwn_hip_tracker_set_state(self.h, k, 1, C.byref(st)))
+
+    def globalT(self, s: int): return self.state(s)["globalT"]
+    def numKeyframes(self, s: int): return self.state(s)["numKeyframes"]
+
+    def keyCloud(self, s: int):
+        """the stream's key cloud after the last call (a borrowed handle: the next call may overwrite it), or None"""
+        h = C.c_void_p()
+        self.ctx.check(self.ctx._L.pwn_hip_tracker_key_cloud(self.h, int(s), C.byref(h)))
+        return _BorrowedCloud(self.ctx, h, (self._rows // self._scale) * (self._cols // self._scale)) if h.value else None
+
+    def callParams(self, sensorOffset, cameraMatrix):
+        """(converter params, aligner params) of a call, with the side effects of makeCloud (pwn_matcher_base.cpp:57-86) and of processFrame's
+        aligner set-up (pwn_tracker.cpp:120-130) on the collaborators"""
+        a = self._aligner
+        off = np.asarray(sensorOffset, np.float32)
+        projector = self._converter.projector()
+        invScale = np.float32(1.0) / np.float32(self._scale)
+        scaled = (np.asarray(cameraMatrix, np.float32).reshape(3, 3) * invScale).astype(np.float32)
+        scaled[2, 2] = 1.0
+        projector.setCameraMatrix(scaled)
+        r, c = self._rows // self._scale, self._cols // self._scale
+        projector.setImageSize(r, c)
+        projector.setTransform(np.eye(4, dtype=np.float32))
+        cp = self._converter.params(off)
+        a.setCurrentSensorOffset(off); a.setReferenceSensorOffset(off)
+        a.correspondenceFinder().setImageSize(r, c)
+        a.projector().setCameraMatrix(scaled); a.projector().setImageSize(r, c)
+        return cp, a.params()
+
+    def processFramesRaw(self, frames, sensorOffset, cameraMatrix, guesses=None, raw_scale=0.001, max_depth_cov=0.01, params=None):
+        """frames[f][s]: frame f of stream s (None: the stream idles in that step) -> the F x S result records as the library wrote them"""
+        F, S = len(frames), self._streams
+        if any(len(row) != S for row in frames):
+            raise ValueError("processFrames: one frame (or None) per stream in every step")
+        keep = [[None if d is None else (d if hasattr(d, "data_ptr") else np.ascontiguousarray(d, np.uint16)) for d in row] for row in frames]
+        for row in keep:
+            for d in row:
+                if d is not None and tuple(d.shape) != (self._rows, self._cols):
+                    raise ValueError("processFrames: a frame of another size than the tracker's")
+        ptrs = (C.c_void_p * (F * S))(*[None if d is None else _ptr(d) for row in keep for d in row])
+        g = None
+        if guesses is not None:
+            I = np.eye(4, dtype=np.float32)
+            g = np.ascontiguousarray(np.stack([_colmajor(Aligner._iso(I if guesses[f][s] is None else guesses[f][s]), 4) for f in range(F) for s in range(S)]), np.float32)
+        cp, ap = params if params is not None else self.callParams(sensorOffset, cameraMatrix)
+        res = (TrackResult * (F * S))()
+        self.ctx.check(self.ctx._L.pwn_hip_track_frames(self.ctx.h, self.h, C.byref(cp), C.byref(ap), F, ptrs, raw_scale, max_depth_cov, _ptr(g),
+                                                        self._newFrameInliersFraction, res))
+        self.numCalls += sum(d is not None for row in keep for d in row)
+        return res
+
+    def processFrames(self, frames, sensorOffset, cameraMatrix, guesses=None, raw_scale=0.001, max_depth_cov=0.01):
+        """-> per step a list with, per stream, the dict PwnTracker.processFrame returns (None where the stream idled)"""
+        F, S = len(frames), self._streams
+        res = self.processFramesRaw(frames, sensorOffset, cameraMatrix, guesses, raw_scale, max_depth_cov)
+        out = []
+        for f in range(F):
+            row = []
+            for s in range(S):
+                r = res[f * S + s]
+                if frames[f][s] is None:
+                    row.append(None); continue
+                d = dict(newFrame=bool(r.new_frame), aligned=bool(r.aligned), inliers=r.inliers, error=r.error, T=_from_colmajor(r.T, 4) if r.aligned else None,
+                         globalT=_from_colmajor(r.globalT, 4), n_points=r.n_points)
+                if r.aligned:
+                    d["inliersFraction"] = float(r.inliers_fraction)
+                row.append(d)
+            out.append(row)
+        return out
+
+
+def track_pose_update(state: dict, initialGuess, T, inliers: int, pixels: int, threshold: float, slot: int = 0):
+    """pwn_hip_track_pose_update: the host compilation of what the device does with one alignment's result.  state: dict with globalT,
+    previousCloudTransform, counter, numKeyframes, keySlot -> (new state dict, result dict)"""
+    st = TrackerState()
+    _set(st.globalT, state["globalT"], 4); _set(st.previous_cloud_transform, state["previousCloudTransform"], 4)
+    _set(st.sensor_offset, np.eye(4, dtype=np.float32), 4)
+    st.counter, st.num_keyframes, st.key_slot = int(state["counter"]), int(state["numKeyframes"]), int(state.get("keySlot", 0))
+    r = TrackResult()
+    g = None if initialGuess is None else _colmajor(initialGuess, 4)
+    _lib.lib().pwn_hip_track_pose_update(C.byref(st), _ptr(g), _ptr(_colmajor(T, 4)), int(inliers), int(pixels), float(threshold), int(slot), C.byref(r))
+    new = dict(globalT=_from_colmajor(st.globalT, 4), previousCloudTransform=_from_colmajor(st.previous_cloud_transform, 4), counter=st.counter,
+               numKeyframes=st.num_keyframes, keySlot=st.key_slot)
+    return new, dict(newFrame=bool(r.new_frame), inliersFraction=r.inliers_fraction, globalT=_from_colmajor(r.globalT, 4))
 
 
 def v2t(v):

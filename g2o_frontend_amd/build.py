@@ -6,7 +6,7 @@ import subprocess
 import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("pwn_hip_capi.hip", "pwn_buffers.h", "pwn_kernels.h", "pwn_math.h", "pwn_scene_kernels.h", "pwn_scene_capi.h", "pwn_stats.h", "pwn_consensus.h")]
+SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("pwn_hip_capi.hip", "pwn_buffers.h", "pwn_kernels.h", "pwn_math.h", "pwn_scene_kernels.h", "pwn_scene_capi.h", "pwn_stats.h", "pwn_consensus.h", "pwn_track.h", "pwn_track_capi.h")]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "pwn_hip.h")
 TEST_HEADER = os.path.join(os.path.dirname(_HERE), "include", "pwn_hip_testing.h")
 OUT = os.path.join(_HERE, "libpwn_hip.so")
@@ -128,6 +128,13 @@ def build_tools(force: bool = False) -> str:
     deps15 = [src15] + deps[1:]
     if force or (not os.path.exists(out15)) or any(os.path.getmtime(d) > os.path.getmtime(out15) for d in deps15):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src15, "-o", out15, "-L", _HERE, "-lpwn_hip",
+                               "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
+    # PwnTrackerBatch::processFrames of the C++ mirror against the result records, states and key clouds the Python mirror wrote to a file (exit status 0 = equal bit for bit)
+    src16 = os.path.join(root, "tools", "pwn_hip_track_streams_check.cpp")
+    out16 = os.path.join(root, "tools", "pwn_hip_track_streams_check")
+    deps16 = [src16] + deps[1:]
+    if force or (not os.path.exists(out16)) or any(os.path.getmtime(d) > os.path.getmtime(out16) for d in deps16):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", root, src16, "-o", out16, "-L", _HERE, "-lpwn_hip",
                                "-Wl,-rpath,$ORIGIN/../g2o_frontend_amd"])
     # PwnCloser::processPartition over the GPUs of a node in native code: the mirror + RCCL (broadcast of the flat `current` cloud, all-gather of the
     # match records); the program's own streams and events come from the HIP runtime

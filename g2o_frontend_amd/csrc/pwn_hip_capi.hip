@@ -14,6 +14,7 @@
 #include "pwn_scene_kernels.h"
 #include "pwn_stats.h"
 #include "pwn_consensus.h"
+#include "pwn_track.h"
 
 #include <algorithm>
 #include <chrono>
@@ -185,6 +186,8 @@ struct pwn_hip_cloud {
   const pwn_hip_ctx* owner = nullptr;    // the context it was created on (pwn_hip_project_merge_batch refuses another context's cloud)
 };
 
+struct pwn_hip_tracker;
+void tracker_orphan(pwn_hip_tracker* tr);      // pwn_track_capi.h: the context goes, the handle stays valid for pwn_hip_tracker_destroy alone
 struct pwn_hip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -273,6 +276,7 @@ struct pwn_hip_ctx {
   DevBuf<unsigned> zdepth_ws;
   int settle_guard = kSettleGuard;                       // pwn_hip_debug_set_settle_guard (test hook)
   int last_align_fault = 0;                              // the last alignment call ended with the fault word raised
+  int host_waits = 0;                                    // waits of the calling thread for one of the context's streams so far (pwn_hip_debug_host_waits)
   int projection_fallbacks = 0;                          // calls repeated with the two-pass projection so far (pwn_hip_debug_projection_fallbacks)
   // the frames of a step's current clouds, per pair (CurDepthSrc::raw), and how many sub-batches of the last batch alignment ran the fused pass
   // on them (pwn_hip_debug_cur_depth_sub_batches)
@@ -303,6 +307,8 @@ struct pwn_hip_ctx {
   // them the empty-column word, the staging of the call's host-side arrays, and the page-locked copy of the empty-column word
   DevBuf<ConsensusRel> consensus_rel; DevBuf<unsigned long long> consensus_bits; DevBuf<int> consensus_counts;
   DevBuf<char> consensus_stage; HostBuf<int> consensus_flag_host;
+  // the multi-stream trackers created on the context (pwn_hip_tracker_create): their clouds and device records go with the context; a handle that outlives it is only good for pwn_hip_tracker_destroy
+  std::vector<pwn_hip_tracker*> trackers;
 };
 
 namespace {
@@ -332,6 +338,8 @@ void launch_corr_linearize(const pwn_hip_ctx* ctx, const PairLaunch& L, unsigned
   else launch_corr_linearize_s<SAME_T, FULL_H, false>(ctx, L, tag, usePrevTc, ownRef);
 }
 
+// every wait of the calling thread for a stream goes through here, so that a test can count the waits of a call
+hipError_t host_wait(pwn_hip_ctx* ctx, hipStream_t st) { if (ctx) ++ctx->host_waits; return hipStreamSynchronize(st); }
 int fail(pwn_hip_ctx* ctx, int code, const std::string& msg) {
   if (ctx) ctx->err = msg;
   g_err = msg;
@@ -651,7 +659,7 @@ int align_nblocks(int N) { return (N + kAlignBlock * kPixPerThread - 1) / (kAlig
 // descriptor / state arrays for a batch of n items
 int ensure_desc(pwn_hip_ctx* ctx, int n) {
   if (n <= ctx->desc_cap) return PWN_HIP_OK;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   ctx->desc_cap = 0;
   ctx->img.invalidate();                     // the descriptor of the last alignment's pair goes with the old arrays
   const size_t B = (size_t)std::max(n, 16);
@@ -767,7 +775,7 @@ int cloud_replace(pwn_hip_ctx* ctx, pwn_hip_cloud* c, bool keep_stats, bool plan
                   bool gauss = false) {
   cloud_changes(ctx, c);
   if (const unsigned which = (keep_stats ? kArrSt : 0u) | (planes ? kArrOmN : 0u) | (gauss ? kArrGauss : 0u)) { if (int rc = cloud_own(ctx, c, which)) return rc; }
-  if (!planes && c->d.OmN) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH); c->drop_omega_n(); }
+  if (!planes && c->d.OmN) { HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH); c->drop_omega_n(); }
   if (cls) { std::memcpy(c->d.omN, cls->omN, sizeof(cls->omN)); c->d.clsThr = cls->clsThr; }
   c->content.replace(keep_stats, key, promised);
   c->stripoff_filled = false;      // the table went with the index image it belonged to; a conversion that fills it says so after this (convert_prepare)
@@ -833,7 +841,7 @@ int counts_apply(pwn_hip_ctx* ctx, pwn_hip_cloud* const* clouds, int n, bool gau
 // frames_dev[0..n) must describe clouds[0..n): the counts and the fault flag back (direct: the kernels stored them in counts_host themselves), the wait
 int sync_counts(pwn_hip_ctx* ctx, int n, bool direct = false) {
   if (n > 0 && !direct) { if (int rc = counts_enqueue(ctx, n)) return rc; }
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   collect_stage_times(ctx);
   return PWN_HIP_OK;
 }
@@ -865,7 +873,7 @@ int make_scale_spec(pwn_hip_ctx* ctx, int rows, int cols, int step, float max_de
 // ensure_desc grows its arrays)
 int ensure_scale(pwn_hip_ctx* ctx, int n) {
   HIPCHK(ctx, ctx->scaled_ws.ensure((size_t)ctx->max_batch * ctx->N), PWN_HIP_ERR_ALLOCATION);
-  if ((size_t)n > ctx->scale_dev.cap) HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  if ((size_t)n > ctx->scale_dev.cap) HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   const size_t B = (size_t)std::max(n, 16);
   HIPCHK(ctx, ctx->scale_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
   HIPCHK(ctx, ctx->scale_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
@@ -900,7 +908,7 @@ struct GaussSpec {
 };
 // the per-frame Gaussian arrays of a call of n frames (grown after a wait for the stream, as ensure_desc grows its arrays)
 int ensure_gauss_desc(pwn_hip_ctx* ctx, int n) {
-  if ((size_t)n > ctx->gauss_dev.cap) HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  if ((size_t)n > ctx->gauss_dev.cap) HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   const size_t B = (size_t)std::max(n, 16);
   HIPCHK(ctx, ctx->gauss_dev.ensure(B), PWN_HIP_ERR_ALLOCATION);
   HIPCHK(ctx, ctx->gauss_host.ensure(B), PWN_HIP_ERR_ALLOCATION);
@@ -976,7 +984,7 @@ int convert_prepare(pwn_hip_ctx* ctx, const ConvertCall& c, const std::vector<in
     float* scaled = sc.step ? ctx->scaled_ws + (size_t)slot[i] * ctx->N : nullptr;      // a down-sampling job: the box kernel writes, the front end reads the slot's frame
     fill_frame(ctx, e0 + i, slot[i], sc.step ? scaled : raw ? nullptr : static_cast<const float*>(src), cl->d);
     if (cl->idximg.cap < N) {
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+      HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
       HIPCHK(ctx, cl->idximg.ensure(N), PWN_HIP_ERR_ALLOCATION);
     }
     ctx->frames_host[e0 + i].index = cl->idximg;
@@ -986,7 +994,7 @@ int convert_prepare(pwn_hip_ctx* ctx, const ConvertCall& c, const std::vector<in
     if (cp.hasOffset == 0 && c.cols % kIR_Cols == 0) {
       const size_t words = (size_t)c.rows * (size_t)strips_of(c.cols);
       if (cl->stripoff.cap < words) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+        HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
         HIPCHK(ctx, cl->stripoff.ensure(words), PWN_HIP_ERR_ALLOCATION);
       }
       ctx->frames_host[e0 + i].rowoff = cl->stripoff;
@@ -1217,7 +1225,7 @@ int depth_scale_batch_impl(pwn_hip_ctx* ctx, const ConvertCall& c, float* const*
       HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
       HIPCHK(ctx, hipMemcpyAsync(ctx->counts_host, ctx->counts_dev, sizeof(int) * m, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
     }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);      // the descriptors and the slots are reused by the next chunk
+    HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);      // the descriptors and the slots are reused by the next chunk
     if (valid) std::copy(ctx->counts_host.p, ctx->counts_host.p + m, valid + base);
   }
   collect_stage_times(ctx);
@@ -1297,7 +1305,7 @@ int debug_stats_impl(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, int ro
   HIPCHK(ctx, hipMemcpyAsync(ctx->frames_dev, ctx->frames_host, sizeof(FrameDesc) * nframes, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
   launch_stats(cp, ctx->frames_dev, nframes, ctx->stream);      // launch_convert's grid
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   for (int i = 0; i < nframes; ++i) cloud_commit(clouds[i], npoints[i]);
   return PWN_HIP_OK;
 }
@@ -1345,7 +1353,7 @@ int pwn_hip_device_free(pwn_hip_ctx* ctx, void* ptr) {
   }
   HIPCHK(ctx, hipSetDevice(ctx->device), PWN_HIP_ERR_NO_DEVICE);
   if (int rc = absorb_copies(ctx)) return rc;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);       // nothing queued may still read or write it
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);       // nothing queued may still read or write it
   HIPCHK(ctx, hipFree(ptr), PWN_HIP_ERR_INVALID_ARGUMENT);
   return PWN_HIP_OK;
 }
@@ -1355,7 +1363,7 @@ int pwn_hip_copy(pwn_hip_ctx* ctx, void* dst, const void* src, size_t bytes) {
   HIPCHK(ctx, hipSetDevice(ctx->device), PWN_HIP_ERR_NO_DEVICE);
   if (int rc = absorb_copies(ctx)) return rc;
   HIPCHK(ctx, copy_any(dst, src, bytes, ctx->stream), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_COPY);
   return PWN_HIP_OK;
 }
 int pwn_hip_device_memset(pwn_hip_ctx* ctx, void* ptr, int value, size_t bytes) {
@@ -1479,6 +1487,8 @@ static int ctx_create(pwn_hip_ctx** out, int device, int max_rows, int max_cols,
 int pwn_hip_ctx_destroy(pwn_hip_ctx* ctx) {
   if (!ctx) return PWN_HIP_OK;
   (void)hipSetDevice(ctx->device);
+  for (pwn_hip_tracker* tr : ctx->trackers) tracker_orphan(tr);
+  ctx->trackers.clear();
   if (AsyncConvert* a = ctx->async) {       // a conversion still in flight finishes first; its result is dropped
     { std::unique_lock<std::mutex> lk(a->m); a->quit = true; }
     a->cv.notify_all();
@@ -1488,7 +1498,7 @@ int pwn_hip_ctx_destroy(pwn_hip_ctx* ctx) {
     delete a; ctx->async = nullptr;
   }
   if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);      // pwn_hip_copy_async transfers still in flight
-  if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  if (ctx->stream) (void)host_wait(ctx, ctx->stream);
   collect_stage_times(ctx);
   for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
   if (ctx->t0) (void)hipEventDestroy(ctx->t0);
@@ -1512,7 +1522,7 @@ int pwn_hip_ctx_destroy(pwn_hip_ctx* ctx) {
 }
 int pwn_hip_ctx_set_stream(pwn_hip_ctx* ctx, void* hip_stream) {
   if (!ctx) return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, "null ctx");
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
   return PWN_HIP_OK;
 }
@@ -1543,7 +1553,7 @@ int pwn_hip_ctx_set_enqueued_callback(pwn_hip_ctx* ctx, void (*fn)(void*), void*
 int pwn_hip_ctx_synchronize(pwn_hip_ctx* ctx) {
   if (!ctx) return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, "null ctx");
   if (int rc = absorb_copies(ctx)) return rc;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
 }
 int pwn_hip_ctx_set_subbatch(pwn_hip_ctx* ctx, int frames, int pairs) {
@@ -1563,7 +1573,7 @@ int pwn_hip_cloud_omega_storage(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, int* m
 }
 int pwn_hip_ctx_set_concurrency(pwn_hip_ctx* ctx, int streams) {
   if (!ctx || streams < 1 || streams > 4) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "streams must be 1..4");
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   ctx->concurrency = streams;
   return PWN_HIP_OK;
 }
@@ -1596,6 +1606,11 @@ int pwn_hip_debug_set_index_shortcut(pwn_hip_ctx* ctx, int enabled) {
 int pwn_hip_debug_set_settle_guard(pwn_hip_ctx* ctx, int rounds) {
   if (!ctx) return fail(nullptr, PWN_HIP_ERR_INVALID_ARGUMENT, "null ctx");
   ctx->settle_guard = rounds < 0 ? kSettleGuard : rounds;
+  return PWN_HIP_OK;
+}
+int pwn_hip_debug_host_waits(pwn_hip_ctx* ctx, int* waits) {
+  if (!ctx || !waits) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  *waits = ctx->host_waits;
   return PWN_HIP_OK;
 }
 int pwn_hip_debug_projection_fallbacks(pwn_hip_ctx* ctx, int* calls) {
@@ -1700,7 +1715,7 @@ int pwn_hip_debug_statistics_eval(pwn_hip_ctx* ctx, int n, const float* H, const
   hipLaunchKernelGGL(k_pair_statistics, dim3(n), dim3(64), 0, st, ctx->pairs_dev, (const SolveOut*)ctx->stats_dev, ctx->pairstats_dev);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   HIPCHK(ctx, hipMemcpyAsync(ctx->pairstats_host, ctx->pairstats_dev, sizeof(PairStats) * n, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, st), PWN_HIP_ERR_LAUNCH);
   for (int i = 0; i < n; ++i) std::memcpy(out + 44 * (size_t)i, &ctx->pairstats_host[i], sizeof(float) * 44);
   return PWN_HIP_OK;
 }
@@ -1807,7 +1822,7 @@ int pwn_hip_cloud_destroy(pwn_hip_ctx* ctx, pwn_hip_cloud* c) {
     ctx->cloud_pool_bytes += c->core_bytes();
     return PWN_HIP_OK;
   }
-  if (ctx) (void)hipStreamSynchronize(ctx->stream);
+  if (ctx) (void)host_wait(ctx, ctx->stream);
   delete c;
   return PWN_HIP_OK;
 }
@@ -1828,7 +1843,7 @@ int pwn_hip_cloud_upload(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int n, const float*
   HIPCHK(ctx, copy_any(hc.data(), curvature, hc.size() * 4, ctx->stream), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, copy_any(hop.data(), omega_p, hop.size() * 4, ctx->stream), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, copy_any(hon.data(), omega_n, hon.size() * 4, ctx->stream), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_COPY);
   const size_t cap = (size_t)c->d.capacity;
   const int sym = c->d.omSym;
   std::vector<float> P((size_t)n * 4), Nm((size_t)n * 4), Om(c->front.Om.cap, 0.f), OmN(cap * 9, 0.f);
@@ -1852,7 +1867,7 @@ int pwn_hip_cloud_upload(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int n, const float*
 int pwn_hip_cloud_download(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, float* points, float* normals, float* curvature, float* omega_p, float* omega_n) {
   if (!ctx || !c) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   const int n = c->content.n; const size_t cap = (size_t)c->d.capacity;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   std::vector<float> P, Nm;
   if (int rc = cloud_fetch_records(ctx, c->d, n, P, Nm)) return rc;
   std::vector<float> hp, hn, hc, hop, hon;
@@ -1890,7 +1905,7 @@ int pwn_hip_cloud_download_stats(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, float
   if (!ctx || !c) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (!c->content.stats || !c->d.St) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "cloud was not converted with keep_stats");
   const int n = c->content.n;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   std::vector<float> St((size_t)n * 16);
   HIPCHK(ctx, hipMemcpy(St.data(), c->d.St, St.size() * 4, hipMemcpyDeviceToHost), PWN_HIP_ERR_COPY);
   std::vector<float> hs, he; std::vector<int> hn;
@@ -1923,7 +1938,7 @@ int pwn_hip_cloud_transform_in_place(pwn_hip_ctx* ctx, pwn_hip_cloud* c, const f
     if (cnt > 0 && (v.d.St || v.gauss > 0)) hipLaunchKernelGGL(k_scene_transform, dim3((cnt + 255) / 256), dim3(256), 0, ctx->stream, v.d, v.sb, v.n, v.gauss, m);
   }
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
 }
 
@@ -1988,7 +2003,7 @@ int pwn_hip_cloud_export(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, void* dst, si
       HIPCHK(ctx, copy_section(out + h.offOmN + (size_t)r * up256(n * 12), c->d.OmN + (size_t)r * cap * 3, n * 12, st), PWN_HIP_ERR_COPY);
   }
   if (npx > 0) HIPCHK(ctx, copy_section(out + h.offIdx, c->idximg, npx * 4, st), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_COPY);      // the buffer is complete on return
+  HIPCHK(ctx, host_wait(ctx, st), PWN_HIP_ERR_COPY);      // the buffer is complete on return
   return PWN_HIP_OK;
 }
 int pwn_hip_cloud_import(pwn_hip_ctx* ctx, pwn_hip_cloud* c, const void* src, size_t src_bytes) {
@@ -1999,7 +2014,7 @@ int pwn_hip_cloud_import(pwn_hip_ctx* ctx, pwn_hip_cloud* c, const void* src, si
   hipStream_t st = ctx->stream;
   CloudFlatHeader h;
   HIPCHK(ctx, copy_any(&h, src, sizeof(h), st), PWN_HIP_ERR_COPY);      // on the context's stream: ordered after pwn_hip_ctx_wait_stream
-  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, host_wait(ctx, st), PWN_HIP_ERR_COPY);
   if (h.magic != kFlatMagic || h.version != 1 || h.n < 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "not a flat cloud buffer (pwn_hip_cloud_export)");
   CloudFlatHeader want; std::memset(&want, 0, sizeof(want));
   const bool idx = h.idxValid != 0 && h.idxRows > 0 && h.idxCols > 0;
@@ -2028,7 +2043,7 @@ int pwn_hip_cloud_import(pwn_hip_ctx* ctx, pwn_hip_cloud* c, const void* src, si
   }
   if (idx) HIPCHK(ctx, copy_section(c->idximg, in + h.offIdx, npx * 4, st), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, copy_any(c->d.count, &hp.n, sizeof(int), st), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_COPY);
+  HIPCHK(ctx, host_wait(ctx, st), PWN_HIP_ERR_COPY);
   const IndexKey key(h.idxRows, h.idxCols, h.idxK, h.idxMinD, h.idxMaxD);
   cloud_commit(c, h.n, idx ? &key : nullptr);
   return PWN_HIP_OK;
@@ -2047,7 +2062,7 @@ int pwn_hip_depth_u16_to_f32(pwn_hip_ctx* ctx, const uint16_t* src, float* dst, 
   hipLaunchKernelGGL(k_u16_to_f32, dim3(std::min((n + 255) / 256, 2048), 1), dim3(256), 0, ctx->stream, ctx->raw_dev, n, scale);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   if (d != dst) HIPCHK(ctx, hipMemcpyAsync(dst, d, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
 }
 int pwn_hip_depth_f32_to_u16(pwn_hip_ctx* ctx, const float* src, uint16_t* dst, int n, float scale) {
@@ -2060,7 +2075,7 @@ int pwn_hip_depth_f32_to_u16(pwn_hip_ctx* ctx, const float* src, uint16_t* dst, 
   hipLaunchKernelGGL(k_f32_to_u16, dim3(std::min((n + 255) / 256, 2048)), dim3(256), 0, ctx->stream, s, d, n, scale);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   if (d != dst) HIPCHK(ctx, hipMemcpyAsync(dst, d, (size_t)n * 2, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
 }
 int pwn_hip_depth_scale(pwn_hip_ctx* ctx, const float* src, int rows, int cols, int step, float max_depth_cov, float* dst) {
@@ -2074,7 +2089,7 @@ int pwn_hip_depth_scale(pwn_hip_ctx* ctx, const float* src, int rows, int cols, 
   if (on > 0) hipLaunchKernelGGL(k_depth_scale, dim3((unsigned)((on + 255) / 256)), dim3(256), 0, ctx->stream, s, rows, cols, step, max_depth_cov, d);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   if (d != dst) HIPCHK(ctx, hipMemcpyAsync(dst, d, on * 4, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
 }
 // the two typed forms' argument checks, then the frames of `c` down-sampled into dst
@@ -2138,7 +2153,7 @@ int pwn_hip_project_intervals(pwn_hip_ctx* ctx, const pwn_hip_converter_params* 
   hipLaunchKernelGGL(k_unproject, dim3(rows, 1), dim3(256), 0, ctx->stream, ctx->frames_dev, cp);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   HIPCHK(ctx, copy_any(interval_image, ctx->frames_host[0].interval, N * 4, ctx->stream), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
 }
 int pwn_hip_integral_image(pwn_hip_ctx* ctx, const int* index_image, const pwn_hip_cloud* cloud, int rows, int cols, float* out) {
@@ -2153,7 +2168,7 @@ int pwn_hip_integral_image(pwn_hip_ctx* ctx, const int* index_image, const pwn_h
   hipLaunchKernelGGL(k_integral_cols, dim3((cols + kIC_Block - 1) / kIC_Block, kIntegralChannels, 1), dim3(kIC_Block), 0, ctx->stream, ctx->frames_dev, rows, cols, (const int*)nullptr, (int*)nullptr, 0);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   HIPCHK(ctx, copy_any(out, ctx->frames_host[0].integral, N * kIntegralChannels * 4, ctx->stream), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
 }
 int pwn_hip_convert(pwn_hip_ctx* ctx, const pwn_hip_converter_params* p, const float* depth, int rows, int cols, pwn_hip_cloud* cloud,
@@ -2264,7 +2279,7 @@ static int async_convert_begin(pwn_hip_ctx* ctx, const pwn_hip_converter_params*
     // a device frame the context's own stream may still be writing (pwn_hip_copy_async above): wait for it.  The raw-frame form does not wait --
     // it is what a caller queues from inside pwn_hip_ctx_set_enqueued_callback while the context's stream is busy with a batch -- and asks for a
     // frame that is complete when the call is made (include/pwn_hip.h)
-    if (depth && is_device_ptr(depth)) HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+    if (depth && is_device_ptr(depth)) HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
     cloud_changes(ctx, cloud);
     a->raw = raw; a->raw_scale = raw_scale; a->flat_dst = flat_dst; a->flat_bytes = flat_bytes; a->flat_written = 0; a->job_ms = 0.f;
     a->p = *p; a->depth = depth; a->rows = rows; a->cols = cols; a->step = step; a->max_depth_cov = max_depth_cov; a->cloud = cloud;
@@ -2353,7 +2368,7 @@ int pwn_hip_project(pwn_hip_ctx* ctx, const float K[9], const float T[16], float
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   if (index_image && di != index_image) HIPCHK(ctx, hipMemcpyAsync(index_image, di, N * 4, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
   if (depth_image && dd != depth_image) HIPCHK(ctx, hipMemcpyAsync(depth_image, dd, N * 4, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   ctx->img.invalidate();
   collect_stage_times(ctx);
   return PWN_HIP_OK;
@@ -2401,7 +2416,7 @@ static int merge_end(pwn_hip_ctx* ctx, const MergeRun& r, int n, float* merged, 
   if (r.merged != merged) HIPCHK(ctx, hipMemcpyAsync(merged, r.merged, (size_t)r.N * 4, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
   if (r.weights != weights) HIPCHK(ctx, hipMemcpyAsync(weights, r.weights, (size_t)r.N * 4, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipMemcpyAsync(ctx->merge_counts_host, ctx->merge_counts_dev, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   if (overlap) std::copy(ctx->merge_counts_host.p, ctx->merge_counts_host.p + n, overlap);
   if (points) *points += ctx->merge_counts_host[n];
   collect_stage_times(ctx);
@@ -2490,7 +2505,7 @@ int pwn_hip_correspondences(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, c
   std::vector<int2> img(N); int cand = 0;
   HIPCHK(ctx, hipMemcpyAsync(img.data(), ctx->corr_ws, N * sizeof(int2), hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipMemcpyAsync(&cand, ctx->counters_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   std::vector<int> out(2 * N, -1);
   int C = 0;
   for (size_t i = 0; i < N; ++i) if (img[i].x >= 0) { out[2 * C] = img[i].x; out[2 * C + 1] = img[i].y; ++C; }   // row-major order
@@ -2513,7 +2528,7 @@ int pwn_hip_linearize(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* p, const p
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   SolveOut so;
   HIPCHK(ctx, hipMemcpyAsync(&so, ctx->solve_dev, sizeof(so), hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   if (H) std::memcpy(H, so.H, sizeof(so.H));
   if (b) std::memcpy(b, so.b, sizeof(so.b));
   if (error) *error = so.chi2;
@@ -2909,7 +2924,7 @@ static int align_batch_once(pwn_hip_ctx* ctx, const AlignCall& call, bool robust
   // everything of the call is queued, nothing has been waited for: the caller's moment to queue what depends on it on other streams, or to prepare
   // the next call, while the device works (pwn_hip_ctx_set_enqueued_callback)
   if (ctx->enqueued_cb && call.n > 0) ctx->enqueued_cb(ctx->enqueued_user);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   return align_finish(ctx, call, run);
 }
 // The call; and once more with the two-pass projection if one of its projections gave up on a pixel (z32_settle): nothing of the failed
@@ -3118,7 +3133,7 @@ int pwn_hip_last_align_steps(pwn_hip_ctx* ctx, int first, int n, pwn_hip_align_s
   if (first < 0 || n < 0 || (long long)first + n > ctx->last_pairs) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "pairs outside the last alignment call");
   if (n > 0 && !ctx->last_states_on_host) {      // the call returned records only: its final states are still in state_ws
     HIPCHK(ctx, hipMemcpyAsync(ctx->state_host, ctx->state_ws, sizeof(PairState) * ctx->last_pairs, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+    HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
     ctx->last_states_on_host = true;
   }
   for (int i = 0; i < n; ++i) {
@@ -3156,7 +3171,7 @@ int pwn_hip_debug_prior_terms_eval(pwn_hip_ctx* ctx, int n, const float* invT, c
                      (PriorTerms*)ctx->prior_terms_dev, (const Mat4*)T, off);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   HIPCHK(ctx, hipMemcpyAsync(out, ctx->prior_terms_dev, sizeof(PriorTerms) * (size_t)first[n], hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, st), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
 }
 int pwn_hip_match_score(pwn_hip_ctx* ctx, float threshold, pwn_hip_match_result* out) {
@@ -3169,7 +3184,7 @@ int pwn_hip_match_score(pwn_hip_ctx* ctx, float threshold, pwn_hip_match_result*
                      ctx->img.cur_tag, 1000.0f, threshold, ctx->match_dev, ctx->img.cur_lazy ? 1 : 0);
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   HIPCHK(ctx, hipMemcpyAsync(ctx->match_host, ctx->match_dev, sizeof(MatchAcc), hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   finish_match(ctx->match_host[0], out);
   return PWN_HIP_OK;
 }
@@ -3203,7 +3218,7 @@ int pwn_hip_align_images(pwn_hip_ctx* ctx, int* ref_index, float* ref_depth, int
     HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
     if (oi && di != oi) HIPCHK(ctx, hipMemcpyAsync(oi, di, N * 4, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
     if (od && dd != od) HIPCHK(ctx, hipMemcpyAsync(od, dd, N * 4, hipMemcpyDeviceToHost, ctx->stream), PWN_HIP_ERR_COPY);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+    HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   }
   return PWN_HIP_OK;
 }
@@ -3258,7 +3273,7 @@ int pwn_hip_debug_project_pairs(pwn_hip_ctx* ctx, const pwn_hip_aligner_params* 
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   if (index_out) HIPCHK(ctx, copy_any(index_out, ctx->index_ws, (size_t)n * N * 4, st), PWN_HIP_ERR_COPY);
   if (depth_out) HIPCHK(ctx, copy_any(depth_out, ctx->depth_ws, (size_t)n * N * 4, st), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, st), PWN_HIP_ERR_LAUNCH);
   // the settle word, read and cleared here: a give-up is this call's result, not an error (take_align_fault would leave its message behind an OK)
   *gave_up = *(volatile int*)ctx->align_fault_host != 0 ? 1 : 0;
   *(volatile int*)ctx->align_fault_host = 0;
@@ -3460,7 +3475,7 @@ int pwn_hip_validate_relations(pwn_hip_ctx* ctx, const pwn_hip_consensus_params*
   for (Staged& s : a)
     if (s.staged && s.down) HIPCHK(ctx, hipMemcpyAsync(s.user, s.dev, s.bytes, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipMemcpyAsync(ctx->consensus_flag_host, emptyDev, sizeof(int), hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, st), PWN_HIP_ERR_LAUNCH);
   collect_stage_times(ctx);
   const int empty = ctx->consensus_flag_host[0];
   if (empty != kConsensusNoEmptyColumn) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "no inliers in column " + std::to_string(empty));
@@ -3470,3 +3485,4 @@ int pwn_hip_validate_relations(pwn_hip_ctx* ctx, const pwn_hip_consensus_params*
 }  // extern "C"
 
 #include "pwn_scene_capi.h"
+#include "pwn_track_capi.h"

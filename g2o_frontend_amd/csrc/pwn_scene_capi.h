@@ -34,7 +34,7 @@ int ensure_scene(pwn_hip_ctx* ctx, pwn_hip_cloud* c, bool with_gauss) {
     if (c->content.n > 0) {
       const std::vector<float> st = default_stats(c->content.n);
       HIPCHK(ctx, hipMemcpyAsync(c->d.St, st.data(), st.size() * 4, hipMemcpyHostToDevice, ctx->stream), PWN_HIP_ERR_COPY);
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_COPY);
+      HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_COPY);
     }
     c->content.set_stats();
   }
@@ -43,7 +43,7 @@ int ensure_scene(pwn_hip_ctx* ctx, pwn_hip_cloud* c, bool with_gauss) {
 }
 // context scratch of the scene stage: int arrays of n entries and 64-bit arrays
 int scene_scratch(pwn_hip_ctx* ctx, size_t n_int, size_t n_u64) {
-  if (n_int + 1024 > ctx->scene_i[0].cap || n_u64 > ctx->scene_k[0].cap) HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  if (n_int + 1024 > ctx->scene_i[0].cap || n_u64 > ctx->scene_k[0].cap) HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   for (auto& b : ctx->scene_i) HIPCHK(ctx, b.ensure(n_int + 1024), PWN_HIP_ERR_ALLOCATION);
   for (auto& b : ctx->scene_k) HIPCHK(ctx, b.ensure(n_u64), PWN_HIP_ERR_ALLOCATION);
   HIPCHK(ctx, ctx->scene_total.ensure(4), PWN_HIP_ERR_ALLOCATION);
@@ -161,7 +161,7 @@ int pwn_hip_cloud_download_gaussians(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, f
   if (!ctx || !c) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "null argument");
   const int n = c->view().gauss;
   if (n == 0) return PWN_HIP_OK;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   std::vector<GaussD> g(n); std::vector<int> f(n);
   HIPCHK(ctx, hipMemcpy(g.data(), c->sb.G, sizeof(GaussD) * (size_t)n, hipMemcpyDeviceToHost), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipMemcpy(f.data(), c->sb.Gf, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost), PWN_HIP_ERR_COPY);
@@ -191,7 +191,7 @@ int pwn_hip_debug_cloud_set_gaussians(pwn_hip_ctx* ctx, pwn_hip_cloud* c, int n,
       std::memcpy(g[i].mean, mean + 3 * (size_t)i, 12); std::memcpy(g[i].cov, cov + 9 * (size_t)i, 36);
       std::memcpy(g[i].infoVec, info_vec + 3 * (size_t)i, 12); std::memcpy(g[i].info, info + 9 * (size_t)i, 36);
     }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+    HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
     HIPCHK(ctx, hipMemcpy(c->sb.G, g.data(), sizeof(GaussD) * (size_t)n, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
     HIPCHK(ctx, hipMemcpy(c->sb.Gf, flags, sizeof(int) * (size_t)n, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);
   }
@@ -230,7 +230,7 @@ int pwn_hip_cloud_add(pwn_hip_ctx* ctx, pwn_hip_cloud* dst, const pwn_hip_cloud*
     dst->content.set_gaussians(newg);
   }
   if (int rc = cloud_edit(ctx, dst, k + n, true)) return rc;      // edit: the host decides the new size
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   return PWN_HIP_OK;
 }
 
@@ -260,7 +260,7 @@ int pwn_hip_merge(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, const float K[9], cons
   const MergeView view = { min_distance, max_distance, max_point_depth, rows, cols, distance_threshold, normal_threshold };
   if (int rc = merge_enqueue(ctx, st, cloud, back, sback, ctx->step_dev, host, view, (size_t)n, (size_t)ngauss, tag)) return rc;
   if (collapsed) HIPCHK(ctx, hipMemcpyAsync(collapsed, merge_scratch(ctx).collapsed, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, st), PWN_HIP_ERR_LAUNCH);
   const int k = host->sizeMerge;
   if (int rc = merge_commit(ctx, cloud, n, k)) return rc;
   ctx->img.invalidate();                  // slot 0 of the z-buffer was used
@@ -467,7 +467,7 @@ int pwn_hip_merge_clouds(pwn_hip_ctx* ctx, const float K[9], const float offset[
   int* h = ctx->merge_counts_host;
   HIPCHK(ctx, hipMemcpyAsync(h, d_counts, sizeof(int) * 2 * (size_t)n, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
   HIPCHK(ctx, hipMemcpyAsync(h + 2 * n, total->d.count, sizeof(int), hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, st), PWN_HIP_ERR_LAUNCH);
   const int k1 = h[2 * n];
   if (w != weights && k1 > 0) HIPCHK(ctx, hipMemcpy(weights, w, sizeof(float) * (size_t)k1, hipMemcpyDeviceToHost), PWN_HIP_ERR_COPY);
   if (appended) std::copy(h, h + n, appended);
@@ -564,7 +564,7 @@ int pwn_hip_manifold_image(pwn_hip_ctx* ctx, int n, pwn_hip_cloud* const* clouds
   }
   if (img != image) HIPCHK(ctx, hipMemcpyAsync(ctx->manifold_img_host.p, img, sizeof(uint16_t) * (size_t)cells, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
   if (inside && n > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->merge_counts_host.p, d_inside, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, st), PWN_HIP_ERR_LAUNCH);
   if (img != image) std::memcpy(image, ctx->manifold_img_host.p, sizeof(uint16_t) * (size_t)cells);
   if (inside && n > 0) std::copy(ctx->merge_counts_host.p, ctx->merge_counts_host.p + n, inside);
   return PWN_HIP_OK;
@@ -605,7 +605,7 @@ int pwn_hip_voxelize(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, float resolution, i
   HIPCHK(ctx, hipGetLastError(), PWN_HIP_ERR_LAUNCH);
   int hostv[2] = { 0, 0 };
   HIPCHK(ctx, hipMemcpyAsync(hostv, ctx->scene_total, 2 * sizeof(int), hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, st), PWN_HIP_ERR_LAUNCH);
   if (hostv[1] != 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, hostv[1] == 1 ? "voxel index outside +-2^20 (or NaN point)" : "voxel table full");
   const int m = hostv[0];
   // the survivors sorted by their 63-bit voxel key (8 passes of 8 bits), stable -> lexicographic (ix, iy, iz) order
@@ -618,7 +618,7 @@ int pwn_hip_voxelize(pwn_hip_ctx* ctx, pwn_hip_cloud* cloud, float resolution, i
   if (int rc = cloud_edit(ctx, cloud, m, true)) return rc;      // edit: the host decides the new size
   cloud->content.set_gaussians(withGauss ? m : 0);
   if (kept && m > 0) HIPCHK(ctx, hipMemcpyAsync(kept, d_order, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, st), PWN_HIP_ERR_COPY);
-  HIPCHK(ctx, hipStreamSynchronize(st), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, st), PWN_HIP_ERR_LAUNCH);
   cloud->swap_sides();
   if (new_size) *new_size = m;
   return PWN_HIP_OK;
@@ -630,7 +630,7 @@ int pwn_hip_cloud_save(pwn_hip_ctx* ctx, const pwn_hip_cloud* c, const char* fil
   if (!ctx || !c || !filename || !T || step <= 0) return fail(ctx, PWN_HIP_ERR_INVALID_ARGUMENT, "bad argument");
   const int n = c->content.n;
   std::vector<float> P, Nm, St;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   if (int rc = cloud_fetch_records(ctx, c->d, n, P, Nm)) return rc;
   if (n > 0) {
     if (c->content.stats && c->d.St) { St.resize((size_t)n * 16); HIPCHK(ctx, hipMemcpy(St.data(), c->d.St, St.size() * 4, hipMemcpyDeviceToHost), PWN_HIP_ERR_COPY); }
@@ -720,7 +720,7 @@ int pwn_hip_cloud_load(pwn_hip_ctx* ctx, pwn_hip_cloud* c, const char* filename,
   // replace: points with Stats.  Cloud::load leaves both information-matrix vectors empty (cloud.cpp:25-82): zero matrices for every point.  The
   // class of the normal information matrix is derived from normal and curvature on the device, so a loaded cloud says "zero" with explicit planes.
   if (int rc = cloud_replace(ctx, c, true, true, nullptr)) return rc;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream), PWN_HIP_ERR_LAUNCH);
+  HIPCHK(ctx, host_wait(ctx, ctx->stream), PWN_HIP_ERR_LAUNCH);
   if (n > 0) {
     if (int rc = cloud_store_records(ctx, c->d, n, P, Nm)) return rc;
     HIPCHK(ctx, hipMemcpy(c->d.St, St.data(), St.size() * 4, hipMemcpyHostToDevice), PWN_HIP_ERR_COPY);

@@ -1070,6 +1070,91 @@ class PwnTracker : public PwnMatcherBase {
   int _counter = 0, _numKeyframes = 0;
 };
 
+// S PwnTrackers that advance in lock-step (pwn_hip_tracker / pwn_hip_track_frames; not in the reference): processFrames runs processFrame
+// (pwn_tracker.cpp:106-215) for frame 0 of every stream, then frame 1 of every stream, ... as one submission with one host wait; guess, pose chain,
+// key-cloud decision and the switch of the reference cloud happen on the device.  Per stream the results, globalT and the key cloud are PwnTracker's,
+// bit for bit.  The streams share camera matrix, image size, parameters and one sensor offset; frames are raw uint16 images (depth = rawScale * raw).
+class PwnTrackerBatch : public PwnMatcherBase {
+ public:
+  using FrameResult = PwnTracker::FrameResult;
+  struct StreamFrame { bool present = false; FrameResult result; int nPoints = 0; };
+  PwnTrackerBatch(Context* ctx, Aligner* aligner, DepthImageConverter* converter, int streams, int framesPerCallMax, int rows, int cols, int scale = 2)
+      : PwnMatcherBase(ctx, aligner, converter), _streams(streams), _framesPerCallMax(framesPerCallMax), _rows(rows), _cols(cols) {
+    setScale(scale);
+    ctx->check(pwn_hip_tracker_create(ctx->handle(), streams, framesPerCallMax, rows, cols, scale, &_h));
+  }
+  ~PwnTrackerBatch() { pwn_hip_tracker_destroy(_h); }      // before or after its context: a context that goes first leaves the handle valid for this call
+  PwnTrackerBatch(const PwnTrackerBatch&) = delete;
+  PwnTrackerBatch& operator=(const PwnTrackerBatch&) = delete;
+  pwn_hip_tracker* handle() const { return _h; }
+  int streams() const { return _streams; }  int framesPerCallMax() const { return _framesPerCallMax; }
+  float newFrameInliersFraction() const { return _newFrameInliersFraction; }  void setNewFrameInliersFraction(float v) { _newFrameInliersFraction = v; }
+  pwn_hip_tracker_state state(int s) const { pwn_hip_tracker_state st; _ctx->check(pwn_hip_tracker_get_state(_h, s, 1, &st)); return st; }
+  void setState(int s, const pwn_hip_tracker_state& st) { _ctx->check(pwn_hip_tracker_set_state(_h, s, 1, &st)); }
+  void init() { for (int s = 0; s < _streams; ++s) init(s); }                                         // pwn_tracker.cpp:38-49, every stream
+  void init(int s) {
+    pwn_hip_tracker_state st = pwn_hip_tracker_state();
+    const Isometry3f I = Isometry3f::Identity();
+    for (int q = 0; q < 16; ++q) st.globalT[q] = st.previous_cloud_transform[q] = st.sensor_offset[q] = I.data()[q];
+    st.key_slot = -1;
+    setState(s, st);
+  }
+  Isometry3f globalT(int s) const { const pwn_hip_tracker_state st = state(s); Isometry3f T; for (int q = 0; q < 16; ++q) T.data()[q] = st.globalT[q]; return T; }
+  int numKeyframes(int s) const { return state(s).num_keyframes; }
+  // the stream's key cloud after the last call: a borrowed handle (the next call may overwrite it), nullptr while the stream has none
+  pwn_hip_cloud* keyCloud(int s) const { pwn_hip_cloud* c = nullptr; _ctx->check(pwn_hip_tracker_key_cloud(_h, s, &c)); return c; }
+  // frames[f][s]: frame f of stream s, nullptr = the stream idles in that step; guesses (optional): [f][s] -> result[f][s]
+  std::vector<std::vector<StreamFrame>> processFrames(const std::vector<std::vector<const RawDepthImage*>>& frames, const Isometry3f& sensorOffset, const Matrix3f& cameraMatrix,
+                                                      const std::vector<std::vector<Isometry3f>>* guesses = nullptr, float rawScale = 0.001f, float maxDepthCov = 0.01f) {
+    const int F = (int)frames.size(), S = _streams;
+    std::vector<const uint16_t*> ptrs((size_t)F * S, nullptr);
+    for (int f = 0; f < F; ++f) {
+      if ((int)frames[f].size() != S) throw Error(PWN_HIP_ERR_INVALID_ARGUMENT, "processFrames: one frame (or null) per stream in every step");
+      for (int s = 0; s < S; ++s) {
+        const RawDepthImage* d = frames[f][s];
+        if (d && (d->rows != _rows || d->cols != _cols)) throw Error(PWN_HIP_ERR_INVALID_ARGUMENT, "processFrames: a frame of another size than the tracker's");
+        ptrs[(size_t)f * S + s] = d ? d->data.data() : nullptr;
+      }
+    }
+    // the side effects of makeCloud (pwn_matcher_base.cpp:57-86) and of processFrame's aligner set-up (pwn_tracker.cpp:120-130) on the collaborators
+    PinholePointProjector* projector = _converter->projector();
+    const float invScale = 1.0f / _scale;
+    Matrix3f scaled = cameraMatrix;
+    for (int i = 0; i < 9; ++i) scaled.m[i] = scaled.m[i] * invScale;
+    scaled(2,2) = 1.0f;
+    const int r = _rows / _scale, c = _cols / _scale;
+    projector->setCameraMatrix(scaled); projector->setImageSize(r, c); projector->setTransform(Isometry3f::Identity());
+    const pwn_hip_converter_params cp = _converter->params(sensorOffset);
+    _aligner->setCurrentSensorOffset(sensorOffset); _aligner->setReferenceSensorOffset(sensorOffset);
+    _aligner->correspondenceFinder()->setImageSize(r, c);
+    _aligner->projector()->setCameraMatrix(scaled); _aligner->projector()->setImageSize(r, c);
+    const pwn_hip_aligner_params ap = _aligner->params();
+    std::vector<float> g;
+    if (guesses) {
+      g.resize((size_t)F * S * 16);
+      for (int f = 0; f < F; ++f) for (int s = 0; s < S; ++s) { Isometry3f T = (*guesses)[f][s]; T.forceLastRow(); for (int q = 0; q < 16; ++q) g[((size_t)f * S + s) * 16 + q] = T.data()[q]; }
+    }
+    std::vector<pwn_hip_track_result> res((size_t)F * S);
+    _ctx->check(pwn_hip_track_frames(_ctx->handle(), _h, &cp, &ap, F, ptrs.data(), rawScale, maxDepthCov, guesses ? g.data() : nullptr, _newFrameInliersFraction, res.data()));
+    std::vector<std::vector<StreamFrame>> out((size_t)F, std::vector<StreamFrame>((size_t)S));
+    for (int f = 0; f < F; ++f)
+      for (int s = 0; s < S; ++s) {
+        if (!ptrs[(size_t)f * S + s]) continue;
+        const pwn_hip_track_result& q = res[(size_t)f * S + s];
+        StreamFrame& o = out[f][s];
+        o.present = true; o.nPoints = q.n_points; ++numCalls;
+        o.result.newFrame = q.new_frame != 0; o.result.aligned = q.aligned != 0; o.result.inliers = q.inliers; o.result.error = q.error;
+        o.result.inliersFraction = q.inliers_fraction;
+        for (int k = 0; k < 16; ++k) { o.result.T.data()[k] = q.T[k]; o.result.globalT.data()[k] = q.globalT[k]; }
+      }
+    return out;
+  }
+ private:
+  pwn_hip_tracker* _h = nullptr;
+  int _streams, _framesPerCallMax, _rows, _cols;
+  float _newFrameInliersFraction = 0.4f;     // pwn_tracker.cpp:36
+};
+
 // ---- the merged closure (pwn_tracker2) --------------------------------------------------------------------------------------------------
 // Eigen::Isometry3d as the closers compose it: row-major 4x4 doubles, products and inverse as plain loops in a fixed order (api.py runs the
 // same loops: the two mirrors arrive at the same bits before the cast to float)

@@ -743,6 +743,81 @@ int pwn_hip_scene_step(pwn_hip_ctx* ctx, const pwn_hip_converter_params* cp, con
                        const void* frame, int raw_u16, float depth_scale, int rows, int cols, const float scene_T[16], pwn_hip_cloud* scene,
                        pwn_hip_cloud* cloud, pwn_hip_cloud* subscene, pwn_hip_scene_step_result* result, int* collapsed);
 
+/* ------------------------------------------------------------------ multi-stream tracker ------ */
+/* PwnTracker::processFrame (pwn_tracker/pwn_tracker.cpp:106-215) for S independent depth streams that advance in lock-step: frame f of every
+ * stream, then frame f + 1 of every stream -- each step one batch of up to S (key cloud, frame) pairs -- and a run of F frames per stream in ONE
+ * submission with ONE host wait.  What the tracker does between two alignments runs on the device: the guess _previousCloudTransform^-1 * _globalT *
+ * initialGuess (:132) and the pairs' initial states in front of a step's alignment kernels, the pose chain (:147-150), the re-orthonormalisation
+ * of every 50th frame (:154-159), the key-cloud decision (:164-185) and the switch of the reference cloud behind them.
+ * The tracker belongs to its context: pwn_hip_ctx_destroy releases the clouds and device records of the trackers that are left, and such a handle is
+ * then good for pwn_hip_tracker_destroy alone (every other call refuses it), so either order of destruction is safe.  It owns, per stream, a ring of frames_per_call_max + 1 clouds of
+ * (rows / step) * (cols / step) points -- ordinary lean clouds of the context, as pwn_hip_convert_batch_u16_scaled fills them -- and one state
+ * record on the device.  A key switch moves no cloud: the state names the slot.  rows, cols: the size of the frames; step: DepthImage_scale's
+ * (>= 1; PwnMatcherBase::_scale).  Refused: streams < 1 or above the context's max_batch (PWN_HIP_ERR_CAPACITY), frames_per_call_max < 1, a
+ * frame larger than the context's, an empty scaled image. */
+typedef struct pwn_hip_tracker pwn_hip_tracker;
+/* The state of one stream: what PwnTracker keeps between two frames.  key_slot = -1: no key cloud (PwnTracker::init(), :38-49, with the other
+ * fields at their initial values: identities and zeros).  sensor_offset is _previousCloudOffset as the stream recorded it with its first key cloud
+ * (:194-200); it is kept for the caller and not read by the alignment (see pwn_hip_track_frames). */
+typedef struct pwn_hip_tracker_state {
+  float globalT[16];
+  float previous_cloud_transform[16];
+  float sensor_offset[16];
+  int   counter;
+  int   num_keyframes;
+  int   key_slot;                  /* slot of the stream's ring that holds the key cloud, 0 .. frames_per_call_max; -1: none */
+  int   reserved;
+} pwn_hip_tracker_state;
+/* What processFrame reports for one frame of one stream.  A first frame (no key cloud before it): new_frame = 1, aligned = 0, the rest of the
+ * alignment's fields zero.  A stream that idled in a step (NULL frame): all zero. */
+typedef struct pwn_hip_track_result {
+  int   new_frame;                 /* the frame became the stream's key cloud */
+  int   aligned;
+  int   inliers;                   /* Aligner::inliers() */
+  float error;                     /* Aligner::error() */
+  float T[16];                     /* Aligner::T() */
+  float globalT[16];               /* _globalT after the frame */
+  float inliers_fraction;          /* (float) inliers / (float) (view rows * view cols) (:163) */
+  int   n_points;                  /* points of the frame's cloud */
+} pwn_hip_track_result;
+int pwn_hip_tracker_create(pwn_hip_ctx* ctx, int streams, int frames_per_call_max, int rows, int cols, int step, pwn_hip_tracker** tracker);
+int pwn_hip_tracker_destroy(pwn_hip_tracker* tracker);
+/* The states of the streams [first, first + n), as the last call (or set_state) left them.  set_state with key_slot >= 0 is refused unless that
+ * slot of the stream's ring holds a cloud; a refused call changes nothing.  set_state waits for the context's queued work. */
+int pwn_hip_tracker_get_state(pwn_hip_tracker* tracker, int first, int n, pwn_hip_tracker_state* states);
+int pwn_hip_tracker_set_state(pwn_hip_tracker* tracker, int first, int n, const pwn_hip_tracker_state* states);
+/* The cloud that is stream s's key cloud after the last call: a borrowed handle (the tracker owns it and a later call may overwrite it), for
+ * pwn_hip_cloud_download and tests; NULL while the stream has none. */
+int pwn_hip_tracker_key_cloud(pwn_hip_tracker* tracker, int s, pwn_hip_cloud** cloud);
+/* processFrame for frame 0 of every stream, then frame 1 of every stream, ... frame F - 1: frames[f * S + s] (raw uint16, rows x cols, ALL host or ALL
+ * device memory) is frame f of stream s; NULL = the stream has no frame in that step and idles (its state, counter included, does not move).
+ * Per frame: makeCloud's data path as pwn_hip_convert_batch_u16_scaled runs it (depth = depth_scale * raw, DepthImage_scale(step, max_depth_cov), the
+ * converter) into a free slot of the stream's ring; then the alignment against the stream's key cloud and the tracker's bookkeeping, or, for a
+ * stream without a key cloud, the frame's cloud taken as the key without an alignment (:194-200).  initial_guesses: F * S column-major 4x4, or NULL
+ * (identities).  new_frame_inliers_fraction: PwnTracker::_newFrameInliersFraction (0.4, :36); the fraction is compared with it in float, as the
+ * reference's float members are.  results: F * S records, results[f * S + s].
+ * K, image size, converter and aligner parameters are the call's, as everywhere in this ABI, and so is the SENSOR OFFSET: the aligner's kernels take
+ * one reference offset per call, so a tracker tracks streams of ONE sensor offset -- cp->sensor_offset for the conversions,
+ * ap->reference_sensor_offset and ap->current_sensor_offset (the same matrix for PwnTracker's use, :194-200) for the alignments.
+ * ap->initial_guess is not read.  The convergence setting (pwn_hip_ctx_set_convergence) is honoured as in every batch call.
+ * The conversions of all steps are queued on a stream of their own, so step f + 1 converts beside step f's alignment; a step's pairs run in the
+ * sub-batches and on the streams of a batch alignment (pwn_hip_ctx_set_subbatch, _set_concurrency); results do not depend on either.
+ * A projection that gives up on a pixel (see pwn_hip_align_batch_records, word 63) or a converter strip whose hand-over times out makes the
+ * library run the whole call once more from the states it started with.  Bit for bit, every stream's results, state and key cloud are those
+ * of pwn_hip_convert_scaled + pwn_hip_align per frame with the host-side bookkeeping in between (what api.PwnTracker does).
+ * Refused, nothing touched (states, clouds, results): a null argument (initial_guesses apart), a tracker of another context, F outside
+ * 1 .. frames_per_call_max, more streams than the context's max_batch, ap->rows x ap->cols other than (rows / step) x (cols / step), what every
+ * alignment call refuses in ap, frames of mixed host and device memory. */
+int pwn_hip_track_frames(pwn_hip_ctx* ctx, pwn_hip_tracker* tracker, const pwn_hip_converter_params* cp, const pwn_hip_aligner_params* ap, int F,
+                         const uint16_t* const* frames, float depth_scale, float max_depth_cov, const float* initial_guesses,
+                         float new_frame_inliers_fraction, pwn_hip_track_result* results);
+/* The host compilation of what the device does with one alignment's result (no context): from *state and initial_guess (NULL: identity) the
+ * guess of :132, then with the aligner's T and inliers the pose chain, the re-orthonormalisation when counter % 50 == 0, the forced last row, the
+ * key-cloud decision against `threshold` (on a switch key_slot = slot, previous_cloud_transform = globalT, num_keyframes + 1) and counter + 1.
+ * *state is updated, *result filled (error and n_points are left zero). */
+void pwn_hip_track_pose_update(pwn_hip_tracker_state* state, const float initial_guess[16], const float T[16], int inliers, int pixels,
+                               float threshold, int slot, pwn_hip_track_result* result);
+
 /* ------------------------------------------------------------------ helpers ------------------ */
 /* PinholePointProjector::_updateMatrices (pinholepointprojector.cpp:17-31): KRt, iKRt (4x4), iK (3x3) */
 void pwn_hip_projector_matrices(const float K[9], const float T[16], float KRt[16], float iKRt[16], float iK[9]);

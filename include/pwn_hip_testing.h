@@ -33,6 +33,10 @@ int pwn_hip_debug_set_index_shortcut(pwn_hip_ctx* ctx, int enabled);
  * Number of calls repeated so far: */
 int pwn_hip_debug_set_settle_guard(pwn_hip_ctx* ctx, int rounds);
 int pwn_hip_debug_projection_fallbacks(pwn_hip_ctx* ctx, int* calls);
+/* How often the calling thread has waited for one of the context's streams so far (every such wait of the library is counted, whatever the
+ * reason: the end of a call, a workspace or descriptor array that has to grow, a cloud's planes that are dropped).  The difference across a call
+ * is the number of host waits of that call: what "one submission, one wait" means for the one-call entry points. */
+int pwn_hip_debug_host_waits(pwn_hip_ctx* ctx, int* waits);
 /* The aligner's projection launch on injected clouds: clouds[i], i < n, projected under the projector transform transforms[16 i ..] (column-major,
  * what pwn_hip_project takes); camera matrix, image size and range from p, as an alignment takes them.  The launch is the function an alignment
  * calls, with its grid, its choice of kernel by n (fewer than 8 pairs: one point per thread; from 8 on: four) and the context's settle guard,
